@@ -19,8 +19,11 @@ frames/s.  `--pipeline config4` times BASELINE configs[3] instead (per GPU: 1024
 STFT+mel128 -> MFCC(40); features reassembled with an RCCL all-gather) and reports its three
 figures: compute only, + all-gather fp32, + all-gather with a bf16 wire format.
 
-Side figures (per-kernel roofline, CPU baselines, PGHI round trip, streaming matrix, parity spot
-check of what the timed loop produced) ride along in the same JSON line.
+A plain run sets up, settles, warms up, times the K steps and prints the headline line.  With
+`--full` the side figures (per-kernel roofline, CPU baselines, PGHI round trip, streaming matrix,
+parity spot check of what the timed loop produced, ...) are measured after the timed steps and ride
+along in the same JSON line.  `--dump-outputs DIR` writes what the last timed step returned (a fixed
+sample of clips, float32) as DIR/<name>.npy, so that two builds can be compared output for output.
 """
 import argparse
 import json
@@ -34,6 +37,12 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
+# --dump-outputs: 8 clips of the headline step are 31 MB (spectrum 22.7, audio 5.6, features 2.8), under the 64 MB bound
+DUMP_CLIPS = 8
+DUMP_SEED = 0
+DUMP_MAX_BYTES = 64_000_000
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -42,17 +51,24 @@ def parse():
     ap.add_argument("--batch", type=int, default=1024, help="clips per GPU")
     ap.add_argument("--pipeline", choices=("step", "config4"), default="step",
                     help="step: configs[1] fwd+mel+invert (the headline); config4: STFT+mel128+MFCC(40) + all-gather")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement and check: the fresh-process figure, "
+                         "per-kernel roofline legs, pattern-copy ceilings, power, the spot checks against the oracle, the "
+                         "config4 / PGHI / north-star / streaming / other-size legs and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned, for a fixed sample of %d clips of rank 0, as "
+                         "DIR/<name>.npy in float32 (complex values with a trailing (re, im) axis)" % DUMP_CLIPS)
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--unfused", action="store_true", help="STFT and Magnitude as two kernels")
-    ap.add_argument("--no-extras", action="store_true", help="skip the side measurements")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the side measurements")
     ap.add_argument("--settle-steps", type=int, default=-1,
                     help="untimed steps run BEFORE the --warmup steps so that the timed region sees the chip's sustained "
                          "clocks (a fresh process runs its first two steps at boost clock, is then clamped ~35 %% below by "
                          "the power controller and recovers over 25 to 60 steps: tools/ramp_probe.py); -1 = until three "
                          "consecutive 10-step averages agree within 1.5 %% (at least 40, at most 600 steps); 0 = none")
-    ap.add_argument("--pghi-clips", type=int, default=1024, help="clips for the DGT+PGHI round-trip side measurement")
-    ap.add_argument("--streams", type=int, default=256, help="concurrent streams for the RealtimeDGT side measurement")
-    ap.add_argument("--stream-steps", type=int, default=1000, help="steps per cell of the streaming matrix")
+    ap.add_argument("--pghi-clips", type=int, default=1024, help="with --full: clips for the DGT+PGHI round-trip side measurement")
+    ap.add_argument("--streams", type=int, default=256, help="with --full: concurrent streams for the RealtimeDGT side measurement")
+    ap.add_argument("--stream-steps", type=int, default=1000, help="with --full: steps per cell of the streaming matrix")
     ap.add_argument("--dry-plan", action="store_true",
                     help="print, WITHOUT touching a GPU or importing torch, what `--gpus N` will do: rank -> device map, clip "
                          "ranges per rank, wire bytes per rank of the three configs[3] figures, timeouts, the keys of the line")
@@ -161,16 +177,17 @@ def dry_plan(args):
                     "gathered_bytes_per_rank_per_step": {
                         "with_allgather_fp32": 4 * feat_elems * n, "with_allgather_bf16_wire": 2 * feat_elems * n,
                         "with_allgather_mfcc40_only_fp32": 4 * B * T * n_mfcc * n},
-                    "where": "the headline line carries them under `config4` (run on all ranks before any rank-0-only leg); "
+                    "where": "with --full the headline line carries them under `config4` (run on all ranks before any "
+                             "rank-0-only leg); "
                              "`--pipeline config4` makes with_allgather_fp32 the line's `value`"},
         "commands": {"driver": "python -m torch.distributed.run --nnodes=1 --nproc-per-node %d --master-addr 127.0.0.1 --master-port P "
                                "bench.py --gpus %d --steps K --warmup W" % (n, n),
                      "self_launch": "python bench.py --gpus %d --steps K --warmup W" % n},
         "line_keys": ["metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
-                      "vs_baseline", "dtype", "data", "config", "world_size_observed", "backend", "roofline", "kernels",
-                      "config4", "hooks_armed", "verification"],
+                      "vs_baseline", "dtype", "data", "config", "world_size_observed", "backend", "hooks_armed", "settle_steps"],
+        "line_keys_added_by_full": ["roofline", "kernels", "config4", "verification"],
         "exit_status": {"0": "measured and verified", "2": "WORLD_SIZE != --gpus / no ROCm device", "3": "fewer devices than ranks",
-                        "4": "a side leg raised", "5": "a spot check of timed output failed", "6": "a rank failed inside a timed region"},
+                        "4": "a side leg raised (--full)", "5": "a spot check of timed output failed (--full)", "6": "a rank failed inside a timed region"},
         "hooks_armed": hooks_armed(),
     }
     if definite and ndev < n:
@@ -486,6 +503,29 @@ def exit_status(result):
     return 0
 
 
+def dump_clips(n_clips):
+    """Clip indices of the --dump-outputs sample: DUMP_CLIPS of `n_clips` drawn with a fixed seed, ascending."""
+    import random
+    return sorted(random.Random(DUMP_SEED).sample(range(n_clips), min(DUMP_CLIPS, n_clips)))
+
+
+def dump_outputs(outdir, outputs, clips):
+    """Write outputs[name][clips] as outdir/<name>.npy in float32 (a complex tensor gets a trailing (re, im) axis).
+    Refuses, before writing anything, a sample larger than DUMP_MAX_BYTES."""
+    import numpy as np
+    arrays = {}
+    for name, t in outputs.items():
+        t = t[clips]
+        arrays[name] = (torch.view_as_real(t) if t.is_complex() else t).float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise ValueError("--dump-outputs: %d bytes for %d clips, more than %d" % (total, len(clips), DUMP_MAX_BYTES))
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
+    return {"dir": outdir, "clips": list(clips), "arrays": {k: list(a.shape) for k, a in arrays.items()}, "bytes": total}
+
+
 class LegFailed(RuntimeError):
     """A measurement leg that holds collectives failed on some rank; raised on EVERY rank (see all_ok)."""
 
@@ -562,6 +602,8 @@ def main():
     X = stft(x[:8])
     mag.scale_data(X)                                                  # one-off calibration, outside the timed region
     del X
+    # built in every run, config4 or not: its device buffers are allocated before the step's outputs, and where those
+    # outputs land moves the step's time (a plain run without it measured ~1 % slower per step, same box, alternating)
     mfcc = A.MFCC(sr=SR, n_fft=N_FFT, hop_length=HOP, n_mels=N_MELS, n_mfcc=N_MFCC).to(dev)
 
     ev = lambda: torch.cuda.Event(enable_timing=True)  # noqa: E731
@@ -661,10 +703,14 @@ def main():
         """log-mel (B, T, 128) from the fused kernel (the spectrum never goes to HBM) and its DCT-II, 40
         coefficients, channel-major (B, 40, T) like the reference's MFCC layout."""
         from acids_transforms_amd import ops as _ops
+        if config4:
+            last.clear()                  # the timed path: its last outputs are kept for --dump-outputs, as step() does
         maybe_fail("config4")
         _, _, logmel = _ops.stft_mel_forward(x, mfcc.window, mfcc._band, "log", None, None, eps=1e-10, power=2,
                                              want_spectrum=False)
         coef = _ops.mel_forward_real(logmel, mfcc.dct, None, None, channel_major_T=logmel.shape[-2])
+        if config4:
+            last["logmel"], last["mfcc"] = logmel, coef
         return logmel, coef
 
     def config4_figures(steps, warmup):
@@ -747,6 +793,8 @@ def main():
             "world_size_observed": dist.get_world_size() if use_dist else 1, "backend": backend,
             "config4": c4, "hooks_armed": hooks_armed(),
         }
+        if rank == 0 and args.dump_outputs:
+            result["outputs"] = dump_outputs(args.dump_outputs, {"logmel": last["logmel"], "mfcc": last["mfcc"]}, dump_clips(B))
         if rank == 0:
             print(json.dumps(result))
         if use_dist:
@@ -754,14 +802,15 @@ def main():
         return
 
     # settle: the power controller's transient of a fresh process is over before the W warm-up steps start
-    # (reported as `settle_steps`; the W warm-up steps and the K timed steps follow as the contract says).  The first
-    # W + K steps of the process are what `--settle-steps 0` would have timed: they are clocked on the way
+    # (reported as `settle_steps`; the W warm-up steps and the K timed steps follow as the contract says).  With --full,
+    # the first W + K steps of the process are what `--settle-steps 0` would have timed: they are clocked on the way
     # (`fresh_process_ms_per_step`, HIP events, no host synchronisation) so that both figures come from one run.
     settled = 0
+    fresh = args.full and args.settle_steps != 0
     fresh_ms = None
     err = None
     try:
-        if args.settle_steps != 0:
+        if fresh:
             fa, fb = ev(), ev()
             for _ in range(args.warmup):
                 step()
@@ -794,7 +843,7 @@ def main():
         for _ in range(args.warmup):
             step()
         torch.cuda.synchronize()
-        if args.settle_steps != 0:
+        if fresh:
             fresh_ms = fa.elapsed_time(fb) / max(1, args.steps)
     except Exception as exc:          # noqa: BLE001 -- every rank must reach the collective below
         err = exc
@@ -805,6 +854,7 @@ def main():
     evs = []
     try:
         for _ in range(args.steps):
+            # the per-kernel events are recorded with or without --full, so that `ms_per_step` times the same work
             evs.append(step(record=True))
         torch.cuda.synchronize()
     except Exception as exc:          # noqa: BLE001
@@ -815,13 +865,37 @@ def main():
     if not ok:
         fail_all_ranks("timed region: %s" % (repr(err) if err is not None else "another rank failed"))
     elapsed = max_over_ranks(elapsed)
+    ms_per_step = elapsed / args.steps * 1e3
+    value = world * frames_per_step * args.steps / elapsed
+    result = {
+        "metric": "spectrogram frames/sec (fwd+invert), n_fft=1024 hop=256",
+        "value": value, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        "config": {"workload": "configs[1]: batch=%d clips/GPU x 4 s mono 44.1 kHz, STFT fwd + Magnitude(mel=128, log1p, "
+                               "unipolar)%s + ISTFT invert, fp32" % (B, " [one fused kernel]" if fused else ""),
+                   "n_fft": N_FFT, "hop": HOP, "frames_per_clip": T_FRAMES, "clips_per_gpu": B,
+                   "sharding": "clips, no data-path collective"},
+        "world_size_observed": dist.get_world_size() if use_dist else 1, "backend": backend,
+        "hooks_armed": hooks_armed(),
+        "settle_steps": settled,
+    }
+    if rank == 0 and args.dump_outputs:
+        # before any side leg: they run step() again, and the spot check's corruption hook writes into `last`
+        result["outputs"] = dump_outputs(args.dump_outputs, {"spectrum": last["X"], "features": last["feat"], "audio": last["y"]},
+                                         dump_clips(B))
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(result))
+            sys.stdout.flush()
+        if use_dist:
+            dist.destroy_process_group()
+        return
     for e in evs:
         ktimes["stft_fwd"].append(e[0].elapsed_time(e[1]))
         ktimes["mel"].append(e[1].elapsed_time(e[2]))
         ktimes["istft"].append(e[2].elapsed_time(e[3]))
     del evs
-    ms_per_step = elapsed / args.steps * 1e3
-    value = world * frames_per_step * args.steps / elapsed
     avg = {k: sum(v) / len(v) for k, v in ktimes.items()}
     step_ms_events = [round(a + b + c, 4) for a, b, c in zip(ktimes["stft_fwd"], ktimes["mel"], ktimes["istft"])]
 
@@ -1308,27 +1382,16 @@ def main():
             if args.streams > 0:
                 guarded("realtime_dgt_stream", extra_stream)
 
-    result = {
-        "metric": "spectrogram frames/sec (fwd+invert), n_fft=1024 hop=256",
-        "value": value, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f32", "data": "synthetic",
-        "config": {"workload": "configs[1]: batch=%d clips/GPU x 4 s mono 44.1 kHz, STFT fwd + Magnitude(mel=128, log1p, "
-                               "unipolar)%s + ISTFT invert, fp32" % (B, " [one fused kernel]" if fused else ""),
-                   "n_fft": N_FFT, "hop": HOP, "frames_per_clip": T_FRAMES, "clips_per_gpu": B,
-                   "sharding": "clips, no data-path collective"},
-        "world_size_observed": dist.get_world_size() if use_dist else 1, "backend": backend,
-        "hooks_armed": hooks_armed(),
+    result.update({
         "roofline": roof,
         "kernels": kernels,
-        "settle_steps": settled,
         "fresh_process_ms_per_step": round(fresh_ms if fresh_ms is not None else ms_per_step, 4),
         "fresh_process_note": ("steps W+1 .. W+K of this process's life, before any settling: what `--settle-steps 0` "
                                "times (HIP events around the K steps); `ms_per_step` is the settled figure"),
         "timed_step_ms": {"first": step_ms_events[0], "last": step_ms_events[-1], "min": min(step_ms_events),
                           "max": max(step_ms_events), "all": step_ms_events,
                           "note": "per-step kernel time (HIP events) inside the timed region: flat = steady state"},
-    }
+    })
     result.update(extras)
     if "pattern_copy" in extras:
         pc = extras["pattern_copy"]

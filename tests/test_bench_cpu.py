@@ -1,6 +1,9 @@
-"""bench.py's own logic that needs no GPU: what its exit status says, and when its launcher refuses a job."""
+"""bench.py's own logic that needs no GPU: what its exit status says, when its launcher refuses a job, and what
+--dump-outputs writes."""
 import os
 import sys
+
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
@@ -78,3 +81,27 @@ def test_dry_plan_prints_the_multi_gpu_sheet_without_torch():
     assert plan["config4"]["gathered_bytes_per_rank_per_step"]["with_allgather_fp32"] == 8 * 4 * per_rank
     assert plan["timeout_s"] == 180 and "torch.distributed.run" in plan["commands"]["driver"]
     assert plan["hooks_armed"] == []
+
+
+def test_dump_outputs_writes_a_fixed_bounded_float32_sample(tmp_path):
+    """--dump-outputs: the clip sample is fixed (same clips in every run) and the headline step's three outputs for it
+    fit the 64 MB bound; complex values are stored as a trailing (re, im) axis; an oversized sample writes nothing."""
+    import numpy as np
+    import torch
+    clips = bench.dump_clips(1024)
+    assert clips == bench.dump_clips(1024) == sorted(set(clips)) and len(clips) == 8 and 0 <= clips[0] and clips[-1] < 1024
+    assert bench.dump_clips(3) == [0, 1, 2]
+    g = torch.Generator().manual_seed(0)
+    outputs = {"spectrum": torch.randn(10, 690, 513, dtype=torch.complex64, generator=g),
+               "features": torch.randn(10, 690, 128, generator=g), "audio": torch.randn(10, 176384, generator=g)}
+    sample = bench.dump_clips(10)
+    info = bench.dump_outputs(str(tmp_path / "out"), outputs, sample)
+    assert info["bytes"] <= 64_000_000 and info["clips"] == sample
+    spec = np.load(tmp_path / "out" / "spectrum.npy")
+    assert spec.dtype == np.float32 and spec.shape == (8, 690, 513, 2)
+    np.testing.assert_array_equal(spec, torch.view_as_real(outputs["spectrum"][sample]).numpy())
+    audio = np.load(tmp_path / "out" / "audio.npy")
+    assert audio.dtype == np.float32 and np.array_equal(audio, outputs["audio"][sample].numpy())
+    with pytest.raises(ValueError):
+        bench.dump_outputs(str(tmp_path / "big"), {"audio": torch.zeros(100, 176384)}, list(range(100)))
+    assert not (tmp_path / "big").exists()

@@ -1,5 +1,6 @@
-"""bench.py end to end on the GPU box, small sizes: the exit status when its own verification fails, and the N > 1
-control flow rehearsed with two ranks on one device (gloo) with a failure injected on rank 1."""
+"""bench.py end to end on the GPU box, small sizes: a plain run and its --dump-outputs, the exit status when its own
+verification fails (--full), and the N > 1 control flow rehearsed with two ranks on one device (gloo) with a failure
+injected on rank 1."""
 import json
 import os
 import subprocess
@@ -10,7 +11,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
-SMALL = ["--batch", "8", "--steps", "2", "--warmup", "1", "--settle-steps", "0", "--no-cpu-baseline",
+SMALL = ["--full", "--batch", "8", "--steps", "2", "--warmup", "1", "--settle-steps", "0", "--no-cpu-baseline",
          "--pghi-clips", "0", "--streams", "0"]
 
 
@@ -22,6 +23,33 @@ def _bench(argv, env_extra, timeout=400):
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + argv, env=env, capture_output=True, text=True,
                        timeout=timeout)
     return r, time.time() - t0
+
+
+def test_a_plain_run_times_the_step_and_dumps_its_outputs(tmp_path):
+    """Without --full the line is the headline alone (no side leg ran); --dump-outputs writes the last timed step's
+    spectrum, features and audio for the fixed sample of clips in float32, and a second run with the same arguments
+    writes the same outputs (the inputs are seeded)."""
+    import numpy as np
+    argv = ["--batch", "12", "--steps", "3", "--warmup", "1", "--settle-steps", "0"]
+    dumps = []
+    for run in ("a", "b"):
+        r, _ = _bench(argv + ["--dump-outputs", str(tmp_path / run)], {})
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads(r.stdout.strip().splitlines()[-1])
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["value"] > 0 and line["ms_per_step"] > 0
+        assert line["unit"] == "frames/s" and line["higher_is_better"] is True and line["dtype"] == "f32"
+        assert not {"roofline", "kernels", "parity_spot_check", "power", "pattern_copy", "config4"} & set(line), sorted(line)
+        clips = line["outputs"]["clips"]
+        assert len(clips) == 8 and clips == sorted(set(clips)) and 0 <= clips[0] and clips[-1] < 12
+        arrays = {name: np.load(tmp_path / run / (name + ".npy")) for name in ("spectrum", "features", "audio")}
+        assert arrays["spectrum"].shape == (8, 690, 513, 2) and arrays["features"].shape == (8, 690, 128)
+        assert arrays["audio"].shape == (8, 176384)
+        assert sum(a.nbytes for a in arrays.values()) == line["outputs"]["bytes"] <= 64_000_000
+        for a in arrays.values():
+            assert a.dtype == np.float32 and np.isfinite(a).all() and np.abs(a).max() > 0
+        dumps.append(arrays)
+    for name, a in dumps[0].items():
+        np.testing.assert_allclose(dumps[1][name], a, rtol=0, atol=1e-6 * float(np.abs(a).max()))
 
 
 def test_a_failed_spot_check_fails_the_bench():

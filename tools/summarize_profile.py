@@ -24,7 +24,7 @@ def short(name):
 print("# rocprofv3 summary `%s`\n" % tag)
 STEPS, WARM = int(os.environ.get("PROFILE_STEPS", "20")), int(os.environ.get("PROFILE_WARMUP", "5"))
 SETTLE = int(os.environ.get("PROFILE_SETTLE", "60"))          # bench.py --settle-steps (untimed, before the warm-up steps)
-print("Command: `python3 bench.py --steps %d --warmup %d --no-cpu-baseline --no-extras` (B=1024 clips x 4 s, 1 GPU; "
+print("Command: `python3 bench.py --full --steps %d --warmup %d --no-cpu-baseline --no-extras` (B=1024 clips x 4 s, 1 GPU; "
       "%d settle steps before the warm-up)\n" % (STEPS, WARM, SETTLE))
 WARM += SETTLE
 print("`timed avg` = the launches of bench.py's timed region only (the last %d of a step kernel before the side "
