@@ -126,8 +126,10 @@ def lib():
     return _lib
 
 
-# kernel variants (include/acids_hip.h AT_VARIANT_*): same results, different kernels; for tests and A/B runs
-VARIANTS = {"epilogue": 0, "frame_kernels": 1, "small_projection": 2, "scan_layout": 3, "pghi_kernel": 4, "istft_runs": 5}
+# kernel variants (include/acids_hip.h AT_VARIANT_*): same results, different kernels or a different cut of the clips
+# (run_length, istft_tile: 0..65535); for tests and A/B runs
+VARIANTS = {"epilogue": 0, "frame_kernels": 1, "small_projection": 2, "scan_layout": 3, "pghi_kernel": 4, "istft_runs": 5,
+            "run_length": 6, "istft_tile": 7}
 
 
 class variant:

@@ -108,11 +108,12 @@ extern "C" {
 
 // 2: at_sinebank_realtime takes the synthesis window; bf16 projection, at_oadd_push
 // 3: any n_fft (odd sizes give torch.istft's hop (T-1) + 1 samples); Cartesian pack / unpack; strided phase scans
-// 4: at_set_variant / at_get_variant (round 4; the library no longer reads environment variables)
+// 4: at_set_variant / at_get_variant (round 4; the library no longer reads environment variables).  The plan variants
+//    (AT_VARIANT_RUN_LENGTH, AT_VARIANT_ISTFT_TILE) are table entries, not signatures: still 4.
 int at_abi_version(void) { return 4; }
 
 int at_set_variant(int which, int value) {
-  if (which < 0 || which >= kVarCount || value < 0 || value > 4) return AT_EINVAL;
+  if (which < 0 || which >= kVarCount || value < 0 || value > (which >= kVarFirstPlan ? 65535 : 4)) return AT_EINVAL;
   g_variants[which].store(value, std::memory_order_relaxed);
   return AT_OK;
 }

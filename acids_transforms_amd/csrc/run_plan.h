@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "variants.h"
+
 namespace at_hip {
 
 inline int num_cus() {
@@ -60,6 +62,15 @@ inline long long plan_units_per_run(long long B, long long units, long long slot
 inline long long short_runs_if_full(long long B, long long units, long long slots, long long planned, long long target) {
   if (planned > target && B * ((units + target - 1) / target) >= 2 * slots) return target;
   return planned;
+}
+
+// The run length a launcher must use in place of its own plan: AT_VARIANT_RUN_LENGTH clamped to [8, units] (what the
+// kernels assume, as the dev switches do), or 0 = keep the plan.  The tests force every run cut with it, whatever the device.
+inline long long forced_units_per_run(long long units) {
+  const long long v = variant(kVarRunLength);
+  if (v <= 0) return 0;
+  if (v > units) return units;
+  return v < 8 ? (units < 8 ? units : 8) : v;
 }
 
 }  // namespace at_hip

@@ -1588,6 +1588,7 @@ int launch_stft1024_h256_fwd(const float* x, long long B, long long L, long long
   // the wave priorities (same-box, r04y).  The fused kernels lose at every run length below the planner's (their run
   // start costs 2.4-3.4 us of wave time) and keep one long run per wave.
   if (!bank && hop == 256) p.frames_per_run = short_runs_if_full(B, T, slots, fpr, 16);
+  if (const long long v = forced_units_per_run(T)) p.frames_per_run = v;
   if (const char* e = dev_env("ACIDS_FWD_FPR")) {     // dev builds: run length A/B, clamped to what the kernels assume
     const long long v = atoll(e);
     if (v >= 8 && v <= T) p.frames_per_run = v;
@@ -1643,6 +1644,9 @@ int launch_istft1024_ola(const float2* X, const float* mag, const float* phase, 
   // Full batches at the default hop: tiles of consecutive frames per workgroup, dispatched in address order, the overlap
   // state handed from wave to wave through LDS (istft1024_tile_kernel).  "Full" = at least two tiles for every workgroup
   // the chip holds; anything smaller keeps the planner's long runs below.  Same bits either way.
+  // AT_VARIANT_ISTFT_TILE = v forces the tiles at any batch with exactly v (>= 6) frames per wave and no balancing: the
+  // tests' handle on every tile geometry (short last tiles, waves of 0-2 frames) whatever the device.
+  const long long forced_n = variant(kVarIstftTile);
   if (hop == 256 && !gl_tprev && T >= 64 && variant(kVarIstftRuns) == 0) {
     int nw = 4, occ = 2;
     long long target = 175;                                  // frames per tile aimed at (same-box A/B of 125 ... 350: gpurun_out r05d)
@@ -1661,10 +1665,15 @@ int launch_istft1024_ola(const float2* X, const float* mag, const float* phase, 
       const long long tiles_per_clip = (T + target - 1) / target;
       const long long want = (T + tiles_per_clip - 1) / tiles_per_clip;      // frames per tile, balanced over the clip
       long long n = (want + 3 + nw - 1) / nw;                                // frames per wave; the last wave n - 3
+      if (forced_n > 0) {
+        tk = X ? istft1024_tile_kernel<IN_COMPLEX, 4, 2> : istft1024_tile_kernel<IN_POLAR, 4, 2>;
+        nw = 4;
+        n = forced_n;
+      }
       if (n < 6) n = 6;
       const long long tile_frames = nw * n - 3;
       const long long tpc = (T + tile_frames - 1) / tile_frames;
-      const long long resident = resident_waves(tk, 64 * nw, 0) / nw;
+      const long long resident = forced_n > 0 ? 0 : resident_waves(tk, 64 * nw, 0) / nw;
       if (B * tpc >= 2 * resident && B * tpc < (1LL << 31)) {
         p.slots_per_run = n;
         p.frames_per_block = tile_frames;
@@ -1678,6 +1687,7 @@ int launch_istft1024_ola(const float2* X, const float* mag, const float* phase, 
   const long long slots = resident_waves(kernel, 64 * WAVES_PER_BLOCK, 0);
   const long long spr = plan_units_per_run(B, nslots, slots, 8, 1024 / hop - 1);
   p.slots_per_run = spr;
+  if (const long long v = forced_units_per_run(nslots)) p.slots_per_run = v;
   if (const char* e = dev_env("ACIDS_ISTFT_SPR")) {   // dev builds: run length A/B
     const long long v = atoll(e);
     if (v >= 8 && v <= nslots) p.slots_per_run = v;

@@ -912,6 +912,7 @@ int launch_stft2048_fwd(const float* x, long long B, long long L, long long clip
     q.B = B; q.L = L; q.clip_stride = clip_stride; q.T = T;
     const long long slots = resident_waves(stft2048_run_fwd_kernel, 64 * W2KR, 0);
     q.frames_per_run = plan_units_per_run(B, T, slots, 8, 1);
+    if (const long long v = forced_units_per_run(T)) q.frames_per_run = v;
     q.runs_per_clip = (T + q.frames_per_run - 1) / q.frames_per_run;
     const long long waves = B * q.runs_per_clip;
     hipLaunchKernelGGL(stft2048_run_fwd_kernel, dim3((unsigned)((waves + W2KR - 1) / W2KR)), dim3(64 * W2KR), 0, stream, q);

@@ -245,7 +245,10 @@ __global__ __launch_bounds__(64 * W5R, 4) void stft512_run_fwd_kernel(P5Run p) {
   const float* clip = p.x + b * p.clip_stride;
   const v2f hh = {0.5f, 0.5f};
 
-  // this lane's frame of pair i: f = 2 i + par, starting at original sample 128 f - 256; slot j = samples 64 j .. + 63
+  // this lane's frame of pair i: f = 2 i + par, starting at original sample 128 f - 256; slot j = samples 64 j .. + 63.
+  // The missing frame f = T of a half pair (odd T) holds what the steady state carries into it from the pair before --
+  // its first four slots, zeros after -- also when the half pair starts a run: the two frames share one complex FFT, so
+  // the present frame's bits depend on its partner's samples, and must not depend on where the run starts.
   float2 raw[8];
   {
     const long long f = 2 * i0 + par;
@@ -254,7 +257,7 @@ __global__ __launch_bounds__(64 * W5R, 4) void stft512_run_fwd_kernel(P5Run p) {
     for (int j = 0; j < 8; ++j) {
       const long long i = s + 2 * (u + 32 * j);
       const bool in = (s + 64 * j >= 0) && (s + 64 * j + 64 <= L);
-      raw[j] = (f < T) ? load_pair5(clip, L, i, in) : make_float2(0.f, 0.f);
+      raw[j] = (f < T || (f == T && j < 4)) ? load_pair5(clip, L, i, in) : make_float2(0.f, 0.f);
     }
   }
 #pragma unroll
@@ -930,6 +933,7 @@ int launch_stft512_fwd(const float* x, long long B, long long L, long long clip_
     const long long slots = resident_waves(stft512_run_fwd_kernel, 64 * W5R, 0);
     const long long pairs = (T + 1) / 2;
     q.pairs_per_run = plan_units_per_run(B, pairs, slots, 8, 1);
+    if (const long long v = forced_units_per_run(pairs)) q.pairs_per_run = v;
     q.runs_per_clip = (pairs + q.pairs_per_run - 1) / q.pairs_per_run;
     const long long waves = B * q.runs_per_clip;
     hipLaunchKernelGGL(stft512_run_fwd_kernel, dim3((unsigned)((waves + W5R - 1) / W5R)), dim3(64 * W5R), 0, stream, q);

@@ -21,7 +21,11 @@ enum {
                             // 2: single-lane kernels; 3: cooperative kernels, realtime on the heap only; 4: realtime with the
                             // rank fast path but without the wavefront-parallel scan path in front of it
   kVarIstftRuns = 5,        // 1: the n_fft-1024 inverse always as one long run per wave (no workgroup tiles with LDS hand-over)
-  kVarCount = 6
+  // Plan variants: same kernel, a different cut of the clips.  0 leaves the plan to the launcher (device-dependent).
+  kVarRunLength = 6,        // v > 0: runs of v units (clamped to [8, units]) for every launcher that plans per-wave runs
+  kVarIstftTile = 7,        // v > 0: the n_fft-1024 inverse on workgroup tiles whatever the batch, v (>= 6) frames per wave
+  kVarCount = 8,
+  kVarFirstPlan = kVarRunLength
 };
 
 int variant(int which);     // capi.hip

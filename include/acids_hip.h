@@ -45,7 +45,8 @@ const char *at_error_string(int code);
  * (the A/B switches of tools/ab*.sh exist only in -DAT_DEV_SWITCHES builds).  Where two kernels compute the same
  * result -- a form specialised for the headline shapes and the generic one -- this process-wide table lets a caller force
  * the generic one; the parity tests use it to compare the two.  No reference counterpart (the reference has one
- * implementation of everything).  value: 0 = default; returns AT_EINVAL for an unknown variant or value. */
+ * implementation of everything).  value: 0 = default (0..4 for the kernel variants, 0..65535 for the plan variants);
+ * returns AT_EINVAL for an unknown variant or value. */
 #define AT_VARIANT_EPILOGUE 0          /* 1: generic mel epilogue / projection even for the 128-mel headline bank */
 #define AT_VARIANT_FRAME_KERNELS 1     /* 1: frame-at-a-time forward at n_fft 512 / 2048 / 4096 (no sliding window) */
 #define AT_VARIANT_SMALL_PROJECTION 2  /* 1: row kernel instead of the matrix-core form of the K <= 128 projection */
@@ -55,6 +56,11 @@ const char *at_error_string(int code);
                                         * wavefront-parallel scan path (round 5) that is tried first by default */
 #define AT_VARIANT_ISTFT_RUNS 5        /* 1: n_fft-1024 inverse as one long run per wave even for full batches (no workgroup
                                         * tiles with the overlap state handed over through LDS) */
+/* Plan variants (round 6; table entries, no signature changed: ABI still 4).  value 0..65535, 0 = the launcher's plan. */
+#define AT_VARIANT_RUN_LENGTH 6        /* v: runs of v units clamped to [8, units] (frames; frame pairs at n_fft 512; hop slots
+                                        * for the long-run n_fft-1024 inverse) for every launcher that plans per-wave runs */
+#define AT_VARIANT_ISTFT_TILE 7        /* v: hop-256 non-Griffin-Lim n_fft-1024 inverse (T >= 64) on workgroup tiles at any
+                                        * batch, max(v, 6) frames per wave, no balancing; AT_VARIANT_ISTFT_RUNS = 1 wins */
 int at_set_variant(int which, int value);
 int at_get_variant(int which);
 

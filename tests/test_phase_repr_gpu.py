@@ -161,7 +161,9 @@ def test_against_oracle_random_shapes(dev):
         ops.phase_scan(torch.zeros(5, dtype=torch.complex64, device=dev), "unwrap")
 
 
-@pytest.mark.parametrize("shape", [(64, 19, 513), (70, 8, 257), (65, 1, 513), (64, 17, 1025), (64, 9, 2049), (66, 23, 300)])
+# (64, 24, 513), (64, 26, 2049): even T >= 10, the blocked two-chain loop of the clip-per-block fint_central
+@pytest.mark.parametrize("shape", [(64, 19, 513), (70, 8, 257), (65, 1, 513), (64, 17, 1025), (64, 9, 2049), (66, 23, 300),
+                                   (64, 24, 513), (64, 26, 2049)])
 def test_clip_per_block_scans_equal_flat_layout_and_oracle(dev, shape):
     """>= 64 clips with rows of >= 256 bins that are not whole 64-byte segments take the one-block-per-clip layout
     (2 or 4 columns per thread, wavefronts in lockstep): bit-identical to the flattened-column layout
@@ -332,7 +334,8 @@ def test_cartesian_and_polarif_work_inside_the_stacked_tensor(dev, shape):
     assert p2._in_place_parts(F, False) is None
 
 
-@pytest.mark.parametrize("shape", [(64, 19, 513), (70, 8, 257), (65, 1, 513), (64, 17, 1025), (66, 23, 300), (64, 3, 2049)])
+@pytest.mark.parametrize("shape", [(64, 19, 513), (70, 8, 257), (65, 1, 513), (64, 17, 1025), (66, 23, 300), (64, 3, 2049),
+                                   (64, 24, 513), (64, 26, 2049)])
 def test_polarif_forward_one_pass_equals_the_two_kernels(dev, shape):
     """>= 64 clips of 256..4096 bins: PolarIF.forward is ONE kernel (at_polarif_forward: the clip-per-block IF scan with
     the banded magnitude of the same rows summed from LDS).  Both halves bit-identical to the stand-alone kernels

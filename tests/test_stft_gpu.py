@@ -550,9 +550,12 @@ def test_float64_inputs_raise_instead_of_being_narrowed(dev):
 def test_tiled_inverse_is_the_long_run_inverse_bit_for_bit(dev):
     """Round 5: full batches take istft1024_tile_kernel (a workgroup owns a tile of consecutive frames, the overlap state
     crosses the cuts between its waves through LDS, additions in frame order); `variant("istft_runs", 1)` forces the
-    long-run kernel.  Every frame count from 64 to 300 -- every remainder of the tile and of a wave's share, clip ends
-    inside the first, middle and last wave of a tile, last waves holding 0, 1, 2 frames -- complex and polar input, STFT
-    and DGT windows: identical bits, and the long-run kernel is the one the goldens and the oracle pin."""
+    long-run kernel.  What this covers depends on the device: the launcher tiles only when B x tiles per clip is at
+    least twice the workgroups the chip holds (1024 on a 256-CU part).  There, B = 600 tiles T = 176..300 (two balanced
+    tiles per clip; polar: 233..235) and both sides run the long-run kernel below that, so the tile kernel is held to
+    the long-run one on balanced tiles only, complex and polar input, STFT and DGT windows; the oracle pins the tiled
+    kernel at the bench's frame count.  Short last tiles, waves of 0-2 frames and clips ending in waves 0-2 are forced
+    through `variant("istft_tile", v)` in test_run_plans_gpu.py."""
     from acids_transforms_amd import ops
     g = torch.Generator(device=dev).manual_seed(77)
     st = A.STFT().to(dev)
