@@ -1,0 +1,111 @@
+"""Autograd for STFT / DGT and Magnitude: torch.autograd.Functions whose backward passes are the HIP adjoints of
+autograd.hip (through ops.stft_backward / ops.magnitude_backward).
+
+The reference is plain torch, so its STFT, DGT and Magnitude (and their composition) sit inside a training loss.  Here
+the forward kernels write into fresh tensors through ctypes, which cuts the graph; the modules therefore route a call
+through these Functions when -- and only when -- grad mode is on and the input requires grad.  Every other call runs
+the plain forward, bit for bit the same kernels.  The forward values of the autograd route are those same kernels too.
+
+All three backward passes are first-order only (@once_differentiable): create_graph=True raises.
+"""
+import torch
+from torch.autograd.function import once_differentiable
+
+from . import ops
+
+__all__ = ["wants_grad", "StftFunction", "MagnitudeFunction", "StftMagnitudeFunction"]
+
+
+def wants_grad(x: torch.Tensor) -> bool:
+    return torch.is_grad_enabled() and x.requires_grad
+
+
+class StftFunction(torch.autograd.Function):
+    """x (B, L) float32 -> (X (B, T, F) complex64, phase (B, T, F) float32 or an empty tensor).
+    Saves nothing but shapes (and the module's window buffer, which is not part of the graph)."""
+
+    @staticmethod
+    def forward(ctx, x, window, n_fft, hop, want_phase):
+        ctx.window, ctx.n_fft, ctx.hop, ctx.L = window, n_fft, hop, x.shape[-1]
+        if want_phase:
+            X, phase = ops.stft_forward(x, window, n_fft, hop, center=True, want_phase=True)
+        else:
+            X, phase = ops.stft_forward(x, window, n_fft, hop, center=True), x.new_empty(0)
+        ctx.mark_non_differentiable(phase)
+        return X, phase
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, G, _gphase):
+        if G is None:
+            return None, None, None, None, None
+        return ops.stft_backward(G, ctx.window, ctx.n_fft, ctx.hop, ctx.L), None, None, None, None
+
+
+def _bank_tables(module, device):
+    """(forward bank, transposed bank) by-column tables of a Magnitude's mel_bank on `device`, or (None, None) when
+    mel=False; cached per bank version."""
+    if not module.mel:
+        return None, None
+    from .utils.banded import bank_columns
+    bank = module.mel_bank
+    key = (bank.data_ptr(), bank._version, str(device))
+    hit = module.__dict__.get("_grad_tables")
+    if hit is None or hit[0] != key:
+        to = lambda arrs: tuple(torch.from_numpy(a).to(device) for a in arrs)   # noqa: E731
+        hit = (key, to(bank_columns(bank)), to(bank_columns(bank.transpose(-2, -1))))
+        module.__dict__["_grad_tables"] = hit
+    return hit[1], hit[2]
+
+
+def _magnitude_grad(module, x, dF, dx_accum=None):
+    fwd, inv = _bank_tables(module, x.device)
+    _, sc = module._affine()
+    return ops.magnitude_backward(x, dF, fwd, inv, module.contrast_mode, sc, module._eps,
+                                  col_off=0 if module.keep_nyquist else 1, dx_accum=dx_accum)
+
+
+class MagnitudeFunction(torch.autograd.Function):
+    """Magnitude.forward with its backward.  Saves its input (the backward recomputes M from it)."""
+
+    @staticmethod
+    def forward(ctx, x, module):
+        ctx.module = module
+        ctx.save_for_backward(x)
+        return module._forward_plain(x)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dF):
+        (x,) = ctx.saved_tensors
+        dx = _magnitude_grad(ctx.module, x, dF.contiguous())
+        return dx.reshape(x.shape), None
+
+
+class StftMagnitudeFunction(torch.autograd.Function):
+    """The fused n_fft = 1024 STFT -> Magnitude forward (ops.stft_mel_forward, spectrum kept) with its backward: the
+    Magnitude backward on the saved spectrum (plus the spectrum's own gradient, when the caller used it), then the
+    STFT adjoint.  x (B, L) -> (X (B, T, 513) complex64, features (B, T, N), phase or an empty tensor)."""
+
+    @staticmethod
+    def forward(ctx, x, stage, module, want_phase):
+        off, sc = module._affine()
+        X, phase, feat = ops.stft_mel_forward(x, stage.window[:1024], module._banded(), module.contrast_mode, off, sc,
+                                              module._eps, want_phase=want_phase, hop=stage._hop)
+        ctx.stage, ctx.module, ctx.L = stage, module, x.shape[-1]
+        ctx.save_for_backward(X)
+        phase = phase if phase is not None else x.new_empty(0)
+        ctx.mark_non_differentiable(phase)
+        ctx.set_materialize_grads(False)
+        return X, feat, phase
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gX, gfeat, _gphase):
+        (X,) = ctx.saved_tensors
+        if gfeat is not None:
+            gX = _magnitude_grad(ctx.module, X, gfeat.contiguous(), dx_accum=gX)
+        if gX is None:
+            return None, None, None, None
+        stage = ctx.stage
+        return ops.stft_backward(gX, stage.window[:stage._n_fft], stage._n_fft, stage._hop, ctx.L), None, None, None

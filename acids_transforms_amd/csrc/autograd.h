@@ -1,0 +1,31 @@
+// autograd.h -- launchers of autograd.hip (the STFT adjoint and the Magnitude backward), for capi.hip.
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace at_hip {
+
+struct MagBwdParams {
+  const void* A;          // rows x K: complex64 (a_kind 0) or float32 (a_kind 3)
+  int a_kind;
+  long long rows;
+  int K, N, col_off;      // dF: rows x (N - col_off)
+  const float* dF;
+  const int *f_start, *f_len, *f_off;   // forward bank by column (N columns); null: mel=False
+  const float* f_w;
+  int f_nnz;                            // weights of the forward bank
+  const int *t_start, *t_len, *t_off;   // transposed bank by column (K columns)
+  const float* t_w;
+  int t_nnz;
+  int contrast;
+  const float* scale;     // null: no Normalize
+  float eps;
+  const void* dX_in;      // null, or rows x K of the same type: added to the result
+  void* dX;
+};
+
+int launch_adj_window(const float* w, int n_fft, float scale, float* out, hipStream_t stream);
+int launch_adj_ola_fold(const float* frames, const float2* G, const float* window, float* dx, long long B, long long T,
+                        long long L, int n_fft, int hop, hipStream_t stream);
+int launch_magnitude_backward(const MagBwdParams& p, hipStream_t stream);
+
+}  // namespace at_hip

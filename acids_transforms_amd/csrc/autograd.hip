@@ -1,0 +1,346 @@
+// autograd.hip -- the backward passes of STFT / DGT (the adjoint of the centred, reflect-padded STFT) and of
+// Magnitude (|.|, mel projection, contrast, Normalize), so that both can sit inside a training loss.
+//
+// Gradient convention (torch's, for a complex tensor): G = dL/dRe + i dL/dIm.
+//
+// STFT adjoint.  Forward, with P = n_fft // 2 and N = n_fft:
+//     p = reflect_pad(x, P),   X[t, k] = sum_m w[m] p[t h + m] e^{-2 pi i k m / N},   k = 0 .. N/2
+// (reference stft.py:98-104, torch.stft(center=True, pad_mode="reflect")).  Its adjoint:
+//   * per frame   q[t, m] = w[m] Re sum_{k=0}^{N/2} G[t, k] e^{+2 pi i k m / N}   -- each bin counts ONCE.
+//     That is N irfft(G') with the interior bins of G halved (even N: 1 .. N/2-1; odd N: 1 .. N/2), the imaginary parts
+//     of DC and Nyquist dropped.  It is computed as irfft(G) times the window scaled by N/2 (the existing irfft kernels,
+//     which already drop those imaginary parts), plus the halves of DC and Nyquist they miss:
+//         q[t, m] = (N/2) w[m] irfft(G)[m] + w[m] (Re G[t,0] / 2 + Re G[t,N/2] (-1)^m / 2)   (Nyquist: even N only)
+//   * overlap-add WITHOUT the ISTFT's envelope division:  dp[j] = sum_t q[t, j - t h]   (t ascending);
+//   * reflect fold:  dx[i] = dp[i + P]  + dp[P - i]        for i in [1, P]
+//                                       + dp[2L + P - 2 - i] for i in [L - P - 1, L - 2].
+// Every output sample is summed by one thread in that fixed order (main term, left fold, right fold; frames ascending), so
+// a clip's gradient bits do not depend on the batch it rides in or on how the clips are cut into chunks.
+//
+// Magnitude backward.  a = |X| (or |x| for real input), M = a @ mel_bank (M = a with mel=False),
+// f = (c(M) - offset) / scale (reference spectral_repr.py:215-226):
+//     dM    = dF / scale * c'(M)
+//     c'    = 1 / (1 + M)                                      log1p
+//           = 1 / M           where M >= eps, else 0           log   (torch.clamp's backward mask)
+//           = 1 / (M ln 10)   where M >= eps, else 0           log10
+//           = 1                                                none
+//     dA[k] = sum_j mel_bank[k, j] dM[j]
+//     dX    = dA X / |X|   (0 where X == 0: torch's sgn);   real input: dx = dA sign(x)
+// M is recomputed from X (nothing is stored by the forward).  Both banks travel as bands (CSR by column): for column j of
+// a (K x N) bank, start[j], len[j], off[j] and len[j] weights at w[off[j] ..]; the transposed bank is the same tables of
+// mel_bank^T (513 "filters" of a few mels each at n_fft 1024).  keep_nyquist=False: dF has N - col_off columns, column c
+// belongs to M column c + col_off, and the dropped columns get zero gradient.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "autograd.h"
+
+namespace at_hip {
+
+// ---- STFT adjoint -----------------------------------------------------------------------------------------------------
+
+__global__ void adj_window_kernel(const float* w, int n, float s, float* out) {
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) out[i] = w[i] * s;
+}
+
+struct AdjOlaParams {
+  const float* frames;   // (B, T, N): (N/2) w[m] irfft(G[t])[m]
+  const float2* G;       // (B, T, N/2 + 1)
+  const float* window;   // N floats, unscaled
+  float* dx;             // (B, L)
+  long long B, T, L;
+  int n_fft, hop;
+};
+
+// dp[j] of clip b: the frames that cover padded sample j, oldest first
+__device__ __forceinline__ float adj_dp(const AdjOlaParams& p, long long b, long long j) {
+  const int N = p.n_fft, h = p.hop, F = N / 2 + 1;
+  long long t_hi = j / h;
+  if (t_hi > p.T - 1) t_hi = p.T - 1;
+  const long long t_lo = (j - N + 1 <= 0) ? 0 : (j - N + h) / h;   // ceil((j - N + 1) / h)
+  float acc = 0.f;
+  for (long long t = t_lo; t <= t_hi; ++t) {
+    const int o = (int)(j - t * h);                                   // in [0, N) by the bounds above
+    const long long f = b * p.T + t;
+    const float2* g = p.G + f * F;
+    float edge = 0.5f * g[0].x;
+    if (!(N & 1)) edge += (o & 1) ? -0.5f * g[N / 2].x : 0.5f * g[N / 2].x;
+    acc += fmaf(p.window[o], edge, p.frames[f * N + o]);
+  }
+  return acc;
+}
+
+// four consecutive padded samples j .. j+3 (j, hop and n_fft multiples of 4): they see the same frames, and every lane
+// sums in the order of adj_dp, so the bits are those of four adj_dp calls
+__device__ __forceinline__ float4 adj_dp4(const AdjOlaParams& p, long long b, long long j) {
+  const int N = p.n_fft, h = p.hop, F = N / 2 + 1;
+  long long t_hi = j / h;
+  if (t_hi > p.T - 1) t_hi = p.T - 1;
+  const long long t_lo = (j - N + 1 <= 0) ? 0 : (j - N + h) / h;
+  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (long long t = t_lo; t <= t_hi; ++t) {
+    const int o = (int)(j - t * h);
+    const long long f = b * p.T + t;
+    const float2* g = p.G + f * F;
+    const float e0 = 0.5f * g[0].x, en = 0.5f * g[N / 2].x;
+    const float ep = e0 + en, em = e0 + -en;        // o even / odd (o is a multiple of 4)
+    const float4 fr = *reinterpret_cast<const float4*>(p.frames + f * N + o);
+    const float4 w = *reinterpret_cast<const float4*>(p.window + o);
+    acc.x += fmaf(w.x, ep, fr.x);
+    acc.y += fmaf(w.y, em, fr.y);
+    acc.z += fmaf(w.z, ep, fr.z);
+    acc.w += fmaf(w.w, em, fr.w);
+  }
+  return acc;
+}
+
+// grid: (samples / 1024 rounded up, clips); thread: samples s0 .. s0+3 of clip blockIdx.y (+ multiples of gridDim.y)
+__global__ void adj_ola_fold_kernel(AdjOlaParams p, int vec4) {
+  const long long P = p.n_fft / 2, L = p.L;
+  const long long s0 = 4 * ((long long)blockIdx.x * blockDim.x + threadIdx.x);
+  if (s0 >= L) return;
+  for (long long b = blockIdx.y; b < p.B; b += gridDim.y) {
+    float* dst = p.dx + b * L;
+    if (vec4 && s0 > P && s0 + 3 < L - P - 1) {       // no fold touches these four samples
+      const float4 v = adj_dp4(p, b, s0 + P);
+      dst[s0] = v.x;
+      dst[s0 + 1] = v.y;
+      dst[s0 + 2] = v.z;
+      dst[s0 + 3] = v.w;
+      continue;
+    }
+    for (long long s = s0; s < s0 + 4 && s < L; ++s) {
+      float v = adj_dp(p, b, s + P);
+      if (s >= 1 && s <= P) v += adj_dp(p, b, P - s);
+      if (s >= L - P - 1 && s <= L - 2) v += adj_dp(p, b, 2 * L + P - 2 - s);
+      dst[s] = v;
+    }
+  }
+}
+
+int launch_adj_window(const float* w, int n_fft, float scale, float* out, hipStream_t stream) {
+  const int blocks = (n_fft + 255) / 256;
+  hipLaunchKernelGGL(adj_window_kernel, dim3(blocks), dim3(256), 0, stream, w, n_fft, scale, out);
+  return hipGetLastError() == hipSuccess ? 0 : -5;
+}
+
+int launch_adj_ola_fold(const float* frames, const float2* G, const float* window, float* dx, long long B, long long T,
+                        long long L, int n_fft, int hop, hipStream_t stream) {
+  if (B <= 0 || L <= 0) return 0;
+  AdjOlaParams p = {frames, G, window, dx, B, T, L, n_fft, hop};
+  const int vec4 = (hop % 4 == 0) && (n_fft % 8 == 0) && (((uintptr_t)frames) & 15) == 0 && (((uintptr_t)window) & 15) == 0;
+  const long long bx = (L + 1023) / 1024;
+  hipLaunchKernelGGL(adj_ola_fold_kernel, dim3((unsigned)bx, (unsigned)(B < 65535 ? B : 65535)), dim3(256), 0, stream, p,
+                     vec4);
+  return hipGetLastError() == hipSuccess ? 0 : -5;
+}
+
+// ---- Magnitude backward -----------------------------------------------------------------------------------------------
+
+__device__ __forceinline__ float mag_cprime(float M, int contrast, float eps) {
+  switch (contrast) {
+    case 1: return 1.0f / (1.0f + M);
+    case 2: return M >= eps ? 1.0f / M : 0.0f;
+    case 3: return M >= eps ? 1.0f / (M * 2.30258509299404568402f) : 0.0f;
+    default: return 1.0f;
+  }
+}
+
+// dA at element e of the input -> the input's gradient (sgn of the input x, loaded by the caller; plus the optional
+// incoming gradient).  Real input: x.y == 0.
+__device__ __forceinline__ void mag_put_x(const MagBwdParams& p, long long e, float dA, float2 x) {
+  if (p.a_kind == 0) {
+    const float a = __builtin_amdgcn_sqrtf(fmaf(x.x, x.x, x.y * x.y));
+    float2 g = make_float2(0.f, 0.f);
+    if (a > 0.f) {
+      const float r = dA / a;
+      g = make_float2(r * x.x, r * x.y);
+    }
+    if (p.dX_in) {
+      const float2 d = reinterpret_cast<const float2*>(p.dX_in)[e];
+      g.x += d.x;
+      g.y += d.y;
+    }
+    reinterpret_cast<float2*>(p.dX)[e] = g;
+  } else {
+    float g = x.x > 0.f ? dA : (x.x < 0.f ? -dA : 0.f);
+    if (p.dX_in) g += reinterpret_cast<const float*>(p.dX_in)[e];
+    reinterpret_cast<float*>(p.dX)[e] = g;
+  }
+}
+
+__device__ __forceinline__ void mag_put(const MagBwdParams& p, long long e, float dA) {
+  const float2 x = p.a_kind == 0 ? reinterpret_cast<const float2*>(p.A)[e]
+                                 : make_float2(reinterpret_cast<const float*>(p.A)[e], 0.f);
+  mag_put_x(p, e, dA, x);
+}
+
+__device__ __forceinline__ float mag_abs(const MagBwdParams& p, long long e) {
+  if (p.a_kind == 0) {
+    const float2 x = reinterpret_cast<const float2*>(p.A)[e];
+    return __builtin_amdgcn_sqrtf(fmaf(x.x, x.x, x.y * x.y));
+  }
+  return fabsf(reinterpret_cast<const float*>(p.A)[e]);
+}
+
+__device__ __forceinline__ float mag_dm(const MagBwdParams& p, long long row, int j, float M) {
+  const int n_out = p.N - p.col_off;
+  if (j < p.col_off) return 0.f;
+  const float g = p.dF[row * n_out + (j - p.col_off)];
+  const float gs = p.scale ? g / p.scale[0] : g;
+  return gs * mag_cprime(M, p.contrast, p.eps);
+}
+
+// mel=False: one thread per element
+__global__ void mag_bwd_pointwise_kernel(MagBwdParams p) {
+  const long long total = p.rows * p.K;
+  for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total;
+       e += (long long)gridDim.x * blockDim.x) {
+    const long long row = e / p.K;
+    const int k = (int)(e - row * p.K);
+    mag_put(p, e, mag_dm(p, row, k, mag_abs(p, e)));
+  }
+}
+
+// banks: one wave per row, |X| and dM of the row in the wave's LDS slice; the loop over row groups is workgroup-uniform
+// so that every wave reaches the barriers.  TAB_LDS: both banks' tables are staged in LDS once per workgroup (the walks'
+// loads are serially dependent: from global memory each one would cost a round trip to L2).
+template <bool TAB_LDS, int KIT>
+__global__ void mag_bwd_banded_kernel(MagBwdParams p, int k_pad, int n_pad, int f_nnz, int t_nnz, int tab_floats) {
+  extern __shared__ float mb_lds[];
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int wpb = blockDim.x >> 6;
+  const int K = p.K, N = p.N;
+  const int *fs = p.f_start, *fl = p.f_len, *fo = p.f_off, *ts = p.t_start, *tl = p.t_len, *to = p.t_off;
+  const float *fw = p.f_w, *tw = p.t_w;
+  if (TAB_LDS) {
+    int* q = reinterpret_cast<int*>(mb_lds);
+    int *fs_l = q, *fl_l = q + N, *fo_l = q + 2 * N, *ts_l = q + 3 * N, *tl_l = ts_l + K, *to_l = ts_l + 2 * K;
+    float* fw_l = reinterpret_cast<float*>(ts_l + 3 * K);
+    float* tw_l = fw_l + f_nnz;
+    for (int i = threadIdx.x; i < N; i += blockDim.x) {
+      fs_l[i] = p.f_start[i];
+      fl_l[i] = p.f_len[i];
+      fo_l[i] = p.f_off[i];
+    }
+    for (int i = threadIdx.x; i < K; i += blockDim.x) {
+      ts_l[i] = p.t_start[i];
+      tl_l[i] = p.t_len[i];
+      to_l[i] = p.t_off[i];
+    }
+    for (int i = threadIdx.x; i < f_nnz; i += blockDim.x) fw_l[i] = p.f_w[i];
+    for (int i = threadIdx.x; i < t_nnz; i += blockDim.x) tw_l[i] = p.t_w[i];
+    fs = fs_l; fl = fl_l; fo = fo_l; ts = ts_l; tl = tl_l; to = to_l; fw = fw_l; tw = tw_l;
+  }
+  float* a = mb_lds + (TAB_LDS ? tab_floats : 0) + wave * (k_pad + n_pad);
+  float* dm = a + k_pad;
+  for (long long r0 = (long long)blockIdx.x * wpb; r0 < p.rows; r0 += (long long)gridDim.x * wpb) {
+    const long long row = r0 + wave;
+    const bool live = row < p.rows;
+    // KIT > 0: the row's input stays in registers from the first phase to the last (KIT loads in flight at once)
+    float2 xv[KIT > 0 ? KIT : 1];
+    if (live) {
+      if (KIT > 0) {
+#pragma unroll
+        for (int q = 0; q < KIT; ++q) {
+          const int k = lane + 64 * q;
+          if (k < K) {
+            const long long e = row * K + k;
+            xv[q] = p.a_kind == 0 ? reinterpret_cast<const float2*>(p.A)[e]
+                                  : make_float2(reinterpret_cast<const float*>(p.A)[e], 0.f);
+          }
+        }
+#pragma unroll
+        for (int q = 0; q < KIT; ++q) {
+          const int k = lane + 64 * q;
+          if (k < K) a[k] = __builtin_amdgcn_sqrtf(fmaf(xv[q].x, xv[q].x, xv[q].y * xv[q].y));
+        }
+      } else {
+        for (int k = lane; k < K; k += 64) a[k] = mag_abs(p, row * K + k);
+      }
+    }
+    __syncthreads();
+    if (live)
+      for (int j = lane; j < N; j += 64) {
+        const int s = fs[j], n = fl[j];
+        const float* w = fw + fo[j];
+        float M = 0.f;
+#pragma unroll 4
+        for (int i = 0; i < n; ++i) M = fmaf(w[i], a[s + i], M);
+        dm[j] = mag_dm(p, row, j, M);
+      }
+    __syncthreads();
+    if (live) {
+      auto walk = [&](int k) {
+        const int s = ts[k], n = tl[k];
+        const float* w = tw + to[k];
+        float dA = 0.f;
+#pragma unroll 4
+        for (int i = 0; i < n; ++i) dA = fmaf(w[i], dm[s + i], dA);
+        return dA;
+      };
+      if (KIT > 0) {
+#pragma unroll
+        for (int q = 0; q < KIT; ++q) {
+          const int k = lane + 64 * q;
+          if (k < K) mag_put_x(p, row * K + k, walk(k), xv[q]);
+        }
+      } else {
+        for (int k = lane; k < K; k += 64) mag_put(p, row * K + k, walk(k));
+      }
+    }
+    __syncthreads();
+  }
+}
+
+template <bool TAB_LDS, int KIT>
+static int launch_mag_banded(const MagBwdParams& p, int wpb, size_t lds, int k_pad, int n_pad, int tab_floats,
+                             hipStream_t stream) {
+  const void* fn = (const void*)mag_bwd_banded_kernel<TAB_LDS, KIT>;
+  if (lds > 64 * 1024 &&
+      hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+    (void)hipGetLastError();
+    return -5;
+  }
+  // as many workgroups as the chip holds at once (the tables are staged once per workgroup), at most one per row group
+  int per_cu = 0, cus = 0, dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess ||
+      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64 * wpb, lds) != hipSuccess) {
+    (void)hipGetLastError();
+    return -5;
+  }
+  long long blocks = (long long)(per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 1);
+  const long long groups = (p.rows + wpb - 1) / wpb;
+  if (blocks > groups) blocks = groups;
+  hipLaunchKernelGGL((mag_bwd_banded_kernel<TAB_LDS, KIT>), dim3((unsigned)blocks), dim3(64 * wpb), lds, stream, p, k_pad,
+                     n_pad, p.f_nnz, p.t_nnz, tab_floats);
+  return hipGetLastError() == hipSuccess ? 0 : -5;
+}
+
+int launch_magnitude_backward(const MagBwdParams& p, hipStream_t stream) {
+  if (p.rows == 0) return 0;
+  if (!p.f_w) {
+    long long blocks = (p.rows * p.K + 255) / 256;
+    if (blocks > 65536) blocks = 65536;
+    hipLaunchKernelGGL(mag_bwd_pointwise_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, p);
+    return hipGetLastError() == hipSuccess ? 0 : -5;
+  }
+  const int k_pad = (p.K + 63) / 64 * 64, n_pad = (p.N + 63) / 64 * 64;
+  const size_t per_wave = sizeof(float) * (size_t)(k_pad + n_pad);
+  const size_t budget = 160 * 1024;
+  // tables: start / len / off of both banks and their weights, padded to a float4 boundary
+  const long long tab = (3LL * (p.N + p.K) + p.f_nnz + p.t_nnz + 3) / 4 * 4;
+  if (tab * sizeof(float) + 4 * per_wave <= budget) {
+    const size_t lds = tab * sizeof(float) + 4 * per_wave;
+    if (p.K <= 9 * 64) return launch_mag_banded<true, 9>(p, 4, lds, k_pad, n_pad, (int)tab, stream);   // n_fft <= 1024
+    return launch_mag_banded<true, 0>(p, 4, lds, k_pad, n_pad, (int)tab, stream);
+  }
+  if (per_wave > budget) return -2;
+  int wpb = (int)(budget / per_wave);
+  if (wpb > 4) wpb = 4;
+  return launch_mag_banded<false, 0>(p, wpb, per_wave * wpb, k_pad, n_pad, 0, stream);
+}
+
+}  // namespace at_hip

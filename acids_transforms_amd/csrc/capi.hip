@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "../../include/acids_hip.h"
+#include "autograd.h"
 #include "band_bank.h"
 #include "fft512.h"
 
@@ -477,6 +478,66 @@ int at_irfft_frames(const float* X_complex, const float* mag, const float* phase
   if (fft_mixed(n_fft))
     return launch_irfft_mixed((const float2*)X_complex, mag, phase, nframes, n_fft, inv_window, frames, s);
   return launch_irfft_generic((const float2*)X_complex, mag, phase, nframes, n_fft, inv_window, frames, s);
+}
+
+
+// ---- backward passes (autograd.hip) ----------------------------------------------------------------------------------
+
+// clips per chunk of the STFT adjoint: its irFFT frames (clips x T x n_fft floats) stay within 1 GiB of workspace
+static int64_t adj_chunk_clips(int64_t B, int64_t T, int n_fft) {
+  const int64_t per_clip = T * (int64_t)n_fft;
+  int64_t c = per_clip > 0 ? (int64_t(1) << 28) / per_clip : B;
+  if (c < 1) c = 1;
+  return c < B ? c : B;
+}
+
+static size_t adj_window_bytes(int n_fft) { return ((size_t)n_fft * sizeof(float) + 255) / 256 * 256; }
+
+size_t at_stft_backward_workspace_bytes(int64_t B, int64_t T, int n_fft, int hop) {
+  if (B <= 0 || T <= 0 || n_fft <= 0 || hop <= 0) return 0;
+  return adj_window_bytes(n_fft) + (size_t)adj_chunk_clips(B, T, n_fft) * (size_t)T * (size_t)n_fft * sizeof(float);
+}
+
+int at_stft_backward(const float* G_complex, int64_t B, int64_t T, int64_t L, int n_fft, int hop, const float* window,
+                     float* dx, void* workspace, size_t workspace_bytes, void* stream) {
+  if (B < 0 || T <= 0 || L <= 0 || hop <= 0 || n_fft <= 0) return AT_EINVAL;
+  if (L <= n_fft / 2 || T != 1 + (L - (n_fft & 1)) / hop) return AT_EINVAL;   // the forward's frames of a reflect-padded clip
+  if (!fft_size_ok(n_fft)) return AT_EUNSUPPORTED;
+  if (B == 0) return AT_OK;
+  if (!G_complex || !window || !dx || !workspace) return AT_EINVAL;
+  if ((((uintptr_t)workspace) & 255) || workspace_bytes < at_stft_backward_workspace_bytes(B, T, n_fft, hop))
+    return AT_EWORKSPACE;
+  hipStream_t s = (hipStream_t)stream;
+  float* wscaled = (float*)workspace;
+  float* frames = (float*)((char*)workspace + adj_window_bytes(n_fft));
+  int rc = launch_adj_window(window, n_fft, 0.5f * (float)n_fft, wscaled, s);
+  if (rc) return rc;
+  const int64_t F = n_fft / 2 + 1, chunk = adj_chunk_clips(B, T, n_fft);
+  for (int64_t b0 = 0; b0 < B; b0 += chunk) {
+    const int64_t nb = (B - b0 < chunk) ? B - b0 : chunk;
+    const float* G = G_complex + 2 * b0 * T * F;
+    rc = at_irfft_frames(G, nullptr, nullptr, nb * T, n_fft, wscaled, frames, stream);
+    if (rc) return rc;
+    rc = launch_adj_ola_fold(frames, (const float2*)G, window, dx + b0 * L, nb, T, L, n_fft, hop, s);
+    if (rc) return rc;
+  }
+  return AT_OK;
+}
+
+int at_magnitude_backward(const void* A, int a_kind, int64_t rows, int K, const float* dF, int N, int col_off,
+                          const int* f_start, const int* f_len, const int* f_off, const float* f_w, int f_nnz,
+                          const int* t_start, const int* t_len, const int* t_off, const float* t_w, int t_nnz, int contrast, const float* scale,
+                          float eps, const void* dX_accum, void* dX, void* stream) {
+  if (rows < 0 || K <= 0 || N <= 0 || col_off < 0 || col_off >= N) return AT_EINVAL;
+  if ((a_kind != 0 && a_kind != 3) || contrast < 0 || contrast > 3) return AT_EINVAL;
+  if (rows == 0) return AT_OK;
+  if (!A || !dF || !dX) return AT_EINVAL;
+  const bool banked = f_w != nullptr;
+  if (banked && !(f_start && f_len && f_off && t_start && t_len && t_off && t_w && f_nnz > 0 && t_nnz > 0)) return AT_EINVAL;
+  if (!banked && N != K) return AT_EINVAL;
+  at_hip::MagBwdParams p = {A, a_kind, rows, K, N, col_off, dF, f_start, f_len, f_off, f_w, f_nnz, t_start, t_len, t_off, t_w, t_nnz,
+                            contrast, scale, eps, dX_accum, dX};
+  return at_hip::launch_magnitude_backward(p, (hipStream_t)stream);
 }
 
 }  // extern "C"

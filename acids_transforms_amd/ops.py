@@ -606,6 +606,50 @@ def stft_mel_forward(x, window, band, contrast=None, offset=None, scale=None, ep
 
 
 # ----------------------------------------------------------------------------------------------
+# backward passes (autograd.hip; the autograd.Functions of autograd.py call these)
+# ----------------------------------------------------------------------------------------------
+def stft_backward(G, window, n_fft, hop, L):
+    """Adjoint of stft_forward(center=True): G (B, T, F) complex64, the gradient of the spectrum -> dx (B, L) float32."""
+    require_device(G, window)
+    G = _c64(G)
+    G = G if G.is_contiguous() else G.contiguous()
+    B, T, F = G.shape
+    assert F == n_fft // 2 + 1, "last dim must be n_fft/2+1"
+    dx = torch.empty((B, L), dtype=torch.float32, device=G.device)
+    wsb = lib().at_stft_backward_workspace_bytes(B, T, n_fft, hop)
+    ws = _workspace(wsb, G.device)
+    check(lib().at_stft_backward(ptr(G), B, T, L, n_fft, hop, ptr(window), ptr(dx), ptr(ws), wsb, stream_ptr()),
+          "at_stft_backward")
+    return dx
+
+
+def magnitude_backward(x, dF, bank_cols=None, bank_t_cols=None, contrast=None, scale=None, eps=1.1920929e-07,
+                       col_off=0, dx_accum=None):
+    """Gradient of Magnitude.forward with respect to x (..., K) complex64 / float32, given dF (..., N - col_off).
+    bank_cols / bank_t_cols: utils.banded.bank_columns of the (K, N) bank and of its transpose, on x's device
+    (None: mel=False).  dx_accum (x's shape and type) is added to the result."""
+    require_device(x, dF, scale, dx_accum)
+    x = _prep_in(x)
+    dF = _f32c(dF)
+    K = x.shape[-1]
+    N = bank_cols[0].numel() if bank_cols is not None else K
+    rows = x.numel() // K
+    assert dF.numel() == rows * (N - col_off), "dF does not match the forward's output"
+    if dx_accum is not None:
+        dx_accum = dx_accum if dx_accum.is_contiguous() else dx_accum.contiguous()
+        assert dx_accum.shape == x.shape and dx_accum.dtype == x.dtype
+    f = bank_cols if bank_cols is not None else (None,) * 4
+    t = bank_t_cols if bank_t_cols is not None else (None,) * 4
+    dx = torch.empty_like(x)
+    check(lib().at_magnitude_backward(ptr(x), 0 if torch.is_complex(x) else 3, rows, K, ptr(dF), N, col_off,
+                                      ptr(f[0]), ptr(f[1]), ptr(f[2]), ptr(f[3]), f[3].numel() if f[3] is not None else 0,
+                                      ptr(t[0]), ptr(t[1]), ptr(t[2]), ptr(t[3]), t[3].numel() if t[3] is not None else 0,
+                                      contrast_code(contrast), ptr(scale), eps, ptr(dx_accum), ptr(dx),
+                                      stream_ptr()), "at_magnitude_backward")
+    return dx
+
+
+# ----------------------------------------------------------------------------------------------
 # phase-side representations (phase_repr.hip)
 # ----------------------------------------------------------------------------------------------
 SCAN_MODES = {"unwrap": 0, "forward": 1, "backward": 2, "central": 3, "angle": 4}

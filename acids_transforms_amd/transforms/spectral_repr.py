@@ -13,6 +13,7 @@ from typing import Union
 import torch
 
 from .. import ops
+from ..autograd import MagnitudeFunction, StftMagnitudeFunction, wants_grad
 from ..utils.banded import BandedBank
 from ..utils.melbank import melscale_fbanks
 from .base import AudioTransform, InversionEnumType
@@ -149,9 +150,13 @@ class Magnitude(AudioTransform):
         off, sc = self._affine()
         xb, batch_shape = reshape_batches(x, -1)
         stage._release_phase_source()
-        X, phase, feat = ops.stft_mel_forward(xb, stage.window[:1024], self._banded(), self.contrast_mode, off, sc,
-                                              self._eps, want_phase=stage.eager_phase, hop=stage._hop)
-        stage._replace_phase_buffer(X, phase)
+        if wants_grad(xb):
+            X, feat, phase = StftMagnitudeFunction.apply(xb, stage, self, stage.eager_phase)
+            stage._replace_phase_buffer(X.detach(), phase if stage.eager_phase else None)
+        else:
+            X, phase, feat = ops.stft_mel_forward(xb, stage.window[:1024], self._banded(), self.contrast_mode, off, sc,
+                                                  self._eps, want_phase=stage.eager_phase, hop=stage._hop)
+            stage._replace_phase_buffer(X, phase)
         feat = feat.reshape(batch_shape + feat.shape[-2:])
         if return_spectrum:
             return X.reshape(batch_shape + X.shape[-2:]), feat
@@ -189,6 +194,11 @@ class Magnitude(AudioTransform):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         self._follow(x)
+        if wants_grad(x):
+            return MagnitudeFunction.apply(x, self)      # the same forward, with the HIP backward (autograd.py)
+        return self._forward_plain(x)
+
+    def _forward_plain(self, x: torch.Tensor) -> torch.Tensor:
         off, sc = self._affine()
         if self.mel and self.bank_dtype == "bf16":
             K, N = self.mel_bank.shape[-2], self.mel_bank.shape[-1]

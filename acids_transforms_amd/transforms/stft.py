@@ -13,6 +13,7 @@ from typing import Dict, Optional
 import torch
 
 from .. import ops
+from ..autograd import StftFunction, wants_grad
 from ..utils.misc import frame, reshape_batches
 from .base import AudioTransform, InversionEnumType
 
@@ -224,7 +225,12 @@ class STFT(AudioTransform):
         x, batch_shape = reshape_batches(x, -1)
         window = self.window[:self._n_fft]
         self._release_phase_source()
-        if self.eager_phase:
+        if wants_grad(x):
+            # autograd route (autograd.py): the same forward kernel, the HIP adjoint as its backward; the lazy phase
+            # buffer keeps a detached spectrum so that it does not pin the graph
+            x_fft, phase = StftFunction.apply(x, window, self._n_fft, self._hop, self.eager_phase)
+            self._replace_phase_buffer(x_fft.detach(), phase if self.eager_phase else None)
+        elif self.eager_phase:
             x_fft, phase = ops.stft_forward(x, window, self._n_fft, self._hop, center=True, want_phase=True)
             self._replace_phase_buffer(None, phase)
         else:

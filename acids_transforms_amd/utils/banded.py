@@ -218,3 +218,18 @@ class BandedBank:
         if key not in self._dev:
             self._dev[key] = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(device) for a in self._host)
         return self._dev[key]
+
+
+def bank_columns(bank: torch.Tensor):
+    """(K, N) or (1, K, N) bank -> the by-column band tables of at_magnitude_backward, as host arrays:
+    (start[N], length[N], offset[N] int32, weights float32): column j is non-zero only on rows start[j] ..
+    start[j] + length[j] - 1, whose weights sit at weights[offset[j] ..].  Any bank (a dense one is one band per column)."""
+    b = bank.detach().reshape(bank.shape[-2], bank.shape[-1]).float().cpu().numpy()
+    nz = b != 0
+    has = nz.any(0)
+    first = np.where(has, nz.argmax(0), 0)
+    last = np.where(has, b.shape[0] - 1 - nz[::-1].argmax(0), -1)
+    length = np.where(has, last - first + 1, 0).astype(np.int32)
+    offset = np.concatenate([[0], np.cumsum(length)[:-1]]).astype(np.int32)
+    flat = np.concatenate([b[first[j]:first[j] + length[j], j] for j in range(b.shape[1])] + [np.zeros(1, np.float32)])
+    return first.astype(np.int32), length, offset, flat.astype(np.float32)

@@ -401,6 +401,40 @@ int at_sinebank_offline(const float *x, int64_t B, int64_t T, int F, const float
 int at_sinebank_realtime(const float *x, int64_t S, int T, int F, int N, const float *c, const float *tau,
                          const float *phi, const float *window_or_null, float *out, void *stream);
 
+/* ---- backward passes (autograd.py) ------------------------------------------------------------------------------
+ * Gradients follow torch's convention for complex tensors: G = dL/dRe + i dL/dIm. */
+
+/* Adjoint of at_stft_forward(center=1), i.e. the gradient of torch.stft(x, n_fft, hop, window, center=True,
+ * pad_mode="reflect", return_complex=True) with respect to x (reference stft.py:98-104; DGT: dgt.py's forward, with its
+ * ANALYSIS window).  With P = n_fft // 2, N = n_fft and G (B, T, N/2+1) complex64 the upstream gradient:
+ *   q[t, m]  = w[m] Re sum_{k=0}^{N/2} G[t, k] e^{+2 pi i k m / N}     (each bin once: N irfft(G') with the interior bins
+ *              halved; the imaginary parts of DC and Nyquist drop out)
+ *   dp[j]    = sum_t q[t, j - t hop]                                   (overlap-add, frames ascending, no envelope)
+ *   dx[i]    = dp[i + P] + dp[P - i] (i in [1, P]) + dp[2L + P - 2 - i] (i in [L - P - 1, L - 2])   (reflect fold)
+ * dx: (B, L) float32.  T must be the forward's frame count 1 + (L - (n_fft & 1)) / hop, and L > n_fft / 2.  Any n_fft the
+ * forward takes.  Runs the irfft kernels of at_irfft_frames on a window scaled by N/2, then one overlap-add + fold kernel
+ * that adds the halves of DC and Nyquist back (autograd.hip).  workspace: at_stft_backward_workspace_bytes, 256-byte
+ * aligned (the clips are processed in chunks whose frames fit 1 GiB).  Every sample is summed in a fixed order by one
+ * thread: a clip's bits do not depend on the batch. */
+size_t at_stft_backward_workspace_bytes(int64_t B, int64_t T, int n_fft, int hop);
+int at_stft_backward(const float *G_complex, int64_t B, int64_t T, int64_t L, int n_fft, int hop, const float *window,
+                     float *dx, void *workspace, size_t workspace_bytes, void *stream);
+
+/* Gradient of Magnitude.forward (reference spectral_repr.py:215-226) with respect to its input A (rows x K): a = |A|,
+ * M = a @ bank (K x N; M = a when f_w is NULL, then N == K), f = (c(M) - offset) / scale, dF (rows x (N - col_off)) the
+ * gradient of f[..., col_off:] (keep_nyquist=False: col_off = 1; the dropped columns get no gradient):
+ *   dM = dF / scale * c'(M),  c' = 1/(1+M) (log1p), 1/M (log), 1/(M ln 10) (log10) -- the last two 0 where M < eps,
+ *        torch.clamp's mask --, 1 (none);  scale NULL: no Normalize (offset never matters)
+ *   dA[k] = sum_j bank[k, j] dM[j],   dX = dA X / |X| (0 where X == 0, torch's sgn); real A: dA sign(A).
+ * a_kind: 0 complex64, 3 float32.  Banks by column (CSR): column j of the forward bank has f_len[j] weights at
+ * f_w[f_off[j] ..] for rows f_start[j] ..; f_nnz: length of f_w; t_* the same tables of the transposed bank (K
+ * columns).  M is recomputed from A (one wave per row, |A| and dM in LDS; the tables too when they fit).  dX_accum (NULL or rows x K of A's type) is added to the result: the
+ * spectrum's own gradient in the fused STFT -> Magnitude chain.  The bf16 projection's backward is this fp32 one. */
+int at_magnitude_backward(const void *A, int a_kind, int64_t rows, int K, const float *dF, int N, int col_off,
+                          const int *f_start, const int *f_len, const int *f_off, const float *f_w, int f_nnz,
+                          const int *t_start, const int *t_len, const int *t_off, const float *t_w, int t_nnz, int contrast, const float *scale,
+                          float eps, const void *dX_accum, void *dX, void *stream);
+
 /* ---- audio front end ------------------------------------------------------------------------------------- */
 /* torchaudio.transforms.Resample(orig, new) with default arguments, as utils/misc.py:31-33 uses it (algorithm
  * restated, torchaudio is not in the reference tree).  x: (rows, L); orig/new: the rates divided by their gcd;

@@ -1,0 +1,80 @@
+"""Backward passes at the bench size (1024 clips x 4 s, n_fft 1024 / hop 256), one process, legs alternated per round:
+
+  adjoint   ops.stft_backward (the STFT's gradient)      against  istft  (the ISTFT: same bytes, 4104 B in / 1024 B out
+                                                                          per frame)
+  magbwd    the Magnitude(n_mels=128) backward alone     as a share of 8 TB/s on X in + dF in + dX out (8720 B per frame)
+  fwd       the fused STFT -> Magnitude forward          against  fwd+bwd (the same with requires_grad, plus backward)
+
+Prints one JSON line (medians over the rounds, ms).  Run under `rocprofv3 --kernel-trace --stats -- python ...` for the
+per-kernel split."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: E402
+
+import acids_transforms_amd as A  # noqa: E402
+from acids_transforms_amd import ops  # noqa: E402
+from acids_transforms_amd.autograd import _magnitude_grad  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--clips", type=int, default=1024)
+    ap.add_argument("--samples", type=int, default=176400)
+    ap.add_argument("--rounds", type=int, default=12)
+    ap.add_argument("--warmup", type=int, default=3)
+    args = ap.parse_args()
+    dev = torch.device("cuda:0")
+    B, L = args.clips, args.samples
+    g = torch.Generator(device=dev).manual_seed(0)
+    stft = A.STFT().to(dev)
+    mag = A.Magnitude(n_mels=128).to(dev)
+    x = torch.randn(B, L, device=dev, generator=g) * 0.1
+    X = stft(x)
+    mag.scale_data(X)
+    T = X.shape[1]
+    G = torch.randn(X.shape, dtype=torch.complex64, device=dev, generator=g)
+    dF = torch.randn(B, T, 128, device=dev, generator=g)
+    window = stft.window[:1024]
+
+    def fwd_bwd():
+        xr = x.detach().requires_grad_()
+        mag.forward_fused(stft, xr).backward(dF)
+
+    legs = {
+        "adjoint": lambda: ops.stft_backward(G, window, 1024, 256, L),
+        "istft": lambda: stft.invert(X),
+        "magbwd": lambda: _magnitude_grad(mag, X, dF),
+        "fwd": lambda: mag.forward_fused(stft, x),
+        "fwd+bwd": fwd_bwd,
+    }
+    times = {k: [] for k in legs}
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    for r in range(args.warmup + args.rounds):
+        for name, fn in legs.items():
+            torch.cuda.synchronize()
+            ev[0].record()
+            fn()
+            ev[1].record()
+            torch.cuda.synchronize()
+            if r >= args.warmup:
+                times[name].append(ev[0].elapsed_time(ev[1]))
+    med = {k: statistics.median(v) for k, v in times.items()}
+    frames = B * T
+    out = {
+        "clips": B, "samples": L, "frames": frames, "rounds": args.rounds, "ms": med,
+        "adjoint_over_istft": med["adjoint"] / med["istft"],
+        "magbwd_TBps": frames * 8720 / (med["magbwd"] * 1e-3) / 1e12,
+        "magbwd_share_of_8TBps": frames * 8720 / (med["magbwd"] * 1e-3) / 8e12,
+        "fwd_bwd_over_fwd": med["fwd+bwd"] / med["fwd"],
+        "min_ms": {k: min(v) for k, v in times.items()},
+    }
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
