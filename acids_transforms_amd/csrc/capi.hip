@@ -516,7 +516,13 @@ int at_stft_backward(const float* G_complex, int64_t B, int64_t T, int64_t L, in
   for (int64_t b0 = 0; b0 < B; b0 += chunk) {
     const int64_t nb = (B - b0 < chunk) ? B - b0 : chunk;
     const float* G = G_complex + 2 * b0 * T * F;
-    rc = at_irfft_frames(G, nullptr, nullptr, nb * T, n_fft, wscaled, frames, stream);
+    // n_fft 128 / 256 / 512: the register kernels transform 8 / 4 / 2 consecutive frames together, so a frame's bits
+    // would depend on the next clip's frames when a group straddles two clips; the generic kernel takes one frame at a
+    // time and keeps a clip's gradient independent of its batch
+    if (n_fft == 128 || n_fft == 256 || n_fft == 512)
+      rc = launch_irfft_generic((const float2*)G, nullptr, nullptr, nb * T, n_fft, wscaled, frames, s);
+    else
+      rc = at_irfft_frames(G, nullptr, nullptr, nb * T, n_fft, wscaled, frames, stream);
     if (rc) return rc;
     rc = launch_adj_ola_fold(frames, (const float2*)G, window, dx + b0 * L, nb, T, L, n_fft, hop, s);
     if (rc) return rc;
