@@ -1,19 +1,20 @@
-"""Autograd for STFT / DGT and Magnitude: torch.autograd.Functions whose backward passes are the HIP adjoints of
-autograd.hip (through ops.stft_backward / ops.magnitude_backward).
+"""Autograd for STFT / DGT (forward and invert) and Magnitude: torch.autograd.Functions whose backward passes are the
+HIP adjoints of autograd.hip (through ops.stft_backward / ops.istft_backward / ops.magnitude_backward).
 
 The reference is plain torch, so its STFT, DGT and Magnitude (and their composition) sit inside a training loss.  Here
 the forward kernels write into fresh tensors through ctypes, which cuts the graph; the modules therefore route a call
 through these Functions when -- and only when -- grad mode is on and the input requires grad.  Every other call runs
 the plain forward, bit for bit the same kernels.  The forward values of the autograd route are those same kernels too.
 
-All three backward passes are first-order only (@once_differentiable): create_graph=True raises.
+All backward passes are first-order only (@once_differentiable): create_graph=True raises.
 """
 import torch
 from torch.autograd.function import once_differentiable
 
 from . import ops
 
-__all__ = ["wants_grad", "StftFunction", "MagnitudeFunction", "StftMagnitudeFunction"]
+__all__ = ["wants_grad", "StftFunction", "IstftFunction", "IstftPolarFunction", "MagnitudeFunction",
+           "StftMagnitudeFunction"]
 
 
 def wants_grad(x: torch.Tensor) -> bool:
@@ -40,6 +41,42 @@ class StftFunction(torch.autograd.Function):
         if G is None:
             return None, None, None, None, None
         return ops.stft_backward(G, ctx.window, ctx.n_fft, ctx.hop, ctx.L), None, None, None, None
+
+
+class IstftFunction(torch.autograd.Function):
+    """X (B, T, F) complex -> ops.istft(X), whose backward is the ISTFT adjoint.  Saves the frame count and the
+    module's window and envelope table (buffers, not part of the graph)."""
+
+    @staticmethod
+    def forward(ctx, X, inv_window, n_fft, hop, env16):
+        ctx.inv_window, ctx.n_fft, ctx.hop, ctx.env16, ctx.T = inv_window, n_fft, hop, env16, X.shape[-2]
+        return ops.istft(X, inv_window, n_fft, hop, env16=env16)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        gX = ops.istft_backward(gy, ctx.inv_window, ctx.n_fft, ctx.hop, ctx.T, env16=ctx.env16)
+        return gX, None, None, None, None
+
+
+class IstftPolarFunction(torch.autograd.Function):
+    """ops.istft(mag e^{i phase}) for a magnitude mag (B, T, F) and a constant phase (anything that broadcasts to mag):
+    the gradient of mag is Re(gX e^{-i phase}), the phase gets none.  Saves the phase (as ops.istft read it)."""
+
+    @staticmethod
+    def forward(ctx, mag, phase, inv_window, n_fft, hop, env16):
+        phase = ops._f32c(phase.detach())
+        if phase.shape != mag.shape:
+            phase = phase.expand_as(mag).contiguous()
+        ctx.inv_window, ctx.n_fft, ctx.hop, ctx.env16, ctx.phase = inv_window, n_fft, hop, env16, phase
+        return ops.istft(None, inv_window, n_fft, hop, env16=env16, mag=mag, phase=phase)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        gmag = ops.istft_backward(gy, ctx.inv_window, ctx.n_fft, ctx.hop, ctx.phase.shape[-2], env16=ctx.env16,
+                                  phase=ctx.phase)
+        return gmag, None, None, None, None, None
 
 
 def _bank_tables(module, device):

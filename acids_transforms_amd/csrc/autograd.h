@@ -1,4 +1,4 @@
-// autograd.h -- launchers of autograd.hip (the STFT adjoint and the Magnitude backward), for capi.hip.
+// autograd.h -- launchers of autograd.hip (the STFT and ISTFT adjoints and the Magnitude backward), for capi.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -27,5 +27,9 @@ int launch_adj_window(const float* w, int n_fft, float scale, float* out, hipStr
 int launch_adj_ola_fold(const float* frames, const float2* G, const float* window, float* dx, long long B, long long T,
                         long long L, int n_fft, int hop, hipStream_t stream);
 int launch_magnitude_backward(const MagBwdParams& p, hipStream_t stream);
+// ISTFT adjoint: u (prep), then, after the forward's rFFT, the DC / Nyquist halves or the polar epilogue (finish)
+int launch_istft_adj_prep(const float* gy, const float* window, float* u, long long B, long long T, int n_fft, int hop,
+                          hipStream_t stream);
+int launch_istft_adj_finish(const float2* gX, const float* phase, void* out, long long rows, int n_fft, hipStream_t stream);
 
 }  // namespace at_hip

@@ -30,6 +30,16 @@
 // a (K x N) bank, start[j], len[j], off[j] and len[j] weights at w[off[j] ..]; the transposed bank is the same tables of
 // mel_bank^T (513 "filters" of a few mels each at n_fft 1024).  keep_nyquist=False: dF has N - col_off columns, column c
 // belongs to M column c + col_off, and the dropped columns get zero gradient.
+//
+// ISTFT adjoint.  Forward (torch.istft, center=True, onesided, length=None), with w the synthesis window, h the hop and
+// T frames: P = N + h (T-1) padded samples, env[m] = sum of w[m - t h]^2 over the frames t covering m,
+// y[i] = ola[i + N/2] / env[i + N/2] for i < Ly = h (T-1) + (N & 1).  Its adjoint, given gy:
+//   * u[m] = gy[m - N/2] / env[m] for N/2 <= m < N/2 + Ly, 0 elsewhere (never divided in the padding: env may vanish there);
+//   * gX[t, k] = (c_k / N) rfft(w u[t h .. t h + N))[k],  c_0 = c_{N/2} = 1 (even N), 2 for every other bin.
+// Computed as the forward rFFT on the window scaled by 2/N, then DC (and Nyquist, even N) halved -- exact at every N.
+// Polar input X = mag e^{i phi}: gmag = Re gX cos phi + Im gX sin phi (the phase is a constant: no gradient).
+// Every size runs the same three steps, in chunks of clips: a prep kernel writes u (the envelope summed per sample from
+// the oldest frame), the forward's rFFT kernels run with center = 0, and one kernel halves DC / Nyquist or writes gmag.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -132,6 +142,84 @@ int launch_adj_ola_fold(const float* frames, const float2* G, const float* windo
   const long long bx = (L + 1023) / 1024;
   hipLaunchKernelGGL(adj_ola_fold_kernel, dim3((unsigned)bx, (unsigned)(B < 65535 ? B : 65535)), dim3(256), 0, stream, p,
                      vec4);
+  return hipGetLastError() == hipSuccess ? 0 : -5;
+}
+
+// ---- ISTFT adjoint ----------------------------------------------------------------------------------------------------
+
+// gmag of one bin: Re(g e^{-i phi}), spelled out so that both paths round alike
+__device__ __forceinline__ float adj_polar(float2 g, float phi) {
+  float s, c;
+  sincosf(phi, &s, &c);
+  return fmaf(g.x, c, __fmul_rn(g.y, s));
+}
+
+// u of the ISTFT adjoint: thread = padded sample m of the clips blockIdx.y, blockIdx.y + gridDim.y, ... (gridDim.y is
+// at most kPrepClipRows, so the envelope of m is summed once for many clips)
+constexpr int kPrepClipRows = 8;
+
+__global__ void istft_adj_prep_kernel(const float* gy, const float* w, float* u, long long B, long long T, long long Ly,
+                                      long long P, int n_fft, int hop) {
+  const long long m = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (m >= P) return;
+  const long long i = m - n_fft / 2;
+  const bool live = i >= 0 && i < Ly;
+  float env = 0.f;
+  if (live) {
+    long long t_hi = m / hop;
+    if (t_hi > T - 1) t_hi = T - 1;
+    const long long t_lo = (m - n_fft + 1 <= 0) ? 0 : (m - n_fft + hop) / hop;   // ceil((m - n_fft + 1) / hop)
+    for (long long t = t_lo; t <= t_hi; ++t) {
+#pragma clang fp contract(off)   // w^2 rounded before the add (as STFT._make_env16 sums it): no fma
+      const float v = w[m - t * hop];
+      env = env + v * v;
+    }
+  }
+  for (long long b = blockIdx.y; b < B; b += gridDim.y) u[b * P + m] = live ? gy[b * Ly + i] / env : 0.f;
+}
+
+// complex output: DC and Nyquist (even N) halved in place, one thread per frame
+__global__ void istft_adj_halve_kernel(float2* gX, long long rows, int F, int nyq) {
+  for (long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += (long long)gridDim.x * blockDim.x) {
+    float2* row = gX + r * F;
+    row[0] = make_float2(0.5f * row[0].x, 0.5f * row[0].y);
+    if (nyq > 0) row[nyq] = make_float2(0.5f * row[nyq].x, 0.5f * row[nyq].y);
+  }
+}
+
+// polar output: gmag from the rFFT rows (DC and Nyquist halved on the way)
+__global__ void istft_adj_polar_kernel(const float2* gX, const float* phase, float* gmag, long long rows, int F, int nyq) {
+  const long long total = rows * F;
+  for (long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long long)gridDim.x * blockDim.x) {
+    const int k = (int)(e % F);
+    float2 g = gX[e];
+    if (k == 0 || k == nyq) g = make_float2(0.5f * g.x, 0.5f * g.y);
+    gmag[e] = adj_polar(g, phase[e]);
+  }
+}
+
+int launch_istft_adj_prep(const float* gy, const float* window, float* u, long long B, long long T, int n_fft, int hop,
+                          hipStream_t stream) {
+  const long long P = n_fft + (long long)hop * (T - 1), Ly = (long long)hop * (T - 1) + (n_fft & 1);
+  if (B <= 0 || P <= 0) return 0;
+  hipLaunchKernelGGL(istft_adj_prep_kernel, dim3((unsigned)((P + 255) / 256), (unsigned)(B < kPrepClipRows ? B : kPrepClipRows)), dim3(256),
+                     0, stream, gy, window, u, B, T, Ly, P, n_fft, hop);
+  return hipGetLastError() == hipSuccess ? 0 : -5;
+}
+
+int launch_istft_adj_finish(const float2* gX, const float* phase, void* out, long long rows, int n_fft, hipStream_t stream) {
+  if (rows <= 0) return 0;
+  const int F = n_fft / 2 + 1, nyq = (n_fft & 1) ? -1 : n_fft / 2;
+  if (phase) {
+    long long blocks = (rows * F + 255) / 256;
+    if (blocks > 65536) blocks = 65536;
+    hipLaunchKernelGGL(istft_adj_polar_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, gX, phase, (float*)out, rows, F,
+                       nyq);
+  } else {
+    long long blocks = (rows + 255) / 256;
+    if (blocks > 65536) blocks = 65536;
+    hipLaunchKernelGGL(istft_adj_halve_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, (float2*)out, rows, F, nyq);
+  }
   return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 

@@ -110,7 +110,8 @@ extern "C" {
 // 2: at_sinebank_realtime takes the synthesis window; bf16 projection, at_oadd_push
 // 3: any n_fft (odd sizes give torch.istft's hop (T-1) + 1 samples); Cartesian pack / unpack; strided phase scans
 // 4: at_set_variant / at_get_variant (round 4; the library no longer reads environment variables).  The plan variants
-//    (AT_VARIANT_RUN_LENGTH, AT_VARIANT_ISTFT_TILE) are table entries, not signatures: still 4.
+//    (AT_VARIANT_RUN_LENGTH, AT_VARIANT_ISTFT_TILE) are table entries, not signatures: still 4.  So are the backward
+//    entries (at_stft_backward, at_magnitude_backward, at_istft_backward): additions only.
 int at_abi_version(void) { return 4; }
 
 int at_set_variant(int which, int value) {
@@ -525,6 +526,69 @@ int at_stft_backward(const float* G_complex, int64_t B, int64_t T, int64_t L, in
       rc = at_irfft_frames(G, nullptr, nullptr, nb * T, n_fft, wscaled, frames, stream);
     if (rc) return rc;
     rc = launch_adj_ola_fold(frames, (const float2*)G, window, dx + b0 * L, nb, T, L, n_fft, hop, s);
+    if (rc) return rc;
+  }
+  return AT_OK;
+}
+
+// ISTFT adjoint: clips per chunk so that u (P floats per clip) and the polar form's rFFT rows (T F
+// complex) stay within 1 GiB of workspace
+static int64_t istft_adj_chunk_clips(int64_t B, int64_t T, int n_fft, int hop) {
+  const int64_t per_clip = (int64_t)n_fft + (int64_t)hop * (T - 1) + 2 * T * (int64_t)(n_fft / 2 + 1);
+  int64_t c = (int64_t(1) << 28) / per_clip;
+  if (c < 1) c = 1;
+  return c < B ? c : B;
+}
+
+size_t at_istft_backward_workspace_bytes(int64_t B, int64_t T, int n_fft, int hop) {
+  if (B <= 0 || T <= 0 || n_fft <= 0 || hop <= 0) return 0;
+  const int64_t c = istft_adj_chunk_clips(B, T, n_fft, hop), P = (int64_t)n_fft + (int64_t)hop * (T - 1);
+  return adj_window_bytes(n_fft) + ((size_t)c * (size_t)P * sizeof(float) + 255) / 256 * 256 +
+         (size_t)c * (size_t)T * (size_t)(n_fft / 2 + 1) * 2 * sizeof(float);
+}
+
+int at_istft_backward(const float* gy, int64_t B, int64_t T, int n_fft, int hop, const float* inv_window,
+                      const float* env16, const float* phase, float* out, void* workspace, size_t workspace_bytes,
+                      void* stream) {
+  if (B < 0 || T < 0 || hop <= 0 || n_fft <= 0) return AT_EINVAL;
+  if (B == 0 || T == 0) return AT_OK;
+  if (!inv_window || !out) return AT_EINVAL;
+  if (!phase && (((uintptr_t)out) & 7)) return AT_EINVAL;    // complex64 rows
+  if (!fft_size_ok(n_fft)) return AT_EUNSUPPORTED;
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t F = n_fft / 2 + 1;
+  if (T == 1 && !(n_fft & 1)) {       // no output sample: nothing flows back
+    const size_t bytes = (size_t)B * (size_t)F * (phase ? sizeof(float) : 2 * sizeof(float));
+    return hipMemsetAsync(out, 0, bytes, s) == hipSuccess ? AT_OK : AT_ELAUNCH;
+  }
+  if (!gy) return AT_EINVAL;
+  (void)env16;   // the envelope is summed per sample (prep kernel); the table is not needed
+  const int64_t chunk = istft_adj_chunk_clips(B, T, n_fft, hop), P = (int64_t)n_fft + (int64_t)hop * (T - 1);
+  const int64_t Ly = (int64_t)hop * (T - 1) + (n_fft & 1);
+  const size_t u_bytes = ((size_t)chunk * (size_t)P * sizeof(float) + 255) / 256 * 256;
+  if (!workspace || (((uintptr_t)workspace) & 255) ||
+      workspace_bytes < adj_window_bytes(n_fft) + u_bytes + (size_t)chunk * (size_t)T * (size_t)F * 2 * sizeof(float))
+    return AT_EWORKSPACE;
+  float* wscaled = (float*)workspace;
+  float* u = (float*)((char*)workspace + adj_window_bytes(n_fft));
+  float2* gx = (float2*)((char*)u + u_bytes);
+  int rc = launch_adj_window(inv_window, n_fft, 2.0f / (float)n_fft, wscaled, s);
+  if (rc) return rc;
+  for (int64_t b0 = 0; b0 < B; b0 += chunk) {
+    const int64_t nb = (B - b0 < chunk) ? B - b0 : chunk;
+    rc = launch_istft_adj_prep(gy + b0 * Ly, inv_window, u, nb, T, n_fft, hop, s);
+    if (rc) return rc;
+    // the complex form writes the caller's rows directly, the polar form the workspace rows
+    float2* X = phase ? gx : (float2*)out + b0 * T * F;
+    // n_fft 128 / 256 / 512: the register kernels transform 8 / 4 / 2 consecutive frames together, which would mix the
+    // rounding of a clip's last frames with the next clip's first (odd T): the generic kernel takes one frame at a time
+    if (n_fft == 128 || n_fft == 256 || n_fft == 512)
+      rc = launch_rfft_generic(u, nb, P, P, T, n_fft, hop, 0, wscaled, X, nullptr, s);
+    else
+      rc = at_stft_forward(u, nb, P, P, T, n_fft, hop, 0, wscaled, (float*)X, nullptr, stream);
+    if (rc) return rc;
+    rc = launch_istft_adj_finish(X, phase ? phase + b0 * T * F : nullptr, phase ? (void*)(out + b0 * T * F) : (void*)X,
+                                 nb * T, n_fft, s);
     if (rc) return rc;
   }
   return AT_OK;

@@ -623,6 +623,28 @@ def stft_backward(G, window, n_fft, hop, L):
     return dx
 
 
+def istft_backward(gy, inv_window, n_fft, hop, T, env16=None, phase=None):
+    """Adjoint of istft: gy (B, hop*(T-1) + (n_fft & 1)) float32, the gradient of its output -> the gradient of the
+    spectrum, (B, T, F) complex64; with phase (B, T, F) float32 (polar input mag e^{i phase}), the gradient of mag,
+    (B, T, F) float32."""
+    require_device(gy, inv_window, phase)
+    gy = _f32c(gy)
+    B, F = gy.shape[0], n_fft // 2 + 1
+    assert gy.shape[-1] == (hop * (T - 1) + (n_fft & 1) if T > 0 else 0), "gy does not match istft's output length"
+    if phase is not None:
+        phase = _f32c(phase)
+        assert phase.shape == (B, T, F), "phase must be (B, T, n_fft/2+1)"
+        out = torch.empty((B, T, F), dtype=torch.float32, device=gy.device)
+    else:
+        out = torch.empty((B, T, F), dtype=torch.complex64, device=gy.device)
+    # env16 (the modules pass theirs) is not read: the prep kernel sums the envelope per sample
+    wsb = lib().at_istft_backward_workspace_bytes(B, T, n_fft, hop)
+    ws = _workspace(wsb, gy.device)
+    check(lib().at_istft_backward(ptr(gy), B, T, n_fft, hop, ptr(inv_window), ptr(env16), ptr(phase), ptr(out),
+                                  ptr(ws), wsb, stream_ptr()), "at_istft_backward")
+    return out
+
+
 def magnitude_backward(x, dF, bank_cols=None, bank_t_cols=None, contrast=None, scale=None, eps=1.1920929e-07,
                        col_off=0, dx_accum=None):
     """Gradient of Magnitude.forward with respect to x (..., K) complex64 / float32, given dF (..., N - col_off).

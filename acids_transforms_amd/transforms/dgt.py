@@ -90,7 +90,9 @@ class DGT(STFT):
             return self.get_sinebank_inversion(x)
         else:
             raise ValueError("inversion mode %s not valid." % self.inversion_mode)
-        return self._istft(mag=x, phase=phase)
+        # PGHI's phase is a function of the magnitude: a gradient through it held constant would be wrong, so that mode
+        # stays without a graph
+        return self._istft(mag=x, phase=phase, grad=inversion_mode != "pghi")
 
     def pghi(self, mag: torch.Tensor, tolerance=1.e-4) -> torch.Tensor:
         """Phase for a (T, F) or (B, T, F) magnitude array (reference dgt.py:156-162,

@@ -13,7 +13,7 @@ from typing import Dict, Optional
 import torch
 
 from .. import ops
-from ..autograd import StftFunction, wants_grad
+from ..autograd import IstftFunction, IstftPolarFunction, StftFunction, wants_grad
 from ..utils.misc import frame, reshape_batches
 from .base import AudioTransform, InversionEnumType
 
@@ -275,11 +275,19 @@ class STFT(AudioTransform):
             raise RuntimeError("istft(n_fft=%d, hop_length=%d): window overlap add min: %g -- the window envelope "
                                "vanishes somewhere (NOLA violated), as torch.istft would report" % (n, h, cache[key]))
 
-    def _istft(self, X=None, mag=None, phase=None):
+    def _istft(self, X=None, mag=None, phase=None, grad=True):
+        """ops.istft with the module's windows.  grad=True and an input that wants a gradient: the autograd route
+        (autograd.py; the same forward kernels, the ISTFT adjoint as backward, the phase a constant).  grad=False: a
+        phase that depends on the magnitude (DGT's PGHI), where that gradient would be wrong."""
         src = X if X is not None else mag
         self._check_nola(int(src.shape[-2]))
         env = self._env16 if self._env16.numel() else None
-        return ops.istft(X, self.inv_window[:self._n_fft], self._n_fft, self._hop, env16=env, mag=mag, phase=phase)
+        w, n, h = self.inv_window[:self._n_fft], self._n_fft, self._hop
+        if grad and wants_grad(src):
+            if X is not None:
+                return IstftFunction.apply(X, w, n, h, env)
+            return IstftPolarFunction.apply(mag, phase, w, n, h, env)
+        return ops.istft(X, w, n, h, env16=env, mag=mag, phase=phase)
 
     def realtime(self):
         mode = self.inversion_mode if self.inversion_mode in RealtimeSTFT.get_inversion_modes() else "random"

@@ -420,6 +420,24 @@ size_t at_stft_backward_workspace_bytes(int64_t B, int64_t T, int n_fft, int hop
 int at_stft_backward(const float *G_complex, int64_t B, int64_t T, int64_t L, int n_fft, int hop, const float *window,
                      float *dx, void *workspace, size_t workspace_bytes, void *stream);
 
+/* Adjoint of at_istft (torch.istft, center=True, onesided, length=None) -- its backward.  w = inv_window, N = n_fft,
+ * h = hop, P = N + h (T-1), env[m] = sum of w[m - t h]^2 over the frames t that cover m (oldest first, w^2 rounded before
+ * each add, as the modules' table STFT._make_env16), Ly = h (T-1) + (N & 1):
+ *   u[m]     = gy[m - N/2] / env[m] for N/2 <= m < N/2 + Ly, 0 elsewhere (no division in the padding)
+ *   gX[t, k] = (c_k / N) rfft(w u[t h .. t h + N))[k],  c_0 = 1, c_{N/2} = 1 (even N), c_k = 2 otherwise
+ * gy: (B, Ly) float32.  phase NULL: out = gX, (B, T, F) complex64.  phase (B, T, F) float32 given (polar input
+ * X = mag e^{i phase}): out = gmag = Re gX cos phase + Im gX sin phase, (B, T, F) float32; gX is not written.  Ly == 0
+ * (T == 1, even N): zeros.  Any n_fft at_istft takes; complex out must be 8-byte aligned (AT_EINVAL), gy, phase and
+ * the window may have any float alignment.  Chunks of clips go through u (one prep kernel, which sums the envelope per
+ * sample), at_stft_forward's kernels with center = 0 on the window scaled by 2/N (the generic one-frame kernel at
+ * n_fft 128 / 256 / 512) and a kernel that halves DC and Nyquist or writes gmag.  env16 is accepted for symmetry with
+ * at_istft and not read.  workspace: at_istft_backward_workspace_bytes (> 0 for every shape), 256-byte aligned.  A
+ * clip's bits depend neither on its batch nor on the chunking. */
+size_t at_istft_backward_workspace_bytes(int64_t B, int64_t T, int n_fft, int hop);
+int at_istft_backward(const float *gy, int64_t B, int64_t T, int n_fft, int hop, const float *inv_window,
+                      const float *env16, const float *phase, float *out, void *workspace, size_t workspace_bytes,
+                      void *stream);
+
 /* Gradient of Magnitude.forward (reference spectral_repr.py:215-226) with respect to its input A (rows x K): a = |A|,
  * M = a @ bank (K x N; M = a when f_w is NULL, then N == K), f = (c(M) - offset) / scale, dF (rows x (N - col_off)) the
  * gradient of f[..., col_off:] (keep_nyquist=False: col_off = 1; the dropped columns get no gradient):

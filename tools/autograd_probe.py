@@ -4,6 +4,8 @@
                                                                           per frame)
   magbwd    the Magnitude(n_mels=128) backward alone     as a share of 8 TB/s on X in + dF in + dX out (8720 B per frame)
   fwd       the fused STFT -> Magnitude forward          against  fwd+bwd (the same with requires_grad, plus backward)
+  istft_adj ops.istft_backward (invert's gradient)       against  stft_fwd (the plain ops.stft_forward: the same bytes,
+            istft_adj_polar (the magnitude's gradient)            1024 B in / 4104 B out per frame)
 
 Prints one JSON line (medians over the rounds, ms).  Run under `rocprofv3 --kernel-trace --stats -- python ...` for the
 per-kernel split."""
@@ -45,12 +47,19 @@ def main():
         xr = x.detach().requires_grad_()
         mag.forward_fused(stft, xr).backward(dF)
 
+    inv_window, env = stft.inv_window[:1024], stft._env16
+    gy = torch.randn(B, 256 * (T - 1), device=dev, generator=g)
+    phase = torch.rand(X.shape, device=dev, generator=g) * 6.283
+
     legs = {
         "adjoint": lambda: ops.stft_backward(G, window, 1024, 256, L),
         "istft": lambda: stft.invert(X),
         "magbwd": lambda: _magnitude_grad(mag, X, dF),
         "fwd": lambda: mag.forward_fused(stft, x),
         "fwd+bwd": fwd_bwd,
+        "stft_fwd": lambda: ops.stft_forward(x, window, 1024, 256),
+        "istft_adj": lambda: ops.istft_backward(gy, inv_window, 1024, 256, T, env16=env),
+        "istft_adj_polar": lambda: ops.istft_backward(gy, inv_window, 1024, 256, T, env16=env, phase=phase),
     }
     times = {k: [] for k in legs}
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
@@ -71,6 +80,8 @@ def main():
         "magbwd_TBps": frames * 8720 / (med["magbwd"] * 1e-3) / 1e12,
         "magbwd_share_of_8TBps": frames * 8720 / (med["magbwd"] * 1e-3) / 8e12,
         "fwd_bwd_over_fwd": med["fwd+bwd"] / med["fwd"],
+        "istft_adj_over_stft_fwd": med["istft_adj"] / med["stft_fwd"],
+        "istft_adj_polar_over_stft_fwd": med["istft_adj_polar"] / med["stft_fwd"],
         "min_ms": {k: min(v) for k, v in times.items()},
     }
     print(json.dumps(out))
