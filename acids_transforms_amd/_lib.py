@@ -134,9 +134,9 @@ def lib():
 
 
 # kernel variants (include/acids_hip.h AT_VARIANT_*): same results, different kernels or a different cut of the clips
-# (run_length, istft_tile: 0..65535); for tests and A/B runs
+# (run_length, istft_tile, row_run: 0..65535); for tests and A/B runs
 VARIANTS = {"epilogue": 0, "frame_kernels": 1, "small_projection": 2, "scan_layout": 3, "pghi_kernel": 4, "istft_runs": 5,
-            "run_length": 6, "istft_tile": 7}
+            "run_length": 6, "istft_tile": 7, "row_run": 8}
 
 
 class variant:

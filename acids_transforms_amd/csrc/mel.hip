@@ -22,6 +22,7 @@
 
 #include "../../include/acids_hip.h"
 #include "mel_gemm.h"
+#include "variants.h"
 
 namespace at_hip {
 
@@ -330,6 +331,7 @@ static int launch_mel(const MelParams& p0, hipStream_t stream) {
   if (rowblocks < 1) rowblocks = 1;
   if (rowblocks > ntiles) rowblocks = ntiles;
   p.tiles_per_block = (ntiles + rowblocks - 1) / rowblocks;
+  if (const long long forced = forced_row_run(ntiles)) p.tiles_per_block = forced;   // AT_VARIANT_ROW_RUN (tests)
   rowblocks = (ntiles + p.tiles_per_block - 1) / p.tiles_per_block;
   const size_t lds = sizeof(float) * 2 * ROWS * (size_t)p.rs + 16;
   auto kern = p.dense ? mel_gemm_kernel<KSTEPS, NL, true> : mel_gemm_kernel<KSTEPS, NL, false>;

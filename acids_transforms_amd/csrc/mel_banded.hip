@@ -460,6 +460,7 @@ static int launch_fixed_proj(const BandedParams& b, hipStream_t s) {
   }
   long long rpw = (p.rows + 4 * slots - 1) / (4 * slots);
   if (rpw < 8) rpw = 8;
+  if (const long long forced = forced_row_run(p.rows)) rpw = forced;     // AT_VARIANT_ROW_RUN (tests)
   p.rows_per_wave = rpw;
   const long long waves = (p.rows + rpw - 1) / rpw;
   hipLaunchKernelGGL((mel_fixed_kernel<8, 2>), dim3((unsigned)((waves + kBandedWaves - 1) / kBandedWaves)), dim3(64 * kBandedWaves), 0, s, p);
@@ -537,6 +538,7 @@ static int launch_banded(const BandedParams& p0, size_t dyn_lds, hipStream_t s) 
   // a few whole rounds of resident waves: the table staging of a block is amortised and the tail stays short
   long long rpw = (p.rows + 4 * slots - 1) / (4 * slots);
   if (rpw < 8) rpw = 8;
+  if (const long long forced = forced_row_run(p.rows)) rpw = forced;     // AT_VARIANT_ROW_RUN (tests)
   p.rows_per_wave = rpw;
   const long long waves = (p.rows + rpw - 1) / rpw;
   const long long blocks = (waves + waves_per_block - 1) / waves_per_block;
@@ -877,6 +879,7 @@ extern "C" int at_project_small(const float* x, int64_t rows, int K, const float
     long long rpw = (rows + waves_target - 1) / waves_target;
     rpw = (rpw + 31) / 32 * 32;
     if (rpw < 64) rpw = 64;
+    if (const long long forced = forced_row_run(rows)) rpw = (forced + 31) / 32 * 32;   // AT_VARIANT_ROW_RUN (tests)
     p.rows_per_wave = rpw;
     const long long waves = (rows + rpw - 1) / rpw;
     const dim3 grid((unsigned)((waves + 3) / 4));
@@ -894,6 +897,7 @@ extern "C" int at_project_small(const float* x, int64_t rows, int K, const float
   const long long waves_target = 256LL * 32;
   long long rpw = (rows + waves_target - 1) / waves_target;
   if (rpw < 4) rpw = 4;
+  if (const long long forced = forced_row_run(rows)) rpw = forced;       // AT_VARIANT_ROW_RUN (tests)
   p.rows_per_wave = rpw;
   const long long waves = (rows + rpw - 1) / rpw;
   const dim3 grid((unsigned)((waves + 3) / 4)), block(256);

@@ -24,6 +24,7 @@
 
 #include "../../include/acids_hip.h"
 #include "mel_gemm.h"
+#include "variants.h"
 
 namespace at_hip {
 
@@ -259,6 +260,7 @@ int at_mel_project_bf16(const void* A, int a_kind, int64_t rows, int64_t lda, in
   }
   const unsigned ychunks = (unsigned)((p.n_pad + nc - 1) / nc);
   long long gx = p.n_tiles < cus ? p.n_tiles : cus;   // one workgroup per CU (LDS-limited), persistent over tiles
+  if (const long long forced = at_hip::forced_row_run(p.n_tiles)) gx = (p.n_tiles + forced - 1) / forced;   // AT_VARIANT_ROW_RUN
   dim3 grid((unsigned)gx, ychunks), block(BF_THREADS);
   void* args[] = {&p};
   if (hipLaunchKernel(fn, grid, block, args, lds, (hipStream_t)stream) != hipSuccess) {

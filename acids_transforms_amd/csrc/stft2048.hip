@@ -847,6 +847,7 @@ int launch_stft2048_mel(const float* x, long long B, long long L, long long clip
   // runs of consecutive frames per wave: long enough for the window and the table staging, short enough to fill the chip
   long long fpw = (nframes + 256LL * 8 * W2K - 1) / (256LL * 8 * W2K);
   if (fpw < 8) fpw = 8;
+  if (const long long forced = forced_row_run(nframes)) fpw = forced;    // AT_VARIANT_ROW_RUN (tests)
   p.frames_per_wave = fpw;
   const long long waves = (nframes + fpw - 1) / fpw;
   const unsigned grid = (unsigned)((waves + W2K - 1) / W2K);

@@ -905,6 +905,7 @@ int launch_stft512_mel(const float* x, long long B, long long L, long long clip_
   const long long npairs = (nframes + 1) / 2;
   long long ppw = (npairs + 256LL * 8 * W5 - 1) / (256LL * 8 * W5);
   if (ppw < 4) ppw = 4;
+  if (const long long forced = forced_row_run(npairs)) ppw = forced;     // AT_VARIANT_ROW_RUN (tests)
   p.pairs_per_wave = ppw;
   const long long waves = (npairs + ppw - 1) / ppw;
   const unsigned grid = (unsigned)((waves + W5 - 1) / W5);

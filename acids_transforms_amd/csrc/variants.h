@@ -22,13 +22,27 @@ enum {
                             // rank fast path but without the wavefront-parallel scan path in front of it
   kVarIstftRuns = 5,        // 1: the n_fft-1024 inverse always as one long run per wave (no workgroup tiles with LDS hand-over)
   // Plan variants: same kernel, a different cut of the clips.  0 leaves the plan to the launcher (device-dependent).
-  kVarRunLength = 6,        // v > 0: runs of v units (clamped to [8, units]) for every launcher that plans per-wave runs
+  kVarRunLength = 6,        // v > 0: runs of v units (clamped to [8, units]) for the streaming STFT / ISTFT launchers: the
+                            // n_fft-1024 forward (fused forms included), the 512 / 2048 / 4096 sliding-window forwards and
+                            // the long-run n_fft-1024 inverse
   kVarIstftTile = 7,        // v > 0: the n_fft-1024 inverse on workgroup tiles whatever the batch, v (>= 6) frames per wave
-  kVarCount = 8,
+  kVarRowRun = 8,           // v > 0: the row cut of the projection launchers, clamped to [1, total] (forced_row_run):
+                            // v rows per wave (banded, fixed, small row form), v rounded up to 32 rows (small MFMA form,
+                            // whole 32-row tile pairs), v frame pairs (n_fft-512 features), v frames (n_fft-2048 features),
+                            // v 32-row tiles per workgroup (dense GEMM), v 128-row tiles per workgroup (bf16)
+  kVarCount = 9,
   kVarFirstPlan = kVarRunLength
 };
 
 int variant(int which);     // capi.hip
+
+// The unit count a projection launcher must cut per wave (or workgroup) in place of its own plan: AT_VARIANT_ROW_RUN
+// clamped to [1, total], or 0 = keep the plan.  Runs of any length already occur in last waves, so 1 is legal everywhere.
+inline long long forced_row_run(long long total) {
+  const long long v = variant(kVarRowRun);
+  if (v <= 0) return 0;
+  return v < total ? v : (total > 0 ? total : 1);
+}
 
 #ifdef AT_DEV_SWITCHES
 inline const char* dev_env(const char* name) { return getenv(name); }

@@ -58,9 +58,15 @@ const char *at_error_string(int code);
                                         * tiles with the overlap state handed over through LDS) */
 /* Plan variants (round 6; table entries, no signature changed: ABI still 4).  value 0..65535, 0 = the launcher's plan. */
 #define AT_VARIANT_RUN_LENGTH 6        /* v: runs of v units clamped to [8, units] (frames; frame pairs at n_fft 512; hop slots
-                                        * for the long-run n_fft-1024 inverse) for every launcher that plans per-wave runs */
+                                        * for the long-run n_fft-1024 inverse) for the streaming STFT / ISTFT launchers: the
+                                        * n_fft-1024 forward (fused forms included), the 512 / 2048 / 4096 sliding-window
+                                        * forwards and the long-run n_fft-1024 inverse */
 #define AT_VARIANT_ISTFT_TILE 7        /* v: hop-256 non-Griffin-Lim n_fft-1024 inverse (T >= 64) on workgroup tiles at any
                                         * batch, max(v, 6) frames per wave, no balancing; AT_VARIANT_ISTFT_RUNS = 1 wins */
+#define AT_VARIANT_ROW_RUN 8           /* v: row cut of the projection kernels clamped to [1, total]: v rows per wave (banded,
+                                        * fixed 513-bin, small row form; small MFMA form: v rounded up to 32), v frame pairs /
+                                        * frames per wave (n_fft-512 / 2048 features-only forward), v 32-row tiles per
+                                        * workgroup (dense MFMA GEMM), v 128-row tiles per workgroup (bf16 projection) */
 int at_set_variant(int which, int value);
 int at_get_variant(int which);
 
