@@ -625,6 +625,9 @@ int launch_istft512_ola(const float2* X, const float* mag, const float* phase, l
   const long long min_per = 16;
   if (per < min_per) per = min_per < pairs ? min_per : pairs;
   if (per < 1) per = 1;
+  // AT_VARIANT_RUN_LENGTH (tests), in frame pairs.  The floor of 16 above is a throughput choice: the kernel's warm-up
+  // ((R + 1) / 2 pairs), carry and masks are per pair, so the variant's own clamp to [8, pairs] holds here too.
+  if (const long long v = forced_units_per_run(pairs)) per = v;
   runs = (pairs + per - 1) / per;
   p.runs_per_clip = runs;
   p.pairs_per_run = per;

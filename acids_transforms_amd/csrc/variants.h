@@ -23,8 +23,9 @@ enum {
   kVarIstftRuns = 5,        // 1: the n_fft-1024 inverse always as one long run per wave (no workgroup tiles with LDS hand-over)
   // Plan variants: same kernel, a different cut of the clips.  0 leaves the plan to the launcher (device-dependent).
   kVarRunLength = 6,        // v > 0: runs of v units (clamped to [8, units]) for the streaming STFT / ISTFT launchers: the
-                            // n_fft-1024 forward (fused forms included), the 512 / 2048 / 4096 sliding-window forwards and
-                            // the long-run n_fft-1024 inverse
+                            // n_fft-1024 forward (fused forms included), the 512 / 2048 / 4096 sliding-window forwards,
+                            // the long-run n_fft-1024 inverse and the fused 512 / 2048 / 4096 inverses (istft512_ola_kernel
+                            // in frame pairs, istft2048_ola_kernel / istft4096_ola_kernel in output hops)
   kVarIstftTile = 7,        // v > 0: the n_fft-1024 inverse on workgroup tiles whatever the batch, v (>= 6) frames per wave
   kVarRowRun = 8,           // v > 0: the row cut of the projection launchers, clamped to [1, total] (forced_row_run):
                             // v rows per wave (banded, fixed, small row form), v rounded up to 32 rows (small MFMA form,

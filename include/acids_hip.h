@@ -57,10 +57,11 @@ const char *at_error_string(int code);
 #define AT_VARIANT_ISTFT_RUNS 5        /* 1: n_fft-1024 inverse as one long run per wave even for full batches (no workgroup
                                         * tiles with the overlap state handed over through LDS) */
 /* Plan variants (round 6; table entries, no signature changed: ABI still 4).  value 0..65535, 0 = the launcher's plan. */
-#define AT_VARIANT_RUN_LENGTH 6        /* v: runs of v units clamped to [8, units] (frames; frame pairs at n_fft 512; hop slots
-                                        * for the long-run n_fft-1024 inverse) for the streaming STFT / ISTFT launchers: the
-                                        * n_fft-1024 forward (fused forms included), the 512 / 2048 / 4096 sliding-window
-                                        * forwards and the long-run n_fft-1024 inverse */
+#define AT_VARIANT_RUN_LENGTH 6        /* v: runs of v units clamped to [8, units] (frames; frame pairs at n_fft 512; output
+                                        * hops for the inverses) for the streaming STFT / ISTFT launchers: the n_fft-1024
+                                        * forward (fused forms included), the 512 / 2048 / 4096 sliding-window forwards, the
+                                        * long-run n_fft-1024 inverse and the fused 512 / 2048 / 4096 inverses (hop n/8,
+                                        * n/4, n/2; complex and polar input) */
 #define AT_VARIANT_ISTFT_TILE 7        /* v: hop-256 non-Griffin-Lim n_fft-1024 inverse (T >= 64) on workgroup tiles at any
                                         * batch, max(v, 6) frames per wave, no balancing; AT_VARIANT_ISTFT_RUNS = 1 wins */
 #define AT_VARIANT_ROW_RUN 8           /* v: row cut of the projection kernels clamped to [1, total]: v rows per wave (banded,

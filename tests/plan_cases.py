@@ -2,8 +2,8 @@
 test_run_plans_gpu.py that force those cuts through the plan variants (AT_VARIANT_RUN_LENGTH, AT_VARIANT_ISTFT_TILE).
 
 test_plan_cases_cpu.py checks that the sweeps reach every geometry class named here; the GPU file runs them.  The
-arithmetic follows csrc/run_plan.h (forced_units_per_run) and csrc/stft1024.hip (launch_istft1024_ola and the share() /
-self_cool rule of istft1024_tile_kernel)."""
+arithmetic follows csrc/run_plan.h (forced_units_per_run), csrc/stft1024.hip (launch_istft1024_ola and the share() /
+self_cool rule of istft1024_tile_kernel) and launch_istft512_ola / launch_istft2048_ola / launch_istft4096_ola."""
 
 TILE_WAVES = 4          # waves per workgroup of the tile kernel
 ONE_RUN = 65535         # AT_VARIANT_RUN_LENGTH value that clamps to one run per clip
@@ -145,3 +145,142 @@ def fwd_case_classes(n_fft, hop, v, T, L):
         pairs = (T + 1) // 2
         return run_classes(pairs, v, tail_unit=(tail_start(n_fft, hop, L) + 1) // 2, half_pair=T % 2 == 1)
     return run_classes(T, v, tail_unit=tail_start(n_fft, hop, L))
+
+
+# ---- fused inverses at n_fft 512 / 2048 / 4096 (istft512_ola_kernel, istft2048_ola_kernel, istft4096_ola_kernel) ---------
+# R = n_fft / hop frames overlap a hop; output hop q is block c = q + lead, summed from frames c - R + 1 .. c; the first
+# lead = R / 2 blocks are torch.istft's trimmed front.  Units: output hops at 2048 / 4096, frame pairs at 512 (pair i holds
+# frames 2 i, 2 i + 1 and completes blocks 2 i, 2 i + 1; the first pair of a clip is pair lead // 2).
+INV_OTHER = [(n, n // d) for n in (512, 2048, 4096) for d in (8, 4, 2)]
+INV_WAVES_PER_BLOCK = 4     # W5, W2K, W4K
+
+
+def inverse_units(n_fft, hop, T):
+    """Units per clip of the launcher: T - 1 output hops, or the frame pairs that hold a valid block at n_fft 512."""
+    if n_fft == 512:
+        lead = 256 // hop
+        return (lead + T) // 2 - lead // 2
+    return T - 1
+
+
+def default_inverse_plan(n_fft, hop, B, T):
+    """(units, per, runs) of the launcher's own plan: from the batch size alone, with a floor of 8 hops / 16 pairs."""
+    units = inverse_units(n_fft, hop, T)
+    full, floor = (4096, 16) if n_fft == 512 else (2048, 8)
+    runs = 1 if B >= full else (full + B - 1) // B
+    per = (units + runs - 1) // runs
+    if per < floor:
+        per = min(floor, units)
+    per = max(per, 1)
+    return units, per, (units + per - 1) // per
+
+
+def forced_inverse_plan(n_fft, hop, v, T):
+    units = inverse_units(n_fft, hop, T)
+    per = forced_run_length(v, units)
+    return units, per, (units + per - 1) // per
+
+
+def inverse_grid(B, runs):
+    """Workgroups of the launch: one wave per run, four waves per workgroup."""
+    return (B * runs + INV_WAVES_PER_BLOCK - 1) // INV_WAVES_PER_BLOCK
+
+
+def hop_is_partial(n_fft, hop, T, q):
+    """Output hop q lacks one of its R frames (clip start or end): the divided-envelope store."""
+    R = n_fft // hop
+    c = q + R // 2
+    return c - (R - 1) < 0 or c > T - 1
+
+
+def run_hops(n_fft, hop, T, a, b):
+    """The valid output hops that the run of units [a, b) stores."""
+    if n_fft != 512:
+        return list(range(a, b))
+    lead = 256 // hop
+    out = []
+    for i in range(lead // 2 + a, lead // 2 + b):
+        out += [c - lead for c in (2 * i, 2 * i + 1) if lead <= c < lead + T - 1]
+    return out
+
+
+def inv_classes(n_fft, hop, v, T):
+    """Geometry classes of one forced cut of a fused 512 / 2048 / 4096 inverse."""
+    R = n_fft // hop
+    units = inverse_units(n_fft, hop, T)
+    rs = runs(units, v)
+    per, last = rs[0][1] - rs[0][0], rs[-1][1] - rs[-1][0]
+    hops = [run_hops(n_fft, hop, T, a, b) for a, b in rs]
+    assert sorted(sum(hops, [])) == list(range(T - 1))             # the runs store every hop exactly once
+    c = set()
+    if len(rs) == 1:
+        c.add("single_run_lt8" if units < 8 else "single_run_ge8")
+    else:
+        c.add("last_run_full" if last == per else "last_run_%d" % last if last <= 7 else "last_run_long")
+        if all(hop_is_partial(n_fft, hop, T, q) for q in hops[-1]):
+            c.add("last_run_partial_hops_only")
+    if all(hop_is_partial(n_fft, hop, T, q) for q in range(T - 1)):
+        c.add("every_hop_partial")
+    # R - 1 warm-up frames before a run's first hop: with T - 1 <= R - 1 they reach before frame 0 for every hop
+    c.add("T-1<R-1" if T < R else "T-1==R-1" if T == R else "T-1>R-1")
+    if n_fft == 512:
+        lead = 256 // hop
+        c.add("T_odd" if T % 2 else "T_even")                       # odd: frame T - 1 is half a pair
+        one_block = (lead + T - 1) % 2 == 1                         # the last pair completes one valid block only
+        c.add("last_pair_one_block" if one_block else "last_pair_two_blocks")
+        if lead % 2:
+            c.add("first_pair_opens_trimmed")                       # hop 256: block 0 of pair 0 is trimmed
+        if len(rs) > 1 and last == 1:
+            if T % 2:
+                c.add("run_starts_at_half_frame_pair")
+            if one_block:
+                c.add("run_starts_at_one_block_pair")
+    return c
+
+
+def inv_want_classes(n_fft, hop):
+    """What a sweep must reach.  At hop n/2 (R = 2) no hop is ever partial (block q + 1 is frames q, q + 1) and
+    T - 1 < R - 1 would be a clip without output: those classes do not exist there."""
+    R = n_fft // hop
+    want = {"single_run_lt8", "single_run_ge8", "last_run_full", "last_run_long", "T-1==R-1", "T-1>R-1"}
+    want |= {"last_run_%d" % i for i in range(1, 8)}
+    if R > 2:
+        want |= {"last_run_partial_hops_only", "every_hop_partial", "T-1<R-1"}
+    if n_fft == 512:
+        want |= {"T_odd", "T_even", "last_pair_one_block", "last_pair_two_blocks", "run_starts_at_half_frame_pair",
+                 "run_starts_at_one_block_pair"}
+        if hop == 256:
+            want.add("first_pair_opens_trimmed")
+    return want
+
+
+def inv_other_sweep(n_fft, v_list=(8, 9, 13)):
+    """[(v, T)]: every frame count up to three forced runs of the longest v, and two long clips."""
+    T_list = list(range(2, 58)) + [80, 81] if n_fft == 512 else list(range(2, 29)) + [40, 41]
+    return [(v, T) for T in T_list for v in v_list]
+
+
+INV_OTHER_SWEEPS = {(n, h): inv_other_sweep(n) for n, h in INV_OTHER}
+
+# The full-batch cases of test_run_plans_gpu.py (hop n/4): (B, samples per clip).  1024 clips of 4 s are what bench.py
+# times under other_sizes; the second batch is the smallest that gets one run per clip (1 s clips: the plan looks at B only).
+INV_FULL_BATCH = {512: [(1024, 176400), (4096, 44100)], 2048: [(1024, 176400), (2048, 44100)],
+                  4096: [(1024, 176400), (2048, 44100)]}
+# (B, T, hop) of the inverse launches the size tests of test_stft_gpu.py make at these sizes: the (B, L, h) list of
+# test_register_core_sizes_512_and_2048 (T = 1 + L // h), test_every_power_of_two_size (2 clips of max(3 n, 2000) samples)
+# and the 13-frame goldens of test_other_sizes_golden
+INV_SMALL_SHAPES = {n: [(3, 1 + (9 * n + 7) // (n // 4), n // 4), (5, 1 + 4 * n // (n // 2), n // 2),
+                        (2, 1 + (7 * n + 2) // (n // 8), n // 8), (1, 1 + 20 * n // (n // 4), n // 4), (2, 13, n // 4)] +
+                       [(2, 1 + max(3 * n, 2000) // (n // d), n // d) for d in (8, 4, 2)]
+                    for n in (512, 2048, 4096)}
+
+
+# two-pass inverse at 2048 / 4096 (irfft2048_frames_kernel / irfft4096_frames_kernel + the overlap-add gather): hops that
+# no fused kernel takes -- n/16, and hops that do not divide n_fft
+TWO_PASS_HOPS = [(2048, 128), (2048, 300), (2048, 333), (4096, 256), (4096, 700)]
+
+
+def frames_per_block_2k_4k(nframes):
+    """frames_per_block_2k / frames_per_block_4k: at most 2048 workgroups of four waves, whole rounds of the waves."""
+    fpb = (nframes + 2047) // 2048
+    return max((fpb + 3) // 4 * 4, 4)

@@ -52,3 +52,66 @@ def test_run_sweeps_reach_every_run_geometry():
     for v, T in P.INV_SWEEP:
         hit |= P.run_classes(T - 1, v)
     assert P.RUN_CLASSES - {"run_in_padded_tail"} <= hit, sorted(P.RUN_CLASSES - {"run_in_padded_tail"} - hit)
+
+
+# ---- fused inverses at n_fft 512 / 2048 / 4096 --------------------------------------------------------------------------
+def test_inverse_units_and_default_plan():
+    # n_fft 512: pairs that hold a valid block; lead = 256 / hop blocks are trimmed at the front
+    assert P.inverse_units(512, 128, 1379) == 689 and P.inverse_units(512, 256, 2) == 1 and P.inverse_units(512, 64, 2) == 1
+    assert P.inverse_units(512, 256, 3) == 2 and P.inverse_units(512, 128, 3) == 1 and P.inverse_units(2048, 512, 345) == 344
+    for n, h in P.INV_OTHER:
+        lead = (n // 2) // h
+        for T in range(2, 70):
+            # every valid block lies in one of the pairs, and the last pair holds one
+            units = P.inverse_units(n, h, T)
+            if n == 512:
+                first, last = lead // 2, lead // 2 + units - 1
+                assert 2 * first <= lead and 2 * last <= lead + T - 2 <= 2 * last + 1
+            for v in (8, 9, 13, P.ONE_RUN):
+                P.inv_classes(n, h, v, T)                  # asserts that the runs store every hop exactly once
+    assert P.default_inverse_plan(2048, 512, 1024, 345) == (344, 172, 2)
+    assert P.default_inverse_plan(4096, 1024, 1024, 173) == (172, 86, 2)
+    assert P.default_inverse_plan(512, 128, 1024, 1379) == (689, 173, 4)
+    assert P.default_inverse_plan(2048, 512, 3, 5) == (4, 4, 1) and P.default_inverse_plan(512, 128, 3, 100) == (50, 16, 4)
+    assert P.inverse_grid(3, 5) == 4 and P.inverse_grid(1024, 2) == 512
+
+
+def test_inverse_sweeps_reach_every_run_geometry():
+    assert set(P.INV_OTHER_SWEEPS) == set(P.INV_OTHER) and len(P.INV_OTHER) == 9
+    for (n, h), sweep in P.INV_OTHER_SWEEPS.items():
+        hit = set()
+        for v, T in sweep:
+            hit |= P.inv_classes(n, h, v, T)
+        want = P.inv_want_classes(n, h)
+        assert want <= hit, (n, h, sorted(want - hit))
+        if n // h == 2:
+            # the classes left out at hop n/2 do not exist there, whatever the clip
+            assert not any(P.hop_is_partial(n, h, T, q) for T in range(2, 200) for q in range(T - 1))
+        # the forcing can show: one cut that is neither the B = 3 default plan nor one run per clip
+        assert any(1 < P.forced_inverse_plan(n, h, v, T)[2] and
+                   P.forced_inverse_plan(n, h, v, T)[1:] != P.default_inverse_plan(n, h, 3, T)[1:] for v, T in sweep), (n, h)
+
+
+def test_full_batches_land_on_the_long_run_plans_and_small_shapes_on_the_floor():
+    for n, cases in P.INV_FULL_BATCH.items():
+        h = n // 4
+        (B1, L1), (B2, L2) = cases
+        assert B1 == 1024 and L1 == 176400 and B2 == (4096 if n == 512 else 2048)
+        units, per, nruns = P.default_inverse_plan(n, h, B1, 1 + L1 // h)
+        assert nruns == (4 if n == 512 else 2) and per > 64 and units - (nruns - 1) * per > 64    # long runs, long last run
+        assert P.default_inverse_plan(n, h, B2, 1 + L2 // h)[2] == 1
+        # the forced 8-unit cut those outputs are compared with is a different plan
+        assert P.forced_inverse_plan(n, h, 8, 1 + L1 // h)[1] == 8 and P.forced_inverse_plan(n, h, 8, 1 + L2 // h)[2] > 1
+        # the record of the gap: every inverse launch of the size tests is runs of exactly the floor, or one run
+        floor = 16 if n == 512 else 8
+        for B, T, hop in P.INV_SMALL_SHAPES[n]:
+            assert B <= 5
+            units, per, nruns = P.default_inverse_plan(n, hop, B, T)
+            assert per == floor or nruns == 1, (n, B, T, hop)
+
+
+def test_two_pass_frame_plan():
+    assert P.frames_per_block_2k_4k(15) == 4 and P.frames_per_block_2k_4k(8192) == 4 and P.frames_per_block_2k_4k(8193) == 8
+    for n, h in P.TWO_PASS_HOPS:
+        assert h not in (n // 8, n // 4, n // 2)            # no fused kernel takes these hops
+    assert {n % h == 0 for n, h in P.TWO_PASS_HOPS} == {True, False}

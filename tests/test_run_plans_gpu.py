@@ -5,7 +5,9 @@ batch size and the device's occupancy, so a test shape alone reaches one plan pe
 AT_VARIANT_ISTFT_TILE make the cut a test input: the sweeps of plan_cases.py (their geometry coverage is checked on the CPU
 by test_plan_cases_cpu.py) run each kernel at short last runs, runs in the reflect-padded tail, last tiles of 1-3 frames,
 waves of 0-2 frames, and hold the result bit for bit to one run per clip (README: bit-identical whatever batch a clip
-rides in), with one oracle check per form."""
+rides in), with one oracle check per form.  The fused inverses at n_fft 512 / 2048 / 4096 get the same sweep with a
+float64 oracle check per geometry class, their full-batch default plans are held to the forced 8-unit cut, and the
+two-pass inverse of 2048 / 4096 runs at the hops no fused kernel takes."""
 import numpy as np
 import pytest
 import torch
@@ -285,3 +287,116 @@ def test_512_half_pair_starting_a_run(dev):
         assert last[1] - last[0] == 1 and T % 2 == 1 and T == 1 + L // 128
         assert torch.equal(X, planned(P.ONE_RUN, fn)), (T, L)
         assert rel_max(cpu(X), O.stft_forward(x.cpu(), w.cpu(), 512, 128).numpy()) < TOL
+
+
+# ---- fused inverses at n_fft 512 / 2048 / 4096 --------------------------------------------------------------------------
+def _inverse_windows(n_fft, hop, dev):
+    """[(name, synthesis window, envelope table)] of STFT (Hann) and DGT (dual of the Gaussian)."""
+    out = []
+    for cls in (A.STFT, A.DGT):
+        m = cls(n_fft=n_fft, hop_length=hop).to(dev)
+        out.append((cls.__name__, m.inv_window[:n_fft], m._env16 if m._env16.numel() else None))
+    return out
+
+
+@pytest.mark.parametrize("n_fft,hop", P.INV_OTHER)
+def test_fused_inverse_512_2048_4096_every_run_length(dev, n_fft, hop):
+    """istft512_ola_kernel (runs of frame pairs), istft2048_ola_kernel and istft4096_ola_kernel (runs of output hops) at
+    hop n/8, n/4, n/2, complex and polar input (phases of about 3e4 rad: the big-argument reduction), STFT and DGT
+    windows: every cut of INV_OTHER_SWEEPS -- single runs, last runs of 1-7 units, runs that hold only the clip's partially
+    overlapped trailing hops, clips of at most R frames, a run that starts at the final half pair -- is bit for bit one run
+    per clip.  Two cuts can share a fault, so the first cut that reaches each geometry class is also held to torch.istft in
+    float64: complex input at 1e-5, polar input (|X|, angle X) at 2e-5."""
+    g = torch.Generator(device=dev).manual_seed(n_fft + hop)
+    F = n_fft // 2 + 1
+    sweep = P.INV_OTHER_SWEEPS[(n_fft, hop)]
+    Xall = torch.randn(B, max(T for _, T in sweep), F, 2, device=dev, generator=g)
+    windows = _inverse_windows(n_fft, hop, dev)
+    seen = {name: set() for name, _, _ in windows}
+    for T in sorted({T for _, T in sweep}):
+        X = torch.view_as_complex(Xall[:, :T].contiguous())
+        mag, ph = Xall[:, :T, :, 0].abs().contiguous(), (Xall[:, :T, :, 1] * 3e4).contiguous()
+        amag, aph = X.abs(), X.angle()
+        for name, w, env in windows:
+            assert env is not None
+            cplx = lambda: ops.istft(X, w, n_fft, hop, env16=env)                            # noqa: E731
+            polar = lambda: ops.istft(None, w, n_fft, hop, env16=env, mag=mag, phase=ph)     # noqa: E731
+            one_c, one_p = planned(P.ONE_RUN, cplx), planned(P.ONE_RUN, polar)
+            assert one_c.shape == (B, hop * (T - 1))
+            yr = None
+            for v in [v for v, t in sweep if t == T]:
+                yc = planned(v, cplx)
+                assert torch.equal(yc, one_c), (name, v, T)
+                assert torch.equal(planned(v, polar), one_p), (name, "polar", v, T)
+                new = P.inv_classes(n_fft, hop, v, T) - seen[name]
+                if new:
+                    seen[name] |= new
+                    if yr is None:
+                        yr = O.istft(X.cpu().to(torch.complex128), w.cpu().double(), n_fft, hop).numpy()
+                    e_c = rel_max(cpu(yc), yr)
+                    e_p = rel_max(cpu(planned(v, lambda: ops.istft(None, w, n_fft, hop, env16=env, mag=amag, phase=aph))), yr)
+                    print("inverse %d/%d %s v=%d T=%d %s: complex %.3g polar %.3g" % (n_fft, hop, name, v, T, sorted(new), e_c, e_p))
+                    assert e_c < TOL, (name, v, T, sorted(new), e_c)
+                    assert e_p < 2e-5, (name, "polar", v, T, sorted(new), e_p)
+    assert all(P.inv_want_classes(n_fft, hop) <= s for s in seen.values())
+
+
+@pytest.mark.parametrize("case", [0, 1], ids=["1024_clips", "one_run_per_clip"])
+@pytest.mark.parametrize("n_fft", [512, 2048, 4096])
+def test_fused_inverse_512_2048_4096_full_batch(dev, n_fft, case):
+    """The plans that ship, at hop n/4: 1024 clips of 4 s (what bench.py times under other_sizes: two runs of 172 / 86
+    hops per clip at 2048 / 4096, four runs of 173 frame pairs at 512) and the smallest batch that gets one run per clip.
+    The whole output is bit for bit the forced 8-unit cut of the same input; clips {0, B/2 - 1, B - 1} against torch.istft in
+    float64 at 1e-5, and each of them alone (a single clip is cut at the launcher's floor) bit for bit the clip inside the
+    batch -- STFT and DGT windows."""
+    Bf, L = P.INV_FULL_BATCH[n_fft][case]
+    hop = n_fft // 4
+    g = torch.Generator(device=dev).manual_seed(n_fft + case)
+    x = torch.randn(Bf, L, device=dev, generator=g) * 0.1
+    X = A.STFT(n_fft=n_fft, hop_length=hop).to(dev)(x)
+    del x
+    T = X.shape[1]
+    assert T == 1 + L // hop
+    units, per, nruns = P.default_inverse_plan(n_fft, hop, Bf, T)
+    assert nruns == (1 if case else 4 if n_fft == 512 else 2) and (case or per > 64)
+    ids = [0, Bf // 2 - 1, Bf - 1]
+    Xi = X[ids].contiguous()
+    for name, w, env in _inverse_windows(n_fft, hop, dev):
+        y = ops.istft(X, w, n_fft, hop, env16=env)
+        assert y.shape == (Bf, hop * (T - 1))
+        assert torch.equal(y, planned(8, lambda: ops.istft(X, w, n_fft, hop, env16=env))), name
+        err = rel_max(cpu(y[ids]), O.istft(Xi.cpu().to(torch.complex128), w.cpu().double(), n_fft, hop).numpy())
+        print("inverse %d/%d B=%d %s: runs of %d x %d, oracle %.3g" % (n_fft, hop, Bf, name, nruns, per, err))
+        assert err < TOL, (name, err)
+        for j, k in enumerate(ids):
+            assert torch.equal(ops.istft(Xi[j:j + 1], w, n_fft, hop, env16=env)[0], y[k]), (name, k)
+        del y
+
+
+@pytest.mark.parametrize("n_fft,hop", P.TWO_PASS_HOPS)
+def test_two_pass_inverse_2048_4096(dev, n_fft, hop):
+    """irfft2048_frames_kernel / irfft4096_frames_kernel + the overlap-add gather as an istft: hop n/16 (STFT and DGT)
+    and hops that do not divide n_fft (STFT), complex at 1e-5 and polar at 2e-5 against torch.istft in float64.  Then a
+    launch of more than 8192 frames, where a workgroup's waves take more than one frame each: three clips against the
+    oracle, and every clip bit for bit what launches of three clips give."""
+    g = torch.Generator(device=dev).manual_seed(n_fft + hop)
+    for cls in ((A.STFT, A.DGT) if n_fft % hop == 0 else (A.STFT,)):
+        m = cls(n_fft=n_fft, hop_length=hop).to(dev)
+        assert m._env16.numel() == 0                       # no fused kernel for this hop
+        w = m.inv_window[:n_fft].cpu().double()
+        for Bs, T in ((3, 41), (24, 401)):
+            x = torch.randn(Bs, hop * (T - 1) + 17, device=dev, generator=g) * 0.1
+            X = m(x)
+            assert X.shape == (Bs, T, n_fft // 2 + 1)
+            assert (P.frames_per_block_2k_4k(Bs * T) > 4) == (Bs == 24)
+            y = m.invert(X)
+            assert y.shape == (Bs, hop * (T - 1))
+            ids = [0, Bs // 2, Bs - 1]
+            yr = O.istft(X[ids].cpu().to(torch.complex128), w, n_fft, hop).numpy()
+            e_c = rel_max(cpu(y[ids]), yr)
+            e_p = rel_max(cpu(m._istft(mag=X.abs(), phase=X.angle())[ids]), yr)
+            print("two-pass %d/%d %s B=%d T=%d: complex %.3g polar %.3g" % (n_fft, hop, cls.__name__, Bs, T, e_c, e_p))
+            assert e_c < TOL and e_p < 2e-5, (cls.__name__, Bs, T, e_c, e_p)
+            if Bs == 24:
+                small = torch.cat([m.invert(X[k:k + 3].contiguous()) for k in range(0, Bs, 3)])
+                assert torch.equal(y, small), cls.__name__
