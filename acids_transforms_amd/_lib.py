@@ -38,6 +38,7 @@ _SIGNATURES = {
     "at_istft_workspace_bytes": [c_i64, c_i64, c_int, c_int],
     "at_istft": [c_f, c_f, c_f, c_i64, c_i64, c_int, c_int, c_f, c_f, c_f, c_f, c_sz, c_f],
     "at_irfft_frames": [c_f, c_f, c_f, c_i64, c_int, c_f, c_f, c_f],
+    "at_irfft_frames_streams": [c_f, c_f, c_f, c_i64, c_i64, c_int, c_f, c_f, c_f],
     "at_angle": [c_f, c_i64, c_f, c_f],
     "at_phase_scan": [c_f, c_f, c_i64, c_i64, c_i64, c_int, c_int, c_f, c_f, c_f, c_f, c_f],
     "at_phase_integrate": [c_f, c_i64, c_i64, c_i64, c_int, c_int, c_f, c_f, c_f, c_f],

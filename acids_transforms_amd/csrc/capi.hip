@@ -53,12 +53,12 @@ int launch_irfft4096_frames(const float2*, const float*, const float*, long long
 // stft_small.hip (n_fft 256 / 128: four / eight frames per wave-level FFT)
 int launch_stft_small_fwd(int, const float*, long long, long long, long long, long long, int, int, const float*, const float2*,
                           const float2*, float2*, float*, hipStream_t);
-int launch_irfft_small_frames(int, const float2*, const float*, const float*, long long, const float*, const float2*,
-                              const float2*, float*, hipStream_t);
+int launch_irfft_small_frames(int, const float2*, const float*, const float*, long long, long long, const float*,
+                              const float2*, const float2*, float*, hipStream_t);
 // stft512.hip
 int launch_stft512_fwd(const float*, long long, long long, long long, long long, int, int, const float*, const float2*,
                        const float2*, float2*, float*, hipStream_t);
-int launch_irfft512_frames(const float2*, const float*, const float*, long long, const float*, const float2*,
+int launch_irfft512_frames(const float2*, const float*, const float*, long long, long long, const float*, const float2*,
                            const float2*, float*, hipStream_t);
 int launch_istft512_ola(const float2*, const float*, const float*, long long, long long, int, const float*, const float*,
                         const float2*, const float2*, float*, hipStream_t);
@@ -406,13 +406,13 @@ int at_istft(const float* X_complex, const float* mag, const float* phase, int64
     const float2* tw = twiddles_for_current_device();
     const float2* tw2k = tw2048_for_current_device();
     if (!tw || !tw2k) return AT_ENOTINIT;
-    rc = launch_irfft_small_frames(n_fft, (const float2*)X_complex, mag, phase, B * T, inv_window, tw,
+    rc = launch_irfft_small_frames(n_fft, (const float2*)X_complex, mag, phase, B * T, T, inv_window, tw,
                                    tw2k + (n_fft == 256 ? 1280 : 1664), (float*)workspace, s);
   } else if (n_fft == 512 && (((uintptr_t)inv_window) & 7) == 0 && (((uintptr_t)workspace) & 7) == 0) {
     const float2* tw = twiddles_for_current_device();
     const float2* tw2k = tw2048_for_current_device();
     if (!tw || !tw2k) return AT_ENOTINIT;
-    rc = launch_irfft512_frames((const float2*)X_complex, mag, phase, B * T, inv_window, tw, tw2k + 1024, (float*)workspace, s);
+    rc = launch_irfft512_frames((const float2*)X_complex, mag, phase, B * T, T, inv_window, tw, tw2k + 1024, (float*)workspace, s);
   } else if (fft_mixed(n_fft)) {
     rc = launch_irfft_mixed((const float2*)X_complex, mag, phase, B * T, n_fft, inv_window, (float*)workspace, s);
   } else {
@@ -438,10 +438,14 @@ int at_istft_griffinlim(const float* mag, const float* rebuilt_complex, const fl
                               (hipStream_t)stream, tprev, mom);
 }
 
-int at_irfft_frames(const float* X_complex, const float* mag, const float* phase, int64_t nframes, int n_fft,
-                    const float* inv_window, float* frames, void* stream) {
+// frames_per_stream: at n_fft 128 / 256 / 512 several frames share one register FFT (stft_small.hip, stft512.hip), and
+// only frames of the same stream may: nothing outside a stream reaches its output.  The other sizes take one frame per
+// transform and ignore it.
+int at_irfft_frames_streams(const float* X_complex, const float* mag, const float* phase, int64_t nframes,
+                            int64_t frames_per_stream, int n_fft, const float* inv_window, float* frames, void* stream) {
   if (nframes < 0 || n_fft <= 0) return AT_EINVAL;
   if (nframes == 0) return AT_OK;
+  if (frames_per_stream <= 0 || nframes % frames_per_stream) return AT_EINVAL;
   if (!inv_window || !frames) return AT_EINVAL;
   if (!X_complex && !(mag && phase)) return AT_EINVAL;
   if (!fft_size_ok(n_fft)) return AT_EUNSUPPORTED;
@@ -467,18 +471,27 @@ int at_irfft_frames(const float* X_complex, const float* mag, const float* phase
     const float2* tw = twiddles_for_current_device();
     const float2* tw2k = tw2048_for_current_device();
     if (!tw || !tw2k) return AT_ENOTINIT;
-    return launch_irfft_small_frames(n_fft, (const float2*)X_complex, mag, phase, nframes, inv_window, tw,
+    return launch_irfft_small_frames(n_fft, (const float2*)X_complex, mag, phase, nframes, frames_per_stream, inv_window, tw,
                                      tw2k + (n_fft == 256 ? 1280 : 1664), frames, s);
   }
   if (n_fft == 512 && (((uintptr_t)inv_window) & 7) == 0 && (((uintptr_t)frames) & 7) == 0) {
     const float2* tw = twiddles_for_current_device();
     const float2* tw2k = tw2048_for_current_device();
     if (!tw || !tw2k) return AT_ENOTINIT;
-    return launch_irfft512_frames((const float2*)X_complex, mag, phase, nframes, inv_window, tw, tw2k + 1024, frames, s);
+    return launch_irfft512_frames((const float2*)X_complex, mag, phase, nframes, frames_per_stream, inv_window, tw, tw2k + 1024,
+                                  frames, s);
   }
   if (fft_mixed(n_fft))
     return launch_irfft_mixed((const float2*)X_complex, mag, phase, nframes, n_fft, inv_window, frames, s);
   return launch_irfft_generic((const float2*)X_complex, mag, phase, nframes, n_fft, inv_window, frames, s);
+}
+
+// the whole call is one stream
+int at_irfft_frames(const float* X_complex, const float* mag, const float* phase, int64_t nframes, int n_fft,
+                    const float* inv_window, float* frames, void* stream) {
+  if (nframes < 0) return AT_EINVAL;
+  return at_irfft_frames_streams(X_complex, mag, phase, nframes, nframes > 0 ? nframes : 1, n_fft, inv_window, frames,
+                                 stream);
 }
 
 

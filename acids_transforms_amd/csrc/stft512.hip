@@ -6,7 +6,10 @@
 // ran on the workgroup-per-frame LDS Stockham kernel of stft_generic.hip.
 //
 // A 512-point real transform is a 256-point complex FFT of a[n] = x[2n] + i x[2n+1] plus the real split.  Two
-// frames A, B (consecutive frame indices) share one 512-point FFT: with y[2n] = a[n], y[2n+1] = b[n],
+// frames A, B -- frames 2 i and 2 i + 1 of ONE clip; the last frame of an odd-T clip is paired with exact zeros, never
+// with the next clip's first frame: the pair's rounding scales with its louder member and a NaN reaches both, so
+// nothing outside a clip (inverse of pre-framed spectra: outside one stream) may sit in its pairs; see stft_small.hip
+// and tests/test_clip_isolation_gpu.py -- share one 512-point FFT: with y[2n] = a[n], y[2n+1] = b[n],
 //   Y[k] = A[k] + W512^k B[k],   Y[k+256] = A[k] - W512^k B[k]          (k = 0 .. 255)
 // so A[k] = (Y[k] + Y[k+256]) / 2 and B[k] = (Y[k] - Y[k+256]) conj(W512^k) / 2 -- lane-local, because the FFT
 // leaves Y[lane + 64 m] in register m and k + 256 is register m + 4 of the same lane.  Even lanes load frame A, odd
@@ -41,7 +44,7 @@ struct P5 {
   const float* phase;
   float* phase_out;
   float* y;              // inverse: (frames, 512)
-  long long L, clip_stride, T, total_frames, pairs_per_block;
+  long long L, clip_stride, T, n_clips, pairs_per_clip, pairs_per_block;   // T: frames per clip (inverse: per stream)
   int hop, center;
 };
 
@@ -51,15 +54,15 @@ __device__ __forceinline__ long long reflect5(long long i, long long L) {
   return i;
 }
 
-// this lane's 8 complex samples of ITS frame (frame f: even lanes of the pair's first frame, odd lanes the second):
-// q[j] = (x[s + 2 n], x[s + 2 n + 1]), n = (lane >> 1) + 32 j; frames past the end read as zeros
-__device__ __forceinline__ void load_half_frame5(const P5& p, long long f, int lane, float2 (&q)[8]) {
-  if (f >= p.total_frames) {
+// this lane's 8 complex samples of ITS frame (frame t of clip b: even lanes of the pair's first frame, odd lanes the
+// second): q[j] = (x[s + 2 n], x[s + 2 n + 1]), n = (lane >> 1) + 32 j; the missing partner of a clip's last frame
+// (odd T) reads as exact zeros, never as the next clip's first frame
+__device__ __forceinline__ void load_half_frame5(const P5& p, long long b, long long t, int lane, float2 (&q)[8]) {
+  if (t >= p.T) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) q[j] = make_float2(0.f, 0.f);
     return;
   }
-  const long long b = f / p.T, t = f - b * p.T;
   const float* clip = p.x + b * p.clip_stride;
   const long long start = t * (long long)p.hop - (p.center ? N5 / 2 : 0);
   const bool interior = (start >= 0) && (start + N5 <= p.L);
@@ -118,20 +121,25 @@ __global__ __launch_bounds__(64 * W5) void stft512_fwd_kernel(P5 p) {
   }
 #pragma unroll
   for (int j = 0; j < 8; ++j) win[j] = reinterpret_cast<const float2*>(p.window)[(lane >> 1) + 32 * j];
-  const long long n_pairs = (p.total_frames + 1) / 2;
+  const long long n_pairs = p.n_clips * p.pairs_per_clip;
   const long long pr_begin = (long long)blockIdx.x * p.pairs_per_block;
   long long pr_end = pr_begin + p.pairs_per_block;
   if (pr_end > n_pairs) pr_end = n_pairs;
   const v2f hh = {0.5f, 0.5f};
 
+  // pair pr is frames 2 i, 2 i + 1 of clip b, pr = b pairs_per_clip + i
+  auto load_pair = [&](long long q, float2 (&dst)[8]) {
+    const long long b = q / p.pairs_per_clip;
+    load_half_frame5(p, b, 2 * (q - b * p.pairs_per_clip) + (lane & 1), lane, dst);
+  };
   long long pr = pr_begin + wave;
   float2 nxt[8];
-  if (pr < pr_end) load_half_frame5(p, 2 * pr + (lane & 1), lane, nxt);
+  if (pr < pr_end) load_pair(pr, nxt);
   for (; pr < pr_end; pr += W5) {
     v2f y[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) y[j] = (v2f){nxt[j].x * win[j].x, nxt[j].y * win[j].y};
-    if (pr + W5 < pr_end) load_half_frame5(p, 2 * (pr + W5) + (lane & 1), lane, nxt);
+    if (pr + W5 < pr_end) load_pair(pr + W5, nxt);
     fft512<false>(y, tw, lds, lane);
     // unpack the two 256-point spectra (halved: the real split wants A/2): HA = (Y[k] + Y[k+256]) / 4 ...
     v2f ha[4], hb[4];
@@ -145,10 +153,12 @@ __global__ __launch_bounds__(64 * W5) void stft512_fwd_kernel(P5 p) {
     v2f pa[4], pb[4];
     mirror256(ha, pa, lane);
     mirror256(hb, pb, lane);
-    const long long fa = 2 * pr, fb = 2 * pr + 1;
+    const long long cb = pr / p.pairs_per_clip;
+    const long long ta = 2 * (pr - cb * p.pairs_per_clip);
+    const long long fa = cb * p.T + ta, fb = fa + 1;
     float2* rowa = p.X + fa * F5;
     float2* rowb = rowa + F5;
-    const bool has_b = fb < p.total_frames;
+    const bool has_b = ta + 1 < p.T;
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
       const v2f xa = add_mi(add_conj(ha[m], pa[m]), cmul_v(sub_conj(ha[m], pa[m]), w5[m]));
@@ -447,14 +457,18 @@ __global__ __launch_bounds__(64 * W5) void irfft512_frames_kernel(P5 p) {
     const float2 w = reinterpret_cast<const float2*>(p.window)[(lane >> 1) + 32 * j];
     win[j] = make_float2(w.x * scale, w.y * scale);
   }
-  const long long n_pairs = (p.total_frames + 1) / 2;
+  const long long n_pairs = p.n_clips * p.pairs_per_clip;
   const long long pr_begin = (long long)blockIdx.x * p.pairs_per_block;
   long long pr_end = pr_begin + p.pairs_per_block;
   if (pr_end > n_pairs) pr_end = n_pairs;
   for (long long pr = pr_begin + wave; pr < pr_end; pr += W5) {
+    // pair pr is frames 2 i, 2 i + 1 of clip cb; a clip's last frame (odd T) is paired with a zero spectrum
+    const long long cb = pr / p.pairs_per_clip;
+    const long long ta = 2 * (pr - cb * p.pairs_per_clip);
+    const long long fa = cb * p.T + ta;
     v2f a[4], b[4];
-    load_split5<POLAR>(p, 2 * pr, 2 * pr < p.total_frames, lane, w5, a);
-    load_split5<POLAR>(p, 2 * pr + 1, 2 * pr + 1 < p.total_frames, lane, w5, b);
+    load_split5<POLAR>(p, fa, true, lane, w5, a);
+    load_split5<POLAR>(p, fa + 1, ta + 1 < p.T, lane, w5, b);
     // Y[k] = A + W512^k B, Y[k+256] = A - W512^k B
     v2f y[8];
 #pragma unroll
@@ -465,8 +479,8 @@ __global__ __launch_bounds__(64 * W5) void irfft512_frames_kernel(P5 p) {
     }
     fft512<true>(y, tw, lds, lane);
     // y[lane + 64 j]: even lanes hold frame A's complex sample (lane >> 1) + 32 j, odd lanes frame B's
-    const long long f = 2 * pr + (lane & 1);
-    if (f < p.total_frames) {
+    const long long f = fa + (lane & 1);
+    if (ta + (lane & 1) < p.T) {
       float2* dst = reinterpret_cast<float2*>(p.y + f * N5);
 #pragma unroll
       for (int j = 0; j < 8; ++j) dst[(lane >> 1) + 32 * j] = make_float2(y[j].x * win[j].x, y[j].y * win[j].y);
@@ -655,7 +669,9 @@ static long long pairs_per_block_5(long long npairs) {
 // (MelSpectrogram / MFCC at the usual speech setting; mel.py:43-44, 68-73 behind stft.py:98-104).  The forward kernel
 // with both spectra of a frame pair kept in registers: |X|^p of frames A and B go into two LDS rows of the wave and the
 // band walk reads every weight quad once for both rows.  Output row-major, or channel-major through the eight-frame
-// register window with sector-aligned flushes (mel_banded.hip).  A wave takes a run of consecutive frame pairs.
+// register window with sector-aligned flushes (mel_banded.hip).  A wave takes a run of consecutive frame pairs of the
+// per-clip pair list (B ceil(T / 2) pairs): its frames stay consecutive, the half pair that ends an odd-T clip emits
+// one frame.
 // ---------------------------------------------------------------------------
 struct P5Mel {
   const float* x;
@@ -665,7 +681,7 @@ struct P5Mel {
   float* feat;           // (B*T, N) or (B, N, T)
   const float* offset;
   const float* scale;
-  long long L, clip_stride, T, total_frames, pairs_per_wave;
+  long long L, clip_stride, T, n_clips, pairs_per_clip, pairs_per_wave;
   BandBank bank;
   int hop, contrast, power2, channel_major, row_floats, table_floats;
   float eps;
@@ -673,7 +689,7 @@ struct P5Mel {
 
 __device__ __forceinline__ float contrast5(float v, int mode, float eps) {
   switch (mode) {
-    case C_LOG1P: return logf(1.0f + v);
+    case C_LOG1P: return log1pf(v);      // not logf(1 + v): the sum rounds v to 6e-8, 3e-5 of a quiet clip's features
     case C_LOG: return logf(fmaxf(v, eps));
     case C_LOG10: return log10f(fmaxf(v, eps));
     default: return v;
@@ -708,7 +724,7 @@ __global__ __launch_bounds__(64 * W5) void stft512_mel_kernel(P5Mel p) {
   }
 #pragma unroll
   for (int j = 0; j < 8; ++j) win[j] = reinterpret_cast<const float2*>(p.window)[(lane >> 1) + 32 * j];
-  const long long n_pairs = (p.total_frames + 1) / 2;
+  const long long n_pairs = p.n_clips * p.pairs_per_clip;
   const long long pr_begin = ((long long)blockIdx.x * W5 + wave) * p.pairs_per_wave;
   long long pr_end = pr_begin + p.pairs_per_wave;
   if (pr_end > n_pairs) pr_end = n_pairs;
@@ -720,10 +736,15 @@ __global__ __launch_bounds__(64 * W5) void stft512_mel_kernel(P5Mel p) {
     sc = *p.scale;
   }
   P5 lp = {};
-  lp.x = p.x; lp.L = p.L; lp.clip_stride = p.clip_stride; lp.T = p.T; lp.total_frames = p.total_frames; lp.hop = p.hop;
+  lp.x = p.x; lp.L = p.L; lp.clip_stride = p.clip_stride; lp.T = p.T; lp.hop = p.hop;
   lp.center = 1;
-  long long f_last = 2 * pr_end - 1;                     // last frame of this wave's run
-  if (f_last > p.total_frames - 1) f_last = p.total_frames - 1;
+  // pair pr is frames 2 i, 2 i + 1 of clip b, pr = b pairs_per_clip + i: a pair never holds frames of two clips
+  long long pb = pr_begin / p.pairs_per_clip, pi = pr_begin - pb * p.pairs_per_clip;
+  long long f_last;                                      // last frame of this wave's run
+  {
+    const long long bl = (pr_end - 1) / p.pairs_per_clip, il = (pr_end - 1) - bl * p.pairs_per_clip;
+    f_last = bl * p.T + (2 * il + 1 < p.T ? 2 * il + 1 : p.T - 1);
+  }
 
   float cm[CMW > 0 ? CMW : 1][8];
   long long e_next[CMW > 0 ? CMW : 1];
@@ -736,7 +757,7 @@ __global__ __launch_bounds__(64 * W5) void stft512_mel_kernel(P5Mel p) {
     for (int k = 0; k < 8; ++k) cm[q][k] = 0.f;
   }
   bool e_valid = false;
-  long long cb = (2 * pr_begin) / p.T, ct = 2 * pr_begin - cb * p.T;
+  long long cb = pb, ct = 2 * pi;
   int fq[CMW > 0 ? CMW : 1];
   if (CMW > 0) {
 #pragma unroll
@@ -799,13 +820,19 @@ __global__ __launch_bounds__(64 * W5) void stft512_mel_kernel(P5Mel p) {
   };
 
   float2 nxt[8];
-  load_half_frame5(lp, 2 * pr_begin + (lane & 1), lane, nxt);
+  load_half_frame5(lp, pb, 2 * pi + (lane & 1), lane, nxt);
   for (long long pr = pr_begin; pr < pr_end; ++pr) {
+    const long long fa = pb * p.T + 2 * pi;
+    const bool has_b = 2 * pi + 1 < p.T;
+    if (++pi == p.pairs_per_clip) {
+      pi = 0;
+      ++pb;
+    }
     wave_priority<3>();        // transform > epilogue, as in stft1024.hip
     v2f y[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) y[j] = (v2f){nxt[j].x * win[j].x, nxt[j].y * win[j].y};
-    if (pr + 1 < pr_end) load_half_frame5(lp, 2 * (pr + 1) + (lane & 1), lane, nxt);
+    if (pr + 1 < pr_end) load_half_frame5(lp, pb, 2 * pi + (lane & 1), lane, nxt);
     fft512<false>(y, tw, lds, lane);
     v2f ha[4], hb[4];
 #pragma unroll
@@ -880,8 +907,8 @@ __global__ __launch_bounds__(64 * W5) void stft512_mel_kernel(P5Mel p) {
         fb_q[q] = vb;
       }
     }
-    emit(2 * pr, fa_q, n_acc);
-    if (2 * pr + 1 < p.total_frames) emit(2 * pr + 1, fb_q, n_acc);
+    emit(fa, fa_q, n_acc);
+    if (has_b) emit(fa + 1, fb_q, n_acc);
     wave_lds_sync();
   }
 }
@@ -894,7 +921,7 @@ int launch_stft512_mel(const float* x, long long B, long long L, long long clip_
   if (nframes == 0) return 0;
   P5Mel p = {};
   p.x = x; p.window = window; p.tw = tw; p.tw512 = tw512; p.feat = feat; p.offset = offset; p.scale = scale;
-  p.L = L; p.clip_stride = clip_stride; p.T = T; p.total_frames = nframes; p.bank = *bank; p.hop = hop;
+  p.L = L; p.clip_stride = clip_stride; p.T = T; p.n_clips = B; p.pairs_per_clip = (T + 1) / 2; p.bank = *bank; p.hop = hop;
   p.contrast = contrast; p.power2 = power2; p.channel_major = channel_major; p.eps = eps;
   int max_walk = 0, table_floats = 0;
   for (int q = 0; q < bank->n_passes; ++q) {
@@ -905,7 +932,7 @@ int launch_stft512_mel(const float* x, long long B, long long L, long long clip_
   p.row_floats = (F5 + max_walk + 63) / 64 * 64;
   const size_t lds = sizeof(float) * ((size_t)2 * W5 * p.row_floats + table_floats) + sizeof(int) * (size_t)2 * 64 * bank->n_passes;
   if (lds > 48 * 1024) return -2;
-  const long long npairs = (nframes + 1) / 2;
+  const long long npairs = B * p.pairs_per_clip;
   long long ppw = (npairs + 256LL * 8 * W5 - 1) / (256LL * 8 * W5);
   if (ppw < 4) ppw = 4;
   if (const long long forced = forced_row_run(npairs)) ppw = forced;     // AT_VARIANT_ROW_RUN (tests)
@@ -926,7 +953,7 @@ int launch_stft512_fwd(const float* x, long long B, long long L, long long clip_
   if (nframes == 0) return 0;
   P5 p = {};
   p.x = x; p.window = window; p.tw = tw; p.tw512 = tw512; p.X = out; p.phase_out = phase;
-  p.L = L; p.clip_stride = clip_stride; p.T = T; p.total_frames = nframes; p.hop = hop; p.center = center;
+  p.L = L; p.clip_stride = clip_stride; p.T = T; p.n_clips = B; p.pairs_per_clip = (T + 1) / 2; p.hop = hop; p.center = center;
   // the sliding-window / aligned-stream kernel: torch.stft's framing at hop n/4, 8-byte aligned clips, a 512-byte aligned
   // output, no phase side output
   if (center && hop == 128 && !phase && L >= 512 && (clip_stride & 1) == 0 && (((uintptr_t)x) & 7) == 0 &&
@@ -943,7 +970,7 @@ int launch_stft512_fwd(const float* x, long long B, long long L, long long clip_
     hipLaunchKernelGGL(stft512_run_fwd_kernel, dim3((unsigned)((waves + W5R - 1) / W5R)), dim3(64 * W5R), 0, stream, q);
     return hipGetLastError() == hipSuccess ? 0 : -5;
   }
-  const long long npairs = (nframes + 1) / 2;
+  const long long npairs = B * p.pairs_per_clip;
   p.pairs_per_block = pairs_per_block_5(npairs);
   const long long blocks = (npairs + p.pairs_per_block - 1) / p.pairs_per_block;
   if (phase) hipLaunchKernelGGL(stft512_fwd_kernel<true>, dim3((unsigned)blocks), dim3(64 * W5), 0, stream, p);
@@ -951,13 +978,15 @@ int launch_stft512_fwd(const float* x, long long B, long long L, long long clip_
   return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 
-int launch_irfft512_frames(const float2* X, const float* mag, const float* phase, long long nframes, const float* window,
+int launch_irfft512_frames(const float2* X, const float* mag, const float* phase, long long nframes,
+                           long long frames_per_clip, const float* window,
                            const float2* tw, const float2* tw512, float* frames, hipStream_t stream) {
   if (nframes == 0) return 0;
   P5 p = {};
   p.X = const_cast<float2*>(X); p.mag = mag; p.phase = phase; p.window = window; p.tw = tw; p.tw512 = tw512; p.y = frames;
-  p.total_frames = nframes;
-  const long long npairs = (nframes + 1) / 2;
+  if (frames_per_clip <= 0 || nframes % frames_per_clip) return -2;
+  p.T = frames_per_clip; p.n_clips = nframes / frames_per_clip; p.pairs_per_clip = (frames_per_clip + 1) / 2;
+  const long long npairs = p.n_clips * p.pairs_per_clip;
   p.pairs_per_block = pairs_per_block_5(npairs);
   const long long blocks = (npairs + p.pairs_per_block - 1) / p.pairs_per_block;
   if (X) hipLaunchKernelGGL(irfft512_frames_kernel<false>, dim3((unsigned)blocks), dim3(64 * W5), 0, stream, p);

@@ -13,6 +13,16 @@
 // one lane recovers K W512^(r k) A_r[k] for every r -- after it EVERY lane holds its bins of all K spectra, so each
 // frame's row is stored by a full wave.  Then the real split of each frame (partner A_r[M - k]: lane 64 - lane), as
 // in the other sizes.  The inverse runs the same steps backwards.
+//
+// Groups are formed PER CLIP: group g of clip b holds its frames K g .. K g + K - 1 (slot r = frame index mod K), a
+// launch has B ceil(T / K) groups and the empty slots of a clip's last group are exact zeros (forward: zero samples;
+// inverse: zero spectra).  Every output of the shared transform carries rounding proportional to the LARGEST member of
+// its group, and a NaN in one member reaches all of them; with groups cut from the launch-wide frame index
+// (f = K g + r over all B T frames, as this file had it) a quiet clip next to a loud one came out wrong by 30 to 60
+// times the 1e-5 bar and a clip's bits depended on its place in the batch.  Now nothing outside a clip -- for the
+// inverse of pre-framed spectra: outside one stream of frames_per_clip frames -- reaches its output; within a clip a
+// frame still shares its rounding (and a NaN) with the up to K - 1 frames of its group.  Cost: ceil(T / K) K / T - 1
+// more transforms (0.1 % at 5513 frames per clip).  tests/shared_fft_cases.py, tests/test_clip_isolation_gpu.py.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -34,7 +44,7 @@ struct PSm {
   const float* phase;
   float* phase_out;
   float* y;              // inverse: (frames, N)
-  long long L, clip_stride, T, total_frames, groups_per_block;
+  long long L, clip_stride, T, n_clips, groups_per_clip, groups_per_block;   // T: frames per clip (inverse: per stream)
   int hop, center;
 };
 
@@ -61,14 +71,15 @@ __device__ __forceinline__ void dftK(v2f (&v)[K]) {
 }
 
 template <int K>
-__device__ __forceinline__ void load_lane_frame(const PSm& p, long long f, int lane, float2 (&q)[8]) {
+__device__ __forceinline__ void load_lane_frame(const PSm& p, long long g, int lane, float2 (&q)[8]) {
   constexpr int N = 1024 / K, PER = 64 / K;
-  if (f >= p.total_frames) {
+  const long long b = g / p.groups_per_clip;
+  const long long t = K * (g - b * p.groups_per_clip) + (lane % K);       // this lane's frame of clip b
+  if (t >= p.T) {                                 // an empty slot of the clip's last group: exact zeros
 #pragma unroll
     for (int j = 0; j < 8; ++j) q[j] = make_float2(0.f, 0.f);
     return;
   }
-  const long long b = f / p.T, t = f - b * p.T;
   const float* clip = p.x + b * p.clip_stride;
   const long long start = t * (long long)p.hop - (p.center ? N / 2 : 0);
   const bool interior = (start >= 0) && (start + N <= p.L);
@@ -128,7 +139,7 @@ __global__ __launch_bounds__(64 * WS) void stft_small_fwd_kernel(PSm p) {
   float2 win[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) win[j] = reinterpret_cast<const float2*>(p.window)[lane / K + PER * j];
-  const long long n_groups = (p.total_frames + K - 1) / K;
+  const long long n_groups = p.n_clips * p.groups_per_clip;
   const long long g_begin = (long long)blockIdx.x * p.groups_per_block;
   long long g_end = g_begin + p.groups_per_block;
   if (g_end > n_groups) g_end = n_groups;
@@ -136,12 +147,12 @@ __global__ __launch_bounds__(64 * WS) void stft_small_fwd_kernel(PSm p) {
 
   long long g = g_begin + wave;
   float2 nxt[8];
-  if (g < g_end) load_lane_frame<K>(p, K * g + (lane % K), lane, nxt);
+  if (g < g_end) load_lane_frame<K>(p, g, lane, nxt);
   for (; g < g_end; g += WS) {
     v2f y[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) y[j] = (v2f){nxt[j].x * win[j].x, nxt[j].y * win[j].y};
-    if (g + WS < g_end) load_lane_frame<K>(p, K * (g + WS) + (lane % K), lane, nxt);
+    if (g + WS < g_end) load_lane_frame<K>(p, g + WS, lane, nxt);
     fft512<false>(y, tw, lds, lane);
     // per m0: inverse K-point DFT over q of Y[k + M q] = K W512^(r k) A_r[k]; H_r = A_r / 2
     v2f h[K][Q];
@@ -156,10 +167,12 @@ __global__ __launch_bounds__(64 * WS) void stft_small_fwd_kernel(PSm p) {
       for (int r = 1; r < K; ++r) h[r][m0] = cmul_conj_v(c[r], wk[r - 1][m0]) * (v2f){inv2k, inv2k};
     }
     // real split of every frame: X[k] = (H + conj H') - i W_N^k (H - conj H'),  W_N^k = W512^((K/2) k)
+    const long long gb = g / p.groups_per_clip;
+    const long long t0 = K * (g - gb * p.groups_per_clip);     // the group's first frame of clip gb
 #pragma unroll
     for (int r = 0; r < K; ++r) {
-      const long long f = K * g + r;
-      if (f >= p.total_frames) break;            // wave-uniform
+      if (t0 + r >= p.T) break;                  // wave-uniform
+      const long long f = gb * p.T + t0 + r;
       v2f pm[Q];
       mirror_small<Q>(h[r], pm, lane);
       float2* row = p.X + f * F;
@@ -208,16 +221,18 @@ __global__ __launch_bounds__(64 * WS) void irfft_small_frames_kernel(PSm p) {
     const float2 w = reinterpret_cast<const float2*>(p.window)[lane / K + PER * j];
     win[j] = make_float2(w.x * scale, w.y * scale);
   }
-  const long long n_groups = (p.total_frames + K - 1) / K;
+  const long long n_groups = p.n_clips * p.groups_per_clip;
   const long long g_begin = (long long)blockIdx.x * p.groups_per_block;
   long long g_end = g_begin + p.groups_per_block;
   if (g_end > n_groups) g_end = n_groups;
   for (long long g = g_begin + wave; g < g_end; g += WS) {
+    const long long gb = g / p.groups_per_clip;
+    const long long t0 = K * (g - gb * p.groups_per_clip);     // the group's first frame of clip gb
     v2f a[K][Q];                                 // 2 A_r[k], then G_r = W512^(r k) 2 A_r
 #pragma unroll
     for (int r = 0; r < K; ++r) {
-      const long long f = K * g + r;
-      if (f >= p.total_frames) {                 // wave-uniform
+      const long long f = gb * p.T + t0 + r;
+      if (t0 + r >= p.T) {                       // wave-uniform: an empty slot of the clip's last group is a zero spectrum
 #pragma unroll
         for (int m0 = 0; m0 < Q; ++m0) a[r][m0] = (v2f){0.f, 0.f};
         continue;
@@ -267,8 +282,8 @@ __global__ __launch_bounds__(64 * WS) void irfft_small_frames_kernel(PSm p) {
       for (int q = 0; q < K; ++q) y[m0 + Q * q] = c[q];
     }
     fft512<true>(y, tw, lds, lane);
-    const long long f = K * g + (lane % K);
-    if (f < p.total_frames) {
+    const long long f = gb * p.T + t0 + (lane % K);
+    if (t0 + (lane % K) < p.T) {
       float2* dst = reinterpret_cast<float2*>(p.y + f * N);
 #pragma unroll
       for (int j = 0; j < 8; ++j) dst[lane / K + PER * j] = make_float2(y[j].x * win[j].x, y[j].y * win[j].y);
@@ -291,8 +306,9 @@ int launch_stft_small_fwd(int n_fft, const float* x, long long B, long long L, l
   const int K = 1024 / n_fft;
   PSm p = {};
   p.x = x; p.window = window; p.tw = tw; p.twk = twk; p.X = out; p.phase_out = phase;
-  p.L = L; p.clip_stride = clip_stride; p.T = T; p.total_frames = nframes; p.hop = hop; p.center = center;
-  const long long ngroups = (nframes + K - 1) / K;
+  p.L = L; p.clip_stride = clip_stride; p.T = T; p.n_clips = B; p.hop = hop; p.center = center;
+  p.groups_per_clip = (T + K - 1) / K;
+  const long long ngroups = B * p.groups_per_clip;
   p.groups_per_block = groups_per_block_sm(ngroups);
   const unsigned blocks = (unsigned)((ngroups + p.groups_per_block - 1) / p.groups_per_block);
   if (K == 4) {
@@ -308,13 +324,15 @@ int launch_stft_small_fwd(int n_fft, const float* x, long long B, long long L, l
 }
 
 int launch_irfft_small_frames(int n_fft, const float2* X, const float* mag, const float* phase, long long nframes,
-                              const float* window, const float2* tw, const float2* twk, float* frames, hipStream_t stream) {
+                              long long frames_per_clip, const float* window, const float2* tw, const float2* twk, float* frames, hipStream_t stream) {
   if (nframes == 0) return 0;
   const int K = 1024 / n_fft;
   PSm p = {};
   p.X = const_cast<float2*>(X); p.mag = mag; p.phase = phase; p.window = window; p.tw = tw; p.twk = twk; p.y = frames;
-  p.total_frames = nframes;
-  const long long ngroups = (nframes + K - 1) / K;
+  if (frames_per_clip <= 0 || nframes % frames_per_clip) return -2;
+  p.T = frames_per_clip; p.n_clips = nframes / frames_per_clip;
+  p.groups_per_clip = (frames_per_clip + K - 1) / K;
+  const long long ngroups = p.n_clips * p.groups_per_clip;
   p.groups_per_block = groups_per_block_sm(ngroups);
   const unsigned blocks = (unsigned)((ngroups + p.groups_per_block - 1) / p.groups_per_block);
   const bool polar = (X == nullptr);

@@ -112,7 +112,8 @@ def istft(X, inv_window, n_fft, hop, env16=None, mag=None, phase=None):
 
 
 def irfft_frames(X, inv_window, n_fft, mag=None, phase=None):
-    """(..., F) spectra -> (..., n_fft) windowed frames (no overlap-add)."""
+    """(..., n, F) spectra -> (..., n, n_fft) windowed frames (no overlap-add).  Each leading-index row of n frames is
+    one stream: frames share a register FFT (n_fft 128 / 256 / 512) within a stream only."""
     src = X if X is not None else mag
     require_device(src, inv_window)
     if X is not None:
@@ -127,8 +128,9 @@ def irfft_frames(X, inv_window, n_fft, mag=None, phase=None):
     for d in lead:
         n *= d
     out = torch.empty(tuple(lead) + (n_fft,), dtype=torch.float32, device=src.device)
-    check(lib().at_irfft_frames(ptr(X), ptr(mag), ptr(phase), n, n_fft, ptr(inv_window), ptr(out), stream_ptr()),
-          "at_irfft_frames")
+    per_stream = max(int(lead[-1]), 1) if len(lead) >= 2 else max(n, 1)
+    check(lib().at_irfft_frames_streams(ptr(X), ptr(mag), ptr(phase), n, per_stream, n_fft, ptr(inv_window), ptr(out),
+                                        stream_ptr()), "at_irfft_frames_streams")
     return out
 
 

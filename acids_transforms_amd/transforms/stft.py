@@ -26,7 +26,9 @@ def _as_clip_layout(x: torch.Tensor, n_fft: int):
 
     Returns (tensor, B, T, clip_stride, hop, L).  A `frame()` view (strides
     (..., Lbuf, hop, 1)) is passed through as overlapping clips; anything else is
-    made contiguous and treated as B*n one-frame clips.
+    made contiguous and treated as one clip of n back-to-back frames per stream
+    (hop = n_fft), so the frames that share a register FFT at n_fft 128 / 256 / 512
+    belong to the same stream.
     """
     if x.dim() >= 2 and x.stride(-1) == 1 and x.dim() >= 3:
         n, hop = x.shape[-2], x.stride(-2)
@@ -40,8 +42,9 @@ def _as_clip_layout(x: torch.Tensor, n_fft: int):
                 B *= d
             return x, B, n, x.stride(-3), hop, (n - 1) * hop + n_fft
     xc = x.contiguous()
-    B = xc.numel() // n_fft
-    return xc, B, 1, n_fft, n_fft, n_fft
+    n = xc.shape[-2] if xc.dim() >= 2 and xc.shape[-2] > 0 else 1
+    B = xc.numel() // (n * n_fft)
+    return xc, B, n, n * n_fft, n_fft, n * n_fft
 
 
 class STFT(AudioTransform):

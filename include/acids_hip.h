@@ -154,9 +154,20 @@ int at_istft(const float *X_complex, const float *mag, const float *phase, int64
              void *stream);
 
 /* torch.fft.irfft(X) * inv_window on (nframes, F) -> (nframes, n_fft)
- *     replaces stft.py:260-266,308-310 / dgt.py:296-302,325-328. */
+ *     replaces stft.py:260-266,308-310 / dgt.py:296-302,325-328.
+ * The call is ONE stream: at n_fft = 128 / 256 / 512, where 8 / 4 / 2 consecutive frames share a register FFT, a
+ * frame's rounding (and a NaN) can reach its up to K - 1 neighbours in the call.  Frames of independent streams go
+ * through at_irfft_frames_streams. */
 int at_irfft_frames(const float *X_complex, const float *mag, const float *phase, int64_t nframes, int n_fft,
                     const float *inv_window, float *frames, void *stream);
+
+/* The same on (nframes / frames_per_stream) independent streams of frames_per_stream consecutive frames each
+ * (nframes % frames_per_stream == 0, else AT_EINVAL): frames share a transform within a stream only, the last
+ * transform of a stream is filled with zeros, so a stream's output -- bits, accuracy, finiteness -- does not depend on
+ * the other streams of the call.  frames_per_stream = 1: one frame per transform. */
+int at_irfft_frames_streams(const float *X_complex, const float *mag, const float *phase, int64_t nframes,
+                            int64_t frames_per_stream, int n_fft, const float *inv_window, float *frames,
+                            void *stream);
 
 /* ---- K8-K12: magnitude / mel projection ---------------------------------- */
 /* a_kind: 0 = complex64 input, |.| taken on load; 1 = complex64, |.|^2 (power=2);

@@ -8,7 +8,7 @@ once under every swept cut, and that the sweeps reach every geometry class named
 
 The arithmetic follows csrc/mel_banded.hip (launch_banded, launch_fixed_proj, at_project_small, the `held` / `e_next` /
 `last_of_run` window of mel_banded_kernel and the `(t & 7) == 7` / `run_t0` window of small_proj_kernel), stft512.hip
-(launch_stft512_mel, the same window over frame pairs), stft2048.hip (launch_stft2048_mel), mel.hip (launch_mel and the
+(launch_stft512_mel, the same window over the frame pairs of each clip), stft2048.hip (launch_stft2048_mel), mel.hip (launch_mel and the
 three-slot non-finite flag ring of mel_gemm_kernel) and mel_bf16.hip (at_mel_project_bf16)."""
 
 ROW_RUN_MAX = 65535     # AT_VARIANT_ROW_RUN value that clamps to the whole launch (one run, one block)
@@ -44,9 +44,10 @@ def small_mfma_rows_per_wave(rows, cus=256, v=0):
     return max(64, cdiv(cdiv(rows, 16 * cus), 32) * 32)
 
 
-def stft512_pairs_per_wave(frames, v=0):
-    """launch_stft512_mel: frame pairs per wave over the flattened B * T frames, at least 4."""
-    pairs = cdiv(frames, 2)
+def stft512_pairs_per_wave(B, T, v=0):
+    """launch_stft512_mel: frame pairs per wave, at least 4.  Pairs are formed per clip (frames 2 i, 2 i + 1 of one
+    clip; the last frame of an odd-T clip is paired with zeros): B * ceil(T / 2) of them."""
+    pairs = B * cdiv(T, 2)
     return forced(v, pairs) or max(4, cdiv(pairs, 256 * 8 * 4))
 
 
@@ -77,9 +78,15 @@ def runs(total, per):
     return [(a, min(a + per, total)) for a in range(0, total, per)]
 
 
-def frame_runs_512(frames, ppw):
-    """stft512_mel_kernel: a wave takes pairs [p0, p1), i.e. frames [2 p0, min(2 p1, frames))."""
-    return [(2 * a, min(2 * b, frames)) for a, b in runs(cdiv(frames, 2), ppw)]
+def frame_runs_512(B, T, ppw):
+    """stft512_mel_kernel: a wave takes pairs [p0, p1) of the per-clip pair list (pair p = clip p // ppc, frames 2 i and
+    2 i + 1 of it, i = p % ppc, ppc = ceil(T / 2)): flat frames from the first frame of pair p0 to the last existing
+    frame of pair p1 - 1.  The frames of a run stay consecutive."""
+    ppc = cdiv(T, 2)
+
+    def first(p):
+        return (p // ppc) * T + 2 * (p % ppc)
+    return [(first(a), (b - 1) // ppc * T + min(2 * ((b - 1) % ppc) + 2, T)) for a, b in runs(B * ppc, ppw)]
 
 
 # ---- channel-major store windows --------------------------------------------------------------------------------------
@@ -211,17 +218,19 @@ CM_CLASSES = ({("float4", 8, "sector")} | {("partial", h, w) for h in range(1, 8
 SMALL_CM_CLASSES = {"first_lt_run_t0"} | {"flush_%d" % n for n in range(1, 9)}
 
 
-def pair_classes(T, frames, ppw):
-    """n_fft 512: where a pair that straddles two clips (odd T) sits in its run."""
+def pair_classes(B, T, ppw):
+    """n_fft 512: where the half pair of an odd-T clip (its last frame, paired with zeros; the next pair starts the next
+    clip at t = 0) sits in its run."""
     c = set()
-    for p0, p1 in runs(cdiv(frames, 2), ppw):
+    ppc = cdiv(T, 2)
+    for p0, p1 in runs(B * ppc, ppw):
         for p in range(p0, p1):
-            if 2 * p + 1 < frames and (2 * p) // T != (2 * p + 1) // T:
-                c.add("straddle_first" if p == p0 else "straddle_last" if p == p1 - 1 else "straddle_mid")
+            if 2 * (p % ppc) + 1 >= T:
+                c.add("half_pair_first" if p == p0 else "half_pair_last" if p == p1 - 1 else "half_pair_mid")
     return c
 
 
-PAIR_CLASSES = {"straddle_first", "straddle_mid", "straddle_last"}
+PAIR_CLASSES = {"half_pair_first", "half_pair_mid", "half_pair_last"}
 
 
 def gemm_classes(ntiles, tpb, bad=()):
@@ -288,5 +297,5 @@ if __name__ == "__main__":
         print("small MFMA form rows %8d: %5d rows per wave" % (rows, small_mfma_rows_per_wave(rows)))
         print("dense GEMM      rows %8d: %5d tiles per block" % (rows, gemm_tiles_per_block(rows, 128)))
         print("bf16            rows %8d: %5d workgroups" % (rows, bf16_grid(rows)))
-        print("stft512 mel   frames %8d: %5d pairs per wave" % (rows, stft512_pairs_per_wave(rows)))
+        print("stft512 mel   frames %8d: %5d pairs per wave" % (rows, stft512_pairs_per_wave(1, rows)))
         print("stft2048 mel  frames %8d: %5d frames per wave" % (rows, stft2048_frames_per_wave(rows)))

@@ -11,12 +11,14 @@ def test_forced_cut_clamps_like_the_library():
     assert P.small_row_rows_per_wave(4096) == 4 and P.small_row_rows_per_wave(40_000) == 5
     assert P.small_mfma_rows_per_wave(4096) == 64 and P.small_mfma_rows_per_wave(4096, v=1) == 32
     assert P.small_mfma_rows_per_wave(4096, v=33) == 64 and P.small_mfma_rows_per_wave(706_560) == 192
-    assert P.stft512_pairs_per_wave(1000) == 4 and P.stft512_pairs_per_wave(1000, v=1) == 1
+    assert P.stft512_pairs_per_wave(4, 250) == 4 and P.stft512_pairs_per_wave(4, 250, v=1) == 1
+    assert P.stft512_pairs_per_wave(4, 7, v=99) == 16                  # an odd-T clip has ceil(T / 2) pairs
     assert P.stft2048_frames_per_wave(1000) == 8 and P.stft2048_frames_per_wave(100_000) == 13
     assert P.gemm_tiles_per_block(200, 128) == 1 and P.gemm_tiles_per_block(20_000, 128) == 3
     assert P.gemm_tiles_per_block(200, 128, v=4) == 4 and P.gemm_tiles_per_block(200, 128, v=99) == 7
     assert P.bf16_grid(1000) == 8 and P.bf16_grid(1000, v=3) == 3 and P.bf16_grid(50_000) == 256
-    assert P.frame_runs_512(7, 2) == [(0, 4), (4, 7)]
+    assert P.frame_runs_512(1, 7, 2) == [(0, 4), (4, 7)]
+    assert P.frame_runs_512(2, 3, 3) == [(0, 5), (5, 6)]              # pairs (0,1) (2,-) (3,4) | (5,-)
 
 
 def test_channel_major_window_stores_every_element_once():
@@ -31,7 +33,8 @@ def test_channel_major_window_stores_every_element_once():
             w += P.cm_window(T, N, f, rr)[0]
         P.check_once(w, B, N, T, lanes)
     for B, T, v in P.S512_SWEEP:
-        rr = P.frame_runs_512(B * T, P.stft512_pairs_per_wave(B * T, v))
+        rr = P.frame_runs_512(B, T, P.stft512_pairs_per_wave(B, T, v))
+        assert rr[0][0] == 0 and rr[-1][1] == B * T and all(a[1] == b[0] for a, b in zip(rr, rr[1:]))
         w = []
         for f in lanes:
             w += P.cm_window(T, N, f, rr)[0]
@@ -65,9 +68,9 @@ def test_channel_major_sweeps_reach_every_geometry():
     assert P.SMALL_CM_CLASSES <= hit, sorted(P.SMALL_CM_CLASSES - hit)
     hit = set()
     for B, T, v in P.S512_SWEEP:
-        ppw = P.stft512_pairs_per_wave(B * T, v)
-        rr = P.frame_runs_512(B * T, ppw)
-        hit |= P.pair_classes(T, B * T, ppw) | P.run_geometry(T, rr)
+        ppw = P.stft512_pairs_per_wave(B, T, v)
+        rr = P.frame_runs_512(B, T, ppw)
+        hit |= P.pair_classes(B, T, ppw) | P.run_geometry(T, rr)
         for f in P.representative_filters(128):
             hit |= P.cm_window(T, 128, f, rr)[1]
     assert P.PAIR_CLASSES <= hit, sorted(P.PAIR_CLASSES - hit)

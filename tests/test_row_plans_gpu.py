@@ -339,7 +339,7 @@ FUSED = [(512, 40, True, 44100), (512, 128, True, 44100), (512, 128, False, 4410
 @pytest.mark.parametrize("n_fft,n_mels,cm,sr", FUSED, ids=["%d_%d_%s" % (a, b, "cm" if c else "rows") for a, b, c, _ in
                                                            FUSED])
 def test_fused_features_every_cut(dev, n_fft, n_mels, cm, sr):
-    """stft512_mel_kernel (runs of frame pairs; a pair straddling two clips first, mid-run and last in a run at odd T)
+    """stft512_mel_kernel (runs of per-clip frame pairs; the half pair that ends an odd-T clip first, mid-run and last in a run)
     and stft2048_mel_kernel (runs of frames): MelSpectrogram's one-kernel forward, 1- and 2-pass banks, channel-major
     through the register window and row-major."""
     F = n_fft // 2 + 1
