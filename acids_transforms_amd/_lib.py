@@ -91,6 +91,8 @@ _SIGNATURES = {
     "at_istft_backward": [c_f, c_i64, c_i64, c_int, c_int, c_f, c_f, c_f, c_f, c_f, c_sz, c_f],
     "at_magnitude_backward": [c_f, c_int, c_i64, c_int, c_f, c_int, c_int, c_f, c_f, c_f, c_f, c_int, c_f, c_f, c_f, c_f,
                               c_int, c_int, c_f, c_flt, c_f, c_f, c_f],
+    "at_mfcc_backward": [c_f, c_i64, c_i64, c_int, c_f, c_int, c_int, c_int, c_f, c_f, c_f, c_f, c_int, c_f, c_f, c_f, c_f,
+                         c_int, c_f, c_f, c_f, c_f],
 }
 _RESTYPES = {"at_error_string": ctypes.c_char_p, "at_istft_workspace_bytes": c_sz, "at_stats_workspace_bytes": c_sz,
              "at_pghi_offline_workspace_bytes": c_sz, "at_mel_bf16_bank_bytes": c_sz, "at_pghi_rt_workspace_bytes": c_sz,

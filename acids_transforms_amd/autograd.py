@@ -1,5 +1,6 @@
-"""Autograd for STFT / DGT (forward and invert) and Magnitude: torch.autograd.Functions whose backward passes are the
-HIP adjoints of autograd.hip (through ops.stft_backward / ops.istft_backward / ops.magnitude_backward).
+"""Autograd for STFT / DGT (forward and invert), Magnitude and MFCC: torch.autograd.Functions whose backward passes are
+the HIP adjoints of autograd.hip and mfcc_grad.hip (through ops.stft_backward / ops.istft_backward /
+ops.magnitude_backward / ops.mfcc_backward).
 
 The reference is plain torch, so its STFT, DGT and Magnitude (and their composition) sit inside a training loss.  Here
 the forward kernels write into fresh tensors through ctypes, which cuts the graph; the modules therefore route a call
@@ -14,7 +15,7 @@ from torch.autograd.function import once_differentiable
 from . import ops
 
 __all__ = ["wants_grad", "StftFunction", "IstftFunction", "IstftPolarFunction", "MagnitudeFunction",
-           "StftMagnitudeFunction"]
+           "StftMagnitudeFunction", "MfccFunction", "mfcc_chunk_clips"]
 
 
 def wants_grad(x: torch.Tensor) -> bool:
@@ -146,3 +147,65 @@ class StftMagnitudeFunction(torch.autograd.Function):
             return None, None, None, None
         stage = ctx.stage
         return ops.stft_backward(gX, stage.window[:stage._n_fft], stage._n_fft, stage._hop, ctx.L), None, None, None
+
+
+MFCC_CHUNK_ELEMS = 1 << 26      # complex64 elements of spectrum per chunk of MfccFunction.backward: 512 MiB
+
+
+def mfcc_chunk_clips(B, T, n_fft):
+    """Clips per chunk of MfccFunction.backward: the most whose spectrum (T frames of n_fft // 2 + 1 bins per clip)
+    stays within MFCC_CHUNK_ELEMS, at least 1 (189 at n_fft 1024 / hop 256 and 4 s clips)."""
+    per_clip = T * (n_fft // 2 + 1)
+    return min(max(MFCC_CHUNK_ELEMS // per_clip, 1), B)
+
+
+def _mfcc_tables(module, device):
+    """(forward bank tables or None, transposed bank tables, DCT matrix transposed or None) of an MFCC on `device`;
+    the forward bank is walked only on the n_mfcc route.  Cached per bank / DCT version."""
+    from .utils.banded import bank_columns
+    bank = module.fbank
+    dct = module.dct if module.n_mfcc is not None else None
+    key = (bank.data_ptr(), bank._version, str(device)) + ((dct.data_ptr(), dct._version) if dct is not None else ())
+    hit = module.__dict__.get("_grad_tables")
+    if hit is None or hit[0] != key:
+        to = lambda arrs: tuple(torch.from_numpy(a).to(device) for a in arrs)   # noqa: E731
+        hit = (key, to(bank_columns(bank)) if dct is not None else None, to(bank_columns(bank.transpose(-2, -1))),
+               dct.to(device).t().contiguous() if dct is not None else None)
+        module.__dict__["_grad_tables"] = hit
+    return hit[1], hit[2], hit[3]
+
+
+class MfccFunction(torch.autograd.Function):
+    """MFCC.forward with its backward.  Saves the audio only: the fused forward never writes a spectrum, so the backward
+    rebuilds it from the audio, a chunk of clips at a time (mfcc_chunk_clips), turns it into its own gradient in place
+    (ops.mfcc_backward) and runs the STFT adjoint into the chunk's rows of dx.  The window, bank, DCT and Normalize
+    statistics are constants of the graph."""
+
+    @staticmethod
+    def forward(ctx, x, module):
+        y = module._forward_plain(x)
+        ctx.window, ctx.n_fft, ctx.hop, ctx.power = module.window, module.n_fft, module.hop_length, int(module.power)
+        ctx.tables = _mfcc_tables(module, x.device)
+        ctx.scale = module.norm._params(x)[1] if module.norm is not None else None
+        ctx.save_for_backward(x)
+        return y
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dF):
+        (x,) = ctx.saved_tensors
+        n, hop = ctx.n_fft, ctx.hop
+        xb = ops._f32c(x.reshape(-1, x.shape[-1]))
+        B, L = xb.shape
+        T = 1 + (L - (n & 1)) // hop
+        dF = ops._f32c(dF).reshape(B, dF.shape[-2], T)
+        fwd, inv, dct_t = ctx.tables
+        dx = torch.empty((B, L), dtype=torch.float32, device=x.device)
+        chunk = mfcc_chunk_clips(B, T, n)
+        for b0 in range(0, B, chunk):
+            X = ops.stft_forward(xb[b0:b0 + chunk], ctx.window, n, hop, center=True)
+            ops.mfcc_backward(X, dF[b0:b0 + chunk], inv, ctx.power, fwd, dct_t, ctx.scale, inplace=True)
+            ops.stft_backward(X, ctx.window, n, hop, L, out=dx[b0:b0 + chunk])
+            del X
+        dx = dx if x.shape == dx.shape else dx.view(x.shape)
+        return dx.to(x.dtype), None

@@ -1,4 +1,5 @@
-// autograd.h -- launchers of autograd.hip (the STFT and ISTFT adjoints and the Magnitude backward), for capi.hip.
+// autograd.h -- launchers of autograd.hip (the STFT and ISTFT adjoints and the Magnitude backward) and of mfcc_grad.hip
+// (the MFCC backward), for capi.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -23,6 +24,24 @@ struct MagBwdParams {
   void* dX;
 };
 
+// the MFCC backward (mfcc_grad.hip): spectrum and channel-major gradient of one chunk of clips
+struct MfccBwdParams {
+  const float2* X;        // (B, T, K)
+  float2* dX;             // (B, T, K); may be X
+  const float* dF;        // (B, C, T)
+  long long B, T;
+  int K, N, C, power;     // N filters; C == N without a DCT; power 1 or 2
+  const int *f_start, *f_len, *f_off;   // forward bank by column (N columns); read on the DCT route only
+  const float* f_w;
+  int f_nnz;
+  const int *t_start, *t_len, *t_off;   // transposed bank by column (K columns)
+  const float* t_w;
+  int t_nnz;
+  const float* dct_t;     // (C, N): the DCT matrix transposed; null: no DCT
+  const float* scale;     // null: no Normalize
+};
+
+int launch_mfcc_backward(const MfccBwdParams& p, hipStream_t stream);
 int launch_adj_window(const float* w, int n_fft, float scale, float* out, hipStream_t stream);
 int launch_adj_ola_fold(const float* frames, const float2* G, const float* window, float* dx, long long B, long long T,
                         long long L, int n_fft, int hop, hipStream_t stream);

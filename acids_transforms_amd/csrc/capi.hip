@@ -111,7 +111,7 @@ extern "C" {
 // 3: any n_fft (odd sizes give torch.istft's hop (T-1) + 1 samples); Cartesian pack / unpack; strided phase scans
 // 4: at_set_variant / at_get_variant (round 4; the library no longer reads environment variables).  The plan variants
 //    (AT_VARIANT_RUN_LENGTH, AT_VARIANT_ISTFT_TILE) are table entries, not signatures: still 4.  So are the backward
-//    entries (at_stft_backward, at_magnitude_backward, at_istft_backward): additions only.
+//    entries (at_stft_backward, at_magnitude_backward, at_istft_backward, at_mfcc_backward): additions only.
 int at_abi_version(void) { return 4; }
 
 int at_set_variant(int which, int value) {
@@ -621,6 +621,22 @@ int at_magnitude_backward(const void* A, int a_kind, int64_t rows, int K, const 
   at_hip::MagBwdParams p = {A, a_kind, rows, K, N, col_off, dF, f_start, f_len, f_off, f_w, f_nnz, t_start, t_len, t_off, t_w, t_nnz,
                             contrast, scale, eps, dX_accum, dX};
   return at_hip::launch_magnitude_backward(p, (hipStream_t)stream);
+}
+
+int at_mfcc_backward(const float* X_complex, int64_t B, int64_t T, int K, const float* dF, int C, int N, int power,
+                     const int* f_start, const int* f_len, const int* f_off, const float* f_w, int f_nnz,
+                     const int* t_start, const int* t_len, const int* t_off, const float* t_w, int t_nnz,
+                     const float* dct_t, const float* scale, float* dX_complex, void* stream) {
+  if (B < 0 || T <= 0 || K <= 0 || N <= 0 || C <= 0 || (power != 1 && power != 2)) return AT_EINVAL;
+  if (!dct_t && C != N) return AT_EINVAL;
+  if (B == 0) return AT_OK;
+  if (!X_complex || !dF || !dX_complex) return AT_EINVAL;
+  if ((((uintptr_t)X_complex) & 7) || (((uintptr_t)dX_complex) & 7)) return AT_EINVAL;    // complex64 rows
+  if (!(t_start && t_len && t_off && t_w && t_nnz > 0)) return AT_EINVAL;
+  if (dct_t && !(f_start && f_len && f_off && f_w && f_nnz > 0)) return AT_EINVAL;
+  at_hip::MfccBwdParams p = {(const float2*)X_complex, (float2*)dX_complex, dF, B, T, K, N, C, power, f_start, f_len, f_off,
+                             f_w, f_nnz, t_start, t_len, t_off, t_w, t_nnz, dct_t, scale};
+  return at_hip::launch_mfcc_backward(p, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -610,14 +610,17 @@ def stft_mel_forward(x, window, band, contrast=None, offset=None, scale=None, ep
 # ----------------------------------------------------------------------------------------------
 # backward passes (autograd.hip; the autograd.Functions of autograd.py call these)
 # ----------------------------------------------------------------------------------------------
-def stft_backward(G, window, n_fft, hop, L):
-    """Adjoint of stft_forward(center=True): G (B, T, F) complex64, the gradient of the spectrum -> dx (B, L) float32."""
-    require_device(G, window)
+def stft_backward(G, window, n_fft, hop, L, out=None):
+    """Adjoint of stft_forward(center=True): G (B, T, F) complex64, the gradient of the spectrum -> dx (B, L) float32
+    (written into `out`, a contiguous (B, L) float32 tensor, when given)."""
+    require_device(G, window, out)
     G = _c64(G)
     G = G if G.is_contiguous() else G.contiguous()
     B, T, F = G.shape
     assert F == n_fft // 2 + 1, "last dim must be n_fft/2+1"
-    dx = torch.empty((B, L), dtype=torch.float32, device=G.device)
+    if out is not None:
+        assert out.shape == (B, L) and out.dtype == torch.float32 and out.is_contiguous()
+    dx = out if out is not None else torch.empty((B, L), dtype=torch.float32, device=G.device)
     wsb = lib().at_stft_backward_workspace_bytes(B, T, n_fft, hop)
     ws = _workspace(wsb, G.device)
     check(lib().at_stft_backward(ptr(G), B, T, L, n_fft, hop, ptr(window), ptr(dx), ptr(ws), wsb, stream_ptr()),
@@ -671,6 +674,32 @@ def magnitude_backward(x, dF, bank_cols=None, bank_t_cols=None, contrast=None, s
                                       contrast_code(contrast), ptr(scale), eps, ptr(dx_accum), ptr(dx),
                                       stream_ptr()), "at_magnitude_backward")
     return dx
+
+
+def mfcc_backward(X, dF, bank_t_cols, power=2, bank_cols=None, dct_t=None, scale=None, inplace=False):
+    """Gradient of MFCC.forward with respect to the spectrum X (B, T, K) complex64 of its STFT, given dF (B, C, T), the
+    gradient of the channel-major output.  bank_t_cols / bank_cols: utils.banded.bank_columns of the transposed
+    (K, N) bank and of the bank itself, on X's device; dct_t (C, N): the module's DCT matrix transposed (None: the mel
+    power route, C == N, bank_cols not read).  inplace=True writes the result over X and returns X."""
+    require_device(X, dF, dct_t, scale)
+    X = _c64(X)
+    dF = _f32c(dF)
+    assert X.is_contiguous() and X.ndim == 3, "X must be a contiguous (B, T, K) spectrum"
+    B, T, K = X.shape
+    assert bank_t_cols[0].numel() == K, "the transposed bank's tables do not match the spectrum"
+    N = dct_t.shape[1] if dct_t is not None else dF.shape[1]
+    C = dF.shape[1]
+    assert dF.shape == (B, C, T), "dF does not match the forward's output"
+    if dct_t is not None:
+        assert dct_t.is_contiguous() and dct_t.shape[0] == C and bank_cols is not None and bank_cols[0].numel() == N
+    f = bank_cols if dct_t is not None else (None,) * 4
+    t = bank_t_cols
+    dX = X if inplace else torch.empty_like(X)
+    check(lib().at_mfcc_backward(ptr(X), B, T, K, ptr(dF), C, N, int(power),
+                                 ptr(f[0]), ptr(f[1]), ptr(f[2]), ptr(f[3]), f[3].numel() if f[3] is not None else 0,
+                                 ptr(t[0]), ptr(t[1]), ptr(t[2]), ptr(t[3]), t[3].numel(),
+                                 ptr(dct_t), ptr(scale), ptr(dX), stream_ptr()), "at_mfcc_backward")
+    return dX
 
 
 # ----------------------------------------------------------------------------------------------

@@ -8,6 +8,10 @@ STFT kernel plus the MFMA projection with a channel-major store.
 DCT-II (ortho) of 10*log10(mel power) is applied on top, giving (..., n_mfcc, T)
 -- the "MFCC(40)" BASELINE config 4 names; it has no counterpart in the
 reference and its parity is checked against scipy.fft.dct only.
+
+Differentiable on every path: a call whose input requires grad goes through
+autograd.MfccFunction (the same forward code; the backward rebuilds the
+spectrum from the audio per chunk of clips, at_mfcc_backward, STFT adjoint).
 """
 import math
 from typing import Union
@@ -15,6 +19,7 @@ from typing import Union
 import torch
 
 from .. import ops
+from ..autograd import MfccFunction, wants_grad
 from ..utils.banded import BandedBank
 from ..utils.melbank import melscale_fbanks
 from ..utils.misc import reshape_batches
@@ -86,6 +91,12 @@ class MFCC(AudioTransform):
             self.norm.scale_data(x)       # statistics of the *input*, as the reference does (mel.py:60-62)
 
     def forward(self, x: torch.Tensor):
+        self._follow(x)
+        if wants_grad(x):
+            return MfccFunction.apply(x, self)           # the same forward, with the HIP backward (autograd.py)
+        return self._forward_plain(x)
+
+    def _forward_plain(self, x: torch.Tensor):
         self._follow(x)
         xb, batch_shape = reshape_batches(x, -1)
         fusable = (self.n_fft == 1024 and self.hop_length == 256 and self._band.fusable

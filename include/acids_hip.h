@@ -471,6 +471,27 @@ int at_magnitude_backward(const void *A, int a_kind, int64_t rows, int K, const 
                           const int *t_start, const int *t_len, const int *t_off, const float *t_w, int t_nnz, int contrast, const float *scale,
                           float eps, const void *dX_accum, void *dX, void *stream);
 
+/* Gradient of MFCC.forward (the reference's mel power spectrogram, transforms/mel.py:31-73, and the n_mfcc build
+ * extension) with respect to the spectrum X (B, T, K) complex64 of its STFT, given dF (B, C, T) float32, the gradient of
+ * the channel-major output.  a = |X|^power (power 1 or 2), M = a @ bank (K x N):
+ *   dct_t NULL (C == N):  f = (M - offset) / scale,                      dM = dF / scale
+ *   dct_t (C x N), the DCT matrix (N x C, the 10 / ln 10 of the dB scale folded in) TRANSPOSED:
+ *                         f = (ln(max(M, 1e-10)) @ dct - offset) / scale,
+ *                         dM[j] = (sum_c dct_t[c, j] dF[c] / scale) / M[j] where M[j] >= 1e-10, else 0 (torch.clamp's mask)
+ *   dA[k] = sum_j bank[k, j] dM[j],   dX = 2 dA X (power 2),  dA X / |X| (power 1; 0 where X == 0, torch's sgn)
+ * scale NULL: no Normalize (offset never matters).  Banks by column, as at_magnitude_backward: t_* the tables of the
+ * transposed bank (K columns), always read; f_* those of the forward bank (N columns), read -- with M recomputed from
+ * X -- only when dct_t is given, and may be NULL otherwise.  dX_complex may be X_complex (in place: every lane reads the
+ * bins it owns before it writes them); both 8-byte aligned.  One workgroup per tile of 32 consecutive frames of one clip
+ * (the last tile of a clip is short) transposes the tile of dF through LDS, then one wave per frame walks the bands; the
+ * tables sit in LDS when they fit 160 KB, in global memory otherwise (mfcc_grad.hip).  A clip's bits depend neither on
+ * the batch nor on how the caller chunks it.  AT_EINVAL on null or ill-sized arguments (no device is touched),
+ * AT_EUNSUPPORTED when a tile of dF (C >= 1280) or one frame's rows do not fit LDS. */
+int at_mfcc_backward(const float *X_complex, int64_t B, int64_t T, int K, const float *dF, int C, int N, int power,
+                     const int *f_start, const int *f_len, const int *f_off, const float *f_w, int f_nnz,
+                     const int *t_start, const int *t_len, const int *t_off, const float *t_w, int t_nnz,
+                     const float *dct_t, const float *scale, float *dX_complex, void *stream);
+
 /* ---- audio front end ------------------------------------------------------------------------------------- */
 /* torchaudio.transforms.Resample(orig, new) with default arguments, as utils/misc.py:31-33 uses it (algorithm
  * restated, torchaudio is not in the reference tree).  x: (rows, L); orig/new: the rates divided by their gcd;

@@ -6,6 +6,10 @@
   fwd       the fused STFT -> Magnitude forward          against  fwd+bwd (the same with requires_grad, plus backward)
   istft_adj ops.istft_backward (invert's gradient)       against  stft_fwd (the plain ops.stft_forward: the same bytes,
             istft_adj_polar (the magnitude's gradient)            1024 B in / 4104 B out per frame)
+  mfcc_fwd  MFCC() on the audio (the fused kernel)       against  mfcc_fwd+bwd (the same with requires_grad, plus the
+                                                                  chunked backward: STFT, at_mfcc_backward, STFT adjoint)
+  mfcc_bwd_kernel / mfcc_bwd_kernel_dct  at_mfcc_backward alone, in place on one 189-clip chunk, for MFCC() and
+            MFCC(n_mfcc=40): X in + dF in + dX out, 8720 B per frame without the DCT (as magbwd), 8368 B with it
 
 Prints one JSON line (medians over the rounds, ms).  Run under `rocprofv3 --kernel-trace --stats -- python ...` for the
 per-kernel split."""
@@ -20,7 +24,7 @@ import torch  # noqa: E402
 
 import acids_transforms_amd as A  # noqa: E402
 from acids_transforms_amd import ops  # noqa: E402
-from acids_transforms_amd.autograd import _magnitude_grad  # noqa: E402
+from acids_transforms_amd.autograd import _magnitude_grad, _mfcc_tables, mfcc_chunk_clips  # noqa: E402
 
 
 def main():
@@ -51,6 +55,18 @@ def main():
     gy = torch.randn(B, 256 * (T - 1), device=dev, generator=g)
     phase = torch.rand(X.shape, device=dev, generator=g) * 6.283
 
+    mfcc, mfcc40 = A.MFCC().to(dev), A.MFCC(n_mfcc=40).to(dev)
+    dFm = torch.randn(B, 128, T, device=dev, generator=g)
+    nb = mfcc_chunk_clips(B, T, 1024)
+    Xc = X[:nb].clone()                 # overwritten in place by each call: the kernel's time does not depend on the values
+    dFc, dFc40 = dFm[:nb].contiguous(), dFm[:nb, :40].contiguous()
+    _, inv_t, _ = _mfcc_tables(mfcc, dev)
+    fwd40, inv40, dct_t = _mfcc_tables(mfcc40, dev)
+
+    def mfcc_fwd_bwd():
+        xr = x.detach().requires_grad_()
+        mfcc(xr).backward(dFm)
+
     legs = {
         "adjoint": lambda: ops.stft_backward(G, window, 1024, 256, L),
         "istft": lambda: stft.invert(X),
@@ -60,6 +76,10 @@ def main():
         "stft_fwd": lambda: ops.stft_forward(x, window, 1024, 256),
         "istft_adj": lambda: ops.istft_backward(gy, inv_window, 1024, 256, T, env16=env),
         "istft_adj_polar": lambda: ops.istft_backward(gy, inv_window, 1024, 256, T, env16=env, phase=phase),
+        "mfcc_fwd": lambda: mfcc(x),
+        "mfcc_fwd+bwd": mfcc_fwd_bwd,
+        "mfcc_bwd_kernel": lambda: ops.mfcc_backward(Xc, dFc, inv_t, 2, inplace=True),
+        "mfcc_bwd_kernel_dct": lambda: ops.mfcc_backward(Xc, dFc40, inv40, 2, fwd40, dct_t, inplace=True),
     }
     times = {k: [] for k in legs}
     ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
@@ -82,6 +102,13 @@ def main():
         "fwd_bwd_over_fwd": med["fwd+bwd"] / med["fwd"],
         "istft_adj_over_stft_fwd": med["istft_adj"] / med["stft_fwd"],
         "istft_adj_polar_over_stft_fwd": med["istft_adj_polar"] / med["stft_fwd"],
+        "mfcc_fwd_bwd_over_fwd": med["mfcc_fwd+bwd"] / med["mfcc_fwd"],
+        "mfcc_chunk_clips": nb,
+        "mfcc_bwd_kernel_TBps": nb * T * 8720 / (med["mfcc_bwd_kernel"] * 1e-3) / 1e12,
+        "mfcc_bwd_kernel_dct_TBps": nb * T * 8368 / (med["mfcc_bwd_kernel_dct"] * 1e-3) / 1e12,
+        # the same bytes per frame as magbwd: per-frame time of the two, same process
+        "mfcc_bwd_kernel_ns_per_frame": med["mfcc_bwd_kernel"] * 1e6 / (nb * T),
+        "magbwd_ns_per_frame": med["magbwd"] * 1e6 / frames,
         "min_ms": {k: min(v) for k, v in times.items()},
     }
     print(json.dumps(out))
