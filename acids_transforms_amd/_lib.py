@@ -137,10 +137,11 @@ def lib():
 
 
 # kernel variants (include/acids_hip.h AT_VARIANT_*): same results, different kernels or a different cut of the clips
-# (run_length, istft_tile, row_run: 0..65535); for tests and A/B runs.  run_length cuts the streaming forwards (n_fft 512 /
-# 1024 / 2048 / 4096), the long-run n_fft-1024 inverse and the fused 512 / 2048 / 4096 inverses
+# (run_length, istft_tile, row_run, frame_walkers: 0..65535); for tests and A/B runs.  run_length cuts the streaming forwards (n_fft 512 /
+# 1024 / 2048 / 4096), the long-run n_fft-1024 inverse and the fused 512 / 2048 / 4096 inverses; frame_walkers sets the
+# workgroups that walk the frames of the fallback STFT kernels and the blocks of the overlap-add gather
 VARIANTS = {"epilogue": 0, "frame_kernels": 1, "small_projection": 2, "scan_layout": 3, "pghi_kernel": 4, "istft_runs": 5,
-            "run_length": 6, "istft_tile": 7, "row_run": 8}
+            "run_length": 6, "istft_tile": 7, "row_run": 8, "frame_walkers": 9}
 
 
 class variant:

@@ -110,7 +110,8 @@ extern "C" {
 // 2: at_sinebank_realtime takes the synthesis window; bf16 projection, at_oadd_push
 // 3: any n_fft (odd sizes give torch.istft's hop (T-1) + 1 samples); Cartesian pack / unpack; strided phase scans
 // 4: at_set_variant / at_get_variant (round 4; the library no longer reads environment variables).  The plan variants
-//    (AT_VARIANT_RUN_LENGTH, AT_VARIANT_ISTFT_TILE) are table entries, not signatures: still 4.  So are the backward
+//    (AT_VARIANT_RUN_LENGTH, AT_VARIANT_ISTFT_TILE, AT_VARIANT_ROW_RUN, AT_VARIANT_FRAME_WALKERS) are table entries, not
+//    signatures: still 4.  So are the backward
 //    entries (at_stft_backward, at_magnitude_backward, at_istft_backward, at_mfcc_backward): additions only.
 int at_abi_version(void) { return 4; }
 
@@ -347,6 +348,8 @@ static bool istft2048_fused(int n_fft, int hop, const float* env, const float* w
          (((uintptr_t)env) & 15) == 0 && (((uintptr_t)y) & 15) == 0;
 }
 
+// The zeros below hold for a 16-byte aligned window (with env16 and y aligned alike): at_istft leaves the fused path for a
+// less aligned one and then asks for the frames workspace (AT_EWORKSPACE before anything is launched).
 size_t at_istft_workspace_bytes(int64_t B, int64_t T, int n_fft, int hop) {
   if (n_fft == 1024 && (hop == 128 || hop == 256 || hop == 512)) return 0;   // with the envelope table; see at_istft
   if (n_fft == 2048 && (hop == 256 || hop == 512 || hop == 1024)) return 0;  // likewise (stft2048.hip)

@@ -6,6 +6,7 @@
 // n_fft = 1024 kernels in stft1024.hip are the tuned ones.
 #include <hip/hip_runtime.h>
 #include "fastmath.h"
+#include "variants.h"
 #include <stdint.h>
 
 namespace at_hip {
@@ -262,7 +263,7 @@ __global__ void ola_gather_kernel(OlaParams p) {
       if (o < 0 || o >= p.n_fft) continue;
       acc += p.frames[(b * p.T + t) * p.n_fft + o];
       const float w = p.window[o];
-      env += w * w;
+      env = fmaf(w, w, env);        // spelled out: the float4 form must round the same way (contraction is the compiler's choice)
     }
     p.y[i] = acc / env;
   }
@@ -270,7 +271,8 @@ __global__ void ola_gather_kernel(OlaParams p) {
 
 // the same four samples at a time (hop, n_fft multiples of 4, 16-byte aligned buffers): an aligned group of four
 // padded positions never straddles a frame start, so all four samples see the same frames t_lo .. t_hi and the same
-// summation order as the scalar kernel
+// summation order as the scalar kernel; with the envelope's fma explicit in both, the same bits (an output or window
+// that is only 4-byte aligned takes the scalar kernel: a caller's alignment must not show in the result)
 __global__ void ola_gather4_kernel(OlaParams p) {
   const long long out_len = (long long)p.hop * (p.T - 1);
   const long long total4 = p.B * out_len / 4;
@@ -290,7 +292,7 @@ __global__ void ola_gather4_kernel(OlaParams p) {
       const float4 v = *reinterpret_cast<const float4*>(p.frames + (b * p.T + t) * p.n_fft + o);
       const float4 w = *reinterpret_cast<const float4*>(p.window + o);
       acc.x += v.x; acc.y += v.y; acc.z += v.z; acc.w += v.w;
-      env.x += w.x * w.x; env.y += w.y * w.y; env.z += w.z * w.z; env.w += w.w * w.w;
+      env.x = fmaf(w.x, w.x, env.x); env.y = fmaf(w.y, w.y, env.y); env.z = fmaf(w.z, w.z, env.z); env.w = fmaf(w.w, w.w, env.w);
     }
     *reinterpret_cast<float4*>(p.y + i) = make_float4(acc.x / env.x, acc.y / env.y, acc.z / env.z, acc.w / env.w);
   }
@@ -309,7 +311,7 @@ static int set_lds(const void* fn, size_t bytes) {
 // workgroups of a launch: every frame its own while there are few, a few resident rounds of frame walkers above that
 static unsigned frame_walkers(long long nframes) {
   const long long cap = 256LL * 16;
-  return (unsigned)(nframes < cap ? nframes : cap);
+  return forced_walkers(nframes, nframes < cap ? nframes : cap);     // AT_VARIANT_FRAME_WALKERS (tests)
 }
 
 int launch_rfft_generic(const float* x, long long B, long long L, long long clip_stride, long long T, int n_fft,
@@ -345,7 +347,7 @@ int launch_ola_gather(const float* frames, long long B, long long T, int n_fft, 
   const bool vec4 = (hop % 4 == 0) && (n_fft % 8 == 0) && (((uintptr_t)frames) & 15) == 0 && (((uintptr_t)window) & 15) == 0 &&
                     (((uintptr_t)y) & 15) == 0;
   long long blocks = ((vec4 ? total / 4 : total) + 255) / 256;
-  if (blocks > 65536) blocks = 65536;
+  blocks = forced_walkers(blocks, blocks > 65536 ? 65536 : blocks);       // AT_VARIANT_FRAME_WALKERS (tests)
   if (vec4) hipLaunchKernelGGL(ola_gather4_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, p);
   else hipLaunchKernelGGL(ola_gather_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, p);
   return hipGetLastError() == hipSuccess ? 0 : -5;

@@ -7,6 +7,7 @@
 // keep their own kernels.
 #include <hip/hip_runtime.h>
 #include "fastmath.h"
+#include "variants.h"
 #include <stdint.h>
 
 namespace at_hip {
@@ -308,7 +309,7 @@ static int mix_threads(int M) {
 
 static unsigned mix_walkers(long long nframes) {
   const long long cap = 256LL * 16;
-  return (unsigned)(nframes < cap ? nframes : cap);
+  return forced_walkers(nframes, nframes < cap ? nframes : cap);     // AT_VARIANT_FRAME_WALKERS (tests)
 }
 
 int launch_rfft_mixed(const float* x, long long B, long long L, long long clip_stride, long long T, int n_fft, int hop,

@@ -31,7 +31,10 @@ enum {
                             // v rows per wave (banded, fixed, small row form), v rounded up to 32 rows (small MFMA form,
                             // whole 32-row tile pairs), v frame pairs (n_fft-512 features), v frames (n_fft-2048 features),
                             // v 32-row tiles per workgroup (dense GEMM), v 128-row tiles per workgroup (bf16)
-  kVarCount = 9,
+  kVarFrameWalkers = 9,     // v > 0: min(v, frames) workgroups walk the frames of the fallback STFT kernels (stft_generic.hip,
+                            // stft_mixed.hip: frames blockIdx.x + k gridDim.x) and min(v, blocks) blocks stride the
+                            // overlap-add gather (forced_walkers)
+  kVarCount = 10,
   kVarFirstPlan = kVarRunLength
 };
 
@@ -43,6 +46,14 @@ inline long long forced_row_run(long long total) {
   const long long v = variant(kVarRowRun);
   if (v <= 0) return 0;
   return v < total ? v : (total > 0 ? total : 1);
+}
+
+// Workgroups of a launch whose kernel strides over `units` (frames, 256-thread blocks of outputs) with its grid:
+// AT_VARIANT_FRAME_WALKERS clamped to [1, units] in place of the launcher's `plan`.  Any count >= 1 is legal.
+inline unsigned forced_walkers(long long units, long long plan) {
+  const long long v = variant(kVarFrameWalkers);
+  if (v <= 0) return (unsigned)plan;
+  return (unsigned)(v < units ? v : units);
 }
 
 #ifdef AT_DEV_SWITCHES

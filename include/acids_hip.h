@@ -68,6 +68,8 @@ const char *at_error_string(int code);
                                         * fixed 513-bin, small row form; small MFMA form: v rounded up to 32), v frame pairs /
                                         * frames per wave (n_fft-512 / 2048 features-only forward), v 32-row tiles per
                                         * workgroup (dense MFMA GEMM), v 128-row tiles per workgroup (bf16 projection) */
+#define AT_VARIANT_FRAME_WALKERS 9     /* v: min(v, frames) workgroups walk the frames of the fallback STFT kernels (generic and
+                                        * mixed radix), min(v, blocks) blocks stride the overlap-add gather; same bits */
 int at_set_variant(int which, int value);
 int at_get_variant(int which);
 
@@ -133,6 +135,10 @@ int at_stft_polar_forward(const float *x, int64_t B, int64_t L, int64_t clip_str
  * Other ratios: AT_EUNSUPPORTED (at_istft then takes its workspace path). */
 int at_istft_envelope_table(const float *inv_window, int n_fft, int hop, float *env16, void *stream);
 
+/* Bytes of workspace at_istft needs: B * T * n_fft floats, or 0 for the fused shapes (n_fft 512 / 1024 / 2048 / 4096 at
+ * hop n/8, n/4, n/2).  The zero holds for a 16-byte aligned inv_window (and env16 and y): a less aligned pointer takes
+ * at_istft off the fused kernels, and it then returns AT_EWORKSPACE, launching nothing, unless B * T * n_fft floats are
+ * passed all the same. */
 size_t at_istft_workspace_bytes(int64_t B, int64_t T, int n_fft, int hop);
 
 /* torch.istft(X.transpose(-2,-1), n_fft, hop, window=inv_window, onesided=True)

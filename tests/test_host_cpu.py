@@ -134,6 +134,14 @@ def test_library_reads_no_environment_and_variants_are_explicit():
     for which in _lib.VARIANTS.values():
         assert lib.at_get_variant(which) == 0
     assert lib.at_set_variant(99, 1) == -1 and lib.at_set_variant(0, 7) == -1 and lib.at_get_variant(-1) == -1
+    # the binding's names are the header's constants; the last entry is a plan variant (0..65535) and ends the table
+    import re
+    hdr = open(os.path.join(ROOT, "include", "acids_hip.h")).read()
+    assert {m.group(1).lower(): int(m.group(2)) for m in re.finditer(r"#define AT_VARIANT_(\w+) +(\d+)", hdr)} == _lib.VARIANTS
+    last = _lib.VARIANTS["frame_walkers"]
+    assert last == 9 == max(_lib.VARIANTS.values()) and lib.at_set_variant(last + 1, 1) == -1
+    assert lib.at_set_variant(last, 65535) == 0 and lib.at_get_variant(last) == 65535 and lib.at_set_variant(last, 65536) == -1
+    assert lib.at_set_variant(last, 0) == 0
     with _lib.variant("pghi_kernel", 2):
         assert lib.at_get_variant(_lib.VARIANTS["pghi_kernel"]) == 2
         with _lib.variant("epilogue", 1):

@@ -337,7 +337,7 @@ def test_griffinlim_update_fused_into_the_inverse(dev, hop):
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("n", [8, 16, 32, 64, 256, 512, 2048, 4096, 16384])
+@pytest.mark.parametrize("n", [8, 16, 32, 64, 256, 512, 2048, 4096, 8192, 16384])
 def test_every_power_of_two_size(dev, n):
     """The generic kernels (radix-4 / radix-2 Stockham in LDS) over the whole range the reference's window buffers
     allow (stft.py:10 MAX_NFFT = 16384), hops n/8, n/4, n/2, STFT and DGT, forward and inverse against the oracle."""
