@@ -23,7 +23,11 @@ __global__ void angle_kernel(const float2* __restrict__ x, long long n, float* _
 //   Normalize.scale_data          reference norm.py:25-38
 //   Magnitude.scale_data          reference spectral_repr.py:242-245 (stats of contrast(|x|), no mel)
 // Two launches: per-block partials, then one block folds them.  Sums are kept in fp64.
+// A NaN in the data makes min and max NaN, like Tensor.min() / max() of the reference (fminf / fmaxf would drop it).
 // ---------------------------------------------------------------------------
+__device__ __forceinline__ float nan_min(float a, float b) { return (b < a || b != b) ? b : a; }
+__device__ __forceinline__ float nan_max(float a, float b) { return (b > a || b != b) ? b : a; }
+
 struct StatsParams {
   const void* A;
   long long n;
@@ -55,8 +59,8 @@ __device__ __forceinline__ void block_fold(float mn, float mx, double s, double 
   __shared__ float s_mn[4], s_mx[4];
   __shared__ double s_s[4], s_ss[4];
   for (int o = 32; o > 0; o >>= 1) {
-    mn = fminf(mn, __shfl_xor(mn, o, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+    mn = nan_min(mn, __shfl_xor(mn, o, 64));
+    mx = nan_max(mx, __shfl_xor(mx, o, 64));
     s += __shfl_xor(s, o, 64);
     ss += __shfl_xor(ss, o, 64);
   }
@@ -67,7 +71,7 @@ __device__ __forceinline__ void block_fold(float mn, float mx, double s, double 
   __syncthreads();
   if (threadIdx.x == 0) {
     for (int i = 1; i < (int)(blockDim.x >> 6); ++i) {
-      mn = fminf(mn, s_mn[i]); mx = fmaxf(mx, s_mx[i]); s += s_s[i]; ss += s_ss[i];
+      mn = nan_min(mn, s_mn[i]); mx = nan_max(mx, s_mx[i]); s += s_s[i]; ss += s_ss[i];
     }
     dst[0] = mn; dst[1] = mx; dst[2] = s; dst[3] = ss;
   }
@@ -78,8 +82,8 @@ __global__ __launch_bounds__(256) void stats_partial_kernel(StatsParams p) {
   double s = 0.0, ss = 0.0;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < p.n; i += (long long)gridDim.x * blockDim.x) {
     float v = stats_value(p, i);
-    mn = fminf(mn, v);
-    mx = fmaxf(mx, v);
+    mn = nan_min(mn, v);
+    mx = nan_max(mx, v);
     s += (double)v;
     ss += (double)v * (double)v;
   }
@@ -90,12 +94,20 @@ __global__ __launch_bounds__(256) void stats_final_kernel(const double* partial,
   float mn = INFINITY, mx = -INFINITY;
   double s = 0.0, ss = 0.0;
   for (int i = threadIdx.x; i < nblocks; i += blockDim.x) {
-    mn = fminf(mn, (float)partial[4 * i]);
-    mx = fmaxf(mx, (float)partial[4 * i + 1]);
+    mn = nan_min(mn, (float)partial[4 * i]);
+    mx = nan_max(mx, (float)partial[4 * i + 1]);
     s += partial[4 * i + 2];
     ss += partial[4 * i + 3];
   }
   block_fold(mn, mx, s, ss, out4);
+}
+
+// x * scale + offset in two roundings, like the reference's `x * scale + offset` on tensors.  __fmul_rn / __fadd_rn are the
+// plain operators in HIP and contract to one FMA under the default -ffp-contract=fast; the pragma keeps them apart.
+__device__ __forceinline__ float mul_then_add(float x, float scale, float offset) {
+#pragma clang fp contract(off)
+  const float prod = x * scale;
+  return prod + offset;
 }
 
 // (x - offset) / scale   and   x * scale + offset      reference norm.py:40-44
@@ -103,7 +115,7 @@ __global__ void affine_kernel(const float* __restrict__ x, long long n, const fl
                               int inverse, float* __restrict__ out) {
   const float off = *offset, sc = *scale;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
-    out[i] = inverse ? __fadd_rn(__fmul_rn(x[i], sc), off) : (x[i] - off) / sc;
+    out[i] = inverse ? mul_then_add(x[i], sc, off) : (x[i] - off) / sc;
 }
 
 // Cartesian (reference spectral_repr.py:403-428): normalise(x.real) and normalise(x.imag) stacked on dim -2, and back.
@@ -188,7 +200,7 @@ __global__ __launch_bounds__(256) void cartesian_unpack_kernel(const float* __re
   for (; i < total; i += stride) {
     const float* src = y + (2 * (unsigned long long)r) * F + f;
     const float re = src[0], im = src[F];
-    out[i] = make_float2(re_off ? __fadd_rn(__fmul_rn(re, rs), ro) : re, im_off ? __fadd_rn(__fmul_rn(im, is), io) : im);
+    out[i] = make_float2(re_off ? mul_then_add(re, rs, ro) : re, im_off ? mul_then_add(im, is, io) : im);
     r += dr;
     f += df;
     if (f >= (Idx)F) {

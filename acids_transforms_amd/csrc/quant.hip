@@ -56,7 +56,7 @@ __global__ void onehot_kernel(const long long* __restrict__ x, long long n, int 
   }
 }
 
-// first index of the maximum over the last dim (Tensor.argmax(-1))
+// first index of the maximum over the last dim (Tensor.argmax(-1)); a NaN counts as the maximum and the first one wins
 __global__ void argmax_last_kernel(const long long* __restrict__ xi, const float* __restrict__ xf, long long rows,
                                    int cols, long long* __restrict__ out) {
   for (long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x; r < rows; r += (long long)gridDim.x * blockDim.x) {
@@ -71,7 +71,7 @@ __global__ void argmax_last_kernel(const long long* __restrict__ xi, const float
       float bv = xf[r * cols];
       for (int c = 1; c < cols; ++c) {
         const float v = xf[r * cols + c];
-        if (v > bv) { bv = v; best = c; }
+        if (bv == bv && (v > bv || v != v)) { bv = v; best = c; }
       }
     }
     out[r] = best;
