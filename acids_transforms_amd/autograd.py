@@ -1,6 +1,8 @@
-"""Autograd for STFT / DGT (forward and invert), Magnitude and MFCC: torch.autograd.Functions whose backward passes are
-the HIP adjoints of autograd.hip and mfcc_grad.hip (through ops.stft_backward / ops.istft_backward /
-ops.magnitude_backward / ops.mfcc_backward).
+"""Autograd for STFT / DGT (forward and invert), Magnitude and MFCC, and for the invert of Magnitude, Polar, Cartesian,
+Real / Imaginary / Phase and Normalize: torch.autograd.Functions whose backward passes are the HIP adjoints of
+autograd.hip, mfcc_grad.hip and invert_grad.hip (through ops.stft_backward / ops.istft_backward /
+ops.magnitude_backward / ops.mfcc_backward / ops.magnitude_invert_backward / ops.polar_to_complex_backward /
+ops.cartesian_inverse_backward).
 
 The reference is plain torch, so its STFT, DGT and Magnitude (and their composition) sit inside a training loss.  Here
 the forward kernels write into fresh tensors through ctypes, which cuts the graph; the modules therefore route a call
@@ -15,7 +17,8 @@ from torch.autograd.function import once_differentiable
 from . import ops
 
 __all__ = ["wants_grad", "StftFunction", "IstftFunction", "IstftPolarFunction", "MagnitudeFunction",
-           "StftMagnitudeFunction", "MfccFunction", "mfcc_chunk_clips"]
+           "StftMagnitudeFunction", "MfccFunction", "mfcc_chunk_clips", "MagnitudeInvertFunction", "PolarInvertFunction",
+           "CartesianInvertFunction", "PolarToComplexFunction", "AffineInvertFunction"]
 
 
 def wants_grad(x: torch.Tensor) -> bool:
@@ -209,3 +212,117 @@ class MfccFunction(torch.autograd.Function):
             del X
         dx = dx if x.shape == dx.shape else dx.view(x.shape)
         return dx.to(x.dtype), None
+
+
+# ---- the invert side: Magnitude, Polar, Cartesian, polar_to_complex, Normalize -----------------------------------------
+
+def _inverse_bank_tables(module, device, forward=False):
+    """By-column tables of a Magnitude's inverse_mel_bank TRANSPOSED on `device` (the walk of the invert's backward), or
+    with forward=True those of the inverse bank itself (the polar form recomputes the magnitude with them); None when
+    mel=False.  Cached per bank version."""
+    if not module.mel:
+        return None
+    from .utils.banded import bank_columns
+    bank = module.inverse_mel_bank
+    key = (bank.data_ptr(), bank._version, str(device))
+    hit = module.__dict__.get("_invert_grad_tables")
+    if hit is None or hit[0] != key:
+        hit = [key, None, None]
+        module.__dict__["_invert_grad_tables"] = hit
+    which = 2 if forward else 1
+    if hit[which] is None:
+        cols = bank_columns(bank if forward else bank.transpose(-2, -1))
+        hit[which] = tuple(torch.from_numpy(a).to(device) for a in cols)
+    return hit[which]
+
+
+class MagnitudeInvertFunction(torch.autograd.Function):
+    """Magnitude.invert with its backward (ops.magnitude_invert_backward): mel or not, any contrast / norm,
+    keep_nyquist both ways.  Saves y; the bank tables and the Normalize statistics are constants of the graph."""
+
+    @staticmethod
+    def forward(ctx, y, module):
+        ctx.tables = _inverse_bank_tables(module, y.device)
+        ctx.off, ctx.sc = module._affine()
+        ctx.contrast, ctx.eps, ctx.pad_last = module.contrast_mode, module._eps, not module.keep_nyquist
+        ctx.save_for_backward(y)
+        return module._invert_plain(y)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        (y,) = ctx.saved_tensors
+        dy = ops.magnitude_invert_backward(y, g, ctx.tables, ctx.contrast, ctx.off, ctx.sc, ctx.eps,
+                                           pad_last=ctx.pad_last)
+        return dy.reshape(y.shape).to(y.dtype), None
+
+
+class PolarInvertFunction(torch.autograd.Function):
+    """The one-pass Polar.invert (ops.polar_inverse) with its backward, the polar form of
+    ops.magnitude_invert_backward: both halves of the stacked gradient from one kernel.  Saves the stacked y."""
+
+    @staticmethod
+    def forward(ctx, y, magnitude, band, m_off, m_sc, p_off, p_sc):
+        ctx.t_cols = _inverse_bank_tables(magnitude, y.device)
+        ctx.f_cols = _inverse_bank_tables(magnitude, y.device, forward=True)
+        ctx.args = (magnitude.contrast_mode, m_off, m_sc, magnitude._eps)
+        ctx.p_off, ctx.p_sc = p_off, p_sc
+        ctx.save_for_backward(y)
+        return ops.polar_inverse(y, band, magnitude.contrast_mode, m_off, m_sc, magnitude._eps, p_off, p_sc)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gX):
+        (y,) = ctx.saved_tensors
+        dy = ops.magnitude_invert_backward(y, gX, ctx.t_cols, *ctx.args, bank_cols=ctx.f_cols, phase_offset=ctx.p_off,
+                                           phase_scale=ctx.p_sc)
+        return dy.reshape(y.shape).to(y.dtype), None, None, None, None, None, None
+
+
+class CartesianInvertFunction(torch.autograd.Function):
+    """The one-pass Cartesian.invert (ops.cartesian_inverse) with its backward.  Saves nothing."""
+
+    @staticmethod
+    def forward(ctx, y, re_off, re_sc, im_off, im_sc):
+        ctx.re_sc, ctx.im_sc, ctx.shape, ctx.dtype = re_sc, im_sc, y.shape, y.dtype
+        return ops.cartesian_inverse(y, re_off, re_sc, im_off, im_sc)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gX):
+        dy = ops.cartesian_inverse_backward(gX, ctx.re_sc, ctx.im_sc)
+        return dy.reshape(ctx.shape).to(ctx.dtype), None, None, None, None
+
+
+class PolarToComplexFunction(torch.autograd.Function):
+    """ops.polar_to_complex(mag, phase) of two tensors of one shape, with gradients for whichever of the two require
+    them.  Saves mag and phase."""
+
+    @staticmethod
+    def forward(ctx, mag, phase):
+        ctx.save_for_backward(mag, phase)
+        return ops.polar_to_complex(mag, phase)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gX):
+        mag, phase = ctx.saved_tensors
+        need_mag, need_phase = ctx.needs_input_grad
+        gmag, gphase = ops.polar_to_complex_backward(gX, mag, phase, need_mag, need_phase)
+        return (gmag.reshape(mag.shape).to(mag.dtype) if need_mag else None,
+                gphase.reshape(phase.shape).to(phase.dtype) if need_phase else None)
+
+
+class AffineInvertFunction(torch.autograd.Function):
+    """Normalize.invert, x * scale + offset (ops.affine, inverse): the invert of Real / Imaginary / Phase before their
+    zero pad.  The gradient is g * scale -- the same kernel with a zero offset.  Saves nothing."""
+
+    @staticmethod
+    def forward(ctx, x, offset, scale):
+        ctx.scale, ctx.dtype = scale, x.dtype
+        return ops.affine(x, offset, scale, inverse=True)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        return ops.affine(g, torch.zeros_like(ctx.scale), ctx.scale, inverse=True).to(ctx.dtype), None, None

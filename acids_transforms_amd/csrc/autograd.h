@@ -1,5 +1,5 @@
-// autograd.h -- launchers of autograd.hip (the STFT and ISTFT adjoints and the Magnitude backward) and of mfcc_grad.hip
-// (the MFCC backward), for capi.hip.
+// autograd.h -- launchers of autograd.hip (the STFT and ISTFT adjoints and the Magnitude backward), of mfcc_grad.hip
+// (the MFCC backward) and of invert_grad.hip (the Magnitude.invert / Polar.invert backward), for the C entry points.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -41,6 +41,28 @@ struct MfccBwdParams {
   const float* scale;     // null: no Normalize
 };
 
+// the backward of Magnitude.invert and of the one-pass Polar.invert (invert_grad.hip)
+struct MagInvBwdParams {
+  const float* y;         // rows x (K - pad_last), row stride ld_y; polar: rows x 2 x K stacked (ld_y = 2 K)
+  long long ld_y;         // also dy's row stride
+  long long rows;
+  int K, N, pad_last;     // the (K x N) inverse bank; pad_last: the last of the K columns is the reference's zero pad
+  const void* g;          // rows x N: float32, or complex64 (polar)
+  int polar;
+  const int *f_start, *f_len, *f_off;   // inverse bank by column (N columns); read by the polar form only
+  const float* f_w;
+  int f_nnz;
+  const int *t_start, *t_len, *t_off;   // transposed inverse bank by column (K columns); null: mel=False
+  const float* t_w;
+  int t_nnz;
+  int contrast;
+  const float *offset, *scale;          // null: no Normalize
+  float eps;
+  const float *ph_offset, *ph_scale;    // polar: the phase half's Normalize, or null
+  float* dy;
+};
+
+int launch_magnitude_invert_backward(const MagInvBwdParams& p, hipStream_t stream);
 int launch_mfcc_backward(const MfccBwdParams& p, hipStream_t stream);
 int launch_adj_window(const float* w, int n_fft, float scale, float* out, hipStream_t stream);
 int launch_adj_ola_fold(const float* frames, const float2* G, const float* window, float* dx, long long B, long long T,

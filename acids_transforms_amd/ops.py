@@ -702,6 +702,78 @@ def mfcc_backward(X, dF, bank_t_cols, power=2, bank_cols=None, dct_t=None, scale
     return dX
 
 
+def _c64_grad(g):
+    """A complex gradient as the kernels read it: complex64, contiguous, 8-byte aligned (a slice of a cat's gradient
+    always is: complex64 elements)."""
+    g = _c64(g)
+    return g if g.is_contiguous() else g.contiguous()
+
+
+def magnitude_invert_backward(y, g, bank_t_cols=None, contrast=None, offset=None, scale=None, eps=1.1920929e-07,
+                              pad_last=False, bank_cols=None, phase_offset=None, phase_scale=None):
+    """Gradient of Magnitude.invert with respect to y (..., K - pad_last) float32, given g (..., N), the gradient of its
+    output.  bank_t_cols: utils.banded.bank_columns of the (K, N) inverse bank TRANSPOSED, on y's device (None:
+    mel=False, N == K).  pad_last: keep_nyquist=False (the reference's zero pad is the last of the K columns).
+    bank_cols given (bank_columns of the inverse bank itself): the one-pass Polar.invert -- y (..., 2, F) stacked, g the
+    complex gradient (..., F), the result has y's shape with both halves written."""
+    polar = bank_cols is not None
+    require_device(y, g, offset, scale, phase_offset, phase_scale)
+    y = _f32c(y)
+    g = _c64_grad(g) if polar else _f32c(g)
+    pad = int(bool(pad_last))
+    if polar:
+        K = N = y.shape[-1]
+        assert y.ndim >= 2 and y.shape[-2] == 2 and bank_t_cols is not None and not pad
+        assert bank_cols[0].numel() == N and bank_t_cols[0].numel() == K, "the tables do not match the stacked tensor"
+        rows = y.numel() // (2 * K)
+    else:
+        K = y.shape[-1] + pad
+        N = g.shape[-1]
+        if bank_t_cols is not None:
+            assert bank_t_cols[0].numel() == K, "the transposed bank's tables do not match the input"
+        else:
+            assert N == K, "mel=False: the gradient has the input's columns (plus the pad)"
+        rows = g.numel() // N
+        assert y.numel() == rows * (K - pad), "g does not match the forward's output"
+    assert g.numel() == rows * N, "g does not match the forward's output"
+    f = bank_cols if polar else (None,) * 4
+    t = bank_t_cols if bank_t_cols is not None else (None,) * 4
+    dy = torch.empty_like(y)
+    check(lib().at_magnitude_invert_backward(ptr(y), rows, K, N, pad, ptr(g), int(polar),
+                                             ptr(f[0]), ptr(f[1]), ptr(f[2]), ptr(f[3]),
+                                             f[3].numel() if f[3] is not None else 0,
+                                             ptr(t[0]), ptr(t[1]), ptr(t[2]), ptr(t[3]),
+                                             t[3].numel() if t[3] is not None else 0,
+                                             contrast_code(contrast), ptr(offset), ptr(scale), eps, ptr(phase_offset),
+                                             ptr(phase_scale), ptr(dy), stream_ptr()), "at_magnitude_invert_backward")
+    return dy
+
+
+def polar_to_complex_backward(gX, mag, phase, need_mag=True, need_phase=True):
+    """Gradient of polar_to_complex: gX complex64 of mag's (contiguous float32) shape -> (gmag, gphase), None for the
+    one that is not needed."""
+    require_device(gX, mag, phase)
+    gX = _c64_grad(gX)
+    mag, phase = _f32c(mag), _f32c(phase)
+    assert gX.shape == mag.shape == phase.shape
+    gmag = torch.empty_like(mag) if need_mag else None
+    gphase = torch.empty_like(phase) if need_phase else None
+    check(lib().at_polar_to_complex_backward(ptr(gX), ptr(mag), ptr(phase), gX.numel(), ptr(gmag), ptr(gphase),
+                                             stream_ptr()), "at_polar_to_complex_backward")
+    return gmag, gphase
+
+
+def cartesian_inverse_backward(gX, re_scale=None, im_scale=None):
+    """Gradient of cartesian_inverse: gX (..., F) complex64 -> (..., 2, F) float32 = [Re gX * re_scale, Im gX * im_scale]."""
+    require_device(gX, re_scale, im_scale)
+    gX = _c64_grad(gX)
+    F = gX.shape[-1]
+    dy = torch.empty(gX.shape[:-1] + (2, F), dtype=torch.float32, device=gX.device)
+    check(lib().at_cartesian_unpack_backward(ptr(gX), gX.numel() // F if F else 0, F, ptr(re_scale), ptr(im_scale),
+                                             ptr(dy), stream_ptr()), "at_cartesian_unpack_backward")
+    return dy
+
+
 # ----------------------------------------------------------------------------------------------
 # phase-side representations (phase_repr.hip)
 # ----------------------------------------------------------------------------------------------

@@ -9,6 +9,7 @@ from typing import Union
 import torch
 
 from .. import ops
+from ..autograd import AffineInvertFunction, wants_grad
 from .base import AudioTransform
 
 __all__ = ["Normalize"]
@@ -74,6 +75,8 @@ class Normalize(AudioTransform):
 
     def invert(self, x: torch.Tensor, inversion_mode=None, **kwargs) -> torch.Tensor:
         off, sc = self._params(x)
+        if wants_grad(x):
+            return AffineInvertFunction.apply(x, off, sc)    # the same kernel; the gradient is g * scale
         return ops.affine(x, off, sc, inverse=True)
 
     # -- self-test hooks (reference norm.py:49-97): every mode on 256-sample frames of the audio ------------

@@ -23,6 +23,8 @@ from typing import Tuple, Union
 import torch
 
 from .. import ops
+from ..autograd import (AffineInvertFunction, CartesianInvertFunction, PolarInvertFunction, PolarToComplexFunction,
+                        wants_grad)
 from .base import AudioTransform, InversionEnumType
 from .norm import Normalize
 from .spectral_repr import Magnitude, _Identity
@@ -64,7 +66,12 @@ class _Representation(AudioTransform):
 
     def invert(self, x, inversion_mode: InversionEnumType = None, tolerance: float = 1.e-4) -> torch.Tensor:
         off, sc = self._affine(x)
-        out = ops.affine(x, off, sc, inverse=True) if off is not None else x
+        if off is None:
+            out = x
+        elif wants_grad(x):
+            out = AffineInvertFunction.apply(x, off, sc)     # the same kernel; the zero pad below is torch's own cat
+        else:
+            out = ops.affine(x, off, sc, inverse=True)
         return out if self.keep_nyquist else _pad_last_bin(out)
 
     # -- self-test hooks (the reference's test file drives every class through them) ------------------
@@ -330,6 +337,8 @@ class SpectralRepresentation(AudioTransform):
         mag._follow(x)
         m_off, m_sc = mag._affine()
         p_off, p_sc = ph._affine(x)
+        if wants_grad(x):       # the same kernel, with the polar form of the Magnitude.invert backward (autograd.py)
+            return PolarInvertFunction.apply(x, mag, band, m_off, m_sc, p_off, p_sc)
         return ops.polar_inverse(x, band, mag.contrast_mode, m_off, m_sc, mag._eps, p_off, p_sc)
 
     def invert(self, x, inversion_mode: InversionEnumType = None, tolerance: float = 1.e-4) -> torch.Tensor:
@@ -338,8 +347,13 @@ class SpectralRepresentation(AudioTransform):
             if fused is not None:
                 return fused
         mag, phase = self._split(x)
-        mag = self.magnitude.invert(mag)
-        phase = self.phase.invert(phase)
+        # an IF phase part (PolarIF) integrates along time without a backward: the whole invert stays without a graph,
+        # as its one-pass route does, instead of handing back a gradient for the magnitude half alone
+        with torch.set_grad_enabled(torch.is_grad_enabled() and not isinstance(self.phase, IF)):
+            mag = self.magnitude.invert(mag)
+            phase = self.phase.invert(phase)
+            if wants_grad(mag) or wants_grad(phase):
+                return PolarToComplexFunction.apply(*torch.broadcast_tensors(mag, phase))
         return ops.polar_to_complex(mag, phase)
 
 
@@ -366,6 +380,8 @@ class Cartesian(SpectralRepresentation):
 
     def invert(self, x, inversion_mode: InversionEnumType = None, tolerance: float = 1.e-4) -> torch.Tensor:
         if self._one_pass_ok(x, True):
+            if wants_grad(x):
+                return CartesianInvertFunction.apply(x, *self.magnitude._affine(x), *self.phase._affine(x))
             return ops.cartesian_inverse(x, *self.magnitude._affine(x), *self.phase._affine(x))
         real, imag = self._split(x)
         return torch.complex(self.magnitude.invert(real).contiguous(), self.phase.invert(imag).contiguous())

@@ -13,7 +13,7 @@ from typing import Union
 import torch
 
 from .. import ops
-from ..autograd import MagnitudeFunction, StftMagnitudeFunction, wants_grad
+from ..autograd import MagnitudeFunction, MagnitudeInvertFunction, StftMagnitudeFunction, wants_grad
 from ..utils.banded import BandedBank
 from ..utils.melbank import melscale_fbanks
 from .base import AudioTransform, InversionEnumType
@@ -214,6 +214,11 @@ class Magnitude(AudioTransform):
 
     def invert(self, x: torch.Tensor, inversion_mode: InversionEnumType = None, tolerance: float = 1.e-4) -> torch.Tensor:
         self._follow(x)
+        if wants_grad(x):
+            return MagnitudeInvertFunction.apply(x, self)   # the same kernels, with the HIP backward (autograd.py)
+        return self._invert_plain(x)
+
+    def _invert_plain(self, x: torch.Tensor) -> torch.Tensor:
         off, sc = self._affine()
         if not self.keep_nyquist:
             # reference order: Normalize.invert, zero-pad the LAST bin, then invert_contrast (+ bank)

@@ -498,6 +498,46 @@ int at_mfcc_backward(const float *X_complex, int64_t B, int64_t T, int K, const 
                      const int *t_start, const int *t_len, const int *t_off, const float *t_w, int t_nnz,
                      const float *dct_t, const float *scale, float *dX_complex, void *stream);
 
+/* Gradient of Magnitude.invert (reference spectral_repr.py:229-240: norm.invert -> zero pad -> invert_contrast ->
+ * matmul(inverse_mel_bank)) with respect to its input y, the adjoint of at_mel_project_banded(inverse=1) /
+ * at_mel_project(inverse=1) / at_mag_pointwise(inverse=1).  z = y * scale + offset (z = y when both are NULL),
+ * x = c(z) @ W with W the (K x N) inverse bank and c the inverse contrast; g (rows x N) the gradient of x:
+ *   dy[k] = scale * c'(z[k]) * sum_n W[k, n] g[n],   c' = exp(z) (log1p, log), ln 10 * 10^z (log10), 1 (none)
+ * pad_last = 1 (keep_nyquist=False): y and dy have K - 1 columns -- the reference pads a zero as the LAST of the K
+ * columns after de-normalising, so that column's gradient is dropped.  The bank travels as the by-column tables of W^T
+ * (K columns, as at_magnitude_backward's t_*): column k holds t_len[k] weights at t_w[t_off[k] ..] for the outputs
+ * t_start[k] ..; t_w NULL: mel=False (W = I, N == K), one thread per element.  With a bank: one wave per row, g of the
+ * row in LDS, the tables too when they fit 160 KB beside four rows (otherwise read from global memory by up to four
+ * waves per workgroup); every dy[k] is summed by one lane in ascending n, so a row's bits do not depend on the batch.
+ * polar = 1: the one-pass Polar.invert (reference :441-452; at_mel_project_banded with phase_in).  y and dy are the
+ * stacked (rows, 2, K) tensors (K == N, no pad), g = gX is complex64 (rows x N), phi = y_phase * phase_scale +
+ * phase_offset (or y_phase), M = c(z) @ W recomputed by a forward walk over f_* (the by-column tables of W itself, N
+ * columns; NULL and unread when polar = 0):
+ *   gM[n] = Re gX cos phi + Im gX sin phi,   dy_phase[n] = phase_scale * M[n] * (Im gX cos phi - Re gX sin phi),
+ *   dy_mag[k] = scale * c'(z[k]) * sum_n W[k, n] gM[n].
+ * y, dy, a real g and the scalars may have any float (4-byte) alignment, a complex g must be 8-byte aligned.  AT_EINVAL on null or ill-sized
+ * arguments (no device is touched), AT_OK and nothing touched for rows == 0, AT_EUNSUPPORTED when one row's slice does
+ * not fit LDS. */
+int at_magnitude_invert_backward(const float *y, int64_t rows, int K, int N, int pad_last, const void *g, int polar,
+                                 const int *f_start, const int *f_len, const int *f_off, const float *f_w, int f_nnz,
+                                 const int *t_start, const int *t_len, const int *t_off, const float *t_w, int t_nnz,
+                                 int contrast, const float *offset, const float *scale, float eps,
+                                 const float *phase_offset, const float *phase_scale, float *dy, void *stream);
+
+/* Adjoint of at_polar_to_complex (SpectralRepresentation.invert, reference spectral_repr.py:449-451), X = mag e^{i phase}:
+ *   gmag = Re gX cos phase + Im gX sin phase,   gphase = mag * (Im gX cos phase - Re gX sin phase)
+ * over n elements; gmag or gphase may be NULL (that gradient is not wanted; mag is read only for gphase).  gX_complex
+ * must be 8-byte aligned, every other pointer 4-byte aligned (AT_EINVAL otherwise, as on null arguments). */
+int at_polar_to_complex_backward(const float *gX_complex, const float *mag, const float *phase, int64_t n, float *gmag,
+                                 float *gphase, void *stream);
+
+/* Adjoint of at_cartesian_unpack (Cartesian.invert, reference spectral_repr.py:497-508): gX (rows, F) complex64 ->
+ * dy (rows, 2, F) float32 with dy[r, 0, :] = Re gX * re_scale and dy[r, 1, :] = Im gX * im_scale (a NULL scale: 1, that
+ * half is not normalised).  gX_complex must be 8-byte aligned, dy_stacked and the scales 4-byte aligned (AT_EINVAL
+ * otherwise, as on null arguments). */
+int at_cartesian_unpack_backward(const float *gX_complex, int64_t rows, int F, const float *re_scale,
+                                 const float *im_scale, float *dy_stacked, void *stream);
+
 /* ---- audio front end ------------------------------------------------------------------------------------- */
 /* torchaudio.transforms.Resample(orig, new) with default arguments, as utils/misc.py:31-33 uses it (algorithm
  * restated, torchaudio is not in the reference tree).  x: (rows, L); orig/new: the rates divided by their gcd;
