@@ -8,75 +8,22 @@
 #include "autograd.h"
 #include "band_bank.h"
 #include "fft512.h"
+#include "stft_launch.h"
 
 #include <atomic>
 #include "variants.h"
 namespace at_hip {
-// stft1024.hip
-int launch_stft1024_fwd(const float*, long long, long long, long long, long long, int, int, const float*,
-                        const float2*, float2*, float*, hipStream_t);
-int launch_stft1024_h256_fwd(const float*, long long, long long, long long, long long, const float*, const float2*,
-                             float2*, float*, const BandBank*, float*, const float*, const float*, float, int, int, int,
-                             hipStream_t, const PolarOut* polar = nullptr, int hop = 256);
-int launch_istft1024_ola(const float2*, const float*, const float*, long long, long long, int, const float*,
-                         const float*, const float2*, float*, hipStream_t, const float2* gl_tprev = nullptr,
-                         float gl_mom = 0.f);
-int launch_irfft1024_frames(const float2*, const float*, const float*, long long, const float*, const float2*,
-                            float*, hipStream_t);
-// stft_generic.hip
-int launch_rfft_generic(const float*, long long, long long, long long, long long, int, int, int, const float*,
-                        float2*, float*, hipStream_t);
-int launch_rfft_mixed(const float*, long long, long long, long long, long long, int, int, int, const float*, float2*,
-                      float*, hipStream_t);
-int launch_irfft_mixed(const float2*, const float*, const float*, long long, int, const float*, float*, hipStream_t);
-int launch_irfft_generic(const float2*, const float*, const float*, long long, int, const float*, float*,
-                         hipStream_t);
-int launch_ola_gather(const float*, long long, long long, int, int, const float*, float*, hipStream_t);
-// stft2048.hip
-int launch_stft2048_fwd(const float*, long long, long long, long long, long long, int, int, const float*, const float2*,
-                        const float2*, float2*, float*, hipStream_t);
-int launch_irfft2048_frames(const float2*, const float*, const float*, long long, const float*, const float2*,
-                            const float2*, float*, hipStream_t);
-int launch_stft512_mel(const float*, long long, long long, long long, long long, int, const float*, const float2*,
-                       const float2*, const BandBank*, int, int, const float*, const float*, float, float*, int, hipStream_t);
-int launch_stft2048_mel(const float*, long long, long long, long long, long long, int, const float*, const float2*,
-                        const float2*, const BandBank*, int, int, const float*, const float*, float, float*, int, hipStream_t);
-int launch_istft2048_ola(const float2*, const float*, const float*, long long, long long, int, const float*,
-                         const float*, const float2*, const float2*, float*, hipStream_t);
-// stft4096.hip
-int launch_stft4096_fwd(const float*, long long, long long, long long, long long, int, int, const float*, const float2*,
-                        const float2*, float2*, float*, hipStream_t);
-int launch_istft4096_ola(const float2*, const float*, const float*, long long, long long, int, const float*, const float*,
-                         const float2*, const float2*, float*, hipStream_t);
-int launch_irfft4096_frames(const float2*, const float*, const float*, long long, const float*, const float2*,
-                            const float2*, float*, hipStream_t);
-// stft_small.hip (n_fft 256 / 128: four / eight frames per wave-level FFT)
-int launch_stft_small_fwd(int, const float*, long long, long long, long long, long long, int, int, const float*, const float2*,
-                          const float2*, float2*, float*, hipStream_t);
-int launch_irfft_small_frames(int, const float2*, const float*, const float*, long long, long long, const float*,
-                              const float2*, const float2*, float*, hipStream_t);
-// stft512.hip
-int launch_stft512_fwd(const float*, long long, long long, long long, long long, int, int, const float*, const float2*,
-                       const float2*, float2*, float*, hipStream_t);
-int launch_irfft512_frames(const float2*, const float*, const float*, long long, long long, const float*, const float2*,
-                           const float2*, float*, hipStream_t);
-int launch_istft512_ola(const float2*, const float*, const float*, long long, long long, int, const float*, const float*,
-                        const float2*, const float2*, float*, hipStream_t);
-
 constexpr int kMaxDevices = 16;
 static float2* g_twiddles[kMaxDevices] = {nullptr};
-static float2* g_tw2048[kMaxDevices] = {nullptr};     // W2048^k, k = 0 .. 1023 (stft2048.hip), then W512^k, k = 0 .. 255 (stft512.hip)
+static float2* g_side[kMaxDevices] = {nullptr};       // the side table (stft_launch.h: kSide*)
 
-static const float2* twiddles_for_current_device() {
+// both twiddle tables of the current device: the fft512 table and the side table, or false before at_init
+static bool device_tables(const float2*& tw, const float2*& side) {
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return nullptr;
-  return g_twiddles[dev];
-}
-
-static const float2* tw2048_for_current_device() {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return nullptr;
-  return g_tw2048[dev];
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices || !g_twiddles[dev]) return false;
+  tw = g_twiddles[dev];
+  side = g_side[dev];
+  return true;
 }
 
 static bool is_pow2(int n) { return n > 0 && (n & (n - 1)) == 0; }
@@ -168,43 +115,26 @@ int at_init(int device) {
   if (rc == AT_OK && hipMemset(d + kTwiddleCount, 0, sizeof(float2) * kTileCtrSlots) != hipSuccess) rc = AT_ELAUNCH;
   float2* d2 = nullptr;
   if (rc == AT_OK) {
-    // [0, 1024): W2048^k; [1024, 1280): W512^k; [1280, 1664): W512^(r k), r = 1..3, k < 128 (n_fft 256);
-    // [1664, 2112): W512^(r k), r = 1..7, k < 64 (n_fft 128)
-    // [2112, 4160): W4096^k, k < 2048; [4160, 5696): W2048^(r k), r = 1..3, k < 512 (n_fft 4096, stft4096.hip)
-    std::vector<float2> t2(1024 + 256 + 384 + 448 + 2048 + 1536);
-    for (int k = 0; k < 2048; ++k) {
-      const double a = -two_pi * (double)k / 4096.0;
-      t2[2112 + k] = make_float2((float)cos(a), (float)sin(a));
-    }
-    for (int r = 1; r < 4; ++r)
-      for (int k = 0; k < 512; ++k) {
-        const double a = -two_pi * (double)(r * k) / 2048.0;
-        t2[4160 + (r - 1) * 512 + k] = make_float2((float)cos(a), (float)sin(a));
+    // W_n^(r k), k < count, at t2[at + k]
+    std::vector<float2> t2(kSideTableCount);
+    auto fill = [&](int at, int count, int r, double n) {
+      for (int k = 0; k < count; ++k) {
+        const double a = -two_pi * (double)(r * k) / n;
+        t2[at + k] = make_float2((float)cos(a), (float)sin(a));
       }
-    for (int r = 1; r < 4; ++r)
-      for (int k = 0; k < 128; ++k) {
-        const double a = -two_pi * (double)(r * k) / 512.0;
-        t2[1280 + (r - 1) * 128 + k] = make_float2((float)cos(a), (float)sin(a));
-      }
-    for (int r = 1; r < 8; ++r)
-      for (int k = 0; k < 64; ++k) {
-        const double a = -two_pi * (double)(r * k) / 512.0;
-        t2[1664 + (r - 1) * 64 + k] = make_float2((float)cos(a), (float)sin(a));
-      }
-    for (int k = 0; k < 1024; ++k) {
-      const double a = -two_pi * (double)k / 2048.0;
-      t2[k] = make_float2((float)cos(a), (float)sin(a));
-    }
-    for (int k = 0; k < 256; ++k) {
-      const double a = -two_pi * (double)k / 512.0;
-      t2[1024 + k] = make_float2((float)cos(a), (float)sin(a));
-    }
+    };
+    fill(kSideW2048, 1024, 1, 2048.0);
+    fill(kSideW512, 256, 1, 512.0);
+    for (int r = 1; r < 4; ++r) fill(kSide256 + (r - 1) * 128, 128, r, 512.0);
+    for (int r = 1; r < 8; ++r) fill(kSide128 + (r - 1) * 64, 64, r, 512.0);
+    fill(kSide4096, 2048, 1, 4096.0);
+    for (int r = 1; r < 4; ++r) fill(kSide4096Radix + (r - 1) * 512, 512, r, 2048.0);
     if (hipMalloc((void**)&d2, sizeof(float2) * t2.size()) != hipSuccess) rc = AT_ELAUNCH;
     if (rc == AT_OK && hipMemcpy(d2, t2.data(), sizeof(float2) * t2.size(), hipMemcpyHostToDevice) != hipSuccess)
       rc = AT_ELAUNCH;
   }
   if (rc == AT_OK) {
-    g_tw2048[device] = d2;
+    g_side[device] = d2;
     g_twiddles[device] = d;
   }
   (void)hipSetDevice(prev);
@@ -219,38 +149,34 @@ int at_stft_forward(const float* x, int64_t B, int64_t L, int64_t clip_stride, i
   if (!fft_size_ok(n_fft)) return AT_EUNSUPPORTED;
   if (center && L <= n_fft / 2) return AT_EINVAL;  // torch.stft: reflect pad must be < L
   hipStream_t s = (hipStream_t)stream;
-  if (n_fft == 1024 && (((uintptr_t)window) & 7) == 0) {
-    const float2* tw = twiddles_for_current_device();
-    if (!tw) return AT_ENOTINIT;
+  const uintptr_t walign = (uintptr_t)window;
+  const float2 *tw = nullptr, *side = nullptr;
+  if (n_fft == 1024 && (walign & 7) == 0) {
+    if (!device_tables(tw, side)) return AT_ENOTINIT;
     if ((hop == 256 || hop == 128 || hop == 512) && center && (clip_stride & 1) == 0)
       return launch_stft1024_h256_fwd(x, B, L, clip_stride, T, window, tw, (float2*)out_complex, phase, nullptr,
                                       nullptr, nullptr, nullptr, 0.f, 0, 0, 0, s, nullptr, hop);
     return launch_stft1024_fwd(x, B, L, clip_stride, T, hop, center, window, tw, (float2*)out_complex, phase, s);
   }
-  if (n_fft == 2048 && (((uintptr_t)window) & 15) == 0) {      // two 512-point register FFTs + a radix-2 stage per frame
-    const float2* tw = twiddles_for_current_device();
-    const float2* tw2k = tw2048_for_current_device();
-    if (!tw || !tw2k) return AT_ENOTINIT;
-    return launch_stft2048_fwd(x, B, L, clip_stride, T, hop, center, window, tw, tw2k, (float2*)out_complex, phase, s);
+  if (n_fft == 2048 && (walign & 15) == 0) {      // two 512-point register FFTs + a radix-2 stage per frame
+    if (!device_tables(tw, side)) return AT_ENOTINIT;
+    return launch_stft2048_fwd(x, B, L, clip_stride, T, hop, center, window, tw, side + kSideW2048, (float2*)out_complex,
+                               phase, s);
   }
-  if (n_fft == 4096 && (((uintptr_t)window) & 15) == 0) {      // four 512-point register FFTs + a radix-4 stage per frame
-    const float2* tw = twiddles_for_current_device();
-    const float2* tw2k = tw2048_for_current_device();
-    if (!tw || !tw2k) return AT_ENOTINIT;
-    return launch_stft4096_fwd(x, B, L, clip_stride, T, hop, center, window, tw, tw2k + 2112, (float2*)out_complex, phase, s);
+  if (n_fft == 4096 && (walign & 15) == 0) {      // four 512-point register FFTs + a radix-4 stage per frame
+    if (!device_tables(tw, side)) return AT_ENOTINIT;
+    return launch_stft4096_fwd(x, B, L, clip_stride, T, hop, center, window, tw, side + kSide4096, (float2*)out_complex,
+                               phase, s);
   }
-  if ((n_fft == 256 || n_fft == 128) && (((uintptr_t)window) & 7) == 0) {     // four / eight frames per register FFT
-    const float2* tw = twiddles_for_current_device();
-    const float2* tw2k = tw2048_for_current_device();
-    if (!tw || !tw2k) return AT_ENOTINIT;
-    return launch_stft_small_fwd(n_fft, x, B, L, clip_stride, T, hop, center, window, tw, tw2k + (n_fft == 256 ? 1280 : 1664),
-                                 (float2*)out_complex, phase, s);
+  if ((n_fft == 256 || n_fft == 128) && (walign & 7) == 0) {     // four / eight frames per register FFT
+    if (!device_tables(tw, side)) return AT_ENOTINIT;
+    return launch_stft_small_fwd(n_fft, x, B, L, clip_stride, T, hop, center, window, tw,
+                                 side + (n_fft == 256 ? kSide256 : kSide128), (float2*)out_complex, phase, s);
   }
-  if (n_fft == 512 && (((uintptr_t)window) & 7) == 0) {        // two frames per 512-point register FFT
-    const float2* tw = twiddles_for_current_device();
-    const float2* tw2k = tw2048_for_current_device();
-    if (!tw || !tw2k) return AT_ENOTINIT;
-    return launch_stft512_fwd(x, B, L, clip_stride, T, hop, center, window, tw, tw2k + 1024, (float2*)out_complex, phase, s);
+  if (n_fft == 512 && (walign & 7) == 0) {        // two frames per 512-point register FFT
+    if (!device_tables(tw, side)) return AT_ENOTINIT;
+    return launch_stft512_fwd(x, B, L, clip_stride, T, hop, center, window, tw, side + kSideW512, (float2*)out_complex,
+                              phase, s);
   }
   if (fft_mixed(n_fft))
     return launch_rfft_mixed(x, B, L, clip_stride, T, n_fft, hop, center, window, (float2*)out_complex, phase, s);
@@ -275,8 +201,8 @@ int at_stft_mel_forward(const float* x, int64_t B, int64_t L, int64_t clip_strid
   if (n_filters <= 0 || n_passes <= 0 || n_passes > 16 || n_filters > 64 * n_passes) return AT_EINVAL;
   if ((offset == nullptr) != (scale == nullptr)) return AT_EINVAL;
   if (L <= n_fft / 2 || (((uintptr_t)window) & (n_fft == 2048 ? 15 : 7)) || (((uintptr_t)band_weights) & 15)) return AT_EINVAL;
-  const float2* tw = twiddles_for_current_device();
-  if (!tw) return AT_ENOTINIT;
+  const float2 *tw = nullptr, *side = nullptr;
+  if (!device_tables(tw, side)) return AT_ENOTINIT;
   BandBank bank = {lane_filter, lane_start, band_weights, n_filters, n_passes, {0}};
   long long table_floats = 0;
   for (int q = 0; q < n_passes; ++q) {
@@ -286,13 +212,11 @@ int at_stft_mel_forward(const float* x, int64_t B, int64_t L, int64_t clip_strid
   }
   if (table_floats > 8192) return AT_EUNSUPPORTED;   // LDS copy of the band weights
   if (feat_only_2048) {
-    const float2* tw2k = tw2048_for_current_device();
-    if (!tw2k) return AT_ENOTINIT;
     if (n_fft == 512)
-      return launch_stft512_mel(x, B, L, clip_stride, T, hop, window, tw, tw2k + 1024, &bank, contrast, power2, offset, scale, eps,
-                                feat, feat_channel_major, (hipStream_t)stream);
-    return launch_stft2048_mel(x, B, L, clip_stride, T, hop, window, tw, tw2k, &bank, contrast, power2, offset, scale, eps, feat,
-                               feat_channel_major, (hipStream_t)stream);
+      return launch_stft512_mel(x, B, L, clip_stride, T, hop, window, tw, side + kSideW512, &bank, contrast, power2, offset,
+                                scale, eps, feat, feat_channel_major, (hipStream_t)stream);
+    return launch_stft2048_mel(x, B, L, clip_stride, T, hop, window, tw, side + kSideW2048, &bank, contrast, power2, offset,
+                               scale, eps, feat, feat_channel_major, (hipStream_t)stream);
   }
   return launch_stft1024_h256_fwd(x, B, L, clip_stride, T, window, tw, (float2*)out_complex_or_null, phase_or_null, &bank,
                                   feat, offset, scale, eps, contrast, power2, feat_channel_major, (hipStream_t)stream,
@@ -313,8 +237,8 @@ int at_stft_polar_forward(const float* x, int64_t B, int64_t L, int64_t clip_str
   if ((mag_offset == nullptr) != (mag_scale == nullptr) || (phase_offset == nullptr) != (phase_scale == nullptr))
     return AT_EINVAL;
   if (L <= n_fft / 2 || (((uintptr_t)window) & 7) || (((uintptr_t)band_weights) & 15)) return AT_EINVAL;
-  const float2* tw = twiddles_for_current_device();
-  if (!tw) return AT_ENOTINIT;
+  const float2 *tw = nullptr, *side = nullptr;
+  if (!device_tables(tw, side)) return AT_ENOTINIT;
   BandBank bank = {lane_filter, lane_start, band_weights, n_filters, n_passes, {0}};
   long long table_floats = 0;
   for (int q = 0; q < n_passes; ++q) {
@@ -339,23 +263,49 @@ int at_istft_envelope_table(const float* inv_window, int n_fft, int hop, float* 
   return hipGetLastError() == hipSuccess ? AT_OK : AT_ELAUNCH;
 }
 
-static bool istft_fast(int n_fft, int hop, const float* env16, const float* w) {
-  return n_fft == 1024 && (hop == 128 || hop == 256 || hop == 512) && env16 != nullptr && (((uintptr_t)w) & 7) == 0 &&
-         (((uintptr_t)env16) & 7) == 0;
+// The fused inverse (irfft + window + overlap-add + envelope in one kernel; stft512.hip ... stft4096.hip) exists at
+// n_fft 512, 1024, 2048, 4096 with hop n/8, n/4, n/2 ...
+static bool istft_fused_size(int n_fft, int hop) {
+  return (n_fft == 512 || n_fft == 1024 || n_fft == 2048 || n_fft == 4096) &&
+         (hop == n_fft / 8 || hop == n_fft / 4 || hop == n_fft / 2);
+}
+// ... and takes the envelope table, with window, table and output aligned to the size's vector width: 8 bytes at 512 and
+// 1024, 16 bytes at 2048 and 4096
+static bool istft_fused(int n_fft, int hop, const float* env16, const float* w, const float* y) {
+  const uintptr_t mask = n_fft >= 2048 ? 15 : 7;
+  return istft_fused_size(n_fft, hop) && env16 != nullptr &&
+         ((((uintptr_t)w) | ((uintptr_t)env16) | ((uintptr_t)y)) & mask) == 0;
 }
 
-static bool istft2048_fused(int n_fft, int hop, const float* env, const float* w, const float* y) {
-  return n_fft == 2048 && (hop == 256 || hop == 512 || hop == 1024) && env != nullptr && (((uintptr_t)w) & 15) == 0 &&
-         (((uintptr_t)env) & 15) == 0 && (((uintptr_t)y) & 15) == 0;
+// irfft(X) * window of pre-framed spectra by size: the register kernels of n_fft 2048 / 4096 (window and frames 16-byte
+// aligned) and 256 / 128 / 512 (8-byte aligned; several frames of one stream of frames_per_stream frames share a
+// transform), else the mixed-radix or the generic kernel.  n_fft 1024 is NOT here: at_irfft_frames_streams takes its
+// register kernel first, at_istft's workspace path (1024 at a hop outside {128, 256, 512}) the generic one.
+static int launch_frames_inverse(int n_fft, const float2* X, const float* mag, const float* phase, long long nframes,
+                                 long long frames_per_stream, const float* window, float* frames, hipStream_t s) {
+  const uintptr_t align = ((uintptr_t)window) | ((uintptr_t)frames);
+  if (((n_fft == 2048 || n_fft == 4096) && (align & 15) == 0) ||
+      ((n_fft == 256 || n_fft == 128 || n_fft == 512) && (align & 7) == 0)) {
+    const float2 *tw = nullptr, *side = nullptr;
+    if (!device_tables(tw, side)) return AT_ENOTINIT;
+    switch (n_fft) {
+      case 2048: return launch_irfft2048_frames(X, mag, phase, nframes, window, tw, side + kSideW2048, frames, s);
+      case 4096: return launch_irfft4096_frames(X, mag, phase, nframes, window, tw, side + kSide4096, frames, s);
+      case 512:
+        return launch_irfft512_frames(X, mag, phase, nframes, frames_per_stream, window, tw, side + kSideW512, frames, s);
+      default:
+        return launch_irfft_small_frames(n_fft, X, mag, phase, nframes, frames_per_stream, window, tw,
+                                         side + (n_fft == 256 ? kSide256 : kSide128), frames, s);
+    }
+  }
+  if (fft_mixed(n_fft)) return launch_irfft_mixed(X, mag, phase, nframes, n_fft, window, frames, s);
+  return launch_irfft_generic(X, mag, phase, nframes, n_fft, window, frames, s);
 }
 
 // The zeros below hold for a 16-byte aligned window (with env16 and y aligned alike): at_istft leaves the fused path for a
 // less aligned one and then asks for the frames workspace (AT_EWORKSPACE before anything is launched).
 size_t at_istft_workspace_bytes(int64_t B, int64_t T, int n_fft, int hop) {
-  if (n_fft == 1024 && (hop == 128 || hop == 256 || hop == 512)) return 0;   // with the envelope table; see at_istft
-  if (n_fft == 2048 && (hop == 256 || hop == 512 || hop == 1024)) return 0;  // likewise (stft2048.hip)
-  if (n_fft == 512 && (hop == 64 || hop == 128 || hop == 256)) return 0;      // likewise (stft512.hip)
-  if (n_fft == 4096 && (hop == 512 || hop == 1024 || hop == 2048)) return 0;  // likewise (stft4096.hip)
+  if (istft_fused_size(n_fft, hop)) return 0;   // with the envelope table; see at_istft
   return (size_t)B * (size_t)T * (size_t)n_fft * sizeof(float);
 }
 
@@ -368,60 +318,20 @@ int at_istft(const float* X_complex, const float* mag, const float* phase, int64
   if (!X_complex && !(mag && phase)) return AT_EINVAL;
   if (!fft_size_ok(n_fft)) return AT_EUNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
-  if (istft_fast(n_fft, hop, env16, inv_window) && (((uintptr_t)y) & 7) == 0) {
-    const float2* tw = twiddles_for_current_device();
-    if (!tw) return AT_ENOTINIT;
-    return launch_istft1024_ola((const float2*)X_complex, mag, phase, B, T, hop, inv_window, env16, tw, y, s);
-  }
-  if (istft2048_fused(n_fft, hop, env16, inv_window, y)) {
-    const float2* tw = twiddles_for_current_device();
-    const float2* tw2k = tw2048_for_current_device();
-    if (!tw || !tw2k) return AT_ENOTINIT;
-    return launch_istft2048_ola((const float2*)X_complex, mag, phase, B, T, hop, inv_window, env16, tw, tw2k, y, s);
-  }
-  if (n_fft == 4096 && (hop == 512 || hop == 1024 || hop == 2048) && env16 && (((uintptr_t)inv_window) & 15) == 0 &&
-      (((uintptr_t)env16) & 15) == 0 && (((uintptr_t)y) & 15) == 0) {
-    const float2* tw = twiddles_for_current_device();
-    const float2* tw2k = tw2048_for_current_device();
-    if (!tw || !tw2k) return AT_ENOTINIT;
-    return launch_istft4096_ola((const float2*)X_complex, mag, phase, B, T, hop, inv_window, env16, tw, tw2k + 2112, y, s);
-  }
-  if (n_fft == 512 && (hop == 64 || hop == 128 || hop == 256) && env16 && (((uintptr_t)inv_window) & 7) == 0 &&
-      (((uintptr_t)env16) & 7) == 0 && (((uintptr_t)y) & 7) == 0) {
-    const float2* tw = twiddles_for_current_device();
-    const float2* tw2k = tw2048_for_current_device();
-    if (!tw || !tw2k) return AT_ENOTINIT;
-    return launch_istft512_ola((const float2*)X_complex, mag, phase, B, T, hop, inv_window, env16, tw, tw2k + 1024, y, s);
+  const float2* X = (const float2*)X_complex;
+  if (istft_fused(n_fft, hop, env16, inv_window, y)) {
+    const float2 *tw = nullptr, *side = nullptr;
+    if (!device_tables(tw, side)) return AT_ENOTINIT;
+    switch (n_fft) {
+      case 512: return launch_istft512_ola(X, mag, phase, B, T, hop, inv_window, env16, tw, side + kSideW512, y, s);
+      case 1024: return launch_istft1024_ola(X, mag, phase, B, T, hop, inv_window, env16, tw, y, s);
+      case 2048: return launch_istft2048_ola(X, mag, phase, B, T, hop, inv_window, env16, tw, side + kSideW2048, y, s);
+      default: return launch_istft4096_ola(X, mag, phase, B, T, hop, inv_window, env16, tw, side + kSide4096, y, s);
+    }
   }
   size_t need = (size_t)B * (size_t)T * (size_t)n_fft * sizeof(float);
   if (!workspace || workspace_bytes < need) return AT_EWORKSPACE;
-  int rc;
-  if (n_fft == 2048 && (((uintptr_t)inv_window) & 15) == 0 && (((uintptr_t)workspace) & 15) == 0) {
-    const float2* tw = twiddles_for_current_device();
-    const float2* tw2k = tw2048_for_current_device();
-    if (!tw || !tw2k) return AT_ENOTINIT;
-    rc = launch_irfft2048_frames((const float2*)X_complex, mag, phase, B * T, inv_window, tw, tw2k, (float*)workspace, s);
-  } else if (n_fft == 4096 && (((uintptr_t)inv_window) & 15) == 0 && (((uintptr_t)workspace) & 15) == 0) {
-    const float2* tw = twiddles_for_current_device();
-    const float2* tw2k = tw2048_for_current_device();
-    if (!tw || !tw2k) return AT_ENOTINIT;
-    rc = launch_irfft4096_frames((const float2*)X_complex, mag, phase, B * T, inv_window, tw, tw2k + 2112, (float*)workspace, s);
-  } else if ((n_fft == 256 || n_fft == 128) && (((uintptr_t)inv_window) & 7) == 0 && (((uintptr_t)workspace) & 7) == 0) {
-    const float2* tw = twiddles_for_current_device();
-    const float2* tw2k = tw2048_for_current_device();
-    if (!tw || !tw2k) return AT_ENOTINIT;
-    rc = launch_irfft_small_frames(n_fft, (const float2*)X_complex, mag, phase, B * T, T, inv_window, tw,
-                                   tw2k + (n_fft == 256 ? 1280 : 1664), (float*)workspace, s);
-  } else if (n_fft == 512 && (((uintptr_t)inv_window) & 7) == 0 && (((uintptr_t)workspace) & 7) == 0) {
-    const float2* tw = twiddles_for_current_device();
-    const float2* tw2k = tw2048_for_current_device();
-    if (!tw || !tw2k) return AT_ENOTINIT;
-    rc = launch_irfft512_frames((const float2*)X_complex, mag, phase, B * T, T, inv_window, tw, tw2k + 1024, (float*)workspace, s);
-  } else if (fft_mixed(n_fft)) {
-    rc = launch_irfft_mixed((const float2*)X_complex, mag, phase, B * T, n_fft, inv_window, (float*)workspace, s);
-  } else {
-    rc = launch_irfft_generic((const float2*)X_complex, mag, phase, B * T, n_fft, inv_window, (float*)workspace, s);
-  }
+  const int rc = launch_frames_inverse(n_fft, X, mag, phase, B * T, T, inv_window, (float*)workspace, s);
   if (rc) return rc;
   return launch_ola_gather((const float*)workspace, B, T, n_fft, hop, inv_window, y, s);
 }
@@ -432,9 +342,9 @@ int at_istft_griffinlim(const float* mag, const float* rebuilt_complex, const fl
   if (B < 0 || T < 0 || hop <= 0 || n_fft <= 0) return AT_EINVAL;
   if (B == 0 || T <= 1) return AT_OK;
   if (!mag || !rebuilt_complex || !inv_window || !y) return AT_EINVAL;
-  if (!istft_fast(n_fft, hop, env16, inv_window) || (((uintptr_t)y) & 7)) return AT_EUNSUPPORTED;
-  const float2* tw = twiddles_for_current_device();
-  if (!tw) return AT_ENOTINIT;
+  if (n_fft != 1024 || !istft_fused(n_fft, hop, env16, inv_window, y)) return AT_EUNSUPPORTED;
+  const float2 *tw = nullptr, *side = nullptr;
+  if (!device_tables(tw, side)) return AT_ENOTINIT;
   // first iteration (no previous spectrum): momentum 0 against the rebuilt spectrum itself
   const float2* tprev = tprev_complex_or_null ? (const float2*)tprev_complex_or_null : (const float2*)rebuilt_complex;
   const float mom = tprev_complex_or_null ? momentum_over_1p : 0.0f;
@@ -454,40 +364,14 @@ int at_irfft_frames_streams(const float* X_complex, const float* mag, const floa
   if (!X_complex && !(mag && phase)) return AT_EINVAL;
   if (!fft_size_ok(n_fft)) return AT_EUNSUPPORTED;
   hipStream_t s = (hipStream_t)stream;
+  const float2* X = (const float2*)X_complex;
+  // only here, ahead of the shared chain: at_istft's workspace path sends n_fft 1024 to the generic kernel
   if (n_fft == 1024 && (((uintptr_t)inv_window) & 7) == 0 && (((uintptr_t)frames) & 7) == 0) {
-    const float2* tw = twiddles_for_current_device();
-    if (!tw) return AT_ENOTINIT;
-    return launch_irfft1024_frames((const float2*)X_complex, mag, phase, nframes, inv_window, tw, frames, s);
+    const float2 *tw = nullptr, *side = nullptr;
+    if (!device_tables(tw, side)) return AT_ENOTINIT;
+    return launch_irfft1024_frames(X, mag, phase, nframes, inv_window, tw, frames, s);
   }
-  if (n_fft == 2048 && (((uintptr_t)inv_window) & 15) == 0 && (((uintptr_t)frames) & 15) == 0) {
-    const float2* tw = twiddles_for_current_device();
-    const float2* tw2k = tw2048_for_current_device();
-    if (!tw || !tw2k) return AT_ENOTINIT;
-    return launch_irfft2048_frames((const float2*)X_complex, mag, phase, nframes, inv_window, tw, tw2k, frames, s);
-  }
-  if (n_fft == 4096 && (((uintptr_t)inv_window) & 15) == 0 && (((uintptr_t)frames) & 15) == 0) {
-    const float2* tw = twiddles_for_current_device();
-    const float2* tw2k = tw2048_for_current_device();
-    if (!tw || !tw2k) return AT_ENOTINIT;
-    return launch_irfft4096_frames((const float2*)X_complex, mag, phase, nframes, inv_window, tw, tw2k + 2112, frames, s);
-  }
-  if ((n_fft == 256 || n_fft == 128) && (((uintptr_t)inv_window) & 7) == 0 && (((uintptr_t)frames) & 7) == 0) {
-    const float2* tw = twiddles_for_current_device();
-    const float2* tw2k = tw2048_for_current_device();
-    if (!tw || !tw2k) return AT_ENOTINIT;
-    return launch_irfft_small_frames(n_fft, (const float2*)X_complex, mag, phase, nframes, frames_per_stream, inv_window, tw,
-                                     tw2k + (n_fft == 256 ? 1280 : 1664), frames, s);
-  }
-  if (n_fft == 512 && (((uintptr_t)inv_window) & 7) == 0 && (((uintptr_t)frames) & 7) == 0) {
-    const float2* tw = twiddles_for_current_device();
-    const float2* tw2k = tw2048_for_current_device();
-    if (!tw || !tw2k) return AT_ENOTINIT;
-    return launch_irfft512_frames((const float2*)X_complex, mag, phase, nframes, frames_per_stream, inv_window, tw, tw2k + 1024,
-                                  frames, s);
-  }
-  if (fft_mixed(n_fft))
-    return launch_irfft_mixed((const float2*)X_complex, mag, phase, nframes, n_fft, inv_window, frames, s);
-  return launch_irfft_generic((const float2*)X_complex, mag, phase, nframes, n_fft, inv_window, frames, s);
+  return launch_frames_inverse(n_fft, X, mag, phase, nframes, frames_per_stream, inv_window, frames, s);
 }
 
 // the whole call is one stream

@@ -1,8 +1,16 @@
-// fastmath.h -- the one transcendental the phase-side kernels are bound by.
+// fastmath.h -- the one transcendental the phase-side kernels are bound by, the large-phase sin / cos of the polar
+// inverses, and the reflect-pad index of every framing kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 
 namespace at_hip {
+
+// index into a clip of L samples under torch.stft's reflect padding (pad < L: one reflection at either end)
+__device__ __forceinline__ long long reflect_index(long long i, long long L) {
+  if (i < 0) i = -i;
+  if (i >= L) i = 2 * (L - 1) - i;
+  return i;
+}
 
 // atan2f in ~24 instructions (ocml's: ~50, and the Polar / IF / unwrap kernels evaluate it 513 times per frame).
 //   t = min(|x|,|y|) / max(|x|,|y|) through v_rcp_f32 (1 ulp);  atan t = t + t s P(s), s = t^2, P of degree 7

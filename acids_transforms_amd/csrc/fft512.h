@@ -19,6 +19,9 @@
 // lanes read 256 contiguous bytes).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "fastmath.h"   // reflect_index
 
 namespace at_hip {
 
@@ -342,41 +345,31 @@ __device__ __forceinline__ void fft512(float2 (&f)[8], const TW& tw, float2* lds
   for (int m = 0; m < 8; ++m) f[m] = to_f2(v[m]);
 }
 
-// Fetch the mirror partner P[m] = Z[(512 - (lane + 64 m)) mod 512] of every element.
-__device__ __forceinline__ void mirror512(const v2f (&v)[8], v2f (&p)[8], int lane) {
-  const int src = (64 - lane) & 63;
-  v2f q[8];
-#pragma unroll
-  for (int m = 0; m < 8; ++m) {
-    q[m].x = __shfl(v[m].x, src, 64);
-    q[m].y = __shfl(v[m].y, src, 64);
-  }
-  // lane 0: partner of k = 64 m is 64 (8 - m) -> own register (8-m)&7
-  // lane>0: partner lives in lane 64-lane, register 7-m
-#pragma unroll
-  for (int m = 0; m < 8; ++m) {
-    const v2f a = q[7 - m];
-    const v2f b = q[(8 - m) & 7];
-    p[m] = (lane == 0) ? b : a;
-  }
-}
-
-// The same with the output columns rotated over the lanes: this lane holds Z[col + 64 m], col = (lane - rot) & 63,
-// and column c sits in lane (c + rot) & 63 -- the partner column (64 - col) & 63 in lane (2 rot - lane) & 63.
-__device__ __forceinline__ void mirror512_rot(const v2f (&v)[8], v2f (&p)[8], int lane, int rot, int col) {
+// Fetch the mirror partner P[m] = Z[(64 Q - k) mod 64 Q] of every element Z[k] of a 64 Q-point spectrum that sits Q
+// registers to the lane (Q = 8: the 512-point FFT above; 4, 16, 32 and 8 / K: the other sizes built on it), with the
+// output columns rotated over the lanes: this lane holds Z[col + 64 m], col = (lane - rot) & 63, and column c sits in lane
+// (c + rot) & 63 -- the partner column (64 - col) & 63 in lane (2 rot - lane) & 63, register Q - 1 - m.  Column 0 is its
+// own partner column: k = 64 m pairs with 64 (Q - m), the lane's own register (Q - m) mod Q.
+template <int Q>
+__device__ __forceinline__ void mirror_regs_rot(const v2f (&v)[Q], v2f (&p)[Q], int lane, int rot, int col) {
   const int src = (2 * rot - lane) & 63;
-  v2f q[8];
+  v2f q[Q];
 #pragma unroll
-  for (int m = 0; m < 8; ++m) {
+  for (int m = 0; m < Q; ++m) {
     q[m].x = __shfl(v[m].x, src, 64);
     q[m].y = __shfl(v[m].y, src, 64);
   }
 #pragma unroll
-  for (int m = 0; m < 8; ++m) {
-    const v2f a = q[7 - m];
-    const v2f b = q[(8 - m) & 7];
+  for (int m = 0; m < Q; ++m) {
+    const v2f a = q[Q - 1 - m];
+    const v2f b = q[(Q - m) % Q];
     p[m] = (col == 0) ? b : a;
   }
+}
+// The same without a rotation: this lane holds Z[lane + 64 m].
+template <int Q>
+__device__ __forceinline__ void mirror_regs(const v2f (&v)[Q], v2f (&p)[Q], int lane) {
+  mirror_regs_rot<Q>(v, p, lane, 0, lane);
 }
 
 // real-FFT merge after the forward complex FFT:
@@ -386,7 +379,7 @@ template <typename TW>
 __device__ __forceinline__ void rfft_merge(v2f (&v)[8], const TW& tw, int lane, float2& nyq) {
   const v2f hh = {0.5f, 0.5f};
   v2f p[8];
-  mirror512(v, p, lane);
+  mirror_regs<8>(v, p, lane);
   nyq = make_float2(v[0].x - v[0].y, 0.0f);
 #pragma unroll
   for (int m = 0; m < 8; ++m) {
@@ -396,13 +389,13 @@ __device__ __forceinline__ void rfft_merge(v2f (&v)[8], const TW& tw, int lane, 
     v[m] = scale_add_mi(e, hh, wd);                  // e/2 - i wd
   }
 }
-// rfft_merge for rotated output columns (see mirror512_rot): `tw` must index its W1024 rows by the COLUMN (an
+// rfft_merge for rotated output columns (see mirror_regs_rot): `tw` must index its W1024 rows by the COLUMN (an
 // LdsTwiddles built with lane = col); X[512] comes out on the lane whose column is 0.
 template <typename TW>
 __device__ __forceinline__ void rfft_merge_rot(v2f (&v)[8], const TW& tw, int lane, int rot, int col, float2& nyq) {
   const v2f hh = {0.5f, 0.5f};
   v2f p[8];
-  mirror512_rot(v, p, lane, rot, col);
+  mirror_regs_rot<8>(v, p, lane, rot, col);
   nyq = make_float2(v[0].x - v[0].y, 0.0f);
 #pragma unroll
   for (int m = 0; m < 8; ++m) {
@@ -430,7 +423,7 @@ __device__ __forceinline__ void irfft_split(v2f (&v)[8], const TW& tw, int lane,
   // c2r ignores the imaginary parts of DC and Nyquist
   if (lane == 0) v[0].y = 0.0f;
   v2f p[8];
-  mirror512(v, p, lane);
+  mirror_regs<8>(v, p, lane);
   if (lane == 0) p[0] = (v2f){xnyq_re, 0.0f};  // partner of k=0 is X[512]
 #pragma unroll
   for (int m = 0; m < 8; ++m) {
@@ -447,6 +440,44 @@ __device__ __forceinline__ void irfft_split(float2 (&f)[8], const TW& tw, int la
   irfft_split(v, tw, lane, xnyq_re);
 #pragma unroll
   for (int m = 0; m < 8; ++m) f[m] = to_f2(v[m]);
+}
+
+// K frames of one clip share a 512-point complex FFT (stft512.hip: K = 2; stft_small.hip: K = 4, 8): lane l carries frame
+// l % K of its group, y[K n + r] = a_r[n].  This lane's 8 complex samples of ITS frame, frame t of clip b:
+// q[j] = (x[s + 2 n], x[s + 2 n + 1]), n = lane / K + (64 / K) j.  A frame past the clip's last one -- an empty slot of
+// its last group -- reads as exact zeros, never as the next clip's first frame.  P: a parameter struct with x,
+// clip_stride, L, T, hop and center; which (b, t) a lane takes is the caller's arithmetic.
+template <int K, typename P>
+__device__ __forceinline__ void load_shared_frame(const P& p, long long b, long long t, int lane, float2 (&q)[8]) {
+  constexpr int N = 1024 / K, PER = 64 / K;
+  if (t >= p.T) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) q[j] = make_float2(0.f, 0.f);
+    return;
+  }
+  const float* clip = p.x + b * p.clip_stride;
+  const long long start = t * (long long)p.hop - (p.center ? N / 2 : 0);
+  const bool interior = (start >= 0) && (start + N <= p.L);
+  const int u = lane / K;
+  if (interior && ((((uintptr_t)(clip + start)) & 7) == 0)) {
+    const float2* src = reinterpret_cast<const float2*>(clip + start);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) q[j] = src[u + PER * j];
+  } else {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const long long i0 = start + 2 * (u + PER * j);
+      float v[2];
+#pragma unroll
+      for (int c = 0; c < 2; ++c) {
+        const long long i = i0 + c;
+        if (interior) v[c] = clip[i];
+        else if (p.center) v[c] = clip[reflect_index(i, p.L)];
+        else v[c] = (i >= 0 && i < p.L) ? clip[i] : 0.0f;     // zero padding past the end (utils/misc.py:156)
+      }
+      q[j] = make_float2(v[0], v[1]);
+    }
+  }
 }
 
 }  // namespace at_hip

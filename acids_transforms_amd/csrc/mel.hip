@@ -31,24 +31,6 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int ROWS = 32;
 constexpr int THREADS = 512;
 
-__device__ __forceinline__ float contrast_fwd(float v, int mode, float eps) {
-  switch (mode) {
-    case C_LOG1P: return logf(1.0f + v);
-    case C_LOG: return logf(fmaxf(v, eps));
-    case C_LOG10: return log10f(fmaxf(v, eps));
-    default: return v;
-  }
-}
-
-__device__ __forceinline__ float contrast_inv(float v, int mode, float eps) {
-  switch (mode) {
-    case C_LOG1P: return expf(v) - 1.0f;
-    case C_LOG: return expf(v) - eps;
-    case C_LOG10: return powf(10.0f, v);
-    default: return v;
-  }
-}
-
 // raw element of A as loaded from HBM (complex pair, or a real value in .x)
 __device__ __forceinline__ float2 load_raw(const MelParams& p, long long row, int k, int colblock) {
   const long long at = row * p.lda + k + (p.a_block_offset ? p.a_block_offset[colblock] : 0);
@@ -63,7 +45,7 @@ __device__ __forceinline__ float finish_a(const MelParams& p, float2 c, float of
     if (p.a_kind == A_REAL_ABS) v = fabsf(v);
     if (p.inverse) {
       if (p.offset) v = __fadd_rn(__fmul_rn(v, sc), off);
-      v = contrast_inv(v, p.contrast, p.eps);
+      v = banded_contrast_inv(v, p.contrast, p.eps);
     }
     return v;
   }
@@ -305,7 +287,7 @@ __global__ void mag_pointwise_kernel(PointParams p) {
     }
     if (p.inverse) {
       if (p.offset) v = __fadd_rn(__fmul_rn(v, sc), off);
-      v = contrast_inv(v, p.contrast, p.eps);
+      v = banded_contrast_inv(v, p.contrast, p.eps);
     } else {
       v = contrast_fwd(v, p.contrast, p.eps);
       if (p.offset) v = (v - off) / sc;

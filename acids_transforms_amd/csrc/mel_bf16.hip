@@ -51,15 +51,6 @@ struct MelBf16Params {
   long long n_tiles;
 };
 
-__device__ __forceinline__ float bf_contrast(float v, int mode, float eps) {
-  switch (mode) {
-    case C_LOG1P: return logf(1.0f + v);
-    case C_LOG: return logf(fmaxf(v, eps));
-    case C_LOG10: return log10f(fmaxf(v, eps));
-    default: return v;
-  }
-}
-
 __device__ __forceinline__ void wave_lds_sync() {
   // the slab is written and read by different lanes of the same wave: LDS operations of one wave complete in
   // order, what has to be pinned is the compiler's ordering
@@ -166,7 +157,7 @@ __global__ __launch_bounds__(BF_THREADS) void mel_bf16_kernel(MelBf16Params p) {
       for (int e = 0; e < 16; ++e) {
         const long long row = row0 + (e & 3) + 8 * (e >> 2) + 4 * h;
         if (row < p.rows && col < p.N) {
-          float v = bf_contrast(acc[t][e], p.contrast, p.eps);
+          float v = contrast_fwd(acc[t][e], p.contrast, p.eps);
           if (norm) v = (v - off) / sc;
           p.out[row * p.ld_out + col] = v;
         }

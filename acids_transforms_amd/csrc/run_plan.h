@@ -73,4 +73,27 @@ inline long long forced_units_per_run(long long units) {
   return v < 8 ? (units < 8 ? units : 8) : v;
 }
 
+// The frame-per-wave kernels (a block's `waves` waves interleave over its units: frames, pairs or groups of frames):
+// units per block in whole rounds of the block's waves, at least one round, at most 2048 workgroups (256 CUs x 8).
+inline long long units_per_block(long long n, int waves) {
+  const long long max_blocks = 256LL * 8;
+  long long upb = (n + max_blocks - 1) / max_blocks;
+  upb = ((upb + waves - 1) / waves) * waves;
+  return upb < waves ? waves : upb;
+}
+
+// Run length of the fused overlap-add kernels, one wave per run of a clip's `units` (output hops; frame pairs at n_fft
+// 512): about `target_waves` waves in the launch, but runs of at least `min_units` -- long enough that the R - 1 warm-up
+// frames stay a small share, short enough to fill the chip -- and never longer than the clip.  The floor is a throughput
+// choice: the kernels take runs of any length >= 1 (warm-up, carry and masks are per unit), so AT_VARIANT_RUN_LENGTH
+// (tests) replaces the plan with its own clamp to [8, units].
+inline long long plan_ola_runs(long long B, long long units, long long target_waves, long long min_units) {
+  const long long runs = (B >= target_waves) ? 1 : (target_waves + B - 1) / B;
+  long long per = (units + runs - 1) / runs;
+  if (per < min_units) per = min_units < units ? min_units : units;
+  if (per < 1) per = 1;
+  if (const long long v = forced_units_per_run(units)) per = v;
+  return per;
+}
+
 }  // namespace at_hip

@@ -24,6 +24,7 @@
 #include "band_bank.h"
 #include "fft512.h"
 #include "run_plan.h"
+#include "stft_launch.h"
 #include "variants.h"
 
 #ifndef AT_ISTFT_NT
@@ -54,12 +55,6 @@ struct FwdParams {
   int hop;
   int center;  // 1: torch.stft center=True/reflect; 0: frame t starts at t*hop
 };
-
-__device__ __forceinline__ long long reflect_index(long long i, long long L) {
-  if (i < 0) i = -i;
-  if (i >= L) i = 2 * (L - 1) - i;
-  return i;
-}
 
 // loads z[lane + 64 m] = (x[2n], x[2n+1]) of frame (b, t) into v
 __device__ __forceinline__ void load_frame(const FwdParams& p, long long f, int lane, float2 (&v)[8]) {
@@ -830,16 +825,6 @@ struct InvParams {
   long long total_frames, frames_per_block;  // OUT_FRAMES
 };
 
-// cos/sin of an unwrapped phase that may be ~1e5 rad (PGHI): reduce in fp64 to revolutions in
-// [-0.5, 0.5] (exact to ~1e-16), then the hardware sin/cos (v_sin_f32 takes revolutions; abs error ~1e-6).
-__device__ __forceinline__ void sincos_big(float phase, float& s, float& c) {
-  double t = (double)phase * 0.15915494309189533577;  // 1 / (2 pi)
-  t -= rint(t);
-  const float r = (float)t;
-  s = __builtin_amdgcn_sinf(r);
-  c = __builtin_amdgcn_cosf(r);
-}
-
 // One frame's spectrum as it sits in HBM, loaded ahead of use and converted when consumed:
 //   IN_COMPLEX: d[m] = X[lane + 64 m],             ny0 = Re X[512]
 //   IN_POLAR:   d[m] = (mag, phase)[lane + 64 m],  (ny0, ny1) = (mag, phase)[512]
@@ -930,11 +915,11 @@ __device__ __forceinline__ void raw_to_spectrum(const RawFrame<IN_POLAR>& q, flo
 #pragma unroll
   for (int m = 0; m < 8; ++m) {
     float sn, cs;
-    sincos_big(q.ph[m], sn, cs);
+    fast_sincosf(q.ph[m], sn, cs);
     v[m] = make_float2(q.a[m] * cs, q.a[m] * sn);
   }
   float sn, cs;
-  sincos_big(q.ny1, sn, cs);
+  fast_sincosf(q.ny1, sn, cs);
   nyq_re = q.ny0 * cs;
 }
 

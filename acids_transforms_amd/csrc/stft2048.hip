@@ -26,6 +26,7 @@
 #include "band_bank.h"
 #include "mel_gemm.h"   // C_* contrast codes
 #include "run_plan.h"
+#include "stft_launch.h"
 #include "variants.h"
 #include <stdlib.h>
 
@@ -48,12 +49,6 @@ struct P2k {
   long long L, clip_stride, T, total_frames, frames_per_block;
   int hop, center;
 };
-
-__device__ __forceinline__ long long reflect2k(long long i, long long L) {
-  if (i < 0) i = -i;
-  if (i >= L) i = 2 * (L - 1) - i;
-  return i;
-}
 
 // q[j] = x[s + 4 (lane + 64 j) .. + 3] of frame f (reflect padding with center, zero padding without)
 __device__ __forceinline__ void load_frame2k(const P2k& p, long long f, int lane, float4 (&q)[8]) {
@@ -80,28 +75,11 @@ __device__ __forceinline__ void load_frame2k(const P2k& p, long long f, int lane
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
         const long long i = i0 + c;
-        if (p.center) v[c] = clip[reflect2k(i, p.L)];
+        if (p.center) v[c] = clip[reflect_index(i, p.L)];
         else v[c] = (i >= 0 && i < p.L) ? clip[i] : 0.0f;     // zero padding past the end (utils/misc.py:156)
       }
       q[j] = make_float4(v[0], v[1], v[2], v[3]);
     }
-  }
-}
-
-// mirror partners P[m] = Z[(1024 - (lane + 64 m)) mod 1024] of the 16 registers
-__device__ __forceinline__ void mirror1024(const v2f (&v)[16], v2f (&p)[16], int lane) {
-  const int src = (64 - lane) & 63;
-  v2f q[16];
-#pragma unroll
-  for (int m = 0; m < 16; ++m) {
-    q[m].x = __shfl(v[m].x, src, 64);
-    q[m].y = __shfl(v[m].y, src, 64);
-  }
-#pragma unroll
-  for (int m = 0; m < 16; ++m) {
-    const v2f a = q[15 - m];            // lane > 0: lane 64 - lane, register 15 - m
-    const v2f b = q[(16 - m) & 15];     // lane 0: own register (16 - m) mod 16
-    p[m] = (lane == 0) ? b : a;
   }
 }
 
@@ -153,7 +131,7 @@ __global__ __launch_bounds__(64 * W2K, 3) void stft2048_fwd_kernel(P2k p) {
       z[m + 8] = e - t;
     }
     v2f pm[16];
-    mirror1024(z, pm, lane);
+    mirror_regs<16>(z, pm, lane);
     // X[k] = (H[k] + conj H') - i W2048^k (H[k] - conj H'),  H = Z / 2,  H' = H[1024 - k]  (k = 0: H' = H[0], X[0] real)
     const float2 nyq = make_float2(2.0f * (z[0].x - z[0].y), 0.0f);    // X[1024] = Re Z[0] - Im Z[0] (lane 0)
     float2* row = p.X + f * F2K;
@@ -195,27 +173,12 @@ struct P2kRun {
   long long B, L, clip_stride, T, runs_per_clip, frames_per_run;
 };
 
-__device__ __forceinline__ void mirror1024_rot(const v2f (&v)[16], v2f (&p)[16], int lane, int rot, int col) {
-  const int src = (2 * rot - lane) & 63;
-  v2f q[16];
-#pragma unroll
-  for (int m = 0; m < 16; ++m) {
-    q[m].x = __shfl(v[m].x, src, 64);
-    q[m].y = __shfl(v[m].y, src, 64);
-  }
-#pragma unroll
-  for (int m = 0; m < 16; ++m) {
-    const v2f a = q[15 - m];
-    const v2f b = q[(16 - m) & 15];
-    p[m] = (col == 0) ? b : a;
-  }
-}
-
 // 256 samples (one register slot of the wave) starting at original index i0 of the clip, reflect-padded
 __device__ __forceinline__ float4 load_slot2k(const float* clip, long long L, long long i0, int lane) {
   const long long i = i0 + 4 * lane;
   if (i0 >= 0 && i0 + 256 <= L) return *reinterpret_cast<const float4*>(clip + i);     // clip base 16-byte aligned (launcher)
-  return make_float4(clip[reflect2k(i, L)], clip[reflect2k(i + 1, L)], clip[reflect2k(i + 2, L)], clip[reflect2k(i + 3, L)]);
+  return make_float4(clip[reflect_index(i, L)], clip[reflect_index(i + 1, L)], clip[reflect_index(i + 2, L)],
+                     clip[reflect_index(i + 3, L)]);
 }
 
 constexpr int W2KR = 8;     // waves per block of the run kernel: two blocks per CU, four waves per SIMD (126 VGPRs)
@@ -284,7 +247,7 @@ __global__ __launch_bounds__(64 * W2KR, 4) void stft2048_run_fwd_kernel(P2kRun p
       z[m + 8] = e - t;
     }
     v2f pm[16];
-    mirror1024_rot(z, pm, lane, rot, col);
+    mirror_regs_rot<16>(z, pm, lane, rot, col);
     const v2f nyq = {2.0f * (z[0].x - z[0].y), 0.0f};          // X[1024], meaningful on the lane whose column is 0
     const v2f* w2 = reinterpret_cast<const v2f*>(w2tab) + col;
 #pragma unroll
@@ -340,14 +303,6 @@ __global__ __launch_bounds__(64 * W2KR, 4) void stft2048_run_fwd_kernel(P2kRun p
   if (lane < rot) put(sp, carry);
 }
 
-__device__ __forceinline__ void sincos_big2k(float phase, float& s, float& c) {
-  double t = (double)phase * 0.15915494309189533577;  // 1 / (2 pi)
-  t -= rint(t);
-  const float r = (float)t;
-  s = __builtin_amdgcn_sinf(r);
-  c = __builtin_amdgcn_cosf(r);
-}
-
 // irfft(X) * window, frames out (the overlap-add is stft_generic.hip's gather): complex or polar input
 template <bool POLAR>
 __global__ __launch_bounds__(64 * W2K, 3) void irfft2048_frames_kernel(P2k p) {
@@ -373,11 +328,11 @@ __global__ __launch_bounds__(64 * W2K, 3) void irfft2048_frames_kernel(P2k p) {
       for (int m = 0; m < 16; ++m) {
         float sn, cs;
         const float a = mrow[lane + 64 * m];
-        sincos_big2k(prow[lane + 64 * m], sn, cs);
+        fast_sincosf(prow[lane + 64 * m], sn, cs);
         v[m] = (v2f){a * cs, a * sn};
       }
       float sn, cs;
-      sincos_big2k(prow[1024], sn, cs);
+      fast_sincosf(prow[1024], sn, cs);
       nyq_re = mrow[1024] * cs;
     } else {
       const float2* row = p.X + f * F2K;
@@ -387,7 +342,7 @@ __global__ __launch_bounds__(64 * W2K, 3) void irfft2048_frames_kernel(P2k p) {
     }
     if (lane == 0) v[0].y = 0.0f;                       // c2r ignores the imaginary parts of DC and Nyquist
     v2f pm[16];
-    mirror1024(v, pm, lane);
+    mirror_regs<16>(v, pm, lane);
     if (lane == 0) pm[0] = (v2f){nyq_re, 0.0f};         // partner of k = 0 is X[1024]
     // Z = E + i O,  E = X + conj X',  O = (X - conj X') conj(W2048^k)   (twice the true value: folded into `scale`)
 #pragma unroll
@@ -514,11 +469,11 @@ __global__ __launch_bounds__(64 * W2K, 2) void istft2048_ola_kernel(P2kOla p) {
         for (int m = 0; m < 16; ++m) {
           float sn, cs;
           const float a = mrow[lane + 64 * m];
-          sincos_big2k(prow[lane + 64 * m], sn, cs);
+          fast_sincosf(prow[lane + 64 * m], sn, cs);
           v[m] = (v2f){a * cs, a * sn};
         }
         float sn, cs;
-        sincos_big2k(prow[1024], sn, cs);
+        fast_sincosf(prow[1024], sn, cs);
         nyq_re = mrow[1024] * cs;
       } else {
 #pragma unroll
@@ -528,7 +483,7 @@ __global__ __launch_bounds__(64 * W2K, 2) void istft2048_ola_kernel(P2kOla p) {
       }
       if (lane == 0) v[0].y = 0.0f;
       v2f pm[16];
-      mirror1024(v, pm, lane);
+      mirror_regs<16>(v, pm, lane);
       if (lane == 0) pm[0] = (v2f){nyq_re, 0.0f};
 #pragma unroll
       for (int m = 0; m < 16; ++m) {
@@ -611,15 +566,6 @@ struct P2kMel {
   float eps;
 };
 
-__device__ __forceinline__ float contrast2k(float v, int mode, float eps) {
-  switch (mode) {
-    case C_LOG1P: return logf(1.0f + v);
-    case C_LOG: return logf(fmaxf(v, eps));
-    case C_LOG10: return log10f(fmaxf(v, eps));
-    default: return v;
-  }
-}
-
 // CMW 1 / 2: channel-major output of a bank with that many passes (register window); 0: anything else.  WINLDS: the
 // analysis window staged in LDS (when the bank's tables leave 8 KB of the two-blocks-per-CU budget).
 template <int CMW, bool WINLDS>
@@ -699,7 +645,7 @@ __global__ __launch_bounds__(64 * W2K, 2) void stft2048_mel_kernel(P2kMel p) {
       z[m + 8] = e - t;
     }
     v2f pm[16];
-    mirror1024(z, pm, lane);
+    mirror_regs<16>(z, pm, lane);
     const float nyq = 2.0f * (z[0].x - z[0].y);          // X[1024] (lane 0), real
 #pragma unroll
     for (int m = 0; m < 16; ++m) {
@@ -748,7 +694,7 @@ __global__ __launch_bounds__(64 * W2K, 2) void stft2048_mel_kernel(P2kMel p) {
           acc2 = __builtin_elementwise_fma((v2f){av.z, av.w}, (v2f){wv.z, wv.w}, acc2);
         }
         w += quads * 64;
-        float acc = contrast2k(acc2.x + acc2.y, p.contrast, p.eps);
+        float acc = contrast_fwd(acc2.x + acc2.y, p.contrast, p.eps);
         if (p.offset) acc = (acc - off) / sc;
 #pragma unroll
         for (int k = 0; k < 7; ++k) cm[q][k] = cm[q][k + 1];
@@ -807,7 +753,7 @@ __global__ __launch_bounds__(64 * W2K, 2) void stft2048_mel_kernel(P2kMel p) {
         }
         w += quads * 64;
         if (filt >= 0) {
-          float acc = contrast2k(acc2.x + acc2.y, p.contrast, p.eps);
+          float acc = contrast_fwd(acc2.x + acc2.y, p.contrast, p.eps);
           if (p.offset) acc = (acc - off) / sc;
           if (p.channel_major) p.feat[(b * p.bank.n_filters + filt) * p.T + t] = acc;
           else p.feat[f * p.bank.n_filters + filt] = acc;
@@ -869,17 +815,9 @@ int launch_istft2048_ola(const float2* X, const float* mag, const float* phase, 
   if (B == 0 || T <= 1) return 0;
   P2kOla p = {X, mag, phase, window, env, tw, tw2k, y, B, T, 0, 0};
   const long long blocks = T - 1;                        // output hops per clip
-  // runs long enough that the R - 1 warm-up frames stay a small share, short enough to fill the chip
-  long long runs = (B >= 2048) ? 1 : (2048 + B - 1) / B;
-  long long per = (blocks + runs - 1) / runs;
-  const long long min_per = 8;
-  if (per < min_per) per = min_per < blocks ? min_per : blocks;
-  // AT_VARIANT_RUN_LENGTH (tests): the kernel takes runs of any length >= 1, its warm-up and masks are per hop
-  if (const long long v = forced_units_per_run(blocks)) per = v;
-  runs = (blocks + per - 1) / per;
-  p.runs_per_clip = runs;
-  p.blocks_per_run = per;
-  const long long waves = B * runs;
+  p.blocks_per_run = plan_ola_runs(B, blocks, 2048, 8);
+  p.runs_per_clip = (blocks + p.blocks_per_run - 1) / p.blocks_per_run;
+  const long long waves = B * p.runs_per_clip;
   const unsigned grid = (unsigned)((waves + W2K - 1) / W2K);
 #define OLA2K(POLAR_, HS_) hipLaunchKernelGGL((istft2048_ola_kernel<POLAR_, HS_>), dim3(grid), dim3(64 * W2K), 0, stream, p)
   const bool polar = (X == nullptr);
@@ -889,13 +827,6 @@ int launch_istft2048_ola(const float2* X, const float* mag, const float* phase, 
   else return -2;
 #undef OLA2K
   return hipGetLastError() == hipSuccess ? 0 : -5;
-}
-
-static long long frames_per_block_2k(long long nframes) {
-  const long long max_blocks = 256LL * 8;
-  long long fpb = (nframes + max_blocks - 1) / max_blocks;
-  fpb = ((fpb + W2K - 1) / W2K) * W2K;
-  return fpb < W2K ? W2K : fpb;
 }
 
 int launch_stft2048_fwd(const float* x, long long B, long long L, long long clip_stride, long long T, int hop, int center,
@@ -921,7 +852,7 @@ int launch_stft2048_fwd(const float* x, long long B, long long L, long long clip
     hipLaunchKernelGGL(stft2048_run_fwd_kernel, dim3((unsigned)((waves + W2KR - 1) / W2KR)), dim3(64 * W2KR), 0, stream, q);
     return hipGetLastError() == hipSuccess ? 0 : -5;
   }
-  p.frames_per_block = frames_per_block_2k(nframes);
+  p.frames_per_block = units_per_block(nframes, W2K);
   const long long blocks = (nframes + p.frames_per_block - 1) / p.frames_per_block;
   if (phase) hipLaunchKernelGGL(stft2048_fwd_kernel<true>, dim3((unsigned)blocks), dim3(64 * W2K), 0, stream, p);
   else hipLaunchKernelGGL(stft2048_fwd_kernel<false>, dim3((unsigned)blocks), dim3(64 * W2K), 0, stream, p);
@@ -934,7 +865,7 @@ int launch_irfft2048_frames(const float2* X, const float* mag, const float* phas
   P2k p = {};
   p.X = const_cast<float2*>(X); p.mag = mag; p.phase = phase; p.window = window; p.tw = tw; p.tw2k = tw2k; p.y = frames;
   p.total_frames = nframes;
-  p.frames_per_block = frames_per_block_2k(nframes);
+  p.frames_per_block = units_per_block(nframes, W2K);
   const long long blocks = (nframes + p.frames_per_block - 1) / p.frames_per_block;
   if (X) hipLaunchKernelGGL(irfft2048_frames_kernel<false>, dim3((unsigned)blocks), dim3(64 * W2K), 0, stream, p);
   else hipLaunchKernelGGL(irfft2048_frames_kernel<true>, dim3((unsigned)blocks), dim3(64 * W2K), 0, stream, p);

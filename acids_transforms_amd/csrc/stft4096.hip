@@ -23,6 +23,7 @@
 #include "fastmath.h"
 #include "fft512.h"
 #include "run_plan.h"
+#include "stft_launch.h"
 #include "variants.h"
 #include <stdlib.h>
 
@@ -31,7 +32,7 @@ namespace at_hip {
 constexpr int N4K = 4096;
 constexpr int F4K = N4K / 2 + 1;     // 2049
 constexpr int W4K = 4;               // waves per block
-constexpr int kTab4k = 2048 + 3 * 512;   // W4096^k, k < 2048; then W2048^(r k), r = 1..3, k < 512 (capi.hip)
+constexpr int kTab4k = kSideTableCount - kSide4096;   // the n_fft-4096 block of the side table (stft_launch.h)
 
 struct P4k {
   const float* x;        // forward: audio, clip b at x + b*clip_stride
@@ -46,12 +47,6 @@ struct P4k {
   long long L, clip_stride, T, total_frames, frames_per_block;
   int hop, center;
 };
-
-__device__ __forceinline__ long long reflect4k(long long i, long long L) {
-  if (i < 0) i = -i;
-  if (i >= L) i = 2 * (L - 1) - i;
-  return i;
-}
 
 // (qa[j], qb[j]) = x[s + 8 (lane + 64 j) .. + 7] of frame f (reflect padding with center, zero padding without)
 __device__ __forceinline__ void load_frame4k(const P4k& p, long long f, int lane, float4 (&qa)[8], float4 (&qb)[8]) {
@@ -82,29 +77,12 @@ __device__ __forceinline__ void load_frame4k(const P4k& p, long long f, int lane
 #pragma unroll
       for (int c = 0; c < 8; ++c) {
         const long long i = i0 + c;
-        if (p.center) v[c] = clip[reflect4k(i, p.L)];
+        if (p.center) v[c] = clip[reflect_index(i, p.L)];
         else v[c] = (i >= 0 && i < p.L) ? clip[i] : 0.0f;     // zero padding past the end (utils/misc.py:156)
       }
       qa[j] = make_float4(v[0], v[1], v[2], v[3]);
       qb[j] = make_float4(v[4], v[5], v[6], v[7]);
     }
-  }
-}
-
-// mirror partners P[m] = Z[(2048 - (lane + 64 m)) mod 2048] of the 32 registers
-__device__ __forceinline__ void mirror2048(const v2f (&v)[32], v2f (&p)[32], int lane) {
-  const int src = (64 - lane) & 63;
-  v2f q[32];
-#pragma unroll
-  for (int m = 0; m < 32; ++m) {
-    q[m].x = __shfl(v[m].x, src, 64);
-    q[m].y = __shfl(v[m].y, src, 64);
-  }
-#pragma unroll
-  for (int m = 0; m < 32; ++m) {
-    const v2f a = q[31 - m];            // lane > 0: lane 64 - lane, register 31 - m
-    const v2f b = q[(32 - m) & 31];     // lane 0: own register (32 - m) mod 32
-    p[m] = (lane == 0) ? b : a;
   }
 }
 
@@ -173,7 +151,7 @@ __global__ __launch_bounds__(64 * W4K, 2) void stft4096_fwd_kernel(P4k p) {
       z[m + 24] = add_pi(b, d);       // b + i d
     }
     v2f pm[32];
-    mirror2048(z, pm, lane);
+    mirror_regs<32>(z, pm, lane);
     // X[k] = (Z[k] + conj Z')/2 - i (W4096^k / 2) (Z[k] - conj Z'),  Z' = Z[2048 - k]  (k = 0: Z' = Z[0], X[0] real)
     const float2 nyq = make_float2(z[0].x - z[0].y, 0.0f);      // X[2048] = Re Z[0] - Im Z[0] (lane 0)
     float2* row = p.X + f * F4K;
@@ -213,22 +191,6 @@ struct P4kRun {
   long long B, L, clip_stride, T, runs_per_clip, frames_per_run;
 };
 
-__device__ __forceinline__ void mirror2048_rot(const v2f (&v)[32], v2f (&p)[32], int lane, int rot, int col) {
-  const int src = (2 * rot - lane) & 63;
-  v2f q[32];
-#pragma unroll
-  for (int m = 0; m < 32; ++m) {
-    q[m].x = __shfl(v[m].x, src, 64);
-    q[m].y = __shfl(v[m].y, src, 64);
-  }
-#pragma unroll
-  for (int m = 0; m < 32; ++m) {
-    const v2f a = q[31 - m];
-    const v2f b = q[(32 - m) & 31];
-    p[m] = (col == 0) ? b : a;
-  }
-}
-
 // 512 samples (one register slot of the wave) starting at original index i0 of the clip, reflect-padded
 __device__ __forceinline__ void load_slot4k(const float* clip, long long L, long long i0, int lane, float4& a, float4& b) {
   const long long i = i0 + 8 * lane;
@@ -239,7 +201,7 @@ __device__ __forceinline__ void load_slot4k(const float* clip, long long L, long
   }
   float v[8];
 #pragma unroll
-  for (int c = 0; c < 8; ++c) v[c] = clip[reflect4k(i + c, L)];
+  for (int c = 0; c < 8; ++c) v[c] = clip[reflect_index(i + c, L)];
   a = make_float4(v[0], v[1], v[2], v[3]);
   b = make_float4(v[4], v[5], v[6], v[7]);
 }
@@ -325,7 +287,7 @@ __global__ __launch_bounds__(64 * W4K, 2) void stft4096_run_fwd_kernel(P4kRun p)
       z[m + 24] = add_pi(bb, d);
     }
     v2f pm[32];
-    mirror2048_rot(z, pm, lane, rot, col);
+    mirror_regs_rot<32>(z, pm, lane, rot, col);
     const v2f nyq = {z[0].x - z[0].y, 0.0f};                           // X[2048], on the lane whose column is 0
 #pragma unroll
     for (int m = 0; m < 32; ++m) {
@@ -381,14 +343,6 @@ __global__ __launch_bounds__(64 * W4K, 2) void stft4096_run_fwd_kernel(P4kRun p)
   if (lane < rot) put(sp, carry);
 }
 
-__device__ __forceinline__ void sincos_big4k(float phase, float& s, float& c) {
-  double t = (double)phase * 0.15915494309189533577;  // 1 / (2 pi)
-  t -= rint(t);
-  const float r = (float)t;
-  s = __builtin_amdgcn_sinf(r);
-  c = __builtin_amdgcn_cosf(r);
-}
-
 // one-sided spectrum of frame f -> the four sub-transform inputs, ready for fft512<true> (shared by the frames kernel)
 template <bool POLAR>
 __device__ __forceinline__ void spectrum_to_subffts4k(const float2* X, const float* mag, const float* phase, long long f,
@@ -403,11 +357,11 @@ __device__ __forceinline__ void spectrum_to_subffts4k(const float2* X, const flo
     for (int m = 0; m < 32; ++m) {
       float sn, cs;
       const float a = mrow[lane + 64 * m];
-      sincos_big4k(prow[lane + 64 * m], sn, cs);
+      fast_sincosf(prow[lane + 64 * m], sn, cs);
       v[m] = (v2f){a * cs, a * sn};
     }
     float sn, cs;
-    sincos_big4k(prow[2048], sn, cs);
+    fast_sincosf(prow[2048], sn, cs);
     nyq_re = mrow[2048] * cs;
   } else {
     const float2* row = X + f * F4K;
@@ -417,7 +371,7 @@ __device__ __forceinline__ void spectrum_to_subffts4k(const float2* X, const flo
   }
   if (lane == 0) v[0].y = 0.0f;                       // c2r ignores the imaginary parts of DC and Nyquist
   v2f pm[32];
-  mirror2048(v, pm, lane);
+  mirror_regs<32>(v, pm, lane);
   if (lane == 0) pm[0] = (v2f){nyq_re, 0.0f};         // partner of k = 0 is X[2048]
   // Z = E + i O,  E = X + conj X',  O = (X - conj X') conj(W4096^k)   (twice the true value: folded into the scale)
 #pragma unroll
@@ -606,16 +560,9 @@ int launch_istft4096_ola(const float2* X, const float* mag, const float* phase, 
   if (B == 0 || T <= 1) return 0;
   P4kOla p = {X, mag, phase, window, env, tw, tw4k, y, B, T, 0, 0};
   const long long blocks = T - 1;                        // output hops per clip
-  long long runs = (B >= 2048) ? 1 : (2048 + B - 1) / B;
-  long long per = (blocks + runs - 1) / runs;
-  const long long min_per = 8;
-  if (per < min_per) per = min_per < blocks ? min_per : blocks;
-  // AT_VARIANT_RUN_LENGTH (tests): the kernel takes runs of any length >= 1, its warm-up and masks are per hop
-  if (const long long v = forced_units_per_run(blocks)) per = v;
-  runs = (blocks + per - 1) / per;
-  p.runs_per_clip = runs;
-  p.blocks_per_run = per;
-  const long long waves = B * runs;
+  p.blocks_per_run = plan_ola_runs(B, blocks, 2048, 8);
+  p.runs_per_clip = (blocks + p.blocks_per_run - 1) / p.blocks_per_run;
+  const long long waves = B * p.runs_per_clip;
   const unsigned grid = (unsigned)((waves + W4K - 1) / W4K);
 #define OLA4K(POLAR_, HS_) hipLaunchKernelGGL((istft4096_ola_kernel<POLAR_, HS_>), dim3(grid), dim3(64 * W4K), 0, stream, p)
   const bool polar = (X == nullptr);
@@ -625,13 +572,6 @@ int launch_istft4096_ola(const float2* X, const float* mag, const float* phase, 
   else return -2;
 #undef OLA4K
   return hipGetLastError() == hipSuccess ? 0 : -5;
-}
-
-static long long frames_per_block_4k(long long nframes) {
-  const long long max_blocks = 256LL * 8;
-  long long fpb = (nframes + max_blocks - 1) / max_blocks;
-  fpb = ((fpb + W4K - 1) / W4K) * W4K;
-  return fpb < W4K ? W4K : fpb;
 }
 
 int launch_stft4096_fwd(const float* x, long long B, long long L, long long clip_stride, long long T, int hop, int center,
@@ -657,7 +597,7 @@ int launch_stft4096_fwd(const float* x, long long B, long long L, long long clip
     hipLaunchKernelGGL(stft4096_run_fwd_kernel, dim3((unsigned)((waves + W4K - 1) / W4K)), dim3(64 * W4K), 0, stream, q);
     return hipGetLastError() == hipSuccess ? 0 : -5;
   }
-  p.frames_per_block = frames_per_block_4k(nframes);
+  p.frames_per_block = units_per_block(nframes, W4K);
   const long long blocks = (nframes + p.frames_per_block - 1) / p.frames_per_block;
   if (phase) hipLaunchKernelGGL(stft4096_fwd_kernel<true>, dim3((unsigned)blocks), dim3(64 * W4K), 0, stream, p);
   else hipLaunchKernelGGL(stft4096_fwd_kernel<false>, dim3((unsigned)blocks), dim3(64 * W4K), 0, stream, p);
@@ -670,7 +610,7 @@ int launch_irfft4096_frames(const float2* X, const float* mag, const float* phas
   P4k p = {};
   p.X = const_cast<float2*>(X); p.mag = mag; p.phase = phase; p.window = window; p.tw = tw; p.tw4k = tw4k; p.y = frames;
   p.total_frames = nframes;
-  p.frames_per_block = frames_per_block_4k(nframes);
+  p.frames_per_block = units_per_block(nframes, W4K);
   const long long blocks = (nframes + p.frames_per_block - 1) / p.frames_per_block;
   if (X) hipLaunchKernelGGL(irfft4096_frames_kernel<false>, dim3((unsigned)blocks), dim3(64 * W4K), 0, stream, p);
   else hipLaunchKernelGGL(irfft4096_frames_kernel<true>, dim3((unsigned)blocks), dim3(64 * W4K), 0, stream, p);

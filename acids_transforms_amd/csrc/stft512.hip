@@ -25,6 +25,7 @@
 #include "band_bank.h"
 #include "mel_gemm.h"   // C_* contrast codes
 #include "run_plan.h"
+#include "stft_launch.h"
 #include "variants.h"
 #include <stdlib.h>
 
@@ -47,63 +48,6 @@ struct P5 {
   long long L, clip_stride, T, n_clips, pairs_per_clip, pairs_per_block;   // T: frames per clip (inverse: per stream)
   int hop, center;
 };
-
-__device__ __forceinline__ long long reflect5(long long i, long long L) {
-  if (i < 0) i = -i;
-  if (i >= L) i = 2 * (L - 1) - i;
-  return i;
-}
-
-// this lane's 8 complex samples of ITS frame (frame t of clip b: even lanes of the pair's first frame, odd lanes the
-// second): q[j] = (x[s + 2 n], x[s + 2 n + 1]), n = (lane >> 1) + 32 j; the missing partner of a clip's last frame
-// (odd T) reads as exact zeros, never as the next clip's first frame
-__device__ __forceinline__ void load_half_frame5(const P5& p, long long b, long long t, int lane, float2 (&q)[8]) {
-  if (t >= p.T) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) q[j] = make_float2(0.f, 0.f);
-    return;
-  }
-  const float* clip = p.x + b * p.clip_stride;
-  const long long start = t * (long long)p.hop - (p.center ? N5 / 2 : 0);
-  const bool interior = (start >= 0) && (start + N5 <= p.L);
-  const int u = lane >> 1;
-  if (interior && ((((uintptr_t)(clip + start)) & 7) == 0)) {
-    const float2* src = reinterpret_cast<const float2*>(clip + start);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) q[j] = src[u + 32 * j];
-  } else {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const long long i0 = start + 2 * (u + 32 * j);
-      float v[2];
-#pragma unroll
-      for (int c = 0; c < 2; ++c) {
-        const long long i = i0 + c;
-        if (interior) v[c] = clip[i];
-        else if (p.center) v[c] = clip[reflect5(i, p.L)];
-        else v[c] = (i >= 0 && i < p.L) ? clip[i] : 0.0f;     // zero padding past the end (utils/misc.py:156)
-      }
-      q[j] = make_float2(v[0], v[1]);
-    }
-  }
-}
-
-// mirror partners P[m] = A[(256 - (lane + 64 m)) mod 256], m = 0 .. 3
-__device__ __forceinline__ void mirror256(const v2f (&v)[4], v2f (&p)[4], int lane) {
-  const int src = (64 - lane) & 63;
-  v2f q[4];
-#pragma unroll
-  for (int m = 0; m < 4; ++m) {
-    q[m].x = __shfl(v[m].x, src, 64);
-    q[m].y = __shfl(v[m].y, src, 64);
-  }
-#pragma unroll
-  for (int m = 0; m < 4; ++m) {
-    const v2f a = q[3 - m];
-    const v2f b = q[(4 - m) & 3];
-    p[m] = (lane == 0) ? b : a;
-  }
-}
 
 template <bool WRITE_PHASE>
 __global__ __launch_bounds__(64 * W5) void stft512_fwd_kernel(P5 p) {
@@ -130,7 +74,7 @@ __global__ __launch_bounds__(64 * W5) void stft512_fwd_kernel(P5 p) {
   // pair pr is frames 2 i, 2 i + 1 of clip b, pr = b pairs_per_clip + i
   auto load_pair = [&](long long q, float2 (&dst)[8]) {
     const long long b = q / p.pairs_per_clip;
-    load_half_frame5(p, b, 2 * (q - b * p.pairs_per_clip) + (lane & 1), lane, dst);
+    load_shared_frame<2>(p, b, 2 * (q - b * p.pairs_per_clip) + (lane & 1), lane, dst);
   };
   long long pr = pr_begin + wave;
   float2 nxt[8];
@@ -151,8 +95,8 @@ __global__ __launch_bounds__(64 * W5) void stft512_fwd_kernel(P5 p) {
       hb[m] = cmul_conj_v(d, w5[m]) * hh;                 // B / 2
     }
     v2f pa[4], pb[4];
-    mirror256(ha, pa, lane);
-    mirror256(hb, pb, lane);
+    mirror_regs<4>(ha, pa, lane);
+    mirror_regs<4>(hb, pb, lane);
     const long long cb = pr / p.pairs_per_clip;
     const long long ta = 2 * (pr - cb * p.pairs_per_clip);
     const long long fa = cb * p.T + ta, fb = fa + 1;
@@ -203,26 +147,10 @@ struct P5Run {
   long long B, L, clip_stride, T, runs_per_clip, pairs_per_run;
 };
 
-__device__ __forceinline__ void mirror256_rot(const v2f (&v)[4], v2f (&p)[4], int lane, int rot, int col) {
-  const int src = (2 * rot - lane) & 63;
-  v2f q[4];
-#pragma unroll
-  for (int m = 0; m < 4; ++m) {
-    q[m].x = __shfl(v[m].x, src, 64);
-    q[m].y = __shfl(v[m].y, src, 64);
-  }
-#pragma unroll
-  for (int m = 0; m < 4; ++m) {
-    const v2f a = q[3 - m];
-    const v2f b = q[(4 - m) & 3];
-    p[m] = (col == 0) ? b : a;
-  }
-}
-
 // two samples of a frame that starts at original index s (reflect-padded)
 __device__ __forceinline__ float2 load_pair5(const float* clip, long long L, long long i, bool interior) {
   if (interior) return *reinterpret_cast<const float2*>(clip + i);        // clip base 8-byte aligned, i even
-  return make_float2(clip[reflect5(i, L)], clip[reflect5(i + 1, L)]);
+  return make_float2(clip[reflect_index(i, L)], clip[reflect_index(i + 1, L)]);
 }
 
 constexpr int W5R = 8;      // waves per block of the run kernel
@@ -324,8 +252,8 @@ __global__ __launch_bounds__(64 * W5R, 4) void stft512_run_fwd_kernel(P5Run p) {
       hb[m] = cmul_conj_v(d, wk[m]) * hh;                  // B / 2
     }
     v2f pa[4], pb[4];
-    mirror256_rot(ha, pa, lane, rot, col);
-    mirror256_rot(hb, pb, lane, rot, col);
+    mirror_regs_rot<4>(ha, pa, lane, rot, col);
+    mirror_regs_rot<4>(hb, pb, lane, rot, col);
     v2f xa[4], xb[4];
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
@@ -389,14 +317,6 @@ __global__ __launch_bounds__(64 * W5R, 4) void stft512_run_fwd_kernel(P5Run p) {
   if (lane < rot) put(sp, carry);
 }
 
-__device__ __forceinline__ void sincos_big5(float phase, float& s, float& c) {
-  double t = (double)phase * 0.15915494309189533577;  // 1 / (2 pi)
-  t -= rint(t);
-  const float r = (float)t;
-  s = __builtin_amdgcn_sinf(r);
-  c = __builtin_amdgcn_cosf(r);
-}
-
 // one frame's one-sided spectrum -> A[k] * 2 (k = lane + 64 m, m = 0..3): E + i O of the inverse split
 template <bool POLAR>
 __device__ __forceinline__ void load_split5(const P5& p, long long f, bool exists, int lane, const v2f (&w5)[4],
@@ -415,11 +335,11 @@ __device__ __forceinline__ void load_split5(const P5& p, long long f, bool exist
     for (int m = 0; m < 4; ++m) {
       float sn, cs;
       const float g = mrow[lane + 64 * m];
-      sincos_big5(prow[lane + 64 * m], sn, cs);
+      fast_sincosf(prow[lane + 64 * m], sn, cs);
       v[m] = (v2f){g * cs, g * sn};
     }
     float sn, cs;
-    sincos_big5(prow[256], sn, cs);
+    fast_sincosf(prow[256], sn, cs);
     nyq_re = mrow[256] * cs;
   } else {
     const float2* row = p.X + f * F5;
@@ -429,7 +349,7 @@ __device__ __forceinline__ void load_split5(const P5& p, long long f, bool exist
   }
   if (lane == 0) v[0].y = 0.0f;                 // c2r ignores the imaginary parts of DC and Nyquist
   v2f pm[4];
-  mirror256(v, pm, lane);
+  mirror_regs<4>(v, pm, lane);
   if (lane == 0) pm[0] = (v2f){nyq_re, 0.0f};   // partner of k = 0 is X[256]
 #pragma unroll
   for (int m = 0; m < 4; ++m) {
@@ -634,18 +554,9 @@ int launch_istft512_ola(const float2* X, const float* mag, const float* phase, l
   P5Ola p = {X, mag, phase, window, env, tw, tw512, y, B, T, 0, 0};
   const long long lead = 256 / hop;
   const long long pairs = (lead + T - 1 + 1) / 2 - lead / 2;             // pairs that hold a valid block
-  long long runs = (B >= 4096) ? 1 : (4096 + B - 1) / B;
-  long long per = (pairs + runs - 1) / runs;
-  const long long min_per = 16;
-  if (per < min_per) per = min_per < pairs ? min_per : pairs;
-  if (per < 1) per = 1;
-  // AT_VARIANT_RUN_LENGTH (tests), in frame pairs.  The floor of 16 above is a throughput choice: the kernel's warm-up
-  // ((R + 1) / 2 pairs), carry and masks are per pair, so the variant's own clamp to [8, pairs] holds here too.
-  if (const long long v = forced_units_per_run(pairs)) per = v;
-  runs = (pairs + per - 1) / per;
-  p.runs_per_clip = runs;
-  p.pairs_per_run = per;
-  const long long waves = B * runs;
+  p.pairs_per_run = plan_ola_runs(B, pairs, 4096, 16);             // in frame pairs
+  p.runs_per_clip = (pairs + p.pairs_per_run - 1) / p.pairs_per_run;
+  const long long waves = B * p.runs_per_clip;
   const unsigned grid = (unsigned)((waves + W5 - 1) / W5);
 #define OLA5(POLAR_, HS_) hipLaunchKernelGGL((istft512_ola_kernel<POLAR_, HS_>), dim3(grid), dim3(64 * W5), 0, stream, p)
   const bool polar = (X == nullptr);
@@ -655,13 +566,6 @@ int launch_istft512_ola(const float2* X, const float* mag, const float* phase, l
   else return -2;
 #undef OLA5
   return hipGetLastError() == hipSuccess ? 0 : -5;
-}
-
-static long long pairs_per_block_5(long long npairs) {
-  const long long max_blocks = 256LL * 8;
-  long long ppb = (npairs + max_blocks - 1) / max_blocks;
-  ppb = ((ppb + W5 - 1) / W5) * W5;
-  return ppb < W5 ? W5 : ppb;
 }
 
 // ---------------------------------------------------------------------------
@@ -820,7 +724,7 @@ __global__ __launch_bounds__(64 * W5) void stft512_mel_kernel(P5Mel p) {
   };
 
   float2 nxt[8];
-  load_half_frame5(lp, pb, 2 * pi + (lane & 1), lane, nxt);
+  load_shared_frame<2>(lp, pb, 2 * pi + (lane & 1), lane, nxt);
   for (long long pr = pr_begin; pr < pr_end; ++pr) {
     const long long fa = pb * p.T + 2 * pi;
     const bool has_b = 2 * pi + 1 < p.T;
@@ -832,7 +736,7 @@ __global__ __launch_bounds__(64 * W5) void stft512_mel_kernel(P5Mel p) {
     v2f y[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) y[j] = (v2f){nxt[j].x * win[j].x, nxt[j].y * win[j].y};
-    if (pr + 1 < pr_end) load_half_frame5(lp, pb, 2 * pi + (lane & 1), lane, nxt);
+    if (pr + 1 < pr_end) load_shared_frame<2>(lp, pb, 2 * pi + (lane & 1), lane, nxt);
     fft512<false>(y, tw, lds, lane);
     v2f ha[4], hb[4];
 #pragma unroll
@@ -843,8 +747,8 @@ __global__ __launch_bounds__(64 * W5) void stft512_mel_kernel(P5Mel p) {
       hb[m] = cmul_conj_v(d, w5[m]) * hh;
     }
     v2f pa[4], pb[4];
-    mirror256(ha, pa, lane);
-    mirror256(hb, pb, lane);
+    mirror_regs<4>(ha, pa, lane);
+    mirror_regs<4>(hb, pb, lane);
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
       const v2f xa = add_mi(add_conj(ha[m], pa[m]), cmul_v(sub_conj(ha[m], pa[m]), w5[m]));
@@ -971,7 +875,7 @@ int launch_stft512_fwd(const float* x, long long B, long long L, long long clip_
     return hipGetLastError() == hipSuccess ? 0 : -5;
   }
   const long long npairs = B * p.pairs_per_clip;
-  p.pairs_per_block = pairs_per_block_5(npairs);
+  p.pairs_per_block = units_per_block(npairs, W5);
   const long long blocks = (npairs + p.pairs_per_block - 1) / p.pairs_per_block;
   if (phase) hipLaunchKernelGGL(stft512_fwd_kernel<true>, dim3((unsigned)blocks), dim3(64 * W5), 0, stream, p);
   else hipLaunchKernelGGL(stft512_fwd_kernel<false>, dim3((unsigned)blocks), dim3(64 * W5), 0, stream, p);
@@ -987,7 +891,7 @@ int launch_irfft512_frames(const float2* X, const float* mag, const float* phase
   if (frames_per_clip <= 0 || nframes % frames_per_clip) return -2;
   p.T = frames_per_clip; p.n_clips = nframes / frames_per_clip; p.pairs_per_clip = (frames_per_clip + 1) / 2;
   const long long npairs = p.n_clips * p.pairs_per_clip;
-  p.pairs_per_block = pairs_per_block_5(npairs);
+  p.pairs_per_block = units_per_block(npairs, W5);
   const long long blocks = (npairs + p.pairs_per_block - 1) / p.pairs_per_block;
   if (X) hipLaunchKernelGGL(irfft512_frames_kernel<false>, dim3((unsigned)blocks), dim3(64 * W5), 0, stream, p);
   else hipLaunchKernelGGL(irfft512_frames_kernel<true>, dim3((unsigned)blocks), dim3(64 * W5), 0, stream, p);

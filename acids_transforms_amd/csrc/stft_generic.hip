@@ -6,6 +6,7 @@
 // n_fft = 1024 kernels in stft1024.hip are the tuned ones.
 #include <hip/hip_runtime.h>
 #include "fastmath.h"
+#include "stft_launch.h"
 #include "variants.h"
 #include <stdint.h>
 
@@ -20,12 +21,6 @@ struct GenFwdParams {
   int n_fft, hop, center;
   int use_tw;   // the twiddle table fits in LDS
 };
-
-__device__ __forceinline__ long long g_reflect(long long i, long long L) {
-  if (i < 0) i = -i;
-  if (i >= L) i = 2 * (L - 1) - i;
-  return i;
-}
 
 __device__ __forceinline__ float2 g_cmul(float2 a, float2 b) {
   return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
@@ -137,8 +132,8 @@ __global__ void rfft_generic_kernel(GenFwdParams p) {
       long long i0 = start + 2 * n, i1 = i0 + 1;
       float x0, x1;
       if (p.center) {
-        x0 = clip[g_reflect(i0, p.L)];
-        x1 = clip[g_reflect(i1, p.L)];
+        x0 = clip[reflect_index(i0, p.L)];
+        x1 = clip[reflect_index(i1, p.L)];
       } else {
         x0 = (i0 < p.L) ? clip[i0] : 0.f;
         x1 = (i1 < p.L) ? clip[i1] : 0.f;

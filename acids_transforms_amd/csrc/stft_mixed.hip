@@ -7,6 +7,7 @@
 // keep their own kernels.
 #include <hip/hip_runtime.h>
 #include "fastmath.h"
+#include "stft_launch.h"
 #include "variants.h"
 #include <stdint.h>
 
@@ -18,11 +19,6 @@ struct MixPlan {
   int radix[kMaxMixStages];   // product = M
 };
 
-__device__ __forceinline__ long long mx_reflect(long long i, long long L) {
-  if (i < 0) i = -i;
-  if (i >= L) i = 2 * (L - 1) - i;
-  return i;
-}
 __device__ __forceinline__ float2 mx_cmul(float2 a, float2 b) {
   return make_float2(a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x);
 }
@@ -158,7 +154,7 @@ __global__ void rfft_mixed_kernel(MixFwdParams p) {
     const long long start = t * (long long)p.hop - (p.center ? Nf / 2 : 0);
     auto sample = [&](int n) -> float {
       const long long i = start + n;
-      const float v = p.center ? clip[mx_reflect(i, p.L)] : (i < p.L ? clip[i] : 0.f);
+      const float v = p.center ? clip[reflect_index(i, p.L)] : (i < p.L ? clip[i] : 0.f);
       return v * p.window[n];
     };
     if (even) {

@@ -29,6 +29,8 @@
 #include "../../include/acids_hip.h"
 #include "fastmath.h"
 #include "fft512.h"
+#include "run_plan.h"
+#include "stft_launch.h"
 
 namespace at_hip {
 
@@ -48,12 +50,6 @@ struct PSm {
   int hop, center;
 };
 
-__device__ __forceinline__ long long reflect_sm(long long i, long long L) {
-  if (i < 0) i = -i;
-  if (i >= L) i = 2 * (L - 1) - i;
-  return i;
-}
-
 // K-point DFT across K registers: forward (INV = false): v[q] <- sum_r v[r] W_K^(r q); inverse: conjugate twiddles
 template <int K, bool INV>
 __device__ __forceinline__ void dftK(v2f (&v)[K]) {
@@ -67,59 +63,6 @@ __device__ __forceinline__ void dftK(v2f (&v)[K]) {
     v[2] = a0 - b0;
     v[1] = rot_add<INV>(a1, b1);      // a1 + W4 b1   (W4 = -i forward, +i inverse)
     v[3] = rot_sub<INV>(a1, b1);      // a1 - W4 b1
-  }
-}
-
-template <int K>
-__device__ __forceinline__ void load_lane_frame(const PSm& p, long long g, int lane, float2 (&q)[8]) {
-  constexpr int N = 1024 / K, PER = 64 / K;
-  const long long b = g / p.groups_per_clip;
-  const long long t = K * (g - b * p.groups_per_clip) + (lane % K);       // this lane's frame of clip b
-  if (t >= p.T) {                                 // an empty slot of the clip's last group: exact zeros
-#pragma unroll
-    for (int j = 0; j < 8; ++j) q[j] = make_float2(0.f, 0.f);
-    return;
-  }
-  const float* clip = p.x + b * p.clip_stride;
-  const long long start = t * (long long)p.hop - (p.center ? N / 2 : 0);
-  const bool interior = (start >= 0) && (start + N <= p.L);
-  const int u = lane / K;
-  if (interior && ((((uintptr_t)(clip + start)) & 7) == 0)) {
-    const float2* src = reinterpret_cast<const float2*>(clip + start);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) q[j] = src[u + PER * j];
-  } else {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const long long i0 = start + 2 * (u + PER * j);
-      float v[2];
-#pragma unroll
-      for (int c = 0; c < 2; ++c) {
-        const long long i = i0 + c;
-        if (interior) v[c] = clip[i];
-        else if (p.center) v[c] = clip[reflect_sm(i, p.L)];
-        else v[c] = (i >= 0 && i < p.L) ? clip[i] : 0.0f;     // zero padding past the end (utils/misc.py:156)
-      }
-      q[j] = make_float2(v[0], v[1]);
-    }
-  }
-}
-
-// mirror partner of A[k], k = lane + 64 m0 (m0 < Q): A[(M - k) mod M]
-template <int Q>
-__device__ __forceinline__ void mirror_small(const v2f (&v)[Q], v2f (&p)[Q], int lane) {
-  const int src = (64 - lane) & 63;
-  v2f q[Q];
-#pragma unroll
-  for (int m = 0; m < Q; ++m) {
-    q[m].x = __shfl(v[m].x, src, 64);
-    q[m].y = __shfl(v[m].y, src, 64);
-  }
-#pragma unroll
-  for (int m = 0; m < Q; ++m) {
-    const v2f a = q[Q - 1 - m];
-    const v2f b = q[(Q - m) % Q];
-    p[m] = (lane == 0) ? b : a;
   }
 }
 
@@ -145,14 +88,19 @@ __global__ __launch_bounds__(64 * WS) void stft_small_fwd_kernel(PSm p) {
   if (g_end > n_groups) g_end = n_groups;
   const float inv2k = 0.5f / (float)K;
 
+  // group g is frames K i .. K i + K - 1 of clip b, g = b groups_per_clip + i; this lane's frame is K i + lane % K
+  auto load_group = [&](long long q, float2 (&dst)[8]) {
+    const long long b = q / p.groups_per_clip;
+    load_shared_frame<K>(p, b, K * (q - b * p.groups_per_clip) + (lane % K), lane, dst);
+  };
   long long g = g_begin + wave;
   float2 nxt[8];
-  if (g < g_end) load_lane_frame<K>(p, g, lane, nxt);
+  if (g < g_end) load_group(g, nxt);
   for (; g < g_end; g += WS) {
     v2f y[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) y[j] = (v2f){nxt[j].x * win[j].x, nxt[j].y * win[j].y};
-    if (g + WS < g_end) load_lane_frame<K>(p, g + WS, lane, nxt);
+    if (g + WS < g_end) load_group(g + WS, nxt);
     fft512<false>(y, tw, lds, lane);
     // per m0: inverse K-point DFT over q of Y[k + M q] = K W512^(r k) A_r[k]; H_r = A_r / 2
     v2f h[K][Q];
@@ -174,7 +122,7 @@ __global__ __launch_bounds__(64 * WS) void stft_small_fwd_kernel(PSm p) {
       if (t0 + r >= p.T) break;                  // wave-uniform
       const long long f = gb * p.T + t0 + r;
       v2f pm[Q];
-      mirror_small<Q>(h[r], pm, lane);
+      mirror_regs<Q>(h[r], pm, lane);
       float2* row = p.X + f * F;
 #pragma unroll
       for (int m0 = 0; m0 < Q; ++m0) {
@@ -191,14 +139,6 @@ __global__ __launch_bounds__(64 * WS) void stft_small_fwd_kernel(PSm p) {
       }
     }
   }
-}
-
-__device__ __forceinline__ void sincos_big_sm(float phase, float& s, float& c) {
-  double t = (double)phase * 0.15915494309189533577;  // 1 / (2 pi)
-  t -= rint(t);
-  const float r = (float)t;
-  s = __builtin_amdgcn_sinf(r);
-  c = __builtin_amdgcn_cosf(r);
 }
 
 template <int K, bool POLAR>
@@ -246,11 +186,11 @@ __global__ __launch_bounds__(64 * WS) void irfft_small_frames_kernel(PSm p) {
         for (int m0 = 0; m0 < Q; ++m0) {
           float sn, cs;
           const float gmag = mrow[lane + 64 * m0];
-          sincos_big_sm(prow[lane + 64 * m0], sn, cs);
+          fast_sincosf(prow[lane + 64 * m0], sn, cs);
           v[m0] = (v2f){gmag * cs, gmag * sn};
         }
         float sn, cs;
-        sincos_big_sm(prow[M], sn, cs);
+        fast_sincosf(prow[M], sn, cs);
         nyq_re = mrow[M] * cs;
       } else {
         const float2* row = p.X + f * F;
@@ -260,7 +200,7 @@ __global__ __launch_bounds__(64 * WS) void irfft_small_frames_kernel(PSm p) {
       }
       if (lane == 0) v[0].y = 0.0f;               // c2r ignores the imaginary parts of DC and Nyquist
       v2f pm[Q];
-      mirror_small<Q>(v, pm, lane);
+      mirror_regs<Q>(v, pm, lane);
       if (lane == 0) pm[0] = (v2f){nyq_re, 0.0f};
 #pragma unroll
       for (int m0 = 0; m0 < Q; ++m0) {
@@ -291,13 +231,6 @@ __global__ __launch_bounds__(64 * WS) void irfft_small_frames_kernel(PSm p) {
   }
 }
 
-static long long groups_per_block_sm(long long ngroups) {
-  const long long max_blocks = 256LL * 8;
-  long long gpb = (ngroups + max_blocks - 1) / max_blocks;
-  gpb = ((gpb + WS - 1) / WS) * WS;
-  return gpb < WS ? WS : gpb;
-}
-
 int launch_stft_small_fwd(int n_fft, const float* x, long long B, long long L, long long clip_stride, long long T, int hop,
                           int center, const float* window, const float2* tw, const float2* twk, float2* out, float* phase,
                           hipStream_t stream) {
@@ -309,7 +242,7 @@ int launch_stft_small_fwd(int n_fft, const float* x, long long B, long long L, l
   p.L = L; p.clip_stride = clip_stride; p.T = T; p.n_clips = B; p.hop = hop; p.center = center;
   p.groups_per_clip = (T + K - 1) / K;
   const long long ngroups = B * p.groups_per_clip;
-  p.groups_per_block = groups_per_block_sm(ngroups);
+  p.groups_per_block = units_per_block(ngroups, WS);
   const unsigned blocks = (unsigned)((ngroups + p.groups_per_block - 1) / p.groups_per_block);
   if (K == 4) {
     if (phase) hipLaunchKernelGGL((stft_small_fwd_kernel<4, true>), dim3(blocks), dim3(64 * WS), 0, stream, p);
@@ -333,7 +266,7 @@ int launch_irfft_small_frames(int n_fft, const float2* X, const float* mag, cons
   p.T = frames_per_clip; p.n_clips = nframes / frames_per_clip;
   p.groups_per_clip = (frames_per_clip + K - 1) / K;
   const long long ngroups = p.n_clips * p.groups_per_clip;
-  p.groups_per_block = groups_per_block_sm(ngroups);
+  p.groups_per_block = units_per_block(ngroups, WS);
   const unsigned blocks = (unsigned)((ngroups + p.groups_per_block - 1) / p.groups_per_block);
   const bool polar = (X == nullptr);
   if (K == 4) {

@@ -281,6 +281,6 @@ TWO_PASS_HOPS = [(2048, 128), (2048, 300), (2048, 333), (4096, 256), (4096, 700)
 
 
 def frames_per_block_2k_4k(nframes):
-    """frames_per_block_2k / frames_per_block_4k: at most 2048 workgroups of four waves, whole rounds of the waves."""
+    """units_per_block(nframes, 4) of run_plan.h: at most 2048 workgroups of four waves, whole rounds of the waves."""
     fpb = (nframes + 2047) // 2048
     return max((fpb + 3) // 4 * 4, 4)

@@ -11,8 +11,8 @@ before (f = K g + r over all B T frames): the GPU tests fail on it, and test_sha
 the swept shapes tell the two apart.
 
 The arithmetic follows csrc/capi.hip (at_stft_forward, at_istft, at_irfft_frames_streams, at_stft_mel_forward),
-csrc/stft512.hip (launch_stft512_fwd, launch_stft512_mel, launch_irfft512_frames, pairs_per_block_5) and
-csrc/stft_small.hip (launch_stft_small_fwd, launch_irfft_small_frames, groups_per_block_sm)."""
+csrc/stft512.hip (launch_stft512_fwd, launch_stft512_mel, launch_irfft512_frames) and csrc/stft_small.hip
+(launch_stft_small_fwd, launch_irfft_small_frames), with units_per_block of csrc/run_plan.h."""
 import numpy as np
 
 K_OF = {128: 8, 256: 4, 512: 2}       # frames per shared transform
@@ -117,7 +117,7 @@ def clips_in_group(grp):
 
 
 def groups_per_block(ngroups):
-    """groups_per_block_sm / pairs_per_block_5: whole rounds of the workgroup's WS waves, 2048 workgroups at most."""
+    """units_per_block (run_plan.h): whole rounds of the workgroup's WS waves, 2048 workgroups at most."""
     gpb = cdiv(cdiv(ngroups, MAX_BLOCKS), WS) * WS
     return max(gpb, WS)
 
