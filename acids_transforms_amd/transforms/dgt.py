@@ -5,7 +5,7 @@ Drop-in for the reference's transforms/dgt.py (DGT :24-236, RealtimeDGT
 :239-519): same constructors, buffers (`tolerance`, `hgi_mag_buffer`,
 `hgi_phase_buffer`, ...), inversion modes and errors.  Forward / inverse reuse
 the STFT kernels with the Gaussian analysis window (:108-112) and its
-canonical dual (:114-123); PGHI runs in pghi.hip with the reference's exact
+canonical dual (:114-123); PGHI runs in pghi_offline.hip / pghi_rt.hip with the reference's exact
 binary-heap order (utils/heapq.py).
 """
 import math

@@ -4,7 +4,7 @@ like the reference does (utils/__init__.py:2).
 Items are compared through `item[0]` with strict `<` only.  `heappop` does not sift the last element down from the root:
 it walks the hole down to a leaf, promoting at every level the LEFT child only if it is strictly smaller than the right
 one (so the right child wins ties), drops the last element into that leaf and lets it rise.  That choice of path is what
-fixes the pop order among equal keys, and the offline PGHI kernels (csrc/pghi.hip) reproduce it on the device; this
+fixes the pop order among equal keys, and the offline PGHI kernels (csrc/pghi_heap.h, csrc/pghi_offline.hip) reproduce it on the device; this
 module is the plain-Python form of the same rule for callers of the reference's helper (`DGT.perform_hgi` there pushes
 `(-magnitude, (frame, bin))` tuples).  No device work happens here.
 """

@@ -394,10 +394,40 @@ def test_realtime_rank_fast_path_equals_the_heap_kernels(dev, n_fft, hop, S, n):
             assert np.all(np.abs(cpu(got) - ref) <= phase_tol(ref, base=2e-3, ulps=16)), kind
 
 
+def test_realtime_rows_that_do_not_fit_lds(dev):
+    """n_fft 4096 (F = 2049): a frame's rows and heap need more than 64 KB of LDS, so every variant runs
+    `pghi_hgi_rt_kernel`, the single-lane flood on rows in global memory -- the product path of every row longer than about
+    1088 bins.  Two streams (the per-stream base offsets) and two new frames (the step from one frame to the next), on noise
+    and on a sparse spectrum (reseeds inside a frame; bins at or below the tolerance keep their draw), against the C
+    restatement of dgt.py:330-466.  The default and variant 2 take the same kernel here: the same bits, so a change of the
+    64 KB rule cannot move this size onto another route unnoticed."""
+    n_fft, hop, S, n = 4096, 1024, 2, 2
+    F = n_fft // 2 + 1
+    g = torch.Generator().manual_seed(n_fft + 7 * S + n)
+    rt = A.RealtimeDGT(n_fft=n_fft, hop_length=hop, batch_size=[S]).to(dev)
+    base = (torch.randn(S, n + 2, F, generator=g) ** 2 + torch.randn(S, n + 2, F, generator=g) ** 2).sqrt()
+    kinds = {"noise": base, "sparse": base * (torch.rand(S, n + 2, F, generator=g) < 0.15) + 1e-6}
+    for kind, m in kinds.items():
+        hist, mag = m[:, :2].contiguous().to(dev), m[:, 2:].contiguous().to(dev)
+        prev = (torch.rand(S, F, generator=g) * 6.28).to(dev)
+        noise = torch.randn(S, n, F, generator=g).to(dev)
+        args = (float(rt.gamma), n_fft, hop, float(rt.tolerance), float(rt.eps))
+        got = ops.pghi_realtime(hist, mag, prev, noise, *args)
+        with variant("pghi_kernel", 2):
+            serial = ops.pghi_realtime(hist, mag, prev, noise, *args)
+        ref = O.pghi_realtime(hist.cpu().numpy(), mag.cpu().numpy(), prev.cpu().numpy(), noise.cpu().numpy(), n_fft, hop,
+                              tol=float(rt.tolerance), gamma=float(rt.gamma), eps=float(rt.eps))["phase"]
+        err = np.abs(cpu(got) - ref)
+        print(f"{kind}: max |got - oracle| = {float(err.max()):.3e}, kept draws = {int((ref == cpu(noise)).sum())}")
+        assert bool(torch.isfinite(got).all()), kind
+        assert np.all(err <= phase_tol(ref, base=2e-3, ulps=16)), (kind, float(err.max()))
+        assert torch.equal(got, serial), (kind, float((got - serial).abs().max()))
+
+
 def test_realtime_scan_path_edge_cases(dev):
     """Round 5: by default a realtime frame is resolved WITHOUT a queue -- two directional scans of clamp functions give
     every bin the level at which it is reached and by whom, the phases follow the parent chains (`rt_scan_frame`,
-    pghi.hip) -- and only competing ties / islands of several unreached bins go to the heap.  The cases the derivation has
+    pghi_rt.hip) -- and only competing ties / islands of several unreached bins go to the heap.  The cases the derivation has
     to get right, each against the cooperative heap kernel (variant 3) bit for bit: the frame maximum (the reference's
     UNMARKED seed, dgt.py:427) at bin 0, 1, F-2, F-1, under a larger / smaller / dead source, between dead neighbours;
     bin 0 under a dead source (never reached from above, :453: a one-bin reseed); onsets (row f live where row f-1 is

@@ -1,4 +1,4 @@
-"""The DERIVATION behind the realtime scan path (csrc/pghi.hip rt_scan_frame), checked on the CPU against
+"""The DERIVATION behind the realtime scan path (csrc/pghi_rt.hip rt_scan_frame), checked on the CPU against
 the exact-heap C restatement of the reference (oracle/pghi_ref.c, dgt.py:396-466): a plain numpy statement of "levels by
 two directional recurrences, parents by the largest level, phases along the parent chains" must give the reference's
 phases BIT FOR BIT on every frame it accepts, over tens of thousands of small random strips -- every sparsity pattern,
