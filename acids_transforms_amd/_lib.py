@@ -97,6 +97,8 @@ _SIGNATURES = {
                                      c_f, c_int, c_int, c_f, c_f, c_flt, c_f, c_f, c_f, c_f],
     "at_polar_to_complex_backward": [c_f, c_f, c_f, c_i64, c_f, c_f, c_f],
     "at_cartesian_unpack_backward": [c_f, c_i64, c_int, c_f, c_f, c_f, c_f],
+    "at_phase_scan_backward": [c_f, c_i64, c_i64, c_i64, c_int, c_f, c_i64, c_f, c_f, c_f, c_f, c_f],
+    "at_cartesian_pack_backward": [c_f, c_i64, c_int, c_f, c_f, c_f, c_f],
 }
 _RESTYPES = {"at_error_string": ctypes.c_char_p, "at_istft_workspace_bytes": c_sz, "at_stats_workspace_bytes": c_sz,
              "at_pghi_offline_workspace_bytes": c_sz, "at_mel_bf16_bank_bytes": c_sz, "at_pghi_rt_workspace_bytes": c_sz,

@@ -1,8 +1,9 @@
-"""Autograd for STFT / DGT (forward and invert), Magnitude and MFCC, and for the invert of Magnitude, Polar, Cartesian,
-Real / Imaginary / Phase and Normalize: torch.autograd.Functions whose backward passes are the HIP adjoints of
-autograd.hip, mfcc_grad.hip and invert_grad.hip (through ops.stft_backward / ops.istft_backward /
-ops.magnitude_backward / ops.mfcc_backward / ops.magnitude_invert_backward / ops.polar_to_complex_backward /
-ops.cartesian_inverse_backward).
+"""Autograd for STFT / DGT (forward and invert), Magnitude and MFCC, for the invert of Magnitude, Polar, Cartesian,
+Real / Imaginary / Phase and Normalize, and for the forward of Normalize, Phase, IF, Cartesian, Polar and PolarIF:
+torch.autograd.Functions whose backward passes are the HIP adjoints of autograd.hip, mfcc_grad.hip, invert_grad.hip and
+repr_grad.hip (through ops.stft_backward / ops.istft_backward / ops.magnitude_backward / ops.mfcc_backward /
+ops.magnitude_invert_backward / ops.polar_to_complex_backward / ops.cartesian_inverse_backward /
+ops.phase_scan_backward / ops.cartesian_forward_backward).
 
 The reference is plain torch, so its STFT, DGT and Magnitude (and their composition) sit inside a training loss.  Here
 the forward kernels write into fresh tensors through ctypes, which cuts the graph; the modules therefore route a call
@@ -18,7 +19,8 @@ from . import ops
 
 __all__ = ["wants_grad", "StftFunction", "IstftFunction", "IstftPolarFunction", "MagnitudeFunction",
            "StftMagnitudeFunction", "MfccFunction", "mfcc_chunk_clips", "MagnitudeInvertFunction", "PolarInvertFunction",
-           "CartesianInvertFunction", "PolarToComplexFunction", "AffineInvertFunction"]
+           "CartesianInvertFunction", "PolarToComplexFunction", "AffineInvertFunction", "AffineForwardFunction",
+           "PhaseScanFunction", "CartesianFunction", "PolarFunction", "PolarIFFunction", "StftPolarFunction"]
 
 
 def wants_grad(x: torch.Tensor) -> bool:
@@ -326,3 +328,136 @@ class AffineInvertFunction(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, g):
         return ops.affine(g, torch.zeros_like(ctx.scale), ctx.scale, inverse=True).to(ctx.dtype), None, None
+
+
+# ---- the forward of the phase-side representations: Normalize, Phase / IF, Cartesian, Polar, PolarIF ---------------------
+
+class AffineForwardFunction(torch.autograd.Function):
+    """Normalize.forward, (x - offset) / scale (ops.affine): Real / Imaginary behind torch's own .real / .imag, and the
+    single-frame central IF.  The gradient is g / scale -- the same kernel with a zero offset.  Saves nothing."""
+
+    @staticmethod
+    def forward(ctx, x, offset, scale):
+        ctx.scale, ctx.dtype = scale, x.dtype
+        return ops.affine(x, offset, scale)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        return ops.affine(g, torch.zeros_like(ctx.scale), ctx.scale).to(ctx.dtype), None, None
+
+
+class PhaseScanFunction(torch.autograd.Function):
+    """ops.phase_scan of a complex spectrum X (..., T, F) for any mode, frame weight and Normalize affine, with its
+    backward (ops.phase_scan_backward: unwrap's derivative is the identity, so the backward of the scan is a three-row
+    stencil and the angle's derivative).  Saves X; the window and the Normalize statistics are constants of the graph."""
+
+    @staticmethod
+    def forward(ctx, X, mode, frame_window, offset, scale):
+        ctx.mode, ctx.window, ctx.scale = mode, frame_window, scale
+        ctx.save_for_backward(X)
+        return ops.phase_scan(X, mode, frame_window=frame_window, offset=offset, scale=scale)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        (X,) = ctx.saved_tensors
+        gX = ops.phase_scan_backward(X, ctx.mode, g, ctx.window, ctx.scale)
+        return gX.reshape(X.shape).to(X.dtype), None, None, None, None
+
+
+class CartesianFunction(torch.autograd.Function):
+    """The one-pass Cartesian.forward (ops.cartesian_forward) with its backward.  Saves nothing."""
+
+    @staticmethod
+    def forward(ctx, X, re_off, re_sc, im_off, im_sc):
+        ctx.re_sc, ctx.im_sc, ctx.shape, ctx.dtype = re_sc, im_sc, X.shape, X.dtype
+        return ops.cartesian_forward(X, re_off, re_sc, im_off, im_sc)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        gX = ops.cartesian_forward_backward(g, ctx.re_sc, ctx.im_sc)
+        return gX.reshape(ctx.shape).to(ctx.dtype), None, None, None, None
+
+
+def _stacked_grad(module, X, dF, mode, frame_window, phase_scale, inplace=False):
+    """Gradient of a stacked (..., T, 2, F) Polar / PolarIF tensor with respect to the spectrum X: the scan backward reads
+    the phase half of dF where it lies, the Magnitude backward handles the magnitude half and adds the two.
+    inplace=True: the sum is formed in the Magnitude backward's result (the audio-only chain, whose X is a scratch)."""
+    dF = dF if dF.is_contiguous() else dF.contiguous()
+    if inplace:
+        dX = _magnitude_grad(module, X, dF[..., 0, :])
+        return ops.phase_scan_backward(X, mode, dF[..., 1, :], frame_window, phase_scale, accum=dX, out=dX)
+    gX = ops.phase_scan_backward(X, mode, dF[..., 1, :], frame_window, phase_scale)
+    return _magnitude_grad(module, X, dF[..., 0, :], dx_accum=gX)
+
+
+class PolarFunction(torch.autograd.Function):
+    """The one-pass Polar.forward (ops.polar_forward: banded Magnitude next to a plain Phase, stacked on dim -2) with its
+    backward.  Saves X."""
+
+    @staticmethod
+    def forward(ctx, X, magnitude, band, m_off, m_sc, p_off, p_sc):
+        ctx.magnitude, ctx.p_sc = magnitude, p_sc
+        ctx.save_for_backward(X)
+        return ops.polar_forward(X, band, magnitude.contrast_mode, m_off, m_sc, magnitude._eps, p_off, p_sc)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dF):
+        (X,) = ctx.saved_tensors
+        dX = _stacked_grad(ctx.magnitude, X, dF, "angle", None, ctx.p_sc)
+        return dX.reshape(X.shape).to(X.dtype), None, None, None, None, None, None
+
+
+class PolarIFFunction(torch.autograd.Function):
+    """The in-place PolarIF.forward (ops.polarif_forward, either of its internal routes) with its backward.  Saves X."""
+
+    @staticmethod
+    def forward(ctx, X, magnitude, band, m_off, m_sc, method, frame_window, p_off, p_sc):
+        ctx.magnitude, ctx.method, ctx.window, ctx.p_sc = magnitude, method, frame_window, p_sc
+        ctx.save_for_backward(X)
+        return ops.polarif_forward(X, band, magnitude.contrast_mode, m_off, m_sc, magnitude._eps, method, frame_window,
+                                   p_off, p_sc)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dF):
+        (X,) = ctx.saved_tensors
+        dX = _stacked_grad(ctx.magnitude, X, dF, ctx.method, ctx.window, ctx.p_sc)
+        return dX.reshape(X.shape).to(X.dtype), None, None, None, None, None, None, None, None
+
+
+class StftPolarFunction(torch.autograd.Function):
+    """The fused STFT -> Polar forward (ops.stft_polar_forward) with its backward.  Saves the audio only, as MfccFunction:
+    the fused forward never writes a spectrum, so the backward rebuilds it from the audio a chunk of clips at a time
+    (mfcc_chunk_clips), runs the Magnitude backward on it, adds the phase half's gradient in place
+    (ops.phase_scan_backward) and runs the STFT adjoint into the chunk's rows of dx."""
+
+    @staticmethod
+    def forward(ctx, x, stage, magnitude, m_off, m_sc, p_off, p_sc):
+        ctx.stage, ctx.magnitude, ctx.p_sc = stage, magnitude, p_sc
+        ctx.save_for_backward(x)
+        return ops.stft_polar_forward(x, stage.window[:1024], magnitude._banded(), magnitude.contrast_mode, m_off, m_sc,
+                                      magnitude._eps, p_off, p_sc)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, dF):
+        (x,) = ctx.saved_tensors
+        stage = ctx.stage
+        n, hop = stage._n_fft, stage._hop
+        window = stage.window[:n]
+        xb = ops._f32c(x)
+        B, L = xb.shape
+        T = 1 + L // hop
+        dF = ops._f32c(dF)
+        dx = torch.empty((B, L), dtype=torch.float32, device=x.device)
+        chunk = mfcc_chunk_clips(B, T, n)
+        for b0 in range(0, B, chunk):
+            X = ops.stft_forward(xb[b0:b0 + chunk], window, n, hop, center=True)
+            dX = _stacked_grad(ctx.magnitude, X, dF[b0:b0 + chunk], "angle", None, ctx.p_sc, inplace=True)
+            ops.stft_backward(dX, window, n, hop, L, out=dx[b0:b0 + chunk])
+            del X, dX
+        return dx.to(x.dtype), None, None, None, None, None, None

@@ -60,7 +60,8 @@ extern "C" {
 //    (AT_VARIANT_RUN_LENGTH, AT_VARIANT_ISTFT_TILE, AT_VARIANT_ROW_RUN, AT_VARIANT_FRAME_WALKERS) are table entries, not
 //    signatures: still 4.  So are the backward
 //    entries (at_stft_backward, at_magnitude_backward, at_istft_backward, at_mfcc_backward, and invert_grad.hip's
-//    at_magnitude_invert_backward, at_polar_to_complex_backward, at_cartesian_unpack_backward): additions only.
+//    at_magnitude_invert_backward, at_polar_to_complex_backward, at_cartesian_unpack_backward, and repr_grad.hip's
+//    at_phase_scan_backward, at_cartesian_pack_backward): additions only.
 int at_abi_version(void) { return 4; }
 
 int at_set_variant(int which, int value) {

@@ -808,6 +808,71 @@ def phase_scan(x, mode, frame_window=None, offset=None, scale=None, bare=False):
     return out
 
 
+def _grad_rows(g, F):
+    """(g, ld_g): a float32 gradient (..., T, F) as evenly spaced rows of ld_g >= F floats.  The half of a stacked
+    (..., T, 2, F) gradient that torch's stack / select hand back (ld_g = 2 F) is read where it lies; anything else that
+    is not contiguous is copied."""
+    _no_fp64(g, "gradient")
+    g = g if g.dtype == torch.float32 else g.float()
+    if g.is_contiguous():
+        return g, F
+    if g.ndim >= 2 and (F == 1 or g.stride(-1) == 1):
+        ld, want = None, None
+        for d in range(g.ndim - 2, -1, -1):
+            if g.shape[d] == 1:
+                continue
+            if ld is None:
+                ld = want = g.stride(d)
+            elif g.stride(d) != want:
+                ld = -1
+                break
+            want = want * g.shape[d]
+        if ld is None:
+            return g, F
+        if ld >= F:
+            return g, ld
+    return g.contiguous(), F
+
+
+def phase_scan_backward(x, mode, g, frame_window=None, scale=None, accum=None, out=None):
+    """Gradient of phase_scan(x, mode, frame_window, offset, scale) with respect to the complex64 spectrum x (..., T, F),
+    given g (..., T, F) float32, the gradient of its output -- the phase half of a stacked (..., T, 2, F) gradient,
+    `g_stacked[..., 1, :]`, is read in place.  accum (complex64, x's shape) is added to the result; out (complex64, x's
+    shape, contiguous) receives it and may be x or accum.  Returns complex64 of x's shape."""
+    if mode not in SCAN_MODES:
+        raise AttributeError("method %s not known" % mode)
+    require_device(x, g, scale, accum, out)
+    assert x.is_complex(), "the gradient is that of a complex spectrum"
+    x = _c64(x)
+    x = x if x.is_contiguous() else x.contiguous()
+    B, T, F = _btf(x)
+    g, ld_g = _grad_rows(g, F)
+    assert g.shape == x.shape, "g does not match the forward's output"
+    if frame_window is not None:
+        frame_window = _f32c(frame_window.to(x.device))
+        assert frame_window.numel() == T
+    for t in (accum, out):
+        assert t is None or (t.shape == x.shape and t.dtype == torch.complex64 and t.is_contiguous())
+    if out is None:
+        out = torch.empty_like(x)
+    check(lib().at_phase_scan_backward(ptr(x), B, T, F, SCAN_MODES[mode], ptr(g), ld_g, ptr(frame_window), ptr(scale),
+                                       ptr(accum), ptr(out), stream_ptr()), "at_phase_scan_backward")
+    return out
+
+
+def cartesian_forward_backward(g, re_scale=None, im_scale=None):
+    """Gradient of cartesian_forward: g (..., 2, F) float32 -> (..., F) complex64 = g[.., 0, :] / re_scale +
+    i g[.., 1, :] / im_scale."""
+    require_device(g, re_scale, im_scale)
+    g = _f32c(g)
+    assert g.ndim >= 2 and g.shape[-2] == 2, "g must be the stacked (..., 2, F) gradient"
+    F = g.shape[-1]
+    out = torch.empty(g.shape[:-2] + (F,), dtype=torch.complex64, device=g.device)
+    check(lib().at_cartesian_pack_backward(ptr(g), g.numel() // (2 * F) if F else 0, F, ptr(re_scale), ptr(im_scale),
+                                           ptr(out), stream_ptr()), "at_cartesian_pack_backward")
+    return out
+
+
 def phase_integrate(y, method, offset=None, scale=None, rescale=True):
     """IF.invert's tail: (de-normalise,) undo the row scaling of `method` (rescale) and integrate along dim -2."""
     if method not in ("forward", "backward", "central"):

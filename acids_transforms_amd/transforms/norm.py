@@ -9,7 +9,7 @@ from typing import Union
 import torch
 
 from .. import ops
-from ..autograd import AffineInvertFunction, wants_grad
+from ..autograd import AffineForwardFunction, AffineInvertFunction, wants_grad
 from .base import AudioTransform
 
 __all__ = ["Normalize"]
@@ -71,6 +71,8 @@ class Normalize(AudioTransform):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         off, sc = self._params(x)
+        if wants_grad(x):
+            return AffineForwardFunction.apply(x, off, sc)   # the same kernel; the gradient is g / scale
         return ops.affine(x, off, sc, inverse=False)
 
     def invert(self, x: torch.Tensor, inversion_mode=None, **kwargs) -> torch.Tensor:

@@ -17,14 +17,19 @@ reference caches a 1-D window and then asks it for `size(-2)`, which raises; fix
 
 The arithmetic is phase_repr.hip: one scan kernel per call reads the complex spectrum once and writes the
 normalised representation (angle, unwrap, finite difference, row scaling, weighting and Normalize fused).
+
+`forward` is differentiable, as the reference's plain-torch expressions are: a call whose input requires grad
+(with grad mode on) runs the same kernels through the Functions of autograd.py, whose backward passes are
+repr_grad.hip; every other call is the plain route, bit for bit.
 """
 from typing import Tuple, Union
 
 import torch
 
 from .. import ops
-from ..autograd import (AffineInvertFunction, CartesianInvertFunction, PolarInvertFunction, PolarToComplexFunction,
-                        wants_grad)
+from ..autograd import (AffineForwardFunction, AffineInvertFunction, CartesianFunction, CartesianInvertFunction,
+                        PhaseScanFunction, PolarFunction, PolarIFFunction, PolarInvertFunction, PolarToComplexFunction,
+                        StftPolarFunction, wants_grad)
 from .base import AudioTransform, InversionEnumType
 from .norm import Normalize
 from .spectral_repr import Magnitude, _Identity
@@ -35,6 +40,20 @@ __all__ = ["Real", "Imaginary", "Phase", "IF", "SpectralRepresentation", "Cartes
 def _as_complex(x: torch.Tensor) -> torch.Tensor:
     """Tensor.angle() of a real tensor is 0 / pi: give the scan kernels a complex view of real input."""
     return x if x.is_complex() else torch.complex(ops._f32c(x), torch.zeros_like(x, dtype=torch.float32))
+
+
+def _normalise(x: torch.Tensor, off, sc) -> torch.Tensor:
+    """ops.affine forward, with its backward when x is part of a graph (the same kernel either way)."""
+    if off is None:
+        return x
+    return AffineForwardFunction.apply(x, off, sc) if wants_grad(x) else ops.affine(x, off, sc)
+
+
+def _scan(x: torch.Tensor, mode: str, frame_window=None, off=None, sc=None, grad: bool = True) -> torch.Tensor:
+    """ops.phase_scan of a complex spectrum, with its backward when x is part of a graph (the same kernel either way)."""
+    if grad and wants_grad(x):
+        return PhaseScanFunction.apply(x, mode, frame_window, off, sc)
+    return ops.phase_scan(x, mode, frame_window=frame_window, offset=off, scale=sc)
 
 
 def _pad_last_bin(x: torch.Tensor) -> torch.Tensor:
@@ -108,8 +127,7 @@ class Real(_Representation):
         if not self.keep_nyquist:
             x = x[..., 1:]
         off, sc = self._affine(x)
-        re = x.real
-        return ops.affine(re, off, sc) if off is not None else re
+        return _normalise(x.real, off, sc)
 
     def test_inversion(self, x: torch.Tensor):
         # the reference's scenario uses n_fft 512 / hop 128 for this class
@@ -126,7 +144,7 @@ class Imaginary(_Representation):
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if torch.is_complex(x):
             off, sc = self._affine(x)
-            x = ops.affine(x.imag, off, sc) if off is not None else x.imag
+            x = _normalise(x.imag, off, sc)
         else:
             x = torch.zeros_like(x)
         return x if self.keep_nyquist else x[..., 1:]
@@ -148,7 +166,7 @@ class Phase(_Representation):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         off, sc = self._affine(x)
-        y = ops.phase_scan(_as_complex(x), "unwrap" if self.unwrap else "angle", offset=off, scale=sc)
+        y = _scan(_as_complex(x), "unwrap" if self.unwrap else "angle", None, off, sc)
         return y if self.keep_nyquist else y[..., 1:]
 
     def test_inversion(self, x: torch.Tensor):
@@ -179,24 +197,26 @@ class IF(_Representation):
             self.weighted_window = ((1.5 * N) / (N ** 2 - 1) * (1 - ((n - (N / 2 - 1)) / (N / 2)) ** 2)).to(x.device)
         return self.weighted_window
 
-    def _scan(self, data, off=None, sc=None):
+    def _scan(self, data, off=None, sc=None, grad=True):
         if self.method not in ("backward", "forward", "central"):
             raise AttributeError("method %s not known" % self.method)
         data = _as_complex(data)
         if self.method == "central" and data.size(-2) == 1:
             # fdiff_central of a single frame concatenates that frame twice (utils/misc.py:77-80)
-            ph = ops.phase_scan(data, "angle")
+            # (under autograd: the angle's backward, torch's own cat and product, the affine's backward)
+            ph = _scan(data, "angle", grad=grad)
             y = torch.cat([ph, ph], -2)
             if self.weighted:
                 y = self._get_weighted_window(y).view(-1, 1) * y
-            return ops.affine(y, off, sc) if off is not None else y
+            return _normalise(y, off, sc)
         window = self._get_weighted_window(data) if self.weighted else None
-        return ops.phase_scan(data, self.method, frame_window=window, offset=off, scale=sc)
+        return _scan(data, self.method, window, off, sc, grad=grad)
 
     def get_if(self, data: torch.Tensor) -> torch.Tensor:
         return self._scan(data)
 
-    _raw = get_if
+    def _raw(self, x):
+        return self._scan(x, grad=False)      # what scale_data measures: the statistics are constants of any graph
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         off, sc = self._affine(x)
@@ -254,6 +274,8 @@ class SpectralRepresentation(AudioTransform):
         mag._follow(x)
         m_off, m_sc = mag._affine()
         p_off, p_sc = ph._affine(x)
+        if wants_grad(x):       # the same kernel, with the scan backward next to the Magnitude backward (autograd.py)
+            return PolarFunction.apply(x, mag, band, m_off, m_sc, p_off, p_sc)
         return ops.polar_forward(x, band, mag.contrast_mode, m_off, m_sc, mag._eps, p_off, p_sc)
 
     # -- fusion with the preceding STFT / DGT stage (ComposeAudioTransform.forward) -----------------------
@@ -278,10 +300,15 @@ class SpectralRepresentation(AudioTransform):
         p_off, p_sc = ph._affine(x)
         xb, batch_shape = reshape_batches(x, -1)
         stage._release_phase_source()
-        y = ops.stft_polar_forward(xb, stage.window[:1024], mag._banded(), mag.contrast_mode, m_off, m_sc, mag._eps,
-                                   p_off, p_sc)
+        if wants_grad(xb):
+            # autograd route (autograd.py): the same kernel; the graph keeps the audio only, and the stage's phase buffer
+            # a detached half so that it does not pin the graph
+            y = StftPolarFunction.apply(xb, stage, mag, m_off, m_sc, p_off, p_sc)
+        else:
+            y = ops.stft_polar_forward(xb, stage.window[:1024], mag._banded(), mag.contrast_mode, m_off, m_sc, mag._eps,
+                                       p_off, p_sc)
         # the stage's phase buffer (keep_input inversion) is the phase half of the result, de-normalised on demand
-        half = y[..., 1, :]
+        half = y.detach()[..., 1, :]
         stage._replace_phase_buffer(
             (lambda: ops.affine(half, p_off, p_sc, inverse=True)) if p_off is not None else (lambda: half.contiguous()))
         return y.reshape(batch_shape + y.shape[-3:])
@@ -375,6 +402,8 @@ class Cartesian(SpectralRepresentation):
 
     def forward(self, x: torch.Tensor) -> SpectralRepresentationType:
         if self._one_pass_ok(x, False):
+            if wants_grad(x):
+                return CartesianFunction.apply(x, *self.magnitude._affine(x), *self.phase._affine(x))
             return ops.cartesian_forward(x, *self.magnitude._affine(x), *self.phase._affine(x))
         return super().forward(x)
 
@@ -433,6 +462,8 @@ class PolarIF(SpectralRepresentation):
                 m_off, m_sc = mag._affine()
                 p_off, p_sc = ph._affine(x)
                 window = ph._get_weighted_window(x) if ph.weighted else None
+                if wants_grad(x):       # the same kernels, with the scan backward next to the Magnitude backward
+                    return PolarIFFunction.apply(x, mag, band, m_off, m_sc, ph.method, window, p_off, p_sc)
                 return ops.polarif_forward(x, band, mag.contrast_mode, m_off, m_sc, mag._eps, ph.method, window, p_off, p_sc)
         return super().forward(x)
 

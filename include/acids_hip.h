@@ -538,6 +538,36 @@ int at_polar_to_complex_backward(const float *gX_complex, const float *mag, cons
 int at_cartesian_unpack_backward(const float *gX_complex, int64_t rows, int F, const float *re_scale,
                                  const float *im_scale, float *dy_stacked, void *stream);
 
+/* Gradient of at_phase_scan / at_phase_scan_strided (Phase, IF and the phase halves of Polar / PolarIF; reference
+ * utils/misc.py:12-26, 65-81 and spectral_repr.py:318-335) with respect to the complex spectrum X (B, T, F).  `mode`: the
+ * codes of at_phase_scan.  In autograd of the reference's statements unwrap has the identity as its derivative, so for
+ *   y_t = (w_t s_t fdiff(unwrap(angle X))_t - offset) / scale   and g = dL/dy (float32 rows of ld_g >= F floats; ld_g = 2 F
+ *   reads the phase half of a stacked (.., T, 2, F) gradient in place):
+ *   a_t = g_t w_t s_t / scale     (w = 1 without frame_window, scale NULL: 1; the offset never matters)
+ *   s_t = 1/pi on rows 0..T-2 (forward), -1/pi on rows 1..T-1 (backward), 1/(2 pi) on rows 1..T-2 (central), else 1
+ *   angle, unwrap:  gu_t = a_t
+ *   forward:        gu_t = c_t a_t - a_{t+1}/2 (while t+1 <= T-1),  c_0 = 1, else 1/2
+ *   backward:       gu_t = c_t a_t - a_{t-1}/2 (while t >= 1),      c_{T-1} = 1, else 1/2
+ *   central:        gu_t = [t = 0] a_0 + [t = T-1] a_{T-1} + a_{t-1}/4 [1 <= t-1 <= T-2] - a_{t+1}/4 [1 <= t+1 <= T-2]
+ *                   (T = 1: the one row at_phase_scan writes, gu_0 = a_0)
+ *   out_t = accum_t + gu_t (-Im X_t + i Re X_t) / |X_t|^2,   the second term 0 where X_t == 0 (torch's angle backward)
+ * frame_window (T floats) and scale (device scalar) may be NULL; accum_complex (NULL, or X's shape) is added to the
+ * result.  out_complex may be X_complex or accum_complex (every thread reads its element before it writes it); g must
+ * not overlap out_complex.  A flat pass over the B T F elements: a bin's bits depend neither on the batch nor on the grid,
+ * and a NaN of g stays within rows t-1..t+1 of its bin.  X, accum and out must be 8-byte aligned, g, frame_window and
+ * scale 4-byte aligned.  AT_EINVAL (no device is touched) on null pointers, negative sizes, ld_g < F, a mode out of
+ * range, a frame_window with angle / unwrap, or misalignment; AT_OK and nothing touched when a size is 0. */
+int at_phase_scan_backward(const float *X_complex, int64_t B, int64_t T, int64_t F, int mode, const float *g, int64_t ld_g,
+                           const float *frame_window, const float *scale, const float *accum_complex, float *out_complex,
+                           void *stream);
+
+/* Adjoint of at_cartesian_pack (Cartesian.forward, reference spectral_repr.py:403-428): g (rows, 2, F) float32, the
+ * gradient of the stacked tensor -> gX (rows, F) complex64 = g[r, 0, :] / re_scale + i g[r, 1, :] / im_scale (a NULL scale:
+ * 1, that half is not normalised).  out_complex must be 8-byte aligned, g_stacked and the scales 4-byte aligned (AT_EINVAL
+ * otherwise, as on null arguments and negative sizes); AT_OK and nothing touched when a size is 0. */
+int at_cartesian_pack_backward(const float *g_stacked, int64_t rows, int F, const float *re_scale, const float *im_scale,
+                               float *out_complex, void *stream);
+
 /* ---- audio front end ------------------------------------------------------------------------------------- */
 /* torchaudio.transforms.Resample(orig, new) with default arguments, as utils/misc.py:31-33 uses it (algorithm
  * restated, torchaudio is not in the reference tree).  x: (rows, L); orig/new: the rates divided by their gcd;
