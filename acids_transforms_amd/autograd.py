@@ -1,14 +1,20 @@
 """Autograd for STFT / DGT (forward and invert), Magnitude and MFCC, for the invert of Magnitude, Polar, Cartesian,
-Real / Imaginary / Phase and Normalize, and for the forward of Normalize, Phase, IF, Cartesian, Polar and PolarIF:
-torch.autograd.Functions whose backward passes are the HIP adjoints of autograd.hip, mfcc_grad.hip, invert_grad.hip and
-repr_grad.hip (through ops.stft_backward / ops.istft_backward / ops.magnitude_backward / ops.mfcc_backward /
-ops.magnitude_invert_backward / ops.polar_to_complex_backward / ops.cartesian_inverse_backward /
-ops.phase_scan_backward / ops.cartesian_forward_backward).
+Real / Imaginary / Phase and Normalize, for the forward of Normalize, Phase, IF, Cartesian, Polar and PolarIF, and for the
+streaming path (OverlapAdd, RealtimeSTFT and RealtimeDGT, forward and invert):
+torch.autograd.Functions whose backward passes are the HIP adjoints of autograd.hip, mfcc_grad.hip, invert_grad.hip,
+repr_grad.hip and stream_grad.hip (through ops.stft_backward / ops.istft_backward / ops.magnitude_backward /
+ops.mfcc_backward / ops.magnitude_invert_backward / ops.polar_to_complex_backward / ops.cartesian_inverse_backward /
+ops.phase_scan_backward / ops.cartesian_forward_backward / ops.rfft_frames_backward / ops.irfft_frames_backward /
+ops.oadd_forward_backward / ops.oadd_invert_backward).
 
 The reference is plain torch, so its STFT, DGT and Magnitude (and their composition) sit inside a training loss.  Here
 the forward kernels write into fresh tensors through ctypes, which cuts the graph; the modules therefore route a call
 through these Functions when -- and only when -- grad mode is on and the input requires grad.  Every other call runs
 the plain forward, bit for bit the same kernels.  The forward values of the autograd route are those same kernels too.
+
+On the streaming path the carried state (OverlapAdd's history and tail, the phase buffer, the PGHI history) is a
+constant of the graph, stored detached: the gradient of a chunk covers that chunk's own samples (truncated
+back-propagation at chunk boundaries).
 
 All backward passes are first-order only (@once_differentiable): create_graph=True raises.
 """
@@ -20,7 +26,8 @@ from . import ops
 __all__ = ["wants_grad", "StftFunction", "IstftFunction", "IstftPolarFunction", "MagnitudeFunction",
            "StftMagnitudeFunction", "MfccFunction", "mfcc_chunk_clips", "MagnitudeInvertFunction", "PolarInvertFunction",
            "CartesianInvertFunction", "PolarToComplexFunction", "AffineInvertFunction", "AffineForwardFunction",
-           "PhaseScanFunction", "CartesianFunction", "PolarFunction", "PolarIFFunction", "StftPolarFunction"]
+           "PhaseScanFunction", "CartesianFunction", "PolarFunction", "PolarIFFunction", "StftPolarFunction",
+           "RtStftFunction", "RtIstftFunction", "RtIstftPolarFunction", "OaddFramesFunction", "OaddInvertFunction"]
 
 
 def wants_grad(x: torch.Tensor) -> bool:
@@ -461,3 +468,113 @@ class StftPolarFunction(torch.autograd.Function):
             ops.stft_backward(dX, window, n, hop, L, out=dx[b0:b0 + chunk])
             del X, dX
         return dx.to(x.dtype), None, None, None, None, None, None
+
+
+# ---- the streaming path: OverlapAdd, RealtimeSTFT, RealtimeDGT ------------------------------------------------------------
+
+class RtStftFunction(torch.autograd.Function):
+    """RealtimeSTFT / RealtimeDGT.forward of frames x (..., n_fft) -- dense, or an overlapping frame() view --
+    -> rfft(x * window) (..., F) complex64, with the frame-analysis adjoint as backward: a DENSE gradient of x's logical
+    shape (torch's own as_strided backward folds it when x is a view).  Saves nothing but x's shape and type."""
+
+    @staticmethod
+    def forward(ctx, x, module):
+        ctx.window, ctx.n_fft, ctx.shape, ctx.dtype = module.window[:module._n_fft], module._n_fft, x.shape, x.dtype
+        return module._rt_forward(x)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, G):
+        gx = ops.rfft_frames_backward(G, ctx.window, ctx.n_fft)
+        return gx.reshape(ctx.shape).to(ctx.dtype), None
+
+
+class RtIstftFunction(torch.autograd.Function):
+    """X (..., n, F) complex -> ops.irfft_frames(X), the windowed frames, with the frame-synthesis adjoint as backward."""
+
+    @staticmethod
+    def forward(ctx, X, inv_window, n_fft):
+        ctx.inv_window, ctx.n_fft, ctx.shape, ctx.dtype = inv_window, n_fft, X.shape, X.dtype
+        return ops.irfft_frames(X, inv_window, n_fft)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        gX = ops.irfft_frames_backward(g, ctx.inv_window, ctx.n_fft)
+        return gX.reshape(ctx.shape).to(ctx.dtype), None, None
+
+
+class RtIstftPolarFunction(torch.autograd.Function):
+    """ops.irfft_frames(mag e^{i phase}) for a magnitude mag (..., n, F) and a constant phase: the gradient of mag is
+    Re(gX e^{-i phase}), the phase gets none.  mag_hist given (RealtimeDGT): the same fused ops.rt_polar_irfft_update as
+    the plain route, whose refreshed PGHI history comes back as two non-differentiable outputs (empty tensors
+    otherwise).  Saves the phase as the kernel read it."""
+
+    @staticmethod
+    def forward(ctx, mag, phase, inv_window, n_fft, mag_hist):
+        phase = ops._f32c(phase.detach())
+        if phase.shape != mag.shape:
+            phase = phase.expand_as(mag).contiguous()
+        ctx.inv_window, ctx.n_fft, ctx.phase, ctx.dtype = inv_window, n_fft, phase, mag.dtype
+        if mag_hist is not None:
+            frames, hist, prev = ops.rt_polar_irfft_update(mag, phase, inv_window, n_fft, mag_hist.detach())
+        else:
+            frames = ops.irfft_frames(None, inv_window, n_fft, mag=mag, phase=phase)
+            hist, prev = mag.new_empty(0), mag.new_empty(0)
+        ctx.mark_non_differentiable(hist, prev)
+        ctx.set_materialize_grads(False)
+        return frames, hist, prev
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, _ghist, _gprev):
+        if g is None:
+            return None, None, None, None, None
+        gmag = ops.irfft_frames_backward(g, ctx.inv_window, ctx.n_fft, phase=ctx.phase)
+        return gmag.to(ctx.dtype), None, None, None, None
+
+
+class OaddFramesFunction(torch.autograd.Function):
+    """OverlapAdd.forward of a chunk x (S, C) behind a constant history (S, keep) or None: the frames, the same zero-copy
+    strided view of [history | chunk | zero pad] as the plain route (shaped lead + (n, n_fft)), and the next history
+    (non-differentiable).  Its backward receives a dense gradient of the view's logical shape and sums, for every chunk
+    sample, the frames that cover it; the history's share is dropped."""
+
+    @staticmethod
+    def forward(ctx, x, hist, module, lead):
+        keep, n_fft, hop = module._keep, module._n_fft, module._hop
+        buf, new_hist, nw = ops.oadd_forward(x, hist, keep, n_fft, hop)
+        ctx.args, ctx.dtype = (n_fft, hop, keep, x.shape[-1]), x.dtype
+        ctx.mark_non_differentiable(new_hist)
+        ctx.set_materialize_grads(False)
+        return module._frames_view(buf, nw, lead), new_hist
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gframes, _ghist):
+        if gframes is None:
+            return None, None, None, None
+        g3 = gframes.reshape((-1,) + tuple(gframes.shape[-2:]))
+        return ops.oadd_forward_backward(g3, *ctx.args).to(ctx.dtype), None, None, None
+
+
+class OaddInvertFunction(torch.autograd.Function):
+    """OverlapAdd.invert of frames (S, n, n_fft) on a constant tail (S, keep) or None -> (out, new tail); the tail is
+    non-differentiable.  The gradient of a frame is gy / gain where the frame reaches this call's output and exactly 0
+    where it only reaches the new tail."""
+
+    @staticmethod
+    def forward(ctx, frames, tail, module):
+        n_fft, hop, keep, gain = module._n_fft, module._hop, module._keep, module.gain_compensation
+        ctx.args, ctx.dtype = (frames.shape[-2], n_fft, hop, keep, gain), frames.dtype
+        out, new_tail = ops.oadd_invert(frames, tail, n_fft, hop, keep, gain)
+        ctx.mark_non_differentiable(new_tail)
+        ctx.set_materialize_grads(False)
+        return out, new_tail
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy, _gtail):
+        if gy is None:
+            return None, None, None
+        return ops.oadd_invert_backward(gy, *ctx.args).to(ctx.dtype), None, None

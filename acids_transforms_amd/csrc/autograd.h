@@ -1,5 +1,6 @@
 // autograd.h -- launchers of autograd.hip (the STFT and ISTFT adjoints and the Magnitude backward), of mfcc_grad.hip
-// (the MFCC backward) and of invert_grad.hip (the Magnitude.invert / Polar.invert backward), for the C entry points.
+// (the MFCC backward), of invert_grad.hip (the Magnitude.invert / Polar.invert backward) and of stream_grad.hip (the
+// streaming path: OverlapAdd, RealtimeSTFT, RealtimeDGT), for the C entry points.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -72,5 +73,13 @@ int launch_magnitude_backward(const MagBwdParams& p, hipStream_t stream);
 int launch_istft_adj_prep(const float* gy, const float* window, float* u, long long B, long long T, int n_fft, int hop,
                           hipStream_t stream);
 int launch_istft_adj_finish(const float2* gX, const float* phase, void* out, long long rows, int n_fft, hipStream_t stream);
+// the streaming path (stream_grad.hip): the DC / Nyquist halves of the frame-analysis adjoint added to its irFFT frames in
+// place, and the adjoints of OverlapAdd.forward and OverlapAdd.invert
+int launch_rfft_adj_edge(float* frames, const float2* G, const float* window, long long rows, int n_fft,
+                         hipStream_t stream);
+int launch_oadd_forward_adj(const float* gframes, long long S, long long n, int n_fft, int hop, int keep, long long C,
+                            float* gx, hipStream_t stream);
+int launch_oadd_invert_adj(const float* gy, long long S, long long n, int n_fft, int hop, int keep, const float* gain,
+                           float* gframes, hipStream_t stream);
 
 }  // namespace at_hip

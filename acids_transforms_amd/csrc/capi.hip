@@ -61,7 +61,8 @@ extern "C" {
 //    signatures: still 4.  So are the backward
 //    entries (at_stft_backward, at_magnitude_backward, at_istft_backward, at_mfcc_backward, and invert_grad.hip's
 //    at_magnitude_invert_backward, at_polar_to_complex_backward, at_cartesian_unpack_backward, and repr_grad.hip's
-//    at_phase_scan_backward, at_cartesian_pack_backward): additions only.
+//    at_phase_scan_backward, at_cartesian_pack_backward, and the streaming path's at_rfft_frames_backward,
+//    at_irfft_frames_backward, at_oadd_forward_backward, at_oadd_invert_backward): additions only.
 int at_abi_version(void) { return 4; }
 
 int at_set_variant(int which, int value) {
@@ -494,6 +495,103 @@ int at_istft_backward(const float* gy, int64_t B, int64_t T, int n_fft, int hop,
     if (rc) return rc;
   }
   return AT_OK;
+}
+
+// ---- the streaming path (stream_grad.hip): per-frame adjoints, no overlap-add --------------------------------------------
+
+size_t at_rfft_frames_backward_workspace_bytes(int64_t nframes, int n_fft) {
+  if (nframes <= 0 || n_fft <= 0) return 0;
+  return adj_window_bytes(n_fft);
+}
+
+int at_rfft_frames_backward(const float* G_complex, int64_t nframes, int64_t frames_per_stream, int n_fft,
+                            const float* window, float* gframes, void* workspace, size_t workspace_bytes, void* stream) {
+  if (nframes < 0 || n_fft <= 0) return AT_EINVAL;
+  if (nframes == 0) return AT_OK;
+  if (frames_per_stream <= 0 || nframes % frames_per_stream) return AT_EINVAL;
+  if (!G_complex || !window || !gframes) return AT_EINVAL;
+  if (((uintptr_t)G_complex) & 7) return AT_EINVAL;    // complex64 rows
+  if (!fft_size_ok(n_fft)) return AT_EUNSUPPORTED;
+  if (!workspace || (((uintptr_t)workspace) & 255) || workspace_bytes < adj_window_bytes(n_fft)) return AT_EWORKSPACE;
+  hipStream_t s = (hipStream_t)stream;
+  float* wscaled = (float*)workspace;
+  int rc = launch_adj_window(window, n_fft, 0.5f * (float)n_fft, wscaled, s);
+  if (rc) return rc;
+  // the forward's own arrangement: at n_fft 128 / 256 / 512 the frames that share a register FFT belong to one stream
+  rc = at_irfft_frames_streams(G_complex, nullptr, nullptr, nframes, frames_per_stream, n_fft, wscaled, gframes, stream);
+  if (rc) return rc;
+  return launch_rfft_adj_edge(gframes, (const float2*)G_complex, window, nframes, n_fft, s);
+}
+
+// streams per chunk of the polar form: its rFFT rows (streams x frames_per_stream x F complex) stay within 1 GiB
+static int64_t rt_adj_chunk_streams(int64_t streams, int64_t frames_per_stream, int n_fft) {
+  const int64_t per_stream = frames_per_stream * (int64_t)(n_fft / 2 + 1);
+  int64_t c = (int64_t(1) << 27) / per_stream;
+  if (c < 1) c = 1;
+  return c < streams ? c : streams;
+}
+
+size_t at_irfft_frames_backward_workspace_bytes(int64_t nframes, int64_t frames_per_stream, int n_fft, int polar) {
+  if (nframes <= 0 || frames_per_stream <= 0 || n_fft <= 0 || nframes % frames_per_stream) return 0;
+  size_t bytes = adj_window_bytes(n_fft);
+  if (polar)
+    bytes += (size_t)rt_adj_chunk_streams(nframes / frames_per_stream, frames_per_stream, n_fft) *
+             (size_t)frames_per_stream * (size_t)(n_fft / 2 + 1) * 2 * sizeof(float);
+  return bytes;
+}
+
+int at_irfft_frames_backward(const float* gframes, const float* phase_or_null, int64_t nframes, int64_t frames_per_stream,
+                             int n_fft, const float* inv_window, float* out, void* workspace, size_t workspace_bytes,
+                             void* stream) {
+  if (nframes < 0 || n_fft <= 0) return AT_EINVAL;
+  if (nframes == 0) return AT_OK;
+  if (frames_per_stream <= 0 || nframes % frames_per_stream) return AT_EINVAL;
+  if (!gframes || !inv_window || !out) return AT_EINVAL;
+  const float* phase = phase_or_null;
+  if (!phase && (((uintptr_t)out) & 7)) return AT_EINVAL;    // complex64 rows
+  if (!fft_size_ok(n_fft)) return AT_EUNSUPPORTED;
+  if (!workspace || (((uintptr_t)workspace) & 255) ||
+      workspace_bytes < at_irfft_frames_backward_workspace_bytes(nframes, frames_per_stream, n_fft, phase != nullptr))
+    return AT_EWORKSPACE;
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t F = n_fft / 2 + 1, S = nframes / frames_per_stream, n = frames_per_stream;
+  const int64_t L = n * (int64_t)n_fft;                 // a stream: n back-to-back frames, hop = n_fft
+  float* wscaled = (float*)workspace;
+  float2* rows = (float2*)((char*)workspace + adj_window_bytes(n_fft));
+  int rc = launch_adj_window(inv_window, n_fft, 2.0f / (float)n_fft, wscaled, s);
+  if (rc) return rc;
+  // the complex form writes the caller's rows in one go, the polar form the workspace rows a chunk of streams at a time
+  const int64_t chunk = phase ? rt_adj_chunk_streams(S, n, n_fft) : S;
+  for (int64_t s0 = 0; s0 < S; s0 += chunk) {
+    const int64_t ns = (S - s0 < chunk) ? S - s0 : chunk;
+    float2* X = phase ? rows : (float2*)out;
+    // the forward's own arrangement (RealtimeSTFT on dense frames): one clip per stream, so that the frames that share a
+    // register FFT at n_fft 128 / 256 / 512 belong to one stream
+    rc = at_stft_forward(gframes + s0 * L, ns, L, L, n, n_fft, n_fft, 0, wscaled, (float*)X, nullptr, stream);
+    if (rc) return rc;
+    rc = launch_istft_adj_finish(X, phase ? phase + s0 * n * F : nullptr, phase ? (void*)(out + s0 * n * F) : (void*)X,
+                                 ns * n, n_fft, s);
+    if (rc) return rc;
+  }
+  return AT_OK;
+}
+
+int at_oadd_forward_backward(const float* gframes, int64_t S, int64_t n, int n_fft, int hop, int keep, int64_t C,
+                             float* gx, void* stream) {
+  if (S < 0 || n <= 0 || n_fft <= 0 || hop <= 0 || keep < 0 || C <= 0) return AT_EINVAL;
+  if (S == 0) return AT_OK;
+  if (!gframes || !gx) return AT_EINVAL;
+  return launch_oadd_forward_adj(gframes, S, n, n_fft, hop, keep, C, gx, (hipStream_t)stream);
+}
+
+int at_oadd_invert_backward(const float* gy, int64_t S, int64_t n, int n_fft, int hop, int keep, const float* gain,
+                            float* gframes, void* stream) {
+  if (S < 0 || n <= 0 || n_fft <= 0 || hop <= 0 || keep < 0) return AT_EINVAL;
+  if ((n - 1) * (int64_t)hop + n_fft < keep) return AT_EINVAL;
+  if (S == 0) return AT_OK;
+  if (!gain || !gframes) return AT_EINVAL;
+  if (!gy && (n - 1) * (int64_t)hop + n_fft > keep) return AT_EINVAL;    // no output sample: gy is not read
+  return launch_oadd_invert_adj(gy, S, n, n_fft, hop, keep, gain, gframes, (hipStream_t)stream);
 }
 
 int at_magnitude_backward(const void* A, int a_kind, int64_t rows, int K, const float* dF, int N, int col_off,

@@ -650,6 +650,74 @@ def istft_backward(gy, inv_window, n_fft, hop, T, env16=None, phase=None):
     return out
 
 
+def _frames_per_stream(t):
+    """Frames per stream of a (..., n, K) tensor of frames, as irfft_frames and RealtimeSTFT.forward count them: each
+    leading-index row of n frames is one stream (a 1-D tensor is one frame)."""
+    return max(int(t.shape[-2]), 1) if t.dim() >= 2 else 1
+
+
+def rfft_frames_backward(G, window, n_fft):
+    """Adjoint of the streaming analysis rfft(frames * window): G (..., n, F) complex64, the gradient of the spectrum ->
+    the dense gradient of the frames, (..., n, n_fft) float32.  Frames share a register FFT within a stream only."""
+    require_device(G, window)
+    G = _c64_grad(G)
+    assert G.shape[-1] == n_fft // 2 + 1, "last dim must be n_fft/2+1"
+    out = torch.empty(tuple(G.shape[:-1]) + (n_fft,), dtype=torch.float32, device=G.device)
+    nframes = out.numel() // n_fft
+    wsb = lib().at_rfft_frames_backward_workspace_bytes(nframes, n_fft)
+    ws = _workspace(wsb, G.device)
+    check(lib().at_rfft_frames_backward(ptr(G), nframes, _frames_per_stream(G), n_fft, ptr(window), ptr(out), ptr(ws), wsb,
+                                        stream_ptr()), "at_rfft_frames_backward")
+    return out
+
+
+def irfft_frames_backward(gframes, inv_window, n_fft, phase=None):
+    """Adjoint of irfft_frames: gframes (..., n, n_fft) float32, the gradient of the windowed frames -> the gradient of
+    the spectrum, (..., n, F) complex64; with phase (..., n, F) float32 (polar input mag e^{i phase}), the gradient of
+    mag, (..., n, F) float32."""
+    require_device(gframes, inv_window, phase)
+    gframes = _f32c(gframes)
+    assert gframes.shape[-1] == n_fft, "last dim must be n_fft"
+    F = n_fft // 2 + 1
+    shape = tuple(gframes.shape[:-1]) + (F,)
+    if phase is not None:
+        phase = _f32c(phase)
+        assert tuple(phase.shape) == shape, "phase must be (..., n, n_fft/2+1)"
+    out = torch.empty(shape, dtype=torch.float32 if phase is not None else torch.complex64, device=gframes.device)
+    nframes, per_stream = gframes.numel() // n_fft, _frames_per_stream(gframes)
+    wsb = lib().at_irfft_frames_backward_workspace_bytes(nframes, per_stream, n_fft, int(phase is not None))
+    ws = _workspace(wsb, gframes.device)
+    check(lib().at_irfft_frames_backward(ptr(gframes), ptr(phase), nframes, per_stream, n_fft, ptr(inv_window), ptr(out),
+                                         ptr(ws), wsb, stream_ptr()), "at_irfft_frames_backward")
+    return out
+
+
+def oadd_forward_backward(gframes, n_fft, hop, keep, C):
+    """Adjoint of oadd_forward with respect to the chunk: gframes (S, n, n_fft) float32, a dense gradient of the frames
+    -> (S, C) float32.  The history's share is dropped; samples that no frame covers get exactly 0."""
+    require_device(gframes)
+    gframes = _f32c(gframes)
+    S, n, N = gframes.shape
+    assert N == n_fft, "last dim must be n_fft"
+    gx = torch.empty((S, C), dtype=torch.float32, device=gframes.device)
+    check(lib().at_oadd_forward_backward(ptr(gframes), S, n, n_fft, hop, keep, C, ptr(gx), stream_ptr()),
+          "at_oadd_forward_backward")
+    return gx
+
+
+def oadd_invert_backward(gy, n, n_fft, hop, keep, gain):
+    """Adjoint of oadd_invert with respect to the frames: gy (S, (n-1)*hop + n_fft - keep) float32 -> (S, n, n_fft)
+    float32 = gy / gain where a frame reaches the output, exactly 0 where it only reaches the new tail."""
+    require_device(gy, gain)
+    gy = _f32c(gy)
+    S = gy.shape[0]
+    assert gy.shape[-1] == (n - 1) * hop + n_fft - keep, "gy does not match oadd_invert's output length"
+    gframes = torch.empty((S, n, n_fft), dtype=torch.float32, device=gy.device)
+    check(lib().at_oadd_invert_backward(ptr(gy), S, n, n_fft, hop, keep, ptr(gain), ptr(gframes), stream_ptr()),
+          "at_oadd_invert_backward")
+    return gframes
+
+
 def magnitude_backward(x, dF, bank_cols=None, bank_t_cols=None, contrast=None, scale=None, eps=1.1920929e-07,
                        col_off=0, dx_accum=None):
     """Gradient of Magnitude.forward with respect to x (..., K) complex64 / float32, given dF (..., N - col_off).

@@ -7,6 +7,15 @@ Drop-in for the reference's transforms/dgt.py (DGT :24-236, RealtimeDGT
 the STFT kernels with the Gaussian analysis window (:108-112) and its
 canonical dual (:114-123); PGHI runs in pghi_offline.hip / pghi_rt.hip with the reference's exact
 binary-heap order (utils/heapq.py).
+
+Gradients: RealtimeDGT's `forward` (dense frames or an overlapping `frame()`
+view), its `invert` of a complex spectrum and its `invert` of a magnitude in
+modes keep_input and random (the phase a constant) carry a gradient when grad
+mode is on and the input requires grad (autograd.RtStftFunction /
+RtIstftFunction / RtIstftPolarFunction; the same kernels forward).  The carried
+state -- `phase_buffer`, `hgi_mag_buffer`, `hgi_phase_buffer`, `random_phase` --
+is a constant of the graph and is stored detached.  Modes pghi and sinebank
+return a tensor without a graph, the same bits as under no_grad.
 """
 import math
 from enum import Enum
@@ -15,6 +24,7 @@ from typing import Dict, List, Union
 import torch
 
 from .. import ops
+from ..autograd import RtIstftFunction, RtIstftPolarFunction, wants_grad
 from ..utils.misc import frame, reshape_batches
 from .base import AudioTransform, InversionEnumType
 from .stft import RealtimeSTFT, STFT
@@ -183,13 +193,11 @@ class RealtimeDGT(DGT):
         return self._lambda()
 
     _rt_forward = RealtimeSTFT._rt_forward
+    _rt_forward_routed = RealtimeSTFT._rt_forward_routed
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         self._follow(x)
-        self._release_phase_source()
-        x_dgt = self._rt_forward(x)
-        self._replace_phase_buffer(x_dgt)
-        return x_dgt
+        return self._rt_forward_routed(x)
 
     def forward_with_time(self, x: torch.Tensor, time: torch.Tensor):
         return self(x), time
@@ -198,6 +206,8 @@ class RealtimeDGT(DGT):
         self._follow(x)
         if not torch.is_complex(x):
             return self.invert_without_phase(x, inversion_mode)
+        if wants_grad(x):
+            return RtIstftFunction.apply(x, self.inv_window[:self._n_fft], self._n_fft)
         return ops.irfft_frames(x, self.inv_window[:self._n_fft], self._n_fft)
 
     def invert_without_phase(self, x: torch.Tensor, inversion_mode: InversionEnumType = None) -> torch.Tensor:
@@ -223,6 +233,12 @@ class RealtimeDGT(DGT):
             phase = phase.expand_as(x)
         # one fused kernel: polar->complex, irfft, window; also refreshes the PGHI history
         # (|x[-2:]| and angle(x[-1]), reference dgt.py:330-336)
+        if inversion_mode != "pghi" and wants_grad(x):
+            # autograd route (autograd.py): the same fused op, the phase and the PGHI history constants of the graph.
+            # PGHI's phase is a function of the magnitude, so that mode stays without a graph (as DGT's)
+            frames, hist, prev = RtIstftPolarFunction.apply(x, phase, self.inv_window[:n], n, self.hgi_mag_buffer)
+            self.hgi_mag_buffer, self.hgi_phase_buffer = hist.detach(), prev.detach()
+            return frames
         frames, self.hgi_mag_buffer, self.hgi_phase_buffer = ops.rt_polar_irfft_update(
             x, phase, self.inv_window[:n], n, self.hgi_mag_buffer)
         return frames

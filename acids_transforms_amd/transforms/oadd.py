@@ -7,12 +7,23 @@ samples (oadd.py:41: shorter ones raise on the following call).  Extension:
 shorter chunks are accepted when they are a whole number of hops (down to one
 hop per call, BASELINE config 5's per-hop step); the frame sequence and the
 overlap-added output stream are then, sample for sample, those of any other
-chunking of the same input (the sums are taken in the same order)."""
+chunking of the same input (the sums are taken in the same order).
+
+Gradients: `forward` and `invert` carry a gradient when grad mode is on and the
+input requires grad (autograd.OaddFramesFunction / OaddInvertFunction: the same
+kernels forward, the HIP adjoints of stream_grad.hip backward).  The carried
+state -- `input_buffer` and `output_buffer` -- is a constant of the graph and is
+stored detached, so the gradient of a chunk covers that chunk's own samples:
+truncated back-propagation at chunk boundaries.  This is a deliberate
+difference from the reference, which stores graph-attached slices
+(oadd.py:41, 103) and therefore raises "backward through the graph a second
+time" on the second chunk.  `_invert_without_update` stays without a graph."""
 from typing import Union
 
 import torch
 
 from .. import ops
+from ..autograd import OaddFramesFunction, OaddInvertFunction, wants_grad
 from ..utils.misc import frame
 from .base import AudioTransform
 
@@ -65,11 +76,19 @@ class OverlapAdd(AudioTransform):
         x2 = x.reshape(-1, x.shape[-1])
         hist = self.input_buffer if self.input_buffer.shape[:-1] == lead else None   # zeros on a new batch shape
         hist2 = hist.reshape(-1, self._keep) if hist is not None else None
+        if wants_grad(x):
+            # autograd route (autograd.py): the same kernel and the same view; the history is a constant of the graph
+            frames, new_hist = OaddFramesFunction.apply(x2, hist2, self, tuple(lead))
+            self.input_buffer = new_hist.detach().reshape(tuple(lead) + (self._keep,))
+            return frames
         buf, new_hist, nw = ops.oadd_forward(x2, hist2, self._keep, self._n_fft, self._hop)
         self.input_buffer = new_hist.reshape(tuple(lead) + (self._keep,))
-        frames = torch.as_strided(buf, (buf.shape[0], nw, self._n_fft), (buf.stride(0), self._hop, 1))
+        return self._frames_view(buf, nw, lead)
+
+    def _frames_view(self, buf: torch.Tensor, nw: int, lead) -> torch.Tensor:
+        """The nw frames of every row of buf = [history | chunk | zero pad] as a zero-copy strided view."""
         if len(lead) == 1:
-            return frames
+            return torch.as_strided(buf, (buf.shape[0], nw, self._n_fft), (buf.stride(0), self._hop, 1))
         # extra leading dims: keep the zero-copy view by splitting dim 0
         return torch.as_strided(buf, tuple(lead) + (nw, self._n_fft),
                                 tuple(buf.stride(0) * s for s in _row_strides(lead)) + (self._hop, 1))
@@ -86,7 +105,11 @@ class OverlapAdd(AudioTransform):
         x3 = x.reshape((-1,) + tuple(x.shape[-2:]))
         tail = self.output_buffer if self.output_buffer.shape[:-1] == lead else None
         tail2 = tail.reshape(-1, self._keep) if tail is not None else None
-        out, new_tail = ops.oadd_invert(x3, tail2, self._n_fft, self._hop, self._keep, self.gain_compensation)
+        if wants_grad(x):
+            out, new_tail = OaddInvertFunction.apply(x3, tail2, self)     # the tail is a constant of the graph
+            new_tail = new_tail.detach()
+        else:
+            out, new_tail = ops.oadd_invert(x3, tail2, self._n_fft, self._hop, self._keep, self.gain_compensation)
         self.output_buffer = new_tail.reshape(tuple(lead) + (self._keep,))
         return out.reshape(tuple(lead) + (out.shape[-1],))
 

@@ -13,7 +13,8 @@ from typing import Dict, Optional
 import torch
 
 from .. import ops
-from ..autograd import IstftFunction, IstftPolarFunction, StftFunction, wants_grad
+from ..autograd import (IstftFunction, IstftPolarFunction, RtIstftFunction, RtIstftPolarFunction, RtStftFunction,
+                        StftFunction, wants_grad)
 from ..utils.misc import frame, reshape_batches
 from .base import AudioTransform, InversionEnumType
 
@@ -362,7 +363,12 @@ class STFT(AudioTransform):
 
 class RealtimeSTFT(STFT):
     """Per-frame transform on pre-framed input (..., n_fft) / (..., n, n_fft):
-    rfft(x * window) and irfft(X) * inv_window (reference stft.py:215-310)."""
+    rfft(x * window) and irfft(X) * inv_window (reference stft.py:215-310).
+
+    Gradients: `forward` (dense frames or an overlapping `frame()` view), `invert` of a complex spectrum and `invert` of
+    a magnitude in modes keep_input and random (the phase a constant) carry one when grad mode is on and the input
+    requires grad (autograd.RtStftFunction / RtIstftFunction / RtIstftPolarFunction).  The phase buffer is stored
+    detached.  Mode sinebank stays without a graph."""
 
     def __init__(self, sr: int = 44100, n_fft: int = 1024, hop_length: int = 256, dtype: torch.dtype = None,
                  inversion_mode: InversionEnumType = "random", window: str = "hann", batch_size: int = 2):
@@ -400,12 +406,22 @@ class RealtimeSTFT(STFT):
         X = ops.stft_forward(xt, self.window[:n], n, hop, center=False, T=T, clip_stride=clip_stride, L=L, B=B)
         return X.reshape(out_shape)
 
+    def _rt_forward_routed(self, x: torch.Tensor) -> torch.Tensor:
+        """_rt_forward, through autograd.RtStftFunction when x wants a gradient (the same kernel forward, the
+        frame-analysis adjoint backward); the lazy phase buffer then keeps a detached spectrum, which does not pin the
+        graph."""
+        self._release_phase_source()
+        if wants_grad(x):
+            x_fft = RtStftFunction.apply(x, self)
+            self._replace_phase_buffer(x_fft.detach())
+        else:
+            x_fft = self._rt_forward(x)
+            self._replace_phase_buffer(x_fft)
+        return x_fft
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         self._follow(x)
-        self._release_phase_source()
-        x_fft = self._rt_forward(x)
-        self._replace_phase_buffer(x_fft)
-        return x_fft
+        return self._rt_forward_routed(x)
 
     def forward_with_time(self, x: torch.Tensor, time: torch.Tensor):
         return self(x), time
@@ -414,6 +430,8 @@ class RealtimeSTFT(STFT):
         self._follow(x)
         if not torch.is_complex(x):
             return self.invert_without_phase(x, inversion_mode)
+        if wants_grad(x):
+            return RtIstftFunction.apply(x, self.inv_window[:self._n_fft], self._n_fft)
         return ops.irfft_frames(x, self.inv_window[:self._n_fft], self._n_fft)
 
     def invert_without_phase(self, x: torch.Tensor, inversion_mode: InversionEnumType = None) -> torch.Tensor:
@@ -429,7 +447,10 @@ class RealtimeSTFT(STFT):
             return self.get_sinebank_inversion(x, windowed=True)
         else:
             raise ValueError("inversion mode %s not valid." % self.inversion_mode)
-        return ops.irfft_frames(None, self.inv_window[:self._n_fft], self._n_fft, mag=x, phase=phase)
+        w, n = self.inv_window[:self._n_fft], self._n_fft
+        if wants_grad(x):      # the phase is a constant of the graph (autograd.RtIstftPolarFunction)
+            return RtIstftPolarFunction.apply(x, phase, w, n, None)[0]
+        return ops.irfft_frames(None, w, n, mag=x, phase=phase)
 
     def get_sinebank_inversion(self, x_fft: torch.Tensor, windowed: bool = False) -> torch.Tensor:
         """Per-chunk oscillator bank with a running clock and per-stream phases (reference stft.py:276-291):

@@ -568,6 +568,59 @@ int at_phase_scan_backward(const float *X_complex, int64_t B, int64_t T, int64_t
 int at_cartesian_pack_backward(const float *g_stacked, int64_t rows, int F, const float *re_scale, const float *im_scale,
                                float *out_complex, void *stream);
 
+/* ---- backward passes of the streaming path (OverlapAdd, RealtimeSTFT, RealtimeDGT; stream_grad.hip) -----------------
+ * N = n_fft, h = hop, F = N / 2 + 1, keep = (N / h - 1) h.  The carried state (history, tail, phase) is a constant of the
+ * graph: a chunk's gradient covers that chunk's own samples.  Frames are grouped in streams of frames_per_stream
+ * consecutive frames (nframes a multiple of it): at n_fft 128 / 256 / 512 the register FFTs transform 8 / 4 / 2 frames
+ * together, and only frames of one stream may share a transform, as at_irfft_frames_streams arranges for the forward --
+ * a stream's bits do not depend on the batch it rides in.  Any n_fft the forward takes. */
+
+/* Adjoint of the frame analysis X[r, k] = sum_m w[m] f[r, m] e^{-2 pi i k m / N} (reference stft.py:251, dgt.py:287:
+ * torch.fft.rfft(x * window)), given G (nframes, F) complex64:
+ *   q[r, m] = (N/2) w[m] irfft(G[r])[m] + w[m] (Re G[r,0] / 2 + Re G[r,N/2] (-1)^m / 2)      (the Nyquist term: even N only)
+ * gframes: (nframes, N) float32.  Three steps: the window scaled by N/2 into the workspace, the irFFT kernels of
+ * at_irfft_frames_streams into gframes, the edge term in place with one fused multiply-add per sample (the per-frame half
+ * of at_stft_backward; no overlap-add follows).  G_complex must be 8-byte aligned (AT_EINVAL); a gframes less aligned
+ * than the register irFFT kernels ask for (8 bytes; 16 at n_fft 2048 / 4096) takes the one-frame kernels.  workspace:
+ * at_rfft_frames_backward_workspace_bytes, 256-byte aligned. */
+size_t at_rfft_frames_backward_workspace_bytes(int64_t nframes, int n_fft);
+int at_rfft_frames_backward(const float *G_complex, int64_t nframes, int64_t frames_per_stream, int n_fft,
+                            const float *window, float *gframes, void *workspace, size_t workspace_bytes, void *stream);
+
+/* Adjoint of the frame synthesis f[r, m] = w[m] irfft(X[r])[m] (reference stft.py:266, dgt.py:302:
+ * torch.fft.irfft(x) * inv_window), given gframes (nframes, N) float32:
+ *   gX[r, k] = (c_k / N) rfft(w gframes[r])[k],   c_0 = 1, c_{N/2} = 1 (even N), c_k = 2 otherwise
+ * phase NULL: out = gX, (nframes, F) complex64, 8-byte aligned.  phase (nframes, F) float32 given (polar input
+ * X = mag e^{i phase}, the phase a constant): out = gmag = Re gX cos phase + Im gX sin phase, (nframes, F) float32; the
+ * rFFT rows then stay in the workspace, a chunk of streams at a time.  Runs the kernels of at_stft_forward with
+ * center = 0, one clip of frames_per_stream back-to-back frames per stream, on the window scaled by 2/N, then the finish
+ * kernel of at_istft_backward.  gframes and phase may have any float alignment.  workspace:
+ * at_irfft_frames_backward_workspace_bytes (polar: 1 with a phase, 0 without), 256-byte aligned. */
+size_t at_irfft_frames_backward_workspace_bytes(int64_t nframes, int64_t frames_per_stream, int n_fft, int polar);
+int at_irfft_frames_backward(const float *gframes, const float *phase_or_null, int64_t nframes, int64_t frames_per_stream,
+                             int n_fft, const float *inv_window, float *out, void *workspace, size_t workspace_bytes,
+                             void *stream);
+
+/* Adjoint of OverlapAdd.forward (reference oadd.py:69-74: the frames are a view of [history | chunk | zero pad]) with
+ * respect to the chunk, given gframes (S, n, N), a DENSE gradient of the n frames of each of S streams:
+ *   gx[s, c] = sum_t gframes[s, t, keep + c - t h]   over the frames t in [0, n) with 0 <= keep + c - t h < N
+ * gx: (S, C) float32.  Summed in ascending t by one thread per sample (no atomics); the history's share is dropped, and a
+ * chunk sample that no frame covers gets exactly 0.  16 bytes per lane when h, N and C are multiples of 4 and both
+ * pointers 16-byte aligned, the same bits otherwise. */
+int at_oadd_forward_backward(const float *gframes, int64_t S, int64_t n, int n_fft, int hop, int keep, int64_t C,
+                             float *gx, void *stream);
+
+/* Adjoint of OverlapAdd.invert (reference oadd.py:90-104: out[s, p] = (tail[s, p] [p < keep] + sum_t f[s, t, p - t h]) /
+ * gain for p < out_len = (n - 1) h + N - keep) with respect to the frames, given gy (S, out_len):
+ *   gframes[s, t, o] = gy[s, t h + o] / gain   where t h + o < out_len, else 0
+ * gframes: (S, n, N) float32; the part of a frame that only reaches the new tail gets exactly 0.  gain: the device scalar
+ * at_oadd_invert reads.  16 bytes per lane when h and N are multiples of 4 and both pointers 16-byte aligned, the same
+ * bits otherwise.
+ * All four: AT_EINVAL on null or ill-shaped arguments before any launch, AT_OK and nothing touched on empty input, no
+ * allocation, asynchronous on `stream`. */
+int at_oadd_invert_backward(const float *gy, int64_t S, int64_t n, int n_fft, int hop, int keep, const float *gain,
+                            float *gframes, void *stream);
+
 /* ---- audio front end ------------------------------------------------------------------------------------- */
 /* torchaudio.transforms.Resample(orig, new) with default arguments, as utils/misc.py:31-33 uses it (algorithm
  * restated, torchaudio is not in the reference tree).  x: (rows, L); orig/new: the rates divided by their gcd;
