@@ -92,20 +92,33 @@ class IstftPolarFunction(torch.autograd.Function):
         return gmag, None, None, None, None, None
 
 
+def _cached(module, slot, src, device, make):
+    """make(src), kept on the module under `slot` until the tensor src is replaced or edited in place."""
+    key = (src.data_ptr(), src._version, str(device))
+    cache = module.__dict__.setdefault("_grad_cols", {})
+    hit = cache.get(slot)
+    if hit is None or hit[0] != key:
+        hit = cache[slot] = (key, make(src))
+    return hit[1]
+
+
+def _bank_cols(module, name, device, transposed=False):
+    """utils.banded.bank_columns of the module's bank `name` (of its transpose with transposed=True) as tensors on
+    `device`: built on first use, cached per bank version."""
+    from .utils.banded import bank_columns
+
+    def make(bank):
+        cols = bank_columns(bank.transpose(-2, -1) if transposed else bank)
+        return tuple(torch.from_numpy(a).to(device) for a in cols)
+    return _cached(module, (name, transposed), getattr(module, name), device, make)
+
+
 def _bank_tables(module, device):
     """(forward bank, transposed bank) by-column tables of a Magnitude's mel_bank on `device`, or (None, None) when
-    mel=False; cached per bank version."""
+    mel=False."""
     if not module.mel:
         return None, None
-    from .utils.banded import bank_columns
-    bank = module.mel_bank
-    key = (bank.data_ptr(), bank._version, str(device))
-    hit = module.__dict__.get("_grad_tables")
-    if hit is None or hit[0] != key:
-        to = lambda arrs: tuple(torch.from_numpy(a).to(device) for a in arrs)   # noqa: E731
-        hit = (key, to(bank_columns(bank)), to(bank_columns(bank.transpose(-2, -1))))
-        module.__dict__["_grad_tables"] = hit
-    return hit[1], hit[2]
+    return _bank_cols(module, "mel_bank", device), _bank_cols(module, "mel_bank", device, transposed=True)
 
 
 def _magnitude_grad(module, x, dF, dx_accum=None):
@@ -173,18 +186,12 @@ def mfcc_chunk_clips(B, T, n_fft):
 
 def _mfcc_tables(module, device):
     """(forward bank tables or None, transposed bank tables, DCT matrix transposed or None) of an MFCC on `device`;
-    the forward bank is walked only on the n_mfcc route.  Cached per bank / DCT version."""
-    from .utils.banded import bank_columns
-    bank = module.fbank
-    dct = module.dct if module.n_mfcc is not None else None
-    key = (bank.data_ptr(), bank._version, str(device)) + ((dct.data_ptr(), dct._version) if dct is not None else ())
-    hit = module.__dict__.get("_grad_tables")
-    if hit is None or hit[0] != key:
-        to = lambda arrs: tuple(torch.from_numpy(a).to(device) for a in arrs)   # noqa: E731
-        hit = (key, to(bank_columns(bank)) if dct is not None else None, to(bank_columns(bank.transpose(-2, -1))),
-               dct.to(device).t().contiguous() if dct is not None else None)
-        module.__dict__["_grad_tables"] = hit
-    return hit[1], hit[2], hit[3]
+    the forward bank is walked only on the n_mfcc route.  The DCT matrix follows its own version."""
+    inv = _bank_cols(module, "fbank", device, transposed=True)
+    if module.n_mfcc is None:
+        return None, inv, None
+    dct_t = _cached(module, "dct_t", module.dct, device, lambda dct: dct.to(device).t().contiguous())
+    return _bank_cols(module, "fbank", device), inv, dct_t
 
 
 class MfccFunction(torch.autograd.Function):
@@ -227,22 +234,11 @@ class MfccFunction(torch.autograd.Function):
 
 def _inverse_bank_tables(module, device, forward=False):
     """By-column tables of a Magnitude's inverse_mel_bank TRANSPOSED on `device` (the walk of the invert's backward), or
-    with forward=True those of the inverse bank itself (the polar form recomputes the magnitude with them); None when
-    mel=False.  Cached per bank version."""
+    with forward=True those of the inverse bank itself (the polar form recomputes the magnitude with them, and only it
+    has them built); None when mel=False."""
     if not module.mel:
         return None
-    from .utils.banded import bank_columns
-    bank = module.inverse_mel_bank
-    key = (bank.data_ptr(), bank._version, str(device))
-    hit = module.__dict__.get("_invert_grad_tables")
-    if hit is None or hit[0] != key:
-        hit = [key, None, None]
-        module.__dict__["_invert_grad_tables"] = hit
-    which = 2 if forward else 1
-    if hit[which] is None:
-        cols = bank_columns(bank if forward else bank.transpose(-2, -1))
-        hit[which] = tuple(torch.from_numpy(a).to(device) for a in cols)
-    return hit[which]
+    return _bank_cols(module, "inverse_mel_bank", device, transposed=not forward)
 
 
 class MagnitudeInvertFunction(torch.autograd.Function):

@@ -1,10 +1,19 @@
 // autograd.h -- launchers of autograd.hip (the STFT and ISTFT adjoints and the Magnitude backward), of mfcc_grad.hip
 // (the MFCC backward), of invert_grad.hip (the Magnitude.invert / Polar.invert backward) and of stream_grad.hip (the
-// streaming path: OverlapAdd, RealtimeSTFT, RealtimeDGT), for the C entry points.
+// streaming path: OverlapAdd, RealtimeSTFT, RealtimeDGT), for the C entry points.  The three banded backward kernels
+// take their banks as BandCols (band_cols.h, with everything else they share): f the bank by column, t its transpose.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "band_cols.h"
+
 namespace at_hip {
+
+// blocks of 256 threads of a flat grid-stride pass over n > 0 elements
+inline unsigned flat_grid(long long n) {
+  const long long blocks = (n + 255) / 256;
+  return (unsigned)(blocks > 65536 ? 65536 : blocks);
+}
 
 struct MagBwdParams {
   const void* A;          // rows x K: complex64 (a_kind 0) or float32 (a_kind 3)
@@ -12,12 +21,8 @@ struct MagBwdParams {
   long long rows;
   int K, N, col_off;      // dF: rows x (N - col_off)
   const float* dF;
-  const int *f_start, *f_len, *f_off;   // forward bank by column (N columns); null: mel=False
-  const float* f_w;
-  int f_nnz;                            // weights of the forward bank
-  const int *t_start, *t_len, *t_off;   // transposed bank by column (K columns)
-  const float* t_w;
-  int t_nnz;
+  BandCols f;             // forward bank by column (N columns); f.w null: mel=False
+  BandCols t;             // transposed bank by column (K columns)
   int contrast;
   const float* scale;     // null: no Normalize
   float eps;
@@ -32,12 +37,8 @@ struct MfccBwdParams {
   const float* dF;        // (B, C, T)
   long long B, T;
   int K, N, C, power;     // N filters; C == N without a DCT; power 1 or 2
-  const int *f_start, *f_len, *f_off;   // forward bank by column (N columns); read on the DCT route only
-  const float* f_w;
-  int f_nnz;
-  const int *t_start, *t_len, *t_off;   // transposed bank by column (K columns)
-  const float* t_w;
-  int t_nnz;
+  BandCols f;             // forward bank by column (N columns); read on the DCT route only
+  BandCols t;             // transposed bank by column (K columns)
   const float* dct_t;     // (C, N): the DCT matrix transposed; null: no DCT
   const float* scale;     // null: no Normalize
 };
@@ -50,12 +51,8 @@ struct MagInvBwdParams {
   int K, N, pad_last;     // the (K x N) inverse bank; pad_last: the last of the K columns is the reference's zero pad
   const void* g;          // rows x N: float32, or complex64 (polar)
   int polar;
-  const int *f_start, *f_len, *f_off;   // inverse bank by column (N columns); read by the polar form only
-  const float* f_w;
-  int f_nnz;
-  const int *t_start, *t_len, *t_off;   // transposed inverse bank by column (K columns); null: mel=False
-  const float* t_w;
-  int t_nnz;
+  BandCols f;             // inverse bank by column (N columns); read by the polar form only
+  BandCols t;             // transposed inverse bank by column (K columns); t.w null: mel=False
   int contrast;
   const float *offset, *scale;          // null: no Normalize
   float eps;

@@ -211,14 +211,10 @@ int launch_istft_adj_finish(const float2* gX, const float* phase, void* out, lon
   if (rows <= 0) return 0;
   const int F = n_fft / 2 + 1, nyq = (n_fft & 1) ? -1 : n_fft / 2;
   if (phase) {
-    long long blocks = (rows * F + 255) / 256;
-    if (blocks > 65536) blocks = 65536;
-    hipLaunchKernelGGL(istft_adj_polar_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, gX, phase, (float*)out, rows, F,
-                       nyq);
+    hipLaunchKernelGGL(istft_adj_polar_kernel, dim3(flat_grid(rows * F)), dim3(256), 0, stream, gX, phase,
+                       (float*)out, rows, F, nyq);
   } else {
-    long long blocks = (rows + 255) / 256;
-    if (blocks > 65536) blocks = 65536;
-    hipLaunchKernelGGL(istft_adj_halve_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, (float2*)out, rows, F, nyq);
+    hipLaunchKernelGGL(istft_adj_halve_kernel, dim3(flat_grid(rows)), dim3(256), 0, stream, (float2*)out, rows, F, nyq);
   }
   return hipGetLastError() == hipSuccess ? 0 : -5;
 }
@@ -292,53 +288,33 @@ __global__ void mag_bwd_pointwise_kernel(MagBwdParams p) {
 
 // banks: one wave per row, |X| and dM of the row in the wave's LDS slice; the loop over row groups is workgroup-uniform
 // so that every wave reaches the barriers.  TAB_LDS: both banks' tables are staged in LDS once per workgroup (the walks'
-// loads are serially dependent: from global memory each one would cost a round trip to L2).
+// loads are serially dependent: from global memory each one would cost a round trip to L2); the first barrier of the
+// row loop publishes them.  KIT > 0: the row's input stays in registers from the first phase to the last.
 template <bool TAB_LDS, int KIT>
-__global__ void mag_bwd_banded_kernel(MagBwdParams p, int k_pad, int n_pad, int f_nnz, int t_nnz, int tab_floats) {
+__global__ void mag_bwd_banded_kernel(MagBwdParams p, int k_pad, int n_pad, int tab_floats) {
   extern __shared__ float mb_lds[];
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   const int wpb = blockDim.x >> 6;
   const int K = p.K, N = p.N;
-  const int *fs = p.f_start, *fl = p.f_len, *fo = p.f_off, *ts = p.t_start, *tl = p.t_len, *to = p.t_off;
-  const float *fw = p.f_w, *tw = p.t_w;
+  BandCols f = p.f, t = p.t;
   if (TAB_LDS) {
-    int* q = reinterpret_cast<int*>(mb_lds);
-    int *fs_l = q, *fl_l = q + N, *fo_l = q + 2 * N, *ts_l = q + 3 * N, *tl_l = ts_l + K, *to_l = ts_l + 2 * K;
-    float* fw_l = reinterpret_cast<float*>(ts_l + 3 * K);
-    float* tw_l = fw_l + f_nnz;
-    for (int i = threadIdx.x; i < N; i += blockDim.x) {
-      fs_l[i] = p.f_start[i];
-      fl_l[i] = p.f_len[i];
-      fo_l[i] = p.f_off[i];
-    }
-    for (int i = threadIdx.x; i < K; i += blockDim.x) {
-      ts_l[i] = p.t_start[i];
-      tl_l[i] = p.t_len[i];
-      to_l[i] = p.t_off[i];
-    }
-    for (int i = threadIdx.x; i < f_nnz; i += blockDim.x) fw_l[i] = p.f_w[i];
-    for (int i = threadIdx.x; i < t_nnz; i += blockDim.x) tw_l[i] = p.t_w[i];
-    fs = fs_l; fl = fl_l; fo = fo_l; ts = ts_l; tl = tl_l; to = to_l; fw = fw_l; tw = tw_l;
+    float* cur = mb_lds;
+    t = band_stage(p.t, cur);
+    f = band_stage(p.f, cur);
   }
   float* a = mb_lds + (TAB_LDS ? tab_floats : 0) + wave * (k_pad + n_pad);
   float* dm = a + k_pad;
   for (long long r0 = (long long)blockIdx.x * wpb; r0 < p.rows; r0 += (long long)gridDim.x * wpb) {
     const long long row = r0 + wave;
     const bool live = row < p.rows;
-    // KIT > 0: the row's input stays in registers from the first phase to the last (KIT loads in flight at once)
     float2 xv[KIT > 0 ? KIT : 1];
     if (live) {
       if (KIT > 0) {
-#pragma unroll
-        for (int q = 0; q < KIT; ++q) {
-          const int k = lane + 64 * q;
-          if (k < K) {
-            const long long e = row * K + k;
-            xv[q] = p.a_kind == 0 ? reinterpret_cast<const float2*>(p.A)[e]
-                                  : make_float2(reinterpret_cast<const float*>(p.A)[e], 0.f);
-          }
-        }
+        if (p.a_kind == 0)
+          band_row_load<KIT>(xv, reinterpret_cast<const float2*>(p.A) + row * K, lane, K);
+        else
+          band_row_load<KIT>(xv, reinterpret_cast<const float*>(p.A) + row * K, lane, K);
 #pragma unroll
         for (int q = 0; q < KIT; ++q) {
           const int k = lane + 64 * q;
@@ -350,85 +326,43 @@ __global__ void mag_bwd_banded_kernel(MagBwdParams p, int k_pad, int n_pad, int 
     }
     __syncthreads();
     if (live)
-      for (int j = lane; j < N; j += 64) {
-        const int s = fs[j], n = fl[j];
-        const float* w = fw + fo[j];
-        float M = 0.f;
-#pragma unroll 4
-        for (int i = 0; i < n; ++i) M = fmaf(w[i], a[s + i], M);
-        dm[j] = mag_dm(p, row, j, M);
-      }
+      for (int j = lane; j < N; j += 64) dm[j] = mag_dm(p, row, j, band_dot(f, j, a));
     __syncthreads();
     if (live) {
-      auto walk = [&](int k) {
-        const int s = ts[k], n = tl[k];
-        const float* w = tw + to[k];
-        float dA = 0.f;
-#pragma unroll 4
-        for (int i = 0; i < n; ++i) dA = fmaf(w[i], dm[s + i], dA);
-        return dA;
-      };
       if (KIT > 0) {
 #pragma unroll
         for (int q = 0; q < KIT; ++q) {
           const int k = lane + 64 * q;
-          if (k < K) mag_put_x(p, row * K + k, walk(k), xv[q]);
+          if (k < K) mag_put_x(p, row * K + k, band_dot(t, k, dm), xv[q]);
         }
       } else {
-        for (int k = lane; k < K; k += 64) mag_put(p, row * K + k, walk(k));
+        for (int k = lane; k < K; k += 64) mag_put(p, row * K + k, band_dot(t, k, dm));
       }
     }
     __syncthreads();
   }
 }
 
-template <bool TAB_LDS, int KIT>
-static int launch_mag_banded(const MagBwdParams& p, int wpb, size_t lds, int k_pad, int n_pad, int tab_floats,
-                             hipStream_t stream) {
-  const void* fn = (const void*)mag_bwd_banded_kernel<TAB_LDS, KIT>;
-  if (lds > 64 * 1024 &&
-      hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-    (void)hipGetLastError();
-    return -5;
-  }
-  // as many workgroups as the chip holds at once (the tables are staged once per workgroup), at most one per row group
-  int per_cu = 0, cus = 0, dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64 * wpb, lds) != hipSuccess) {
-    (void)hipGetLastError();
-    return -5;
-  }
-  long long blocks = (long long)(per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 1);
-  const long long groups = (p.rows + wpb - 1) / wpb;
-  if (blocks > groups) blocks = groups;
-  hipLaunchKernelGGL((mag_bwd_banded_kernel<TAB_LDS, KIT>), dim3((unsigned)blocks), dim3(64 * wpb), lds, stream, p, k_pad,
-                     n_pad, p.f_nnz, p.t_nnz, tab_floats);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
-}
-
 int launch_magnitude_backward(const MagBwdParams& p, hipStream_t stream) {
   if (p.rows == 0) return 0;
-  if (!p.f_w) {
-    long long blocks = (p.rows * p.K + 255) / 256;
-    if (blocks > 65536) blocks = 65536;
-    hipLaunchKernelGGL(mag_bwd_pointwise_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, p);
+  if (!p.f.w) {
+    hipLaunchKernelGGL(mag_bwd_pointwise_kernel, dim3(flat_grid(p.rows * p.K)), dim3(256), 0, stream, p);
     return hipGetLastError() == hipSuccess ? 0 : -5;
   }
-  const int k_pad = (p.K + 63) / 64 * 64, n_pad = (p.N + 63) / 64 * 64;
+  const int k_pad = pad64(p.K), n_pad = pad64(p.N);
   const size_t per_wave = sizeof(float) * (size_t)(k_pad + n_pad);
-  const size_t budget = 160 * 1024;
-  // tables: start / len / off of both banks and their weights, padded to a float4 boundary
-  const long long tab = (3LL * (p.N + p.K) + p.f_nnz + p.t_nnz + 3) / 4 * 4;
-  if (tab * sizeof(float) + 4 * per_wave <= budget) {
-    const size_t lds = tab * sizeof(float) + 4 * per_wave;
-    if (p.K <= 9 * 64) return launch_mag_banded<true, 9>(p, 4, lds, k_pad, n_pad, (int)tab, stream);   // n_fft <= 1024
-    return launch_mag_banded<true, 0>(p, 4, lds, k_pad, n_pad, (int)tab, stream);
-  }
-  if (per_wave > budget) return -2;
-  int wpb = (int)(budget / per_wave);
+  const long long tab = band_tab_floats(band_cols_floats(p.t) + band_cols_floats(p.f));
+  auto run = [&](auto kernel, int wpb, long long tab_floats) {   // one row group: the wpb rows of a workgroup
+    return band_launch(kernel, wpb, sizeof(float) * tab_floats + wpb * per_wave, (p.rows + wpb - 1) / wpb, stream, p, k_pad,
+                       n_pad, (int)tab_floats);
+  };
+  if (sizeof(float) * tab + 4 * per_wave <= kBandLdsBudget)
+    return p.K <= 9 * 64 ? run(mag_bwd_banded_kernel<true, 9>, 4, tab)    // n_fft <= 1024
+                         : run(mag_bwd_banded_kernel<true, 0>, 4, tab);
+  if (per_wave > kBandLdsBudget) return -2;
+  int wpb = (int)(kBandLdsBudget / per_wave);
   if (wpb > 4) wpb = 4;
-  return launch_mag_banded<false, 0>(p, wpb, per_wave * wpb, k_pad, n_pad, 0, stream);
+  return run(mag_bwd_banded_kernel<false, 0>, wpb, 0);
 }
 
 }  // namespace at_hip

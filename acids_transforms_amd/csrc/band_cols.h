@@ -1,0 +1,104 @@
+// band_cols.h -- what the banded backward kernels share (mag_bwd_banded_kernel of autograd.hip, maginv_bwd_banded_kernel
+// of invert_grad.hip, mfcc_bwd_kernel of mfcc_grad.hip): a bank as bands by column, its staging in LDS, the walk of one
+// column, the row kept in registers, the LDS plan and the launcher.
+//
+// A (K x N) bank by column (utils.banded.bank_columns): column j holds len[j] weights at w[off[j] ..] for the rows
+// start[j] .. start[j] + len[j] - 1.  The transposed bank is the same tables of bank^T (K columns).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+
+namespace at_hip {
+
+struct BandCols {
+  const int *start, *len, *off;   // n entries each
+  const float* w;                 // nnz weights; null: no bank
+  int n, nnz;
+};
+
+// ---- LDS plan ---------------------------------------------------------------------------------------------------------
+
+constexpr size_t kBandLdsBudget = 160 * 1024;   // dynamic LDS of one workgroup (the tests' case files restate it)
+
+inline int pad64(int x) { return (x + 63) / 64 * 64; }
+// floats of one bank's tables in LDS
+inline long long band_cols_floats(const BandCols& c) { return 3LL * c.n + c.nnz; }
+// the staged tables end on a float4 boundary
+inline long long band_tab_floats(long long floats) { return (floats + 3) / 4 * 4; }
+
+// ---- device side ------------------------------------------------------------------------------------------------------
+
+// Copies c's tables to LDS at cur as start | len | off | w, the whole workgroup together, moves cur past them and returns
+// the tables in LDS.  No barrier in here: the caller's first __syncthreads() before a walk publishes them.
+__device__ __forceinline__ BandCols band_stage(const BandCols& c, float*& cur) {
+  int* start = reinterpret_cast<int*>(cur);
+  int *len = start + c.n, *off = len + c.n;
+  float* w = reinterpret_cast<float*>(off + c.n);
+  for (int i = threadIdx.x; i < c.n; i += blockDim.x) {
+    start[i] = c.start[i];
+    len[i] = c.len[i];
+    off[i] = c.off[i];
+  }
+  for (int i = threadIdx.x; i < c.nnz; i += blockDim.x) w[i] = c.w[i];
+  cur = w + c.nnz;
+  return {start, len, off, w, c.n, c.nnz};
+}
+
+// sum_i w[i] v[start[j] + i] over column j in ascending i: every "bits do not depend on batch or grid" rests on that order
+__device__ __forceinline__ float band_dot(const BandCols& c, int j, const float* v) {
+  const int s = c.start[j], n = c.len[j];
+  const float* w = c.w + c.off[j];
+  float acc = 0.f;
+#pragma unroll 4
+  for (int i = 0; i < n; ++i) acc = fmaf(w[i], v[s + i], acc);
+  return acc;
+}
+
+// The row's K <= 64 KIT elements in registers, element lane + 64 q in xv[q]: all loads are issued before any is used.
+// Fully unrolled, so that xv never leaves the registers.  KIT == 0: nothing.
+template <int KIT>
+__device__ __forceinline__ void band_row_load(float2 (&xv)[KIT > 0 ? KIT : 1], const float2* row, int lane, int K) {
+#pragma unroll
+  for (int q = 0; q < KIT; ++q) {
+    const int k = lane + 64 * q;
+    if (k < K) xv[q] = row[k];
+  }
+}
+
+// a real row, as (x, 0)
+template <int KIT>
+__device__ __forceinline__ void band_row_load(float2 (&xv)[KIT > 0 ? KIT : 1], const float* row, int lane, int K) {
+#pragma unroll
+  for (int q = 0; q < KIT; ++q) {
+    const int k = lane + 64 * q;
+    if (k < K) xv[q] = make_float2(row[k], 0.f);
+  }
+}
+
+// ---- launcher ---------------------------------------------------------------------------------------------------------
+
+// Launches kernel(args...) with wpb waves per workgroup and lds bytes of dynamic LDS on as many workgroups as the chip
+// holds at once (the tables are staged once per workgroup), at most one per work unit (a row group, a tile).  The device
+// is asked on every call: the current one, on a host with several.  0, or -5.
+template <typename Kernel, typename... Args>
+int band_launch(Kernel kernel, int wpb, size_t lds, long long units, hipStream_t stream, Args... args) {
+  const void* fn = (const void*)kernel;
+  if (lds > 64 * 1024 &&
+      hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+    (void)hipGetLastError();
+    return -5;
+  }
+  int per_cu = 0, cus = 0, dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess ||
+      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64 * wpb, lds) != hipSuccess) {
+    (void)hipGetLastError();
+    return -5;
+  }
+  long long blocks = (long long)(per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 1);
+  if (blocks > units) blocks = units;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(64 * wpb), lds, stream, args...);
+  return hipGetLastError() == hipSuccess ? 0 : -5;
+}
+
+}  // namespace at_hip

@@ -605,8 +605,8 @@ int at_magnitude_backward(const void* A, int a_kind, int64_t rows, int K, const 
   const bool banked = f_w != nullptr;
   if (banked && !(f_start && f_len && f_off && t_start && t_len && t_off && t_w && f_nnz > 0 && t_nnz > 0)) return AT_EINVAL;
   if (!banked && N != K) return AT_EINVAL;
-  at_hip::MagBwdParams p = {A, a_kind, rows, K, N, col_off, dF, f_start, f_len, f_off, f_w, f_nnz, t_start, t_len, t_off, t_w, t_nnz,
-                            contrast, scale, eps, dX_accum, dX};
+  at_hip::MagBwdParams p = {A, a_kind, rows, K, N, col_off, dF, {f_start, f_len, f_off, f_w, N, f_nnz},
+                            {t_start, t_len, t_off, t_w, K, t_nnz}, contrast, scale, eps, dX_accum, dX};
   return at_hip::launch_magnitude_backward(p, (hipStream_t)stream);
 }
 
@@ -621,8 +621,8 @@ int at_mfcc_backward(const float* X_complex, int64_t B, int64_t T, int K, const 
   if ((((uintptr_t)X_complex) & 7) || (((uintptr_t)dX_complex) & 7)) return AT_EINVAL;    // complex64 rows
   if (!(t_start && t_len && t_off && t_w && t_nnz > 0)) return AT_EINVAL;
   if (dct_t && !(f_start && f_len && f_off && f_w && f_nnz > 0)) return AT_EINVAL;
-  at_hip::MfccBwdParams p = {(const float2*)X_complex, (float2*)dX_complex, dF, B, T, K, N, C, power, f_start, f_len, f_off,
-                             f_w, f_nnz, t_start, t_len, t_off, t_w, t_nnz, dct_t, scale};
+  at_hip::MfccBwdParams p = {(const float2*)X_complex, (float2*)dX_complex, dF, B, T, K, N, C, power,
+                             {f_start, f_len, f_off, f_w, N, f_nnz}, {t_start, t_len, t_off, t_w, K, t_nnz}, dct_t, scale};
   return at_hip::launch_mfcc_backward(p, (hipStream_t)stream);
 }
 

@@ -66,7 +66,8 @@ __global__ void maginv_bwd_pointwise_kernel(MagInvBwdParams p) {
 
 // banks: one wave per row; the wave's LDS slice holds g (N floats) -- in the polar form gM, next to c(z) and c'(z) (K
 // floats each).  The loop over row groups is workgroup-uniform so that every wave reaches the barriers.  TAB_LDS: the
-// tables are staged in LDS once per workgroup (the walks' loads are serially dependent).
+// tables are staged in LDS once per workgroup (the walks' loads are serially dependent); the first barrier of the row
+// loop publishes them.
 template <bool TAB_LDS, bool POLAR>
 __global__ void maginv_bwd_banded_kernel(MagInvBwdParams p, int k_pad, int n_pad, int tab_floats) {
   extern __shared__ __attribute__((aligned(16))) float mi_lds[];
@@ -74,31 +75,11 @@ __global__ void maginv_bwd_banded_kernel(MagInvBwdParams p, int k_pad, int n_pad
   const int wave = threadIdx.x >> 6;
   const int wpb = blockDim.x >> 6;
   const int K = p.K, N = p.N, k_in = p.K - p.pad_last;
-  const int *fs = p.f_start, *fl = p.f_len, *fo = p.f_off, *ts = p.t_start, *tl = p.t_len, *to = p.t_off;
-  const float *fw = p.f_w, *tw = p.t_w;
+  BandCols f = p.f, t = p.t;
   if (TAB_LDS) {
-    int* q = reinterpret_cast<int*>(mi_lds);
-    int *ts_l = q, *tl_l = q + K, *to_l = q + 2 * K;
-    float* tw_l = reinterpret_cast<float*>(q + 3 * K);
-    for (int i = threadIdx.x; i < K; i += blockDim.x) {
-      ts_l[i] = p.t_start[i];
-      tl_l[i] = p.t_len[i];
-      to_l[i] = p.t_off[i];
-    }
-    for (int i = threadIdx.x; i < p.t_nnz; i += blockDim.x) tw_l[i] = p.t_w[i];
-    ts = ts_l; tl = tl_l; to = to_l; tw = tw_l;
-    if (POLAR) {
-      int* fs_l = reinterpret_cast<int*>(tw_l + p.t_nnz);
-      int *fl_l = fs_l + N, *fo_l = fs_l + 2 * N;
-      float* fw_l = reinterpret_cast<float*>(fs_l + 3 * N);
-      for (int i = threadIdx.x; i < N; i += blockDim.x) {
-        fs_l[i] = p.f_start[i];
-        fl_l[i] = p.f_len[i];
-        fo_l[i] = p.f_off[i];
-      }
-      for (int i = threadIdx.x; i < p.f_nnz; i += blockDim.x) fw_l[i] = p.f_w[i];
-      fs = fs_l; fl = fl_l; fo = fo_l; fw = fw_l;
-    }
+    float* cur = mi_lds;
+    t = band_stage(p.t, cur);
+    if (POLAR) f = band_stage(p.f, cur);
   }
   const int per_wave = POLAR ? n_pad + 2 * k_pad : n_pad;
   float* gl = mi_lds + (TAB_LDS ? tab_floats : 0) + wave * per_wave;
@@ -132,11 +113,7 @@ __global__ void maginv_bwd_banded_kernel(MagInvBwdParams p, int k_pad, int n_pad
         for (int n = lane; n < N; n += 64) {
           const float2 gx = g[n];
           const float phi = maginv_z(y[N + n], pnorm, ps, po);
-          const int s = fs[n], len = fl[n];
-          const float* w = fw + fo[n];
-          float M = 0.f;
-#pragma unroll 4
-          for (int i = 0; i < len; ++i) M = fmaf(w[i], cz[s + i], M);
+          const float M = band_dot(f, n, cz);
           float sn, cs;
           sincosf(phi, &sn, &cs);
           gl[n] = fmaf(gx.x, cs, __fmul_rn(gx.y, sn));
@@ -148,11 +125,7 @@ __global__ void maginv_bwd_banded_kernel(MagInvBwdParams p, int k_pad, int n_pad
     }
     if (live)
       for (int k = lane; k < k_in; k += 64) {
-        const int s = ts[k], len = tl[k];
-        const float* w = tw + to[k];
-        float acc = 0.f;
-#pragma unroll 4
-        for (int i = 0; i < len; ++i) acc = fmaf(w[i], gl[s + i], acc);
+        const float acc = band_dot(t, k, gl);
         const float c = POLAR ? cp[k] : maginv_cprime(maginv_z(y[k], norm, sc, off), p.contrast);
         dy[k] = maginv_dy(acc, c, norm, sc);
       }
@@ -160,53 +133,29 @@ __global__ void maginv_bwd_banded_kernel(MagInvBwdParams p, int k_pad, int n_pad
   }
 }
 
-template <bool TAB_LDS, bool POLAR>
-static int launch_maginv_banded(const MagInvBwdParams& p, int wpb, size_t lds, int k_pad, int n_pad, int tab_floats,
-                                hipStream_t stream) {
-  const void* fn = (const void*)maginv_bwd_banded_kernel<TAB_LDS, POLAR>;
-  if (lds > 64 * 1024 &&
-      hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-    (void)hipGetLastError();
-    return -5;
-  }
-  // as many workgroups as the chip holds at once (the tables are staged once per workgroup), at most one per row group
-  int per_cu = 0, cus = 0, dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64 * wpb, lds) != hipSuccess) {
-    (void)hipGetLastError();
-    return -5;
-  }
-  long long blocks = (long long)(per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 1);
-  const long long groups = (p.rows + wpb - 1) / wpb;
-  if (blocks > groups) blocks = groups;
-  hipLaunchKernelGGL((maginv_bwd_banded_kernel<TAB_LDS, POLAR>), dim3((unsigned)blocks), dim3(64 * wpb), lds, stream, p,
-                     k_pad, n_pad, tab_floats);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
-}
-
 template <bool POLAR>
 static int launch_maginv_form(const MagInvBwdParams& p, hipStream_t stream) {
-  const int k_pad = (p.K + 63) / 64 * 64, n_pad = (p.N + 63) / 64 * 64;
+  const int k_pad = pad64(p.K), n_pad = pad64(p.N);
   const size_t per_wave = sizeof(float) * (size_t)(POLAR ? n_pad + 2 * k_pad : n_pad);
-  const size_t budget = 160 * 1024;
-  // tables: start / len / off and weights of the transposed bank (and, polar, of the bank), padded to a float4 boundary
-  const long long tab = ((POLAR ? 3LL * (p.N + p.K) + p.f_nnz : 3LL * p.K) + p.t_nnz + 3) / 4 * 4;
-  if (tab * sizeof(float) + 4 * per_wave <= budget)
-    return launch_maginv_banded<true, POLAR>(p, 4, tab * sizeof(float) + 4 * per_wave, k_pad, n_pad, (int)tab, stream);
-  if (per_wave > budget) return -2;
-  int wpb = (int)(budget / per_wave);
+  // tables: the transposed bank's and, polar, the bank's
+  const long long tab = band_tab_floats(band_cols_floats(p.t) + (POLAR ? band_cols_floats(p.f) : 0));
+  auto run = [&](auto kernel, int wpb, long long tab_floats) {   // one row group: the wpb rows of a workgroup
+    return band_launch(kernel, wpb, sizeof(float) * tab_floats + wpb * per_wave, (p.rows + wpb - 1) / wpb, stream, p, k_pad,
+                       n_pad, (int)tab_floats);
+  };
+  if (sizeof(float) * tab + 4 * per_wave <= kBandLdsBudget) return run(maginv_bwd_banded_kernel<true, POLAR>, 4, tab);
+  if (per_wave > kBandLdsBudget) return -2;
+  int wpb = (int)(kBandLdsBudget / per_wave);
   if (wpb > 4) wpb = 4;
-  return launch_maginv_banded<false, POLAR>(p, wpb, per_wave * wpb, k_pad, n_pad, 0, stream);
+  return run(maginv_bwd_banded_kernel<false, POLAR>, wpb, 0);
 }
 
 int launch_magnitude_invert_backward(const MagInvBwdParams& p, hipStream_t stream) {
   if (p.rows == 0) return 0;
-  if (!p.t_w) {
-    long long blocks = (p.rows * (p.K - p.pad_last) + 255) / 256;
-    if (blocks > 65536) blocks = 65536;
-    if (blocks < 1) return 0;
-    hipLaunchKernelGGL(maginv_bwd_pointwise_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, p);
+  if (!p.t.w) {
+    const long long total = p.rows * (p.K - p.pad_last);
+    if (total < 1) return 0;
+    hipLaunchKernelGGL(maginv_bwd_pointwise_kernel, dim3(flat_grid(total)), dim3(256), 0, stream, p);
     return hipGetLastError() == hipSuccess ? 0 : -5;
   }
   return p.polar ? launch_maginv_form<true>(p, stream) : launch_maginv_form<false>(p, stream);
@@ -239,11 +188,6 @@ __global__ void cartesian_unpack_bwd_kernel(const float2* gX, long long rows, in
   }
 }
 
-static unsigned pointwise_blocks(long long n) {
-  long long blocks = (n + 255) / 256;
-  return (unsigned)(blocks > 65536 ? 65536 : blocks);
-}
-
 }  // namespace at_hip
 
 using namespace at_hip;
@@ -271,7 +215,7 @@ int at_magnitude_invert_backward(const float* y, int64_t rows, int K, int N, int
   if ((((uintptr_t)y) & 3) || (((uintptr_t)dy) & 3) || (((uintptr_t)g) & (polar ? 7 : 3))) return AT_EINVAL;
   if (((uintptr_t)offset | (uintptr_t)scale | (uintptr_t)phase_offset | (uintptr_t)phase_scale) & 3) return AT_EINVAL;
   MagInvBwdParams p = {y, polar ? 2LL * K : (long long)(K - pad_last), rows, K, N, pad_last, g, polar,
-                       f_start, f_len, f_off, f_w, f_nnz, t_start, t_len, t_off, t_w, t_nnz,
+                       {f_start, f_len, f_off, f_w, N, f_nnz}, {t_start, t_len, t_off, t_w, K, t_nnz},
                        contrast, offset, scale, eps, phase_offset, phase_scale, dy};
   return launch_magnitude_invert_backward(p, (hipStream_t)stream);
 }
@@ -283,7 +227,7 @@ int at_polar_to_complex_backward(const float* gX_complex, const float* mag, cons
   if (!gX_complex || !phase || (gphase && !mag)) return AT_EINVAL;
   if (((uintptr_t)gX_complex) & 7) return AT_EINVAL;    // complex64 elements
   if (((uintptr_t)mag | (uintptr_t)phase | (uintptr_t)gmag | (uintptr_t)gphase) & 3) return AT_EINVAL;
-  hipLaunchKernelGGL(polar_to_complex_bwd_kernel, dim3(pointwise_blocks(n)), dim3(256), 0, (hipStream_t)stream,
+  hipLaunchKernelGGL(polar_to_complex_bwd_kernel, dim3(flat_grid(n)), dim3(256), 0, (hipStream_t)stream,
                      (const float2*)gX_complex, mag, phase, (long long)n, gmag, gphase);
   return hipGetLastError() == hipSuccess ? AT_OK : AT_ELAUNCH;
 }
@@ -295,7 +239,7 @@ int at_cartesian_unpack_backward(const float* gX_complex, int64_t rows, int F, c
   if (!gX_complex || !dy_stacked) return AT_EINVAL;
   if (((uintptr_t)gX_complex) & 7) return AT_EINVAL;    // complex64 elements
   if (((uintptr_t)dy_stacked | (uintptr_t)re_scale | (uintptr_t)im_scale) & 3) return AT_EINVAL;
-  hipLaunchKernelGGL(cartesian_unpack_bwd_kernel, dim3(pointwise_blocks((long long)rows * F)), dim3(256), 0,
+  hipLaunchKernelGGL(cartesian_unpack_bwd_kernel, dim3(flat_grid((long long)rows * F)), dim3(256), 0,
                      (hipStream_t)stream, (const float2*)gX_complex, (long long)rows, F, re_scale, im_scale, dy_stacked);
   return hipGetLastError() == hipSuccess ? AT_OK : AT_ELAUNCH;
 }

@@ -17,8 +17,8 @@
 // Layout.  dF is channel-major: a lane that walks one frame's channels would read it with stride T.  A workgroup
 // therefore takes a tile of kMfccTile consecutive frames of ONE clip, reads each channel's run of the tile contiguous in
 // t (dividing by scale on the way), and writes it transposed into LDS: g[frame of the tile][channel], row stride C | 1
-// (odd, so that the 32 frames of one channel fall on 32 different banks).  Then one wave per frame does the walks, as
-// mag_bwd_banded_kernel does: on the n_mfcc None route straight on the frame's row of g, with no barrier in between; on
+// (odd, so that the 32 frames of one channel fall on 32 different banks).  Then one wave per frame does the walks
+// (band_cols.h): on the n_mfcc None route straight on the frame's row of g, with no barrier in between; on
 // the n_mfcc route through two wave-private LDS rows (a, then dM) with a workgroup barrier after each.  The last tile of a
 // clip is short when 32 does not divide T; a tile never spans two clips.
 //
@@ -32,8 +32,7 @@
 
 namespace at_hip {
 
-constexpr int kMfccTile = 32;                  // frames per tile (mfcc_grad_cases.py restates it)
-constexpr size_t kMfccLdsBudget = 160 * 1024;  // as launch_magnitude_backward
+constexpr int kMfccTile = 32;   // frames per tile (mfcc_grad_cases.py restates it)
 
 __device__ __forceinline__ float mfcc_pow(float2 x, int power) {
   const float s = fmaf(x.x, x.x, x.y * x.y);
@@ -61,31 +60,15 @@ __global__ void mfcc_bwd_kernel(MfccBwdParams p, int gs, int g_floats, int k_pad
   const int wave = threadIdx.x >> 6;
   const int wpb = blockDim.x >> 6;
   const int K = p.K, N = p.N, C = p.C, power = p.power;
-  const int *ts = p.t_start, *tl = p.t_len, *to = p.t_off, *fs = p.f_start, *fl = p.f_len, *fo = p.f_off;
-  const float *tw = p.t_w, *fw = p.f_w, *dct = p.dct_t;
+  BandCols f = p.f, t = p.t;
+  const float* dct = p.dct_t;
   if (TAB_LDS) {
-    int* q = reinterpret_cast<int*>(mf_lds);
-    int *ts_l = q, *tl_l = q + K, *to_l = q + 2 * K;
-    float* tw_l = reinterpret_cast<float*>(q + 3 * K);
-    for (int i = threadIdx.x; i < K; i += blockDim.x) {
-      ts_l[i] = p.t_start[i];
-      tl_l[i] = p.t_len[i];
-      to_l[i] = p.t_off[i];
-    }
-    for (int i = threadIdx.x; i < p.t_nnz; i += blockDim.x) tw_l[i] = p.t_w[i];
-    ts = ts_l; tl = tl_l; to = to_l; tw = tw_l;
+    float* cur = mf_lds;
+    t = band_stage(p.t, cur);
     if (DCT) {
-      int *fs_l = reinterpret_cast<int*>(tw_l + p.t_nnz), *fl_l = fs_l + N, *fo_l = fs_l + 2 * N;
-      float* fw_l = reinterpret_cast<float*>(fs_l + 3 * N);
-      float* dct_l = fw_l + p.f_nnz;
-      for (int i = threadIdx.x; i < N; i += blockDim.x) {
-        fs_l[i] = p.f_start[i];
-        fl_l[i] = p.f_len[i];
-        fo_l[i] = p.f_off[i];
-      }
-      for (int i = threadIdx.x; i < p.f_nnz; i += blockDim.x) fw_l[i] = p.f_w[i];
-      for (int i = threadIdx.x; i < C * N; i += blockDim.x) dct_l[i] = p.dct_t[i];
-      fs = fs_l; fl = fl_l; fo = fo_l; fw = fw_l; dct = dct_l;
+      f = band_stage(p.f, cur);
+      for (int i = threadIdx.x; i < C * N; i += blockDim.x) cur[i] = p.dct_t[i];
+      dct = cur;
     }
   }
   float* g = mf_lds + tab_floats;
@@ -101,28 +84,22 @@ __global__ void mfcc_bwd_kernel(MfccBwdParams p, int gs, int g_floats, int k_pad
     // the tile of dF, transposed: 32 consecutive lanes read 32 consecutive frames of one channel
     const float* src = p.dF + b * C * p.T + t0;
     for (int i = threadIdx.x; i < C * kMfccTile; i += blockDim.x) {
-      const int c = i / kMfccTile, f = i % kMfccTile;
-      if (f < nt) {
-        const float v = src[(long long)c * p.T + f];
-        g[f * gs + c] = scaled ? v / sc : v;
+      const int c = i / kMfccTile, fr = i % kMfccTile;
+      if (fr < nt) {
+        const float v = src[(long long)c * p.T + fr];
+        g[fr * gs + c] = scaled ? v / sc : v;
       }
     }
     __syncthreads();   // (also the tables, the first time round)
     for (int f0 = 0; f0 < nt; f0 += wpb) {      // workgroup-uniform: every wave reaches the barriers
-      const int f = f0 + wave;
-      const bool live = f < nt;
-      const long long row = b * p.T + t0 + f;
+      const int fr = f0 + wave;
+      const bool live = fr < nt;
+      const long long row = b * p.T + t0 + fr;
       const float2* xr = p.X + row * K;
       float2* dxr = p.dX + row * K;
-      const float* grow = g + f * gs;
+      const float* grow = g + fr * gs;
       float2 xv[KIT > 0 ? KIT : 1];
-      if (live && KIT > 0) {
-#pragma unroll
-        for (int q = 0; q < KIT; ++q) {
-          const int k = lane + 64 * q;
-          if (k < K) xv[q] = xr[k];
-        }
-      }
+      if (live) band_row_load<KIT>(xv, xr, lane, K);
       if (DCT) {
         if (live) {
           if (KIT > 0) {
@@ -138,11 +115,7 @@ __global__ void mfcc_bwd_kernel(MfccBwdParams p, int gs, int g_floats, int k_pad
         __syncthreads();
         if (live)
           for (int j = lane; j < N; j += 64) {
-            const int s = fs[j], n = fl[j];
-            const float* w = fw + fo[j];
-            float M = 0.f;
-#pragma unroll 4
-            for (int i = 0; i < n; ++i) M = fmaf(w[i], a[s + i], M);
+            const float M = band_dot(f, j, a);
             float dl = 0.f;
 #pragma unroll 4
             for (int c = 0; c < C; ++c) dl = fmaf(dct[c * N + j], grow[c], dl);
@@ -152,24 +125,16 @@ __global__ void mfcc_bwd_kernel(MfccBwdParams p, int gs, int g_floats, int k_pad
       }
       if (live) {
         const float* d = DCT ? dm : grow;
-        auto walk = [&](int k) {
-          const int s = ts[k], n = tl[k];
-          const float* w = tw + to[k];
-          float dA = 0.f;
-#pragma unroll 4
-          for (int i = 0; i < n; ++i) dA = fmaf(w[i], d[s + i], dA);
-          return dA;
-        };
         if (KIT > 0) {
 #pragma unroll
           for (int q = 0; q < KIT; ++q) {
             const int k = lane + 64 * q;
-            if (k < K) dxr[k] = mfcc_dx(walk(k), xv[q], power);
+            if (k < K) dxr[k] = mfcc_dx(band_dot(t, k, d), xv[q], power);
           }
         } else {
           for (int k = lane; k < K; k += 64) {
             const float2 x = xr[k];          // read before the write: dX may alias X
-            dxr[k] = mfcc_dx(walk(k), x, power);
+            dxr[k] = mfcc_dx(band_dot(t, k, d), x, power);
           }
         }
       }
@@ -178,57 +143,31 @@ __global__ void mfcc_bwd_kernel(MfccBwdParams p, int gs, int g_floats, int k_pad
   }
 }
 
-template <bool TAB_LDS, bool DCT, int KIT>
-static int launch_mfcc(const MfccBwdParams& p, int wpb, size_t lds, int gs, int g_floats, int k_pad, int n_pad,
-                       int tab_floats, hipStream_t stream) {
-  const void* fn = (const void*)mfcc_bwd_kernel<TAB_LDS, DCT, KIT>;
-  if (lds > 64 * 1024 &&
-      hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-    (void)hipGetLastError();
-    return -5;
-  }
-  // as many workgroups as the chip holds at once (the tables are staged once per workgroup), at most one per tile
-  int per_cu = 0, cus = 0, dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64 * wpb, lds) != hipSuccess) {
-    (void)hipGetLastError();
-    return -5;
-  }
-  const long long tiles_per_clip = (p.T + kMfccTile - 1) / kMfccTile, tiles = p.B * tiles_per_clip;
-  long long blocks = (long long)(per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 1);
-  if (blocks > tiles) blocks = tiles;
-  hipLaunchKernelGGL((mfcc_bwd_kernel<TAB_LDS, DCT, KIT>), dim3((unsigned)blocks), dim3(64 * wpb), lds, stream, p, gs,
-                     g_floats, k_pad, n_pad, tab_floats, tiles_per_clip, tiles);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
-}
-
 int launch_mfcc_backward(const MfccBwdParams& p, hipStream_t stream) {
   if (p.B == 0) return 0;
   const bool dct = p.dct_t != nullptr;
   const int gs = p.C | 1;
   const int g_floats = (kMfccTile * gs + 3) / 4 * 4;
-  const int k_pad = (p.K + 63) / 64 * 64, n_pad = (p.N + 63) / 64 * 64;
+  const int k_pad = pad64(p.K), n_pad = pad64(p.N);
   const size_t g_bytes = sizeof(float) * (size_t)g_floats;
   const size_t per_wave = dct ? sizeof(float) * (size_t)(k_pad + n_pad) : 0;
-  if (g_bytes > kMfccLdsBudget) return -2;
-  // tables: start / len / off of the transposed bank and its weights; the n_mfcc route adds the forward bank's and the
-  // DCT matrix; padded to a float4 boundary
-  long long tab = 3LL * p.K + p.t_nnz;
-  if (dct) tab += 3LL * p.N + p.f_nnz + (long long)p.C * p.N;
-  tab = (tab + 3) / 4 * 4;
-  const size_t lds_tab = tab * sizeof(float) + g_bytes + 4 * per_wave;
-  if (lds_tab <= kMfccLdsBudget) {
-    if (p.K <= 9 * 64) {   // n_fft <= 1024
-      return dct ? launch_mfcc<true, true, 9>(p, 4, lds_tab, gs, g_floats, k_pad, n_pad, (int)tab, stream)
-                 : launch_mfcc<true, false, 9>(p, 4, lds_tab, gs, g_floats, k_pad, n_pad, (int)tab, stream);
-    }
-    return dct ? launch_mfcc<true, true, 0>(p, 4, lds_tab, gs, g_floats, k_pad, n_pad, (int)tab, stream)
-               : launch_mfcc<true, false, 0>(p, 4, lds_tab, gs, g_floats, k_pad, n_pad, (int)tab, stream);
+  if (g_bytes > kBandLdsBudget) return -2;
+  // tables: the transposed bank's; the n_mfcc route adds the forward bank's and the DCT matrix
+  const long long tab =
+      band_tab_floats(band_cols_floats(p.t) + (dct ? band_cols_floats(p.f) + (long long)p.C * p.N : 0));
+  const long long tiles_per_clip = (p.T + kMfccTile - 1) / kMfccTile, tiles = p.B * tiles_per_clip;
+  auto run = [&](auto kernel, long long tab_floats) {   // four waves on a tile at a time
+    return band_launch(kernel, 4, sizeof(float) * tab_floats + g_bytes + 4 * per_wave, tiles, stream, p, gs, g_floats,
+                       k_pad, n_pad, (int)tab_floats, tiles_per_clip, tiles);
+  };
+  if (sizeof(float) * tab + g_bytes + 4 * per_wave <= kBandLdsBudget) {
+    if (p.K <= 9 * 64)   // n_fft <= 1024
+      return dct ? run(mfcc_bwd_kernel<true, true, 9>, tab) : run(mfcc_bwd_kernel<true, false, 9>, tab);
+    return dct ? run(mfcc_bwd_kernel<true, true, 0>, tab) : run(mfcc_bwd_kernel<true, false, 0>, tab);
   }
-  if (!dct) return launch_mfcc<false, false, 0>(p, 4, g_bytes, gs, g_floats, k_pad, n_pad, 0, stream);
-  if (g_bytes + 4 * per_wave > kMfccLdsBudget) return -2;   // (n_fft 16384 with 128 mels and 40 coefficients: 136 KB)
-  return launch_mfcc<false, true, 0>(p, 4, g_bytes + 4 * per_wave, gs, g_floats, k_pad, n_pad, 0, stream);
+  if (!dct) return run(mfcc_bwd_kernel<false, false, 0>, 0);
+  if (g_bytes + 4 * per_wave > kBandLdsBudget) return -2;   // (n_fft 16384 with 128 mels and 40 coefficients: 136 KB)
+  return run(mfcc_bwd_kernel<false, true, 0>, 0);
 }
 
 }  // namespace at_hip

@@ -54,22 +54,16 @@ __global__ void rfft_adj_edge_kernel(float* frames, const float2* G, const float
   }
 }
 
-static unsigned grid_1d(long long threads) {
-  long long blocks = (threads + 255) / 256;
-  if (blocks > 65536) blocks = 65536;
-  return (unsigned)(blocks > 0 ? blocks : 1);
-}
-
 int launch_rfft_adj_edge(float* frames, const float2* G, const float* window, long long rows, int n_fft,
                          hipStream_t stream) {
   if (rows <= 0) return 0;
   const bool vec4 = (n_fft % 4 == 0) && ((((uintptr_t)frames) | ((uintptr_t)window)) & 15) == 0;
   if (vec4)
-    hipLaunchKernelGGL(rfft_adj_edge_kernel<4>, dim3(grid_1d(rows * (n_fft / 4))), dim3(256), 0, stream, frames, G, window,
-                       rows, n_fft);
+    hipLaunchKernelGGL(rfft_adj_edge_kernel<4>, dim3(flat_grid(rows * (n_fft / 4))), dim3(256), 0, stream, frames, G,
+                       window, rows, n_fft);
   else
-    hipLaunchKernelGGL(rfft_adj_edge_kernel<1>, dim3(grid_1d(rows * n_fft)), dim3(256), 0, stream, frames, G, window, rows,
-                       n_fft);
+    hipLaunchKernelGGL(rfft_adj_edge_kernel<1>, dim3(flat_grid(rows * n_fft)), dim3(256), 0, stream, frames, G, window,
+                       rows, n_fft);
   return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 

@@ -718,6 +718,12 @@ def oadd_invert_backward(gy, n, n_fft, hop, keep, gain):
     return gframes
 
 
+def _cols_args(cols):
+    """The five C arguments of one bank's by-column tables (start, len, off, w, nnz); None: no bank."""
+    start, length, off, w = cols if cols is not None else (None,) * 4
+    return ptr(start), ptr(length), ptr(off), ptr(w), w.numel() if w is not None else 0
+
+
 def magnitude_backward(x, dF, bank_cols=None, bank_t_cols=None, contrast=None, scale=None, eps=1.1920929e-07,
                        col_off=0, dx_accum=None):
     """Gradient of Magnitude.forward with respect to x (..., K) complex64 / float32, given dF (..., N - col_off).
@@ -733,14 +739,10 @@ def magnitude_backward(x, dF, bank_cols=None, bank_t_cols=None, contrast=None, s
     if dx_accum is not None:
         dx_accum = dx_accum if dx_accum.is_contiguous() else dx_accum.contiguous()
         assert dx_accum.shape == x.shape and dx_accum.dtype == x.dtype
-    f = bank_cols if bank_cols is not None else (None,) * 4
-    t = bank_t_cols if bank_t_cols is not None else (None,) * 4
     dx = torch.empty_like(x)
     check(lib().at_magnitude_backward(ptr(x), 0 if torch.is_complex(x) else 3, rows, K, ptr(dF), N, col_off,
-                                      ptr(f[0]), ptr(f[1]), ptr(f[2]), ptr(f[3]), f[3].numel() if f[3] is not None else 0,
-                                      ptr(t[0]), ptr(t[1]), ptr(t[2]), ptr(t[3]), t[3].numel() if t[3] is not None else 0,
-                                      contrast_code(contrast), ptr(scale), eps, ptr(dx_accum), ptr(dx),
-                                      stream_ptr()), "at_magnitude_backward")
+                                      *_cols_args(bank_cols), *_cols_args(bank_t_cols), contrast_code(contrast),
+                                      ptr(scale), eps, ptr(dx_accum), ptr(dx), stream_ptr()), "at_magnitude_backward")
     return dx
 
 
@@ -760,12 +762,9 @@ def mfcc_backward(X, dF, bank_t_cols, power=2, bank_cols=None, dct_t=None, scale
     assert dF.shape == (B, C, T), "dF does not match the forward's output"
     if dct_t is not None:
         assert dct_t.is_contiguous() and dct_t.shape[0] == C and bank_cols is not None and bank_cols[0].numel() == N
-    f = bank_cols if dct_t is not None else (None,) * 4
-    t = bank_t_cols
     dX = X if inplace else torch.empty_like(X)
     check(lib().at_mfcc_backward(ptr(X), B, T, K, ptr(dF), C, N, int(power),
-                                 ptr(f[0]), ptr(f[1]), ptr(f[2]), ptr(f[3]), f[3].numel() if f[3] is not None else 0,
-                                 ptr(t[0]), ptr(t[1]), ptr(t[2]), ptr(t[3]), t[3].numel(),
+                                 *_cols_args(bank_cols if dct_t is not None else None), *_cols_args(bank_t_cols),
                                  ptr(dct_t), ptr(scale), ptr(dX), stream_ptr()), "at_mfcc_backward")
     return dX
 
@@ -804,14 +803,9 @@ def magnitude_invert_backward(y, g, bank_t_cols=None, contrast=None, offset=None
         rows = g.numel() // N
         assert y.numel() == rows * (K - pad), "g does not match the forward's output"
     assert g.numel() == rows * N, "g does not match the forward's output"
-    f = bank_cols if polar else (None,) * 4
-    t = bank_t_cols if bank_t_cols is not None else (None,) * 4
     dy = torch.empty_like(y)
     check(lib().at_magnitude_invert_backward(ptr(y), rows, K, N, pad, ptr(g), int(polar),
-                                             ptr(f[0]), ptr(f[1]), ptr(f[2]), ptr(f[3]),
-                                             f[3].numel() if f[3] is not None else 0,
-                                             ptr(t[0]), ptr(t[1]), ptr(t[2]), ptr(t[3]),
-                                             t[3].numel() if t[3] is not None else 0,
+                                             *_cols_args(bank_cols), *_cols_args(bank_t_cols),
                                              contrast_code(contrast), ptr(offset), ptr(scale), eps, ptr(phase_offset),
                                              ptr(phase_scale), ptr(dy), stream_ptr()), "at_magnitude_invert_backward")
     return dy

@@ -87,8 +87,9 @@ def test_chunk_and_tile_restatement():
         assert C.chunk_clips(Bk, Tk, nk) == autograd.mfcc_chunk_clips(Bk, Tk, nk)
     assert autograd.MFCC_CHUNK_ELEMS == C.CHUNK_ELEMS
     assert C.tiles(690) == (22, 18) and C.tiles(64) == (2, 32) and C.tiles(1) == (1, 1) and C.tiles(33) == (2, 1)
-    src = open(os.path.join(ROOT, "acids_transforms_amd", "csrc", "mfcc_grad.hip")).read()
-    assert re.search(r"kMfccTile = %d;" % C.TILE, src) and re.search(r"kMfccLdsBudget = 160 \* 1024;", src)
+    csrc = os.path.join(ROOT, "acids_transforms_amd", "csrc")
+    assert re.search(r"kMfccTile = %d;" % C.TILE, open(os.path.join(csrc, "mfcc_grad.hip")).read())
+    assert re.search(r"kBandLdsBudget = 160 \* 1024;", open(os.path.join(csrc, "band_cols.h")).read())
 
 
 def _sweep():
