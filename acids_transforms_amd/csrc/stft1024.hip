@@ -23,6 +23,7 @@
 
 #include "band_bank.h"
 #include "fft512.h"
+#include "fwd1024_forms.h"
 #include "run_plan.h"
 #include "stft_launch.h"
 #include "variants.h"
@@ -184,41 +185,15 @@ __device__ __forceinline__ float2 load_pair(const float* clip, long long L, long
 // (1 ulp) times ln 2 / log10 2 is within ~2 ulp of logf / log10f at a sixth of the instructions.
 __device__ __forceinline__ float fwd_contrast(float v, int mode, float eps) { return band_contrast_fast(v, mode, eps); }
 
-// MEL: 0 = spectrum only; 1 = spectrum + fused banded-filterbank features; 2 = features only.
-// FWD_WAVES waves per workgroup share the LDS constant tables (twiddles are always staged there; TWLDS makes
-// the FFT read them at the point of use instead of holding 44 VGPRs, which buys a fourth wave per SIMD).
-// CMBUF (MEL != 0, channel-major features): number of passes whose outputs are kept for eight frames in
-// registers and written as 32 contiguous bytes per filter; 0 = every frame scatters 4-byte stores (each
-// lane its own row of the (B, N, T) tensor), which leaves partly written lines to be evicted and re-fetched.
-// POLAR (with MEL == 2): besides the features, normalise(angle X) of every bin goes to p.phase with row stride
-// p.phase_ld -- Compose(STFT + Polar) in one kernel, the complex spectrum never reaches HBM.
-// HS: hop in 128-sample register slots (1, 2 = the reference's default hop 256, 4): the window slides HS slots per
-// frame and HS new segments are fetched.
-// SP (row-major features of a one- or two-pass bank -- the 128-mel bank of the headline step): the passes are
-// unrolled and what a lane needs for them (its filter, where its walk starts, the walk's length) is read once per
-// run instead of once per pass and frame.
-// FQ0 / FQ1 (with SP == 2): the two passes' walk lengths in quads as compile-time constants, log1p contrast and
-// |X| (not |X|^2) fixed -- the headline configuration (128 mel filters at 44.1 kHz: 8 and 2 quads).  The generic
-// epilogue spends more instructions on run-time switches (contrast mode, power, layout, loop control: 112 scalar
-// and 137 vector instructions per frame in the listing) than on the 20 multiply-adds of the walk itself; with
-// everything fixed both passes are straight-line code, their LDS reads batched and their sums independent.
-// AL: the spectrum leaves as ONE byte stream in 512-byte aligned blocks.  (B, T, 513) complex64 is contiguous and a
-// wave writes consecutive frames, but a row is 4104 bytes: row f starts 8 f bytes past a 128-byte line, every one of its
-// eight 512-byte stores straddles five lines and the Nyquist bin is a ninth, one-lane store.  With AL the output
-// COLUMNS of the FFT are rotated over the lanes by rot = (f 513) mod 64 (free: the last exchange reads through the
-// rotated index, fft512's out_lane), so that the lane number IS the position inside an aligned block of 64 bins: lanes
-// >= rot hold block j of the frame in register j, lanes < rot hold block j + 1 in register j, block 8 (the tail of
-// register 7, then the Nyquist bin on lane rot) is carried into the next frame's block 0.  Eight full, aligned 512-byte
-// stores per frame (a ninth every 64 frames), two selects per store, no masked store in the steady state.
-// NT: those stores non-temporal.  tools/ubench/stream_pattern2.hip prices the pattern: rows 4.7 TB/s, aligned blocks
-// 4.95, aligned + nt 5.0-5.3 (profiles/r03a_*).
-template <bool WRITE_PHASE, int MEL, int FWD_WAVES, bool TWLDS, int CMBUF = 0, bool POLAR = false, int HS = 2, int SP = 0,
-          int FQ0 = 0, int FQ1 = 0, bool AL = false, bool NT = false, int HYB = 0, int FC = 1, bool FP2 = false, bool PW = false,
-          fqp_t FQP = 0, int FNP = 0>
-__global__ __launch_bounds__(64 * FWD_WAVES, (TWLDS && !CMBUF && !HYB) ? 4 : 3) void stft1024_h256_fwd_kernel(FwdRunParams p) {
-  // HYB (with TWLDS): bit 0 -- the two pass twiddle tables in registers, only the merge's W1024 rows from LDS
-  // (HybridTwiddles); bit 1 -- the analysis window in registers.  Both trade LDS reads (the busiest unit of these
-  // kernels) for VGPRs, i.e. for the fourth wave per SIMD.
+// One instantiation per form of fwd1024_forms.h, which says what each switch does.  The body goes by their short names.
+template <class Form>
+__global__ __launch_bounds__(64 * Form::waves, fwd1024::waves_per_simd<Form>()) void stft1024_h256_fwd_kernel(FwdRunParams p) {
+  constexpr bool WRITE_PHASE = Form::write_phase, TWLDS = Form::lds_twiddles, POLAR = Form::polar;
+  constexpr bool AL = Form::aligned_stores, NT = Form::nontemporal, FP2 = Form::fixed_power2, PW = Form::persistent;
+  constexpr int MEL = Form::mel, FWD_WAVES = Form::waves, CMBUF = Form::window_passes, HS = Form::hop_slots;
+  constexpr int SP = Form::hoisted_passes, FQ0 = Form::fixed_quads0, FQ1 = Form::fixed_quads1, FC = Form::fixed_contrast;
+  constexpr int HYB = Form::register_tables, FNP = Form::packed_passes;
+  constexpr fqp_t FQP = Form::packed_quads;
   constexpr int H = 128 * HS;
   constexpr int kNP = FQP ? FNP : 1;
   constexpr int kPkStride = (kNP + 3) / 4 * 4;       // dwords per lane in the packed descriptor table (16-byte rows)
@@ -1370,17 +1345,30 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void irfft1024_frames_kernel(
 // ---------------------------------------------------------------------------
 namespace at_hip {
 
-// pass lengths of the reference's default bank at sr 44100 / n_fft 1024 in quads, one per nibble (band_bank.h).  The packed
-// epilogue also hard-codes the feature row as 513 floats (its 1-KB block stream): the dispatch below asks for
-// n_filters == 513 as well -- a 514..576-filter bank can have the same nine pass lengths
-constexpr fqp_t kDefaultBankQuads = 0x001111223ull;
-constexpr int kDefaultBankPasses = 9;      // 513 filters: seven passes of walks, two of empty filters
-static bool bank_is(const BandBank* bank, fqp_t fqp, int n_passes) {
-  if (bank->n_passes != n_passes) return false;
-  for (int q = 0; q < bank->n_passes; ++q)
-    if (bank->pass_len[q] != 4 * fqp_quads(fqp, q)) return false;
-  return true;
+// What the launcher needs of a form, every field from the form's own type: the block size cannot disagree with the kernel.
+struct FwdFormEntry {
+  void (*kernel)(FwdRunParams);
+  const char* name;
+  int waves;               // per workgroup
+  int packed_lds_bytes;    // dynamic LDS of the packed descriptors
+  bool persistent;
+};
+template <class Form> constexpr FwdFormEntry fwd_form_entry(const char* name) {
+  return {stft1024_h256_fwd_kernel<Form>, name, Form::waves, fwd1024::packed_lds_bytes<Form>(), Form::persistent};
 }
+static const FwdFormEntry kFwdForms[] = {      // indexed by Fwd1024Form
+#define X(F) fwd_form_entry<fwd1024::F>(#F),
+    AT_FWD1024_FORMS(X)
+#ifdef AT_DEV_SWITCHES
+    AT_FWD1024_DEV_FORMS(X)
+#endif
+#undef X
+};
+#ifdef AT_DEV_SWITCHES
+static_assert(sizeof(kFwdForms) / sizeof(kFwdForms[0]) == kFwd1024Forms, "one entry per form");
+#else
+static_assert(sizeof(kFwdForms) / sizeof(kFwdForms[0]) == kFwd1024ProductForms, "one entry per product form; no switch picks a dev form here");
+#endif
 
 // Counter pairs of the persistent kernels live behind the device's twiddle table (capi.hip: at_init allocates
 // kTwiddleCount float2 + kTileCtrSlots pairs, zeroed).  Every launch takes the next pair of the ring; a kernel leaves
@@ -1418,10 +1406,26 @@ int launch_stft1024_h256_fwd(const float* x, long long B, long long L, long long
                              const float* window, const float2* tw, float2* out, float* phase, const BandBank* bank,
                              float* feat, const float* offset, const float* scale, float eps, int contrast, int power2,
                              int feat_channel_major, hipStream_t stream, const PolarOut* polar, int hop) {
-  if (hop != 256 && hop != 128 && hop != 512) return -1;
-  // at hop 128 / 512 the fused epilogue exists in its two plain forms (spectrum + features, features only); the
-  // channel-major (MFCC) and Polar variants are built for the reference's hop 256
-  if (hop != 256 && bank && (polar || feat_channel_major)) return -1;
+  Fwd1024Call call = {};
+  call.hop = hop;
+  call.spectrum = out; call.phase = phase; call.polar = polar; call.channel_major = feat_channel_major;
+  call.bank = bank;
+  if (bank) { call.n_passes = bank->n_passes; call.n_filters = bank->n_filters; call.pass_len = bank->pass_len; }
+  call.contrast = contrast; call.power2 = power2;
+  call.out_aligned_512 = (((uintptr_t)out) & 511) == 0; call.feat_aligned_16 = (((uintptr_t)feat) & 15) == 0;
+  call.epilogue = variant(kVarEpilogue);
+  // dev builds only: ACIDS_FWD_STORES = rows | aligned | aligned_nt picks the store form for A/B runs
+  static const int store_mode = [] {
+    const char* e = dev_env("ACIDS_FWD_STORES");
+    return !e ? 2 : !strcmp(e, "rows") ? 0 : !strcmp(e, "aligned") ? 1 : 2;
+  }();
+  static const bool pw_mode = [] { const char* e = dev_env("ACIDS_FWD_PW"); return e && e[0] == '1'; }();
+  call.dev_stores = store_mode; call.dev_persistent = pw_mode;
+  if (const char* e = dev_env("ACIDS_FWD_HYB")) call.dev_register_tables = atoi(e);
+  call.dev_no_register_tables = dev_env("ACIDS_FWD_NOHYB");
+  const int form_id = pick_fwd1024(call);
+  if (form_id < 0 || form_id >= (int)(sizeof(kFwdForms) / sizeof(kFwdForms[0]))) return -1;   // rejected, or a form not built
+  const FwdFormEntry& form = kFwdForms[form_id];
   FwdRunParams p = {};
   p.x = x; p.window = window; p.tw = tw; p.out = out; p.phase = phase;
   p.B = B; p.L = L; p.clip_stride = clip_stride; p.T = T;
@@ -1430,7 +1434,6 @@ int launch_stft1024_h256_fwd(const float* x, long long B, long long L, long long
     p.power2 = power2; p.feat_channel_major = feat_channel_major;
   }
   if (polar) {
-    if (!bank || out) return -1;
     p.phase = polar->phase; p.feat_ld = polar->feat_ld; p.phase_ld = polar->phase_ld;
     p.ph_offset = polar->ph_offset; p.ph_scale = polar->ph_scale;
   }
@@ -1441,130 +1444,12 @@ int launch_stft1024_h256_fwd(const float* x, long long B, long long L, long long
     if (dyn_lds > kMaxBandFloats * sizeof(float)) return -2;
     dyn_lds += (size_t)2 * 64 * bank->n_passes * sizeof(int);   // lane_start, lane_filter
   }
-  // plain forward: 4 waves per block, twiddles in registers (3 waves per SIMD).  Fused: 8 waves share the band
-  // table and read their twiddles from a workgroup LDS copy, which frees 44 VGPRs for a 4th wave per SIMD to
-  // cover the epilogue's LDS round trips (4 % faster than the 3-wave form, A/B on one device).
-  int NW = 4;
-  bool default_bank_fixed = false;
-  bool fq_logpow = false;
-  bool persistent = false;
-  void (*kernel)(FwdRunParams) = nullptr;
-  if (!bank) {
-    if (hop == 128)
-      kernel = phase ? stft1024_h256_fwd_kernel<true, 0, 4, false, 0, false, 1> : stft1024_h256_fwd_kernel<false, 0, 4, false, 0, false, 1>;
-    else if (hop == 512)
-      kernel = phase ? stft1024_h256_fwd_kernel<true, 0, 4, false, 0, false, 4> : stft1024_h256_fwd_kernel<false, 0, 4, false, 0, false, 4>;
-    else
-      kernel = phase ? stft1024_h256_fwd_kernel<true, 0, 4, false> : stft1024_h256_fwd_kernel<false, 0, 4, false>;
-  } else {
-    NW = 8;
-    if (!out && !polar && feat_channel_major && bank->n_passes == 1) kernel = stft1024_h256_fwd_kernel<false, 2, 8, true, 1>;
-    else if (!out && !polar && feat_channel_major && bank->n_passes == 2) kernel = stft1024_h256_fwd_kernel<false, 2, 8, true, 2>;
-    else if (!out && polar) kernel = stft1024_h256_fwd_kernel<false, 2, 8, true, 0, true>;
-    else if (!out) kernel = stft1024_h256_fwd_kernel<false, 2, 8, true>;
-    else kernel = phase ? stft1024_h256_fwd_kernel<true, 1, 8, true> : stft1024_h256_fwd_kernel<false, 1, 8, true>;
-    // row-major features of a one- / two-pass bank at the default hop: passes unrolled, lane constants hoisted
-    if (hop == 256 && !polar && !phase && !feat_channel_major && bank->n_passes <= 2) {
-      if (bank->n_passes == 1)
-        kernel = out ? stft1024_h256_fwd_kernel<false, 1, 8, true, 0, false, 2, 1> : stft1024_h256_fwd_kernel<false, 2, 8, true, 0, false, 2, 1>;
-      else
-        kernel = out ? stft1024_h256_fwd_kernel<false, 1, 8, true, 0, false, 2, 2> : stft1024_h256_fwd_kernel<false, 2, 8, true, 0, false, 2, 2>;
-    }
-    // ... and with the walk lengths of the headline bank (128 mel filters at 44.1 kHz: 8 + 2 quads), log1p and |X|:
-    // the fixed-length epilogue
-    if (hop == 256 && !polar && !phase && !feat_channel_major && bank->n_passes == 2 && contrast == 1 && !power2 &&
-        bank->pass_len[0] == 32 && bank->pass_len[1] == 8 && variant(kVarEpilogue) == 0)
-      kernel = out ? stft1024_h256_fwd_kernel<false, 1, 8, true, 0, false, 2, 2, 8, 2>
-                   : stft1024_h256_fwd_kernel<false, 2, 8, true, 0, false, 2, 2, 8, 2>;
-    // the log-mel of BASELINE configs[3] (log contrast, |X|^2, features only) on the same fixed-length epilogue
-    if (hop == 256 && !polar && !phase && !feat_channel_major && !out && bank->n_passes == 2 && contrast == 2 && power2 &&
-        bank->pass_len[0] == 32 && bank->pass_len[1] == 8 && variant(kVarEpilogue) == 0) {
-      kernel = stft1024_h256_fwd_kernel<false, 2, 4, true, 0, false, 2, 2, 8, 2, false, false, 3, 2, true>;
-      fq_logpow = true;
-    }
-    // MelSpectrogram (the reference's MFCC: |X|^2 on the 128-filter bank, no contrast, channel-major (.., N, T) output,
-    // spectrum never stored) on the same fixed-length epilogue, its two results parked in the register windows
-    if (hop == 256 && !polar && !phase && feat_channel_major && !out && bank->n_passes == 2 && contrast == 0 && power2 &&
-        bank->pass_len[0] == 32 && bank->pass_len[1] == 8 && variant(kVarEpilogue) == 0) {
-      // 4-wave blocks at three waves per SIMD (142 registers); with the pass twiddles in registers as well (HYB = 3) the
-      // two windows no longer fit and spill (0.75 ms against 0.72; the run-time-length epilogue: 0.755)
-      kernel = stft1024_h256_fwd_kernel<false, 2, 4, true, 2, false, 2, 2, 8, 2, false, false, 0, 0, true>;
-      fq_logpow = true;
-    }
-    // The reference's default bank -- Magnitude() at sr 44100: 404 non-empty filters of 513 in seven passes of 3, 2, 2, 1,
-    // 1, 1, 1 quads (and two of empty filters) -- with log1p and |X|, FEATURES ONLY (the README chain's forward): the
-    // packed fixed-length epilogue, 0.92 -> 0.78-0.84 ms per 1024 clips.  The spectrum-storing form keeps the generic
-    // epilogue: it is bound by the memory system's rate for one read and two write streams (~4.1 TB/s), and neither fewer
-    // instructions (-31 %) nor fewer write requests (115 -> 96 per frame) nor aligned spectrum blocks moved it
-    // (1.25-1.34 ms in every combination, same boxes: profiles/r04_default_bank_513.md).
-    if (hop == 256 && !polar && !phase && !feat_channel_major && !out && contrast == 1 && !power2 &&
-        bank->n_filters == F && bank_is(bank, kDefaultBankQuads, kDefaultBankPasses) && (((uintptr_t)feat) & 15) == 0 &&
-        variant(kVarEpilogue) == 0) {
-      kernel = stft1024_h256_fwd_kernel<false, 2, 8, true, 0, false, 2, 0, 0, 0, false, false, 0, 1, false, false, kDefaultBankQuads, kDefaultBankPasses>;
-      default_bank_fixed = true;
-    }
-    if (hop == 128) {
-      if (!out) kernel = stft1024_h256_fwd_kernel<false, 2, 8, true, 0, false, 1>;
-      else kernel = phase ? stft1024_h256_fwd_kernel<true, 1, 8, true, 0, false, 1> : stft1024_h256_fwd_kernel<false, 1, 8, true, 0, false, 1>;
-    } else if (hop == 512) {
-      if (!out) kernel = stft1024_h256_fwd_kernel<false, 2, 8, true, 0, false, 4>;
-      else kernel = phase ? stft1024_h256_fwd_kernel<true, 1, 8, true, 0, false, 4> : stft1024_h256_fwd_kernel<false, 1, 8, true, 0, false, 4>;
-    }
-  }
+  dyn_lds += form.packed_lds_bytes;
   // Runs of at least 8 frames.  The planner minimises rounds x (run length + per-run overhead), counting 1024 / hop - 3
   // >= 1 frames of overhead per run start: a full batch still gets long runs (1024 clips: 173 frames each, one round),
   // while a handful of clips is cut into many short runs that fill the idle chip -- one clip 63 -> 29 us, eight clips
   // 66 -> 31 us (it used to stop at 24-frame runs, i.e. seven waves per second of audio).
-  // Aligned stream stores (template flags AL / NT) for the two headline forms at the default hop: the plain forward and
-  // the fixed-length fused epilogue.  ACIDS_FWD_STORES = rows | aligned | aligned_nt picks the form for A/B runs.
-  {
-    static const int store_mode = [] {
-      const char* e = dev_env("ACIDS_FWD_STORES");        // dev builds only
-      if (!e) return 2;
-      return !strcmp(e, "rows") ? 0 : !strcmp(e, "aligned") ? 1 : 2;
-    }();
-    const bool al_ok = store_mode != 0 && hop == 256 && out && !phase && !polar && (((uintptr_t)out) & 511) == 0;
-    // persistent workgroups (PW): measured slower than one long run per wave on the product kernels
-    // (profiles/r04_launch_shape.md); a development variant
-    static const bool pw_mode = [] { const char* e = dev_env("ACIDS_FWD_PW"); return e && e[0] == '1'; }();
-    if (al_ok && !bank) {
-      NW = 8;
-      kernel = store_mode == 1 ? stft1024_h256_fwd_kernel<false, 0, 8, true, 0, false, 2, 0, 0, 0, true, false>
-                               : stft1024_h256_fwd_kernel<false, 0, 8, true, 0, false, 2, 0, 0, 0, true, true>;
-      if (store_mode == 2 && pw_mode) {
-        kernel = stft1024_h256_fwd_kernel<false, 0, 8, true, 0, false, 2, 0, 0, 0, true, true, 0, 1, false, true>;
-        persistent = true;
-      }
-    } else if (al_ok && kernel == (void (*)(FwdRunParams))stft1024_h256_fwd_kernel<false, 1, 8, true, 0, false, 2, 2, 8, 2>) {
-      kernel = store_mode == 1 ? stft1024_h256_fwd_kernel<false, 1, 8, true, 0, false, 2, 2, 8, 2, true, false>
-                               : stft1024_h256_fwd_kernel<false, 1, 8, true, 0, false, 2, 2, 8, 2, true, true>;
-      if (store_mode == 2 && pw_mode) {
-        kernel = stft1024_h256_fwd_kernel<false, 1, 8, true, 0, false, 2, 2, 8, 2, true, true, 0, 1, false, true>;
-        persistent = true;
-      }
-#ifdef AT_DEV_SWITCHES
-      // dev A/B (round 5, energy): pass twiddles (1) / + window (3) in registers, three waves per SIMD in 4-wave blocks
-      if (const char* e = dev_env("ACIDS_FWD_HYB")) {
-        if (atoi(e) == 1) { kernel = stft1024_h256_fwd_kernel<false, 1, 4, true, 0, false, 2, 2, 8, 2, true, true, 1>; NW = 4; }
-        if (atoi(e) == 3) { kernel = stft1024_h256_fwd_kernel<false, 1, 4, true, 0, false, 2, 2, 8, 2, true, true, 3>; NW = 4; }
-      }
-#endif
-    }
-    // Features only (the spectrum never stored) is bound by the LDS and by instruction issue, not by HBM: with both
-    // pass-twiddle tables and the window in registers (HYB = 3: 30 fewer LDS reads per frame) at three waves per SIMD --
-    // three 4-wave blocks per CU -- it runs 4 % faster than with four waves that read everything from LDS (0.642 ->
-    // 0.615 ms, same box, alternating runs).  The spectrum-storing forms did not move with any HYB setting (fused 0.867
-    // / 0.866 / 0.869 ms, plain 0.756 / 0.758 / 0.779): their waves wait on store issue, and the plain one loses its
-    // fifth and sixth wave.  5 waves per SIMD (10-wave blocks, 96 registers, 2 spilled): 0.65 -> 0.69 ms.
-    if (kernel == (void (*)(FwdRunParams))stft1024_h256_fwd_kernel<false, 2, 8, true, 0, false, 2, 2, 8, 2> &&
-        !dev_env("ACIDS_FWD_NOHYB")) {
-      NW = 4;
-      kernel = stft1024_h256_fwd_kernel<false, 2, 4, true, 0, false, 2, 2, 8, 2, false, false, 3>;
-    }
-    if (fq_logpow) NW = 4;
-  }
-  if (default_bank_fixed) dyn_lds += (size_t)64 * ((kDefaultBankPasses + 3) / 4 * 4) * sizeof(int);   // packed descriptors
-  const long long slots = resident_waves(kernel, 64 * NW, dyn_lds);
+  const long long slots = resident_waves(form.kernel, 64 * form.waves, dyn_lds);
   const long long fpr = plan_units_per_run(B, T, slots, 8, hop == 128 ? 5 : 1);
   p.frames_per_run = fpr;
   // The plain forward (no epilogue) with work for every slot several times over: 16-frame runs.  One workgroup's eight
@@ -1582,26 +1467,26 @@ int launch_stft1024_h256_fwd(const float* x, long long B, long long L, long long
   const long long waves = B * p.runs_per_clip;
   if (dev_env("ACIDS_DEBUG_PLAN")) {
     hipFuncAttributes fa = {};
-    (void)hipFuncGetAttributes(&fa, (const void*)kernel);
-    fprintf(stderr, "[plan fwd] NW %d slots %lld (regs %d, static lds %zu, dyn %zu) frames/run %lld runs/clip %lld waves %lld\n", NW,
-            slots, fa.numRegs, fa.sharedSizeBytes, dyn_lds, p.frames_per_run, p.runs_per_clip, waves);
+    (void)hipFuncGetAttributes(&fa, (const void*)form.kernel);
+    fprintf(stderr, "[plan fwd] %s NW %d slots %lld (regs %d, static lds %zu, dyn %zu) frames/run %lld runs/clip %lld waves %lld\n",
+            form.name, form.waves, slots, fa.numRegs, fa.sharedSizeBytes, dyn_lds, p.frames_per_run, p.runs_per_clip, waves);
   }
-  long long blocks = (waves + NW - 1) / NW;
-  if (persistent) {
-    // short runs (the planner's figure is one long run per resident wave), tiles of NW runs, as many workgroups as fit
+  long long blocks = (waves + form.waves - 1) / form.waves;
+  if (form.persistent) {
+    // short runs (the planner's figure is one long run per resident wave), tiles of form.waves runs, as many workgroups as fit
     long long g = 8;
     if (const char* e = dev_env("ACIDS_FWD_PW_RUN")) g = atoll(e) >= 2 ? atoll(e) : 8;
     if (g > T) g = T;
     p.frames_per_run = g;
     p.runs_per_clip = (T + g - 1) / g;
-    const long long tiles = (B * p.runs_per_clip + NW - 1) / NW;
+    const long long tiles = (B * p.runs_per_clip + form.waves - 1) / form.waves;
     if (tiles >= (1LL << 31)) return -1;
     p.n_tiles = (unsigned)tiles;
     p.tile_ctr = tile_counter_slot(tw);
-    blocks = slots / NW;
+    blocks = slots / form.waves;
     if (blocks > tiles) blocks = tiles;
   }
-  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(64 * NW), dyn_lds, stream, p);
+  hipLaunchKernelGGL(form.kernel, dim3((unsigned)blocks), dim3(64 * form.waves), dyn_lds, stream, p);
   return hipGetLastError() == hipSuccess ? 0 : -5;
 }
 

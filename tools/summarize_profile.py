@@ -73,7 +73,8 @@ if traffic:
     # what bench.py reports as roofline.traffic: per-launch HBM bytes of the step kernels from THIS pass
     bt = {"_comment": "HBM bytes per launch from rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE (separate passes) of `%s`; FETCH_SIZE "
                       "doubled per MI355X_MICROARCH.md (gfx950)" % tag}
-    for key, needle in (("stft_fwd", "stft1024_h256_fwd_kernel<false, 1, 8, true, 0, false, 2, 2, 8, 2"), ("stft_fwd_unfused", "stft1024_h256_fwd_kernel<false, 0"),
+    # needles are matched against short() names, which carry no "at_hip::"
+    for key, needle in (("stft_fwd", "stft1024_h256_fwd_kernel<fwd1024::FixedMel128Spectrum"), ("stft_fwd_unfused", "stft1024_h256_fwd_kernel<fwd1024::Plain"),
                         ("istft", "istft1024_tile_kernel"), ("istft", "istft1024_ola_kernel"), ("mel", "mel_banded_kernel")):
         if key in bt:
             continue
