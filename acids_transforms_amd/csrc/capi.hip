@@ -105,8 +105,8 @@ int at_init(int device) {
     }
   for (int m = 0; m < 8; ++m)
     for (int l = 0; l < 64; ++l) {
-      double a = -two_pi * (double)(l + 64 * m) / 1024.0;
-      tab[(14 + m) * 64 + l] = make_float2((float)cos(a), (float)sin(a));
+      float2& w = tab[(14 + m) * 64 + l];
+      inv1024::w1024(l + 64 * m, w.x, w.y);     // the inverse split relies on W^(512-k) = -conj(W^k) holding exactly
     }
   float2* d = nullptr;
   int rc = AT_OK;

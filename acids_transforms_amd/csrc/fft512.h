@@ -22,6 +22,7 @@
 #include <stdint.h>
 
 #include "fastmath.h"   // reflect_index
+#include "inv1024_pairs.h"
 
 namespace at_hip {
 
@@ -120,6 +121,12 @@ __device__ __forceinline__ v2f sub_conj(v2f a, v2f b) {
   asm("v_pk_add_f32 %0, %1, %2 neg_lo:[0,1]" : "=v"(r) : "v"(a), "v"(b));
   return r;
 }
+// conj(a - i b) = conj(a) + i conj(b) = {a.x + b.y, b.x - a.y}
+__device__ __forceinline__ v2f conj_add_mi(v2f a, v2f b) {
+  v2f r;
+  asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_hi:[1,0]" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
 // h a + (-i) b = {h a.x + b.y, h a.y - b.x};  hh = {h, h} in scalar registers
 __device__ __forceinline__ v2f scale_add_mi(v2f a, v2f hh, v2f b) {
   v2f r;
@@ -184,14 +191,16 @@ __device__ __forceinline__ void wave_lds_sync() {
 // Twiddles are stored with the forward sign in every kernel (the inverse multiplies by the conjugate in the
 // same two instructions).  `tr` holds W1024^k / 2 in forward kernels (the real-FFT merge wants the half) and
 // W1024^k in inverse ones: `TR_SCALE`.
-// twiddles held in registers (loop invariant, 44 VGPRs) ...
+// twiddles held in registers (loop invariant, 44 VGPRs; the inverse split reads only rows 0..3 of `tr`: 36) ...
 struct Twiddles {
   v2f t1[7];
   v2f t2[7];
   v2f tr[8];
+  v2f tr_self;   // inverse tables: W1024^256, the twiddle of the bin that is its own mirror partner (wave-uniform)
   __device__ __forceinline__ v2f get1(int k) const { return t1[k]; }
   __device__ __forceinline__ v2f get2(int k) const { return t2[k]; }
   __device__ __forceinline__ v2f getr(int m) const { return tr[m]; }
+  __device__ __forceinline__ v2f getr_self() const { return tr_self; }
 };
 
 // ... or read at the point of use from a workgroup-shared LDS copy of the table
@@ -205,6 +214,7 @@ struct LdsTwiddles {
   __device__ __forceinline__ v2f get1(int k) const { return lds_read_single(reinterpret_cast<const v2f*>(tab) + k * 64 + lane); }
   __device__ __forceinline__ v2f get2(int k) const { return lds_read_single(reinterpret_cast<const v2f*>(tab) + (7 + k) * 64 + lane); }
   __device__ __forceinline__ v2f getr(int m) const { return lds_read_single(reinterpret_cast<const v2f*>(tab) + (14 + m) * 64 + lane); }
+  __device__ __forceinline__ v2f getr_self() const { return lds_read_single(reinterpret_cast<const v2f*>(tab) + (14 + inv1024::kSelfPairedRow) * 64); }
 };
 // ... or both: the two pass tables (14 rows, indexed by the physical lane) in registers, the W1024 rows of the real
 // merge read from LDS through `col` -- what the kernels with rotated output columns need (the merge's twiddle follows
@@ -234,6 +244,11 @@ __device__ __forceinline__ void load_twiddles(Twiddles& tw, const float2* __rest
   }
 #pragma unroll
   for (int m = 0; m < 8; ++m) tw.tr[m] = to_v(twiddle_for_lds<INV>(tab, (14 + m) * 64 + lane));
+  if (INV) {
+    const float2 w = tab[(14 + inv1024::kSelfPairedRow) * 64];   // one address for the wave: scalar registers
+    tw.tr_self = (v2f){__int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(w.x))),
+                       __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(w.y)))};
+  }
 }
 
 // 512-point complex FFT of one wave.  In: v[m] = z[lane + 64 m].
@@ -415,29 +430,55 @@ __device__ __forceinline__ void rfft_merge(float2 (&f)[8], const TW& tw, int lan
   for (int m = 0; m < 8; ++m) f[m] = to_f2(v[m]);
 }
 
-// inverse of rfft_merge: from one-sided X (X[512] passed as xnyq_re to lane 0)
-// build Z[k] = E[k] + i O[k] with E = (X[k] + conj X[512-k]), O = (X[k] - conj X[512-k]) conj(W1024^k)
-// (the common factor 1/2 is folded into the caller's 1/N scale).  `tw.getr` = W1024^k (inverse tables).
+// inverse of rfft_merge: from one-sided X build Z[k] = E[k] + i O[k] with E = (X[k] + conj X[512-k]),
+// O = (X[k] - conj X[512-k]) conj(W1024^k) (the common factor 1/2 is folded into the caller's 1/N scale).
+// `tw.getr` = W1024^k (inverse tables).
+// In: the paired layout of inv1024_pairs.h -- v[m] = X[inv1024::load_bin(lane, m)], so v[m] and v[7 - m] are mirror
+// partners in every lane; `x256` = X[256] (used by lane 0).  Out: v[m] = Z[lane + 64 m], what fft512<true> takes.
+// A pair is split once: with a = X[k], b = X[512-k], e = a + conj b and d = (a - conj b) conj(W1024^k),
+//   Z[k] = e + i d,   Z[512-k] = conj(e) + i conj(d) = conj(e - i d).
+// The second line is what the per-bin expression gives for 512-k BIT FOR BIT (up to the sign of an exact zero):
+// b + conj a = conj(e) and b - conj a = -conj(a - conj b) exactly, W1024^(512-k) = -conj(W1024^k) exactly in the host's
+// table (tests/test_inv1024_pairs_cpu.py), and rounding is symmetric under negation, so the partner's product is conj(d).
 template <typename TW>
-__device__ __forceinline__ void irfft_split(v2f (&v)[8], const TW& tw, int lane, float xnyq_re) {
-  // c2r ignores the imaginary parts of DC and Nyquist
-  if (lane == 0) v[0].y = 0.0f;
-  v2f p[8];
-  mirror_regs<8>(v, p, lane);
-  if (lane == 0) p[0] = (v2f){xnyq_re, 0.0f};  // partner of k=0 is X[512]
+__device__ __forceinline__ void irfft_split(v2f (&v)[8], const TW& tw, int lane, v2f x256) {
+  // c2r ignores the imaginary parts of DC and Nyquist: lane 0's registers 0 and 7
+  if (lane == 0) {
+    v[0].y = 0.0f;
+    v[7].y = 0.0f;
+  }
 #pragma unroll
-  for (int m = 0; m < 8; ++m) {
-    const v2f e = add_conj(v[m], p[m]);
-    const v2f d = cmul_conj_v(sub_conj(v[m], p[m]), tw.getr(m));
-    v[m] = add_pi(e, d);                              // Z = e + i d
+  for (int m = 0; m < inv1024::kPairs; ++m) {
+    const int n = inv1024::partner_reg(m);
+    const v2f e = add_conj(v[m], v[n]);
+    const v2f d = cmul_conj_v(sub_conj(v[m], v[n]), tw.getr(m));
+    v[m] = add_pi(e, d);                              // Z[k] = e + i d
+    v[n] = conj_add_mi(e, d);                         // Z[512-k]; lane 0, m = 0: "Z[512]", dropped below
+  }
+  if (lane == 0) {
+    // column 0: Z[320], Z[384], Z[448] move up one register and Z[256], whose partner is itself, comes in below them.
+    // Lane 0 exchanges with itself, so this may come first -- and then waits for no cross-lane result.
+    const v2f e = add_conj(x256, x256);
+    const v2f d = cmul_conj_v(sub_conj(x256, x256), tw.getr_self());
+    v[7] = v[6];
+    v[6] = v[5];
+    v[5] = v[4];
+    v[4] = add_pi(e, d);
+  }
+  // registers 4..7 hold column (64 - lane) & 63 at its natural index: swap them with that column's lane
+  const int src = inv1024::exchange_lane(lane);
+#pragma unroll
+  for (int m = inv1024::kPairs; m < 8; ++m) {
+    v[m].x = __shfl(v[m].x, src, 64);
+    v[m].y = __shfl(v[m].y, src, 64);
   }
 }
 template <typename TW>
-__device__ __forceinline__ void irfft_split(float2 (&f)[8], const TW& tw, int lane, float xnyq_re) {
+__device__ __forceinline__ void irfft_split(float2 (&f)[8], const TW& tw, int lane, float2 x256) {
   v2f v[8];
 #pragma unroll
   for (int m = 0; m < 8; ++m) v[m] = to_v(f[m]);
-  irfft_split(v, tw, lane, xnyq_re);
+  irfft_split(v, tw, lane, to_v(x256));
 #pragma unroll
   for (int m = 0; m < 8; ++m) f[m] = to_f2(v[m]);
 }

@@ -800,9 +800,11 @@ struct InvParams {
   long long total_frames, frames_per_block;  // OUT_FRAMES
 };
 
-// One frame's spectrum as it sits in HBM, loaded ahead of use and converted when consumed:
-//   IN_COMPLEX: d[m] = X[lane + 64 m],             ny0 = Re X[512]
-//   IN_POLAR:   d[m] = (mag, phase)[lane + 64 m],  (ny0, ny1) = (mag, phase)[512]
+// One frame's spectrum as it sits in HBM, loaded ahead of use and converted when consumed, in the paired layout of
+// inv1024_pairs.h: register m holds bin inv1024::load_bin(lane, m) -- lane + 64 m below 4, (64 - lane) + 64 m from 4 on, so
+// that registers m and 7 - m are mirror partners -- and bin 256, its own partner, is one extra element per frame:
+//   IN_COMPLEX: d[m] = X[bin(m)],             mid = X[256]
+//   IN_POLAR:   (a, ph)[m] = (mag, phase)[bin(m)],  (mid0, mid1) = (mag, phase)[256]
 // (the polar form keeps mag and phase in separate registers: each is the target of its own dword load)
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 template <int IN_MODE>
@@ -810,12 +812,12 @@ struct RawFrame;
 template <>
 struct RawFrame<IN_COMPLEX> {
   f32x2 d[8];
-  float ny0;
+  f32x2 mid;
 };
 template <>
 struct RawFrame<IN_POLAR> {
   float a[8], ph[8];
-  float ny0, ny1;
+  float mid0, mid1;
 };
 // IN_GL: the Griffin-Lim phase update (torchaudio.functional.griffinlim as called at reference stft.py:174-178)
 // taken at load time -- X = mag * normalise(rebuilt - m' tprev) never exists in HBM
@@ -823,8 +825,8 @@ template <>
 struct RawFrame<IN_GL> {
   f32x2 r[8], t[8];
   float a[8];
-  f32x2 rny, tny;
-  float any;
+  f32x2 rmid, tmid;
+  float amid;
 };
 
 __device__ __forceinline__ void load_raw(const InvParams& p, long long f, int lane, RawFrame<IN_COMPLEX>& q) {
@@ -832,26 +834,25 @@ __device__ __forceinline__ void load_raw(const InvParams& p, long long f, int la
 #pragma unroll
   for (int m = 0; m < 8; ++m) {
 #if AT_ISTFT_NTLOAD
-    q.d[m] = __builtin_nontemporal_load(row + lane + 64 * m);
+    q.d[m] = __builtin_nontemporal_load(row + inv1024::load_start(lane, m) + inv1024::load_step(m));
 #else
-    q.d[m] = row[lane + 64 * m];
+    q.d[m] = (row + inv1024::load_start(lane, m))[inv1024::load_step(m)];
 #endif
   }
-  // broadcast load; only lane 0 uses it.  A 4-byte load of the real part alone: as `row[512].x` it was an 8-byte
-  // load whose dead upper register the allocator handed to the next instruction at once -- a write-after-write
-  // hazard on a load just issued, i.e. `s_waitcnt vmcnt(0)` in the steady-state loop, draining both frames of lookahead.
-  q.ny0 = reinterpret_cast<const float*>(row + 512)[0];
+  // broadcast load; only lane 0 uses it.  Both halves are live (a load with a dead register is a write-after-write
+  // hazard on a load just issued: `s_waitcnt vmcnt(0)` in the steady-state loop, draining both frames of lookahead).
+  q.mid = row[inv1024::kSelfPairedBin];
 }
 __device__ __forceinline__ void load_raw(const InvParams& p, long long f, int lane, RawFrame<IN_POLAR>& q) {
   const float* mrow = p.mag + f * F;
   const float* prow = p.phase + f * F;
 #pragma unroll
   for (int m = 0; m < 8; ++m) {
-    q.a[m] = mrow[lane + 64 * m];
-    q.ph[m] = prow[lane + 64 * m];
+    q.a[m] = (mrow + inv1024::load_start(lane, m))[inv1024::load_step(m)];
+    q.ph[m] = (prow + inv1024::load_start(lane, m))[inv1024::load_step(m)];
   }
-  q.ny0 = mrow[512];
-  q.ny1 = prow[512];
+  q.mid0 = mrow[inv1024::kSelfPairedBin];
+  q.mid1 = prow[inv1024::kSelfPairedBin];
 }
 
 __device__ __forceinline__ void load_raw(const InvParams& p, long long f, int lane, RawFrame<IN_GL>& q) {
@@ -860,13 +861,13 @@ __device__ __forceinline__ void load_raw(const InvParams& p, long long f, int la
   const float* mrow = p.mag + f * F;
 #pragma unroll
   for (int m = 0; m < 8; ++m) {
-    q.r[m] = rrow[lane + 64 * m];
-    q.t[m] = trow[lane + 64 * m];
-    q.a[m] = mrow[lane + 64 * m];
+    q.r[m] = (rrow + inv1024::load_start(lane, m))[inv1024::load_step(m)];
+    q.t[m] = (trow + inv1024::load_start(lane, m))[inv1024::load_step(m)];
+    q.a[m] = (mrow + inv1024::load_start(lane, m))[inv1024::load_step(m)];
   }
-  q.rny = rrow[512];
-  q.tny = trow[512];
-  q.any = mrow[512];
+  q.rmid = rrow[inv1024::kSelfPairedBin];
+  q.tmid = trow[inv1024::kSelfPairedBin];
+  q.amid = mrow[inv1024::kSelfPairedBin];
 }
 
 __device__ __forceinline__ float2 gl_update(f32x2 r, f32x2 t, float mag, float mom) {
@@ -881,12 +882,13 @@ __device__ __forceinline__ float2 gl_update(f32x2 r, f32x2 t, float mag, float m
   return make_float2(s * ax, s * ay);
 }
 
-__device__ __forceinline__ void raw_to_spectrum(const RawFrame<IN_COMPLEX>& q, float2 (&v)[8], float& nyq_re) {
+// v[m] = X[inv1024::load_bin(lane, m)], x256 = X[256]: the conversions are per element and keep the loads' layout
+__device__ __forceinline__ void raw_to_spectrum(const RawFrame<IN_COMPLEX>& q, float2 (&v)[8], float2& x256) {
 #pragma unroll
   for (int m = 0; m < 8; ++m) v[m] = make_float2(q.d[m].x, q.d[m].y);
-  nyq_re = q.ny0;
+  x256 = make_float2(q.mid.x, q.mid.y);
 }
-__device__ __forceinline__ void raw_to_spectrum(const RawFrame<IN_POLAR>& q, float2 (&v)[8], float& nyq_re) {
+__device__ __forceinline__ void raw_to_spectrum(const RawFrame<IN_POLAR>& q, float2 (&v)[8], float2& x256) {
 #pragma unroll
   for (int m = 0; m < 8; ++m) {
     float sn, cs;
@@ -894,21 +896,21 @@ __device__ __forceinline__ void raw_to_spectrum(const RawFrame<IN_POLAR>& q, flo
     v[m] = make_float2(q.a[m] * cs, q.a[m] * sn);
   }
   float sn, cs;
-  fast_sincosf(q.ny1, sn, cs);
-  nyq_re = q.ny0 * cs;
+  fast_sincosf(q.mid1, sn, cs);
+  x256 = make_float2(q.mid0 * cs, q.mid0 * sn);
 }
 
-__device__ __forceinline__ void raw_to_spectrum(const RawFrame<IN_GL>& q, float2 (&v)[8], float& nyq_re, float mom) {
+__device__ __forceinline__ void raw_to_spectrum(const RawFrame<IN_GL>& q, float2 (&v)[8], float2& x256, float mom) {
 #pragma unroll
   for (int m = 0; m < 8; ++m) v[m] = gl_update(q.r[m], q.t[m], q.a[m], mom);
-  nyq_re = gl_update(q.rny, q.tny, q.any, mom).x;
+  x256 = gl_update(q.rmid, q.tmid, q.amid, mom);
 }
 
 template <int IN_MODE>
-__device__ __forceinline__ void load_spectrum(const InvParams& p, long long f, int lane, float2 (&v)[8], float& nyq_re) {
+__device__ __forceinline__ void load_spectrum(const InvParams& p, long long f, int lane, float2 (&v)[8], float2& x256) {
   RawFrame<IN_MODE> q;
   load_raw(p, f, lane, q);
-  raw_to_spectrum(q, v, nyq_re);
+  raw_to_spectrum(q, v, x256);
 }
 
 // the synthesis window with the transform's 1/N folded in (a power of two: the products round the same)
@@ -917,16 +919,17 @@ __device__ __forceinline__ float2 scaled_window(const float* window, int i) {
   return make_float2(w.x * (1.0f / 1024.0f), w.y * (1.0f / 1024.0f));
 }
 
-// one frame: spectrum -> time samples z[m] = (x[2n], x[2n+1]), n = lane + 64 m, BEFORE the synthesis window.  The
+// one frame: spectrum in the paired layout (v, x256: raw_to_spectrum) -> time samples z[m] = (x[2n], x[2n+1]),
+// n = lane + 64 m, BEFORE the synthesis window.  The
 // overlap-add kernels take the window inside their accumulation, acc = fma(z, w, acc), spelled out: left to the
 // compiler's contraction the same sum came out as fma in one kernel and as round(z w) + acc in another (whose pieces
 // travel through LDS), and a clip's bits must not depend on which kernel its batch size selects.
 template <typename TW>
-__device__ __forceinline__ void synth_frame_nowin(const float2 (&v)[8], float nyq_re, const TW& tw, float2* lds, int lane,
+__device__ __forceinline__ void synth_frame_nowin(const float2 (&v)[8], float2 x256, const TW& tw, float2* lds, int lane,
                                                   v2f (&z)[8]) {
 #pragma unroll
   for (int m = 0; m < 8; ++m) z[m] = to_v(v[m]);
-  irfft_split(z, tw, lane, nyq_re);
+  irfft_split(z, tw, lane, to_v(x256));
   fft512<true>(z, tw, lds, lane);
 }
 __device__ __forceinline__ v2f ola_window(const float2* win, int lane, int m) {
@@ -935,12 +938,12 @@ __device__ __forceinline__ v2f ola_window(const float2* win, int lane, int m) {
 
 // one frame: spectrum -> windowed time samples y[m] = (x[2n], x[2n+1]) * w, n = lane + 64 m
 template <typename TW>
-__device__ __forceinline__ void synth_frame(float2 (&v)[8], float nyq_re, const TW& tw, const float2* win,
+__device__ __forceinline__ void synth_frame(float2 (&v)[8], float2 x256, const TW& tw, const float2* win,
                                             float2* lds, int lane) {
   v2f z[8];
 #pragma unroll
   for (int m = 0; m < 8; ++m) z[m] = to_v(v[m]);
-  irfft_split(z, tw, lane, nyq_re);
+  irfft_split(z, tw, lane, to_v(x256));
   fft512<true>(z, tw, lds, lane);
 #pragma unroll
   for (int m = 0; m < 8; ++m) {
@@ -989,9 +992,9 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, IN_MODE == IN_GL ? 2 : (TWLDS
   Twiddles tw_regs;
   if (!TWLDS) load_twiddles<true>(tw_regs, p.tw, lane);
   const LdsTwiddles<true> tw_lds = {twtab, lane};
-  auto synth = [&](const float2 (&v)[8], float nyq, v2f (&z)[8]) {
-    if (TWLDS) synth_frame_nowin(v, nyq, tw_lds, lds, lane, z);
-    else synth_frame_nowin(v, nyq, tw_regs, lds, lane, z);
+  auto synth = [&](const float2 (&v)[8], float2 x256, v2f (&z)[8]) {
+    if (TWLDS) synth_frame_nowin(v, x256, tw_lds, lds, lane, z);
+    else synth_frame_nowin(v, x256, tw_regs, lds, lane, z);
   };
 
   v2f acc[8];
@@ -1011,11 +1014,11 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, IN_MODE == IN_GL ? 2 : (TWLDS
   // accumulators start aligned with frame t: acc[m] covers padded samples t*H + 2*(lane+64m)
   auto consume = [&](const RawFrame<IN_MODE>& q) {
     float2 v[8];
-    float nyq;
-    if constexpr (IN_MODE == IN_GL) raw_to_spectrum(q, v, nyq, p.gl_mom);
-    else raw_to_spectrum(q, v, nyq);
+    float2 x256;
+    if constexpr (IN_MODE == IN_GL) raw_to_spectrum(q, v, x256, p.gl_mom);
+    else raw_to_spectrum(q, v, x256);
     v2f z[8];
-    synth(v, nyq, z);
+    synth(v, x256, z);
 #pragma unroll
     for (int m = 0; m < 8; ++m) acc[m] = __builtin_elementwise_fma(z[m], ola_window(win, lane, m), acc[m]);
   };
@@ -1197,9 +1200,9 @@ __global__ __launch_bounds__(64 * NW, OCC) void istft1024_tile_kernel(InvParams 
   // z: the frame's samples before the window (what is parked); the window enters in the accumulation, one fma per sample
   auto consume = [&](const RawFrame<IN_MODE>& q, v2f (&z)[8]) {
     float2 v[8];
-    float nyq;
-    raw_to_spectrum(q, v, nyq);
-    synth_frame_nowin(v, nyq, tw, lds, lane, z);
+    float2 x256;
+    raw_to_spectrum(q, v, x256);
+    synth_frame_nowin(v, x256, tw, lds, lane, z);
 #pragma unroll
     for (int m = 0; m < 8; ++m) acc[m] = __builtin_elementwise_fma(z[m], ola_window(win, lane, m), acc[m]);
   };
@@ -1329,9 +1332,9 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void irfft1024_frames_kernel(
   if (f_end > p.total_frames) f_end = p.total_frames;
   for (long long f = f_begin + wave; f < f_end; f += WAVES_PER_BLOCK) {
     float2 v[8];
-    float nyq;
-    load_spectrum<IN_MODE>(p, f, lane, v, nyq);
-    synth_frame(v, nyq, tw, win, lds, lane);
+    float2 x256;
+    load_spectrum<IN_MODE>(p, f, lane, v, x256);
+    synth_frame(v, x256, tw, win, lds, lane);
     float2* dst = reinterpret_cast<float2*>(p.y + f * N);
 #pragma unroll
     for (int m = 0; m < 8; ++m) dst[lane + 64 * m] = v[m];
