@@ -16,6 +16,9 @@ On the streaming path the carried state (OverlapAdd's history and tail, the phas
 constant of the graph, stored detached: the gradient of a chunk covers that chunk's own samples (truncated
 back-propagation at chunk boundaries).
 
+SpectralDistanceFunction is the one Function of two inputs: the multi-scale spectral distance of losses.py, whose
+backward (spectral_distance.hip through ops.spectral_distance_backward) rebuilds both spectra from the saved audio.
+
 All backward passes are first-order only (@once_differentiable): create_graph=True raises.
 """
 import torch
@@ -27,7 +30,8 @@ __all__ = ["wants_grad", "StftFunction", "IstftFunction", "IstftPolarFunction", 
            "StftMagnitudeFunction", "MfccFunction", "mfcc_chunk_clips", "MagnitudeInvertFunction", "PolarInvertFunction",
            "CartesianInvertFunction", "PolarToComplexFunction", "AffineInvertFunction", "AffineForwardFunction",
            "PhaseScanFunction", "CartesianFunction", "PolarFunction", "PolarIFFunction", "StftPolarFunction",
-           "RtStftFunction", "RtIstftFunction", "RtIstftPolarFunction", "OaddFramesFunction", "OaddInvertFunction"]
+           "RtStftFunction", "RtIstftFunction", "RtIstftPolarFunction", "OaddFramesFunction", "OaddInvertFunction",
+           "SpectralDistanceFunction", "specdist_chunk_clips"]
 
 
 def wants_grad(x: torch.Tensor) -> bool:
@@ -228,6 +232,91 @@ class MfccFunction(torch.autograd.Function):
             del X
         dx = dx if x.shape == dx.shape else dx.view(x.shape)
         return dx.to(x.dtype), None
+
+
+# ---- the multi-scale spectral distance (losses.SpectralDistance) -----------------------------------------------------------
+
+SPECDIST_CHUNK_ELEMS = 1 << 26      # complex64 elements of ONE spectrum per chunk: 512 MiB, so x's and y's peak at 1 GiB
+
+
+def specdist_chunk_clips(B, T, n_fft):
+    """Clips per chunk of the spectral distance, forward and backward: the most whose one spectrum (T frames of
+    n_fft // 2 + 1 bins per clip) stays within SPECDIST_CHUNK_ELEMS, at least 1."""
+    per_clip = T * (n_fft // 2 + 1)
+    return min(max(SPECDIST_CHUNK_ELEMS // per_clip, 1), B)
+
+
+def _specdist_chunks(B, L, n_fft, hop):
+    """(b0, b1) of every chunk of B clips of L samples at one scale."""
+    chunk = max(specdist_chunk_clips(B, 1 + (L - (n_fft & 1)) // hop, n_fft), 1)
+    return [(b0, min(b0 + chunk, B)) for b0 in range(0, B, chunk)]
+
+
+def specdist_sums(x, y, windows, scales, eps):
+    """x, y (B, L) float32 -> (B, n_scales, 3) float64, the sums S_D, S_B, S_L of every clip at every scale
+    (ops.spectral_distance_sums on the two spectra of a chunk of clips, which is freed before the next)."""
+    B, L = x.shape
+    per_scale = []
+    for (n, hop), w in zip(scales, windows):
+        out = torch.empty((B, 3), dtype=torch.float64, device=x.device)
+        for b0, b1 in _specdist_chunks(B, L, n, hop):
+            X = ops.stft_forward(x[b0:b1], w, n, hop, center=True)
+            Y = ops.stft_forward(y[b0:b1], w, n, hop, center=True)
+            ops.spectral_distance_sums(X, Y, eps, out=out[b0:b1])
+            del X, Y
+        per_scale.append(out)
+    return torch.stack(per_scale, 1)
+
+
+def specdist_loss(sums, L, scales, lin_weight, log_weight):
+    """The per-clip loss (B,) float32 of the sums: sum over scales of lin_weight S_D / S_B + log_weight S_L / n."""
+    loss = (sums[:, :, 0] / sums[:, :, 1]).sum(1) * lin_weight
+    for s, (n, hop) in enumerate(scales):
+        bins = (1 + (L - (n & 1)) // hop) * (n // 2 + 1)
+        loss = loss + sums[:, s, 2] * (log_weight / bins)
+    return loss.float()
+
+
+class SpectralDistanceFunction(torch.autograd.Function):
+    """The per-clip multi-scale spectral distance of x (generated) and y (target), both (B, L) float32, with its backward.
+    Saves the two audios and the (B, n_scales, 3) sums, and nothing else: the backward rebuilds both spectra per scale
+    and chunk of clips (specdist_chunk_clips), turns them into their own gradients in place
+    (ops.spectral_distance_backward) and runs the STFT adjoint -- into the result for the first scale, into a (chunk, L)
+    scratch that is added to it for every later one.  Only the inputs that require a gradient get one; the windows
+    are constants of the graph."""
+
+    @staticmethod
+    def forward(ctx, x, y, windows, scales, lin_weight, log_weight, eps):
+        sums = specdist_sums(x, y, windows, scales, eps)
+        ctx.windows, ctx.scales, ctx.weights, ctx.eps = windows, scales, (lin_weight, log_weight), eps
+        ctx.save_for_backward(x, y, sums)
+        return specdist_loss(sums, x.shape[-1], scales, lin_weight, log_weight)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gclip):
+        x, y, sums = ctx.saved_tensors
+        need = ctx.needs_input_grad[:2]
+        B, L = x.shape
+        g = ops._f32c(gclip)
+        grads = [torch.empty((B, L), dtype=torch.float32, device=x.device) if nd else None for nd in need]
+        rows = max([b1 - b0 for n, hop in ctx.scales[1:] for b0, b1 in _specdist_chunks(B, L, n, hop)[:1]], default=0)
+        scratch = torch.empty((rows, L), dtype=torch.float32, device=x.device)
+        for s, ((n, hop), w) in enumerate(zip(ctx.scales, ctx.windows)):
+            sums_s = sums[:, s].contiguous()
+            for b0, b1 in _specdist_chunks(B, L, n, hop):
+                X = ops.stft_forward(x[b0:b1], w, n, hop, center=True)
+                Y = ops.stft_forward(y[b0:b1], w, n, hop, center=True)
+                ops.spectral_distance_backward(X, Y, sums_s[b0:b1], g[b0:b1], *ctx.weights, ctx.eps, *need)
+                for G, grad in zip((X, Y), grads):
+                    if grad is None:
+                        continue
+                    out = grad[b0:b1] if s == 0 else scratch[:b1 - b0]      # stft_backward overwrites its out
+                    ops.stft_backward(G, w, n, hop, L, out=out)
+                    if s:
+                        grad[b0:b1].add_(out)
+                del X, Y
+        return grads[0], grads[1], None, None, None, None, None
 
 
 # ---- the invert side: Magnitude, Polar, Cartesian, polar_to_complex, Normalize -----------------------------------------

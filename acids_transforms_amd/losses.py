@@ -1,0 +1,83 @@
+"""Losses on MI355X: SpectralDistance, the multi-scale STFT distance a generative-audio model is trained with.
+
+The transforms of this package make a model differentiable THROUGH a spectrum; this is the distance it is trained
+WITH.  Composed from STFT + Magnitude + torch expressions, every scale keeps its spectrum for the backward; here the
+graph keeps the two audio tensors and three sums per clip and scale, and the backward rebuilds the spectra a chunk of
+clips at a time (autograd.SpectralDistanceFunction, csrc/spectral_distance.hip).
+"""
+import torch
+from torch import nn
+
+from . import ops
+from ._lib import device_scoped, require_device
+from .autograd import SpectralDistanceFunction, specdist_loss, specdist_sums
+from .transforms.stft import MAX_NFFT
+
+__all__ = ["SpectralDistance"]
+
+DEFAULT_SCALES = ((2048, 512), (1024, 256), (512, 128), (256, 64), (128, 32))
+
+
+class SpectralDistance(nn.Module):
+    """loss = crit(x, y): x the generated audio, y the target, one shape (..., L), float32, on the GPU.
+
+    A scale is (n_fft, hop), any pair STFT accepts, with STFT's conventions (periodic window, center=True, reflect
+    padding, T = 1 + L // hop).  For clip b and scale s, A = |STFT_s(x_b)| and Bm = |STFT_s(y_b)| of n = T_s F_s bins:
+
+        S_D = sum (A - Bm)^2        S_B = sum Bm^2        S_L = sum |log(A + eps) - log(Bm + eps)|
+        loss_b = sum_s [ lin_weight * S_D / S_B  +  log_weight * S_L / n ]
+
+    reduction: "none" (shape x.shape[:-1]), "sum" or "mean" over the clips.  A silent target clip (S_B == 0) gives the
+    IEEE result (inf or nan) in that clip only; a clip's value and gradient never depend on the rest of the batch.
+
+    Gradients: for whichever of x and y requires one when grad mode is on (first order only); every other call runs
+    the same kernels without a graph, to the same bits."""
+
+    def __init__(self, scales=DEFAULT_SCALES, window: str = "hann", lin_weight: float = 1.0, log_weight: float = 1.0,
+                 eps: float = torch.finfo(torch.float32).eps, reduction: str = "mean"):
+        super().__init__()
+        if not hasattr(torch, "%s_window" % window):
+            raise ValueError("Window %s is not known" % window)
+        if reduction not in ("none", "sum", "mean"):
+            raise ValueError("reduction %s not known (none, sum, mean)" % reduction)
+        self.scales = tuple((int(n), int(h)) for n, h in scales)
+        if not self.scales:
+            raise ValueError("at least one (n_fft, hop) scale is needed")
+        for n, h in self.scales:
+            if not (1 < n <= MAX_NFFT and h > 0):
+                raise ValueError("scale (%d, %d): n_fft must lie in 2 .. %d and hop be positive" % (n, h, MAX_NFFT))
+        if eps < 0:
+            raise ValueError("eps must not be negative")
+        self.lin_weight, self.log_weight, self.eps, self.reduction = float(lin_weight), float(log_weight), float(eps), reduction
+        for i, (n, _) in enumerate(self.scales):
+            self.register_buffer("window_%d" % i, getattr(torch, "%s_window" % window)(n))
+
+    def __repr__(self):
+        return "SpectralDistance(scales=%s, lin_weight=%g, log_weight=%g, reduction=%s)" % (
+            self.scales, self.lin_weight, self.log_weight, self.reduction)
+
+    def _windows(self):
+        return tuple(getattr(self, "window_%d" % i) for i in range(len(self.scales)))
+
+    def forward(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        if x.shape != y.shape:
+            raise ValueError("x and y must have one shape, got %s and %s" % (tuple(x.shape), tuple(y.shape)))
+        longest = max(n for n, _ in self.scales)
+        if x.dim() < 1 or x.shape[-1] <= longest // 2:
+            raise ValueError("clips of %d samples are too short for n_fft %d (reflect padding needs more than n_fft // 2)"
+                             % (x.shape[-1] if x.dim() else 0, longest))
+        device_scoped(require_device)(x, y)      # no CPU route, and one device for both
+        if self.window_0.device != x.device:
+            self.to(x.device)
+        L = x.shape[-1]
+        # torch's own reshape / float / contiguous: they carry the gradient back to the caller's tensors
+        xb, yb = (ops._no_fp64(t).reshape(-1, L).float().contiguous() for t in (x, y))
+        args = (self._windows(), self.scales, self.lin_weight, self.log_weight, self.eps)
+        if torch.is_grad_enabled() and (x.requires_grad or y.requires_grad):
+            per_clip = SpectralDistanceFunction.apply(xb, yb, *args)
+        else:
+            per_clip = specdist_loss(specdist_sums(xb, yb, args[0], args[1], self.eps), L, *args[1:4])
+        per_clip = per_clip.reshape(x.shape[:-1])
+        if self.reduction == "none":
+            return per_clip
+        return per_clip.sum() if self.reduction == "sum" else per_clip.mean()

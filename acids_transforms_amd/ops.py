@@ -769,6 +769,50 @@ def mfcc_backward(X, dF, bank_t_cols, power=2, bank_cols=None, dct_t=None, scale
     return dX
 
 
+def _sd_spectra(X, Y):
+    """The two spectra of a spectral distance as the kernels read them: contiguous complex64 of one shape (B, ...)."""
+    X, Y = _c64(X), _c64(Y)
+    assert X.shape == Y.shape and X.ndim >= 2, "X and Y must be spectra of one shape (B, ...)"
+    assert X.is_contiguous() and Y.is_contiguous(), "X and Y must be contiguous"
+    n = 1
+    for d in X.shape[1:]:
+        n *= d
+    return X, Y, X.shape[0], n
+
+
+def spectral_distance_sums(X, Y, eps=1.1920929e-07, out=None):
+    """Per-clip sums of the spectral distance between X (generated) and Y (target), both (B, T, F) or (B, n) complex64:
+    (B, 3) float64 holding S_D = sum (|X| - |Y|)^2, S_B = sum |Y|^2 and S_L = sum |ln(|X| + eps) - ln(|Y| + eps)|
+    (written into `out`, a contiguous (B, 3) float64 tensor, when given).  A clip's bits depend on its own bins only."""
+    require_device(X, Y, out)
+    X, Y, B, n = _sd_spectra(X, Y)
+    if out is not None:
+        assert out.shape == (B, 3) and out.dtype == torch.float64 and out.is_contiguous()
+    sums = out if out is not None else torch.empty((B, 3), dtype=torch.float64, device=X.device)
+    wsb = lib().at_spectral_distance_workspace_bytes(B, n)
+    ws = _workspace(wsb, X.device)
+    check(lib().at_spectral_distance_sums(ptr(X), ptr(Y), B, n, eps, ptr(sums), ptr(ws), wsb, stream_ptr()),
+          "at_spectral_distance_sums")
+    return sums
+
+
+def spectral_distance_backward(X, Y, sums, gclip, lin_weight=1.0, log_weight=1.0, eps=1.1920929e-07, need_x=True,
+                               need_y=False):
+    """Backward of lin_weight S_D / S_B + log_weight S_L / n, IN PLACE: X becomes the gradient of its spectrum (need_x)
+    and Y of its own (need_y), in the convention stft_backward takes; a spectrum that is not needed is left as it is.
+    sums (B, 3) float64: what spectral_distance_sums gave for these spectra; gclip (B,) float32: the gradient of the
+    per-clip loss.  Returns (X, Y)."""
+    require_device(X, Y, sums, gclip)
+    assert X.dtype == torch.complex64 and Y.dtype == torch.complex64, "in place: the spectra must be complex64"
+    X, Y, B, n = _sd_spectra(X, Y)
+    gclip = _f32c(gclip)
+    assert sums.shape == (B, 3) and sums.dtype == torch.float64 and sums.is_contiguous() and gclip.shape == (B,)
+    check(lib().at_spectral_distance_backward(ptr(X), ptr(Y), B, n, ptr(sums), ptr(gclip), lin_weight, log_weight, eps,
+                                              int(bool(need_x)), int(bool(need_y)), stream_ptr()),
+          "at_spectral_distance_backward")
+    return X, Y
+
+
 def _c64_grad(g):
     """A complex gradient as the kernels read it: complex64, contiguous, 8-byte aligned (a slice of a cat's gradient
     always is: complex64 elements)."""

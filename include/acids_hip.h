@@ -621,6 +621,33 @@ int at_oadd_forward_backward(const float *gframes, int64_t S, int64_t n, int n_f
 int at_oadd_invert_backward(const float *gy, int64_t S, int64_t n, int n_fft, int hop, int keep, const float *gain,
                             float *gframes, void *stream);
 
+/* ---- spectral distance (spectral_distance.hip; losses.SpectralDistance, autograd.SpectralDistanceFunction) ------------ */
+/* Per-clip sums of the distance between two spectra X (generated) and Y (target), both (B, n) complex64 with n = T F
+ * bins per clip, A = |X|, Bm = |Y|:
+ *   sums[b] = { S_D = sum (A - Bm)^2,  S_B = sum Bm^2,  S_L = sum |ln(A + eps) - ln(Bm + eps)| }      (B, 3) float64
+ * from which the caller forms loss_b = lin_weight S_D / S_B + log_weight S_L / n.  16 bytes read per bin, nothing of
+ * size written.  A clip is cut into slices of 4096 bins; one workgroup reduces one slice (fp32 per lane in bin order, a
+ * fixed tree over the lanes) into the workspace, a second kernel adds a clip's slices in order in double: the order of
+ * a clip's sums is a function of n alone, never of B, of the clip's place in the batch, or of the grid; no atomics.
+ * One 8-byte bin per lane (odd clips of an odd n are only 8-byte aligned).  workspace: 4-byte aligned,
+ * at_spectral_distance_workspace_bytes(B, n) bytes (AT_EWORKSPACE otherwise).  AT_EINVAL on null X, Y or sums, B < 0,
+ * n < 1 or eps < 0, before any launch; AT_OK without a launch when B == 0. */
+size_t at_spectral_distance_workspace_bytes(int64_t B, int64_t n);
+int at_spectral_distance_sums(const float *X_complex, const float *Y_complex, int64_t B, int64_t n, float eps,
+                              double *sums, void *workspace, size_t workspace_bytes, void *stream);
+
+/* Backward of the above, in place: given the sums the forward wrote and gclip (B,) float32, the gradient g of loss_b,
+ * X becomes G_X (need_x) and Y becomes G_Y (need_y), with d = A - Bm:
+ *   dA  = g (lin_weight 2 d / S_B + log_weight sgn(d) / (n (A + eps)))
+ *   dBm = g (lin_weight (-2 d / S_B - 2 Bm S_D / S_B^2) - log_weight sgn(d) / (n (Bm + eps)))
+ *   G_X = dA X / A (0 where A == 0),   G_Y = dBm Y / Bm (0 where Bm == 0)
+ * in the convention at_stft_backward takes (dRe + i dIm).  sgn(d) is the sign of the log difference (ln is monotone):
+ * no logarithm.  Pointwise, one bin per lane; a spectrum whose need_* is 0 is read and not written.  AT_EINVAL on null
+ * X, Y, sums or gclip, B < 0, n < 1, eps < 0 or both need_* zero; AT_OK without a launch when B == 0. */
+int at_spectral_distance_backward(float *X_complex, float *Y_complex, int64_t B, int64_t n, const double *sums,
+                                  const float *gclip, float lin_weight, float log_weight, float eps, int need_x,
+                                  int need_y, void *stream);
+
 /* ---- audio front end ------------------------------------------------------------------------------------- */
 /* torchaudio.transforms.Resample(orig, new) with default arguments, as utils/misc.py:31-33 uses it (algorithm
  * restated, torchaudio is not in the reference tree).  x: (rows, L); orig/new: the rates divided by their gcd;
