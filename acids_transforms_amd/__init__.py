@@ -13,6 +13,6 @@ from .utils import heapq  # noqa: F401,E402
 from .transforms import (base, raw, stft, dgt, norm, spectral_repr, mel, misc, oadd, phase_repr, channels,  # noqa: F401,E402
                          sinebank)
 from . import losses  # noqa: F401,E402  (not in the reference: the spectral distance a model is trained with)
-from .losses import SpectralDistance  # noqa: F401,E402
+from .losses import MelSpectralDistance, SpectralDistance  # noqa: F401,E402
 
 __version__ = "0.1.0"

@@ -18,6 +18,8 @@ back-propagation at chunk boundaries).
 
 SpectralDistanceFunction is the one Function of two inputs: the multi-scale spectral distance of losses.py, whose
 backward (spectral_distance.hip through ops.spectral_distance_backward) rebuilds both spectra from the saved audio.
+MelSpectralDistanceFunction is its mel-scale sibling (mel_distance.hip through ops.mel_rows / ops.mel_distance_sums /
+ops.mel_distance_backward): to differentiate one signal it rebuilds that signal's spectrum and the other's mel rows.
 
 All backward passes are first-order only (@once_differentiable): create_graph=True raises.
 """
@@ -31,7 +33,8 @@ __all__ = ["wants_grad", "StftFunction", "IstftFunction", "IstftPolarFunction", 
            "CartesianInvertFunction", "PolarToComplexFunction", "AffineInvertFunction", "AffineForwardFunction",
            "PhaseScanFunction", "CartesianFunction", "PolarFunction", "PolarIFFunction", "StftPolarFunction",
            "RtStftFunction", "RtIstftFunction", "RtIstftPolarFunction", "OaddFramesFunction", "OaddInvertFunction",
-           "SpectralDistanceFunction", "specdist_chunk_clips"]
+           "SpectralDistanceFunction", "specdist_chunk_clips", "MelSpectralDistanceFunction", "meldist_sums",
+           "meldist_loss"]
 
 
 def wants_grad(x: torch.Tensor) -> bool:
@@ -317,6 +320,93 @@ class SpectralDistanceFunction(torch.autograd.Function):
                         grad[b0:b1].add_(out)
                 del X, Y
         return grads[0], grads[1], None, None, None, None, None
+
+
+# ---- the multi-scale mel distance (losses.MelSpectralDistance) ---------------------------------------------------------------
+# Chunks are _specdist_chunks: only ONE spectrum of a chunk is alive at a time here, so the peak is 512 MiB.
+
+def _meldist_tables(module, device):
+    """Per scale, (bank by column, transposed bank by column) of a MelSpectralDistance's mel_bank_i on `device`: built
+    on first use, cached per bank version."""
+    return tuple((_bank_cols(module, "mel_bank_%d" % i, device), _bank_cols(module, "mel_bank_%d" % i, device, transposed=True))
+                 for i in range(len(module.scales)))
+
+
+def _mel_of(x, w, n, hop, cols):
+    """The mel rows (chunk, T, N) of a chunk of clips; the spectrum is freed before the return."""
+    X = ops.stft_forward(x, w, n, hop, center=True)
+    M = ops.mel_rows(X, cols)
+    del X
+    return M
+
+
+def meldist_sums(x, y, windows, scales, tables, eps):
+    """x, y (B, L) float32 -> (B, n_scales, 3) float64, the sums S_D, S_B, S_L of every clip at every scale
+    (ops.mel_distance_sums on the two arrays of mel rows of a chunk of clips).  One spectrum is alive at a time."""
+    B, L = x.shape
+    per_scale = []
+    for (n, hop, _), w, (cols, _t) in zip(scales, windows, tables):
+        out = torch.empty((B, 3), dtype=torch.float64, device=x.device)
+        for b0, b1 in _specdist_chunks(B, L, n, hop):
+            M = _mel_of(x[b0:b1], w, n, hop, cols)
+            Q = _mel_of(y[b0:b1], w, n, hop, cols)
+            ops.mel_distance_sums(M, Q, eps, out=out[b0:b1])
+            del M, Q
+        per_scale.append(out)
+    return torch.stack(per_scale, 1)
+
+
+def meldist_loss(sums, L, scales, lin_weight, log_weight):
+    """The per-clip loss (B,) float32 of the sums: sum over scales of lin_weight S_D / S_B + log_weight S_L / n,
+    n = T n_mels cells."""
+    loss = (sums[:, :, 0] / sums[:, :, 1]).sum(1) * lin_weight
+    for s, (n, hop, n_mels) in enumerate(scales):
+        cells = (1 + (L - (n & 1)) // hop) * n_mels
+        loss = loss + sums[:, s, 2] * (log_weight / cells)
+    return loss.float()
+
+
+class MelSpectralDistanceFunction(torch.autograd.Function):
+    """The per-clip multi-scale mel distance of x (generated) and y (target), both (B, L) float32, with its backward.
+    Saves the two audios and the (B, n_scales, 3) sums, and nothing else.  Per scale, chunk of clips and input that
+    needs a gradient, the backward rebuilds the OTHER signal's mel rows (spectrum, ops.mel_rows, spectrum freed), then
+    this signal's spectrum, turns it into its own gradient in place (ops.mel_distance_backward) and runs the STFT
+    adjoint -- into the result for the first scale, into a (chunk, L) scratch that is added to it for every later one.
+    The x-only backward never holds two spectra and never runs a backward kernel over Y.  The windows and the banks
+    are constants of the graph."""
+
+    @staticmethod
+    def forward(ctx, x, y, windows, scales, tables, lin_weight, log_weight, eps):
+        sums = meldist_sums(x, y, windows, scales, tables, eps)
+        ctx.windows, ctx.scales, ctx.tables, ctx.weights, ctx.eps = windows, scales, tables, (lin_weight, log_weight), eps
+        ctx.save_for_backward(x, y, sums)
+        return meldist_loss(sums, x.shape[-1], scales, lin_weight, log_weight)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gclip):
+        x, y, sums = ctx.saved_tensors
+        need = ctx.needs_input_grad[:2]
+        B, L = x.shape
+        g = ops._f32c(gclip)
+        grads = [torch.empty((B, L), dtype=torch.float32, device=x.device) if nd else None for nd in need]
+        rows = max([b1 - b0 for n, hop, _ in ctx.scales[1:] for b0, b1 in _specdist_chunks(B, L, n, hop)[:1]], default=0)
+        scratch = torch.empty((rows, L), dtype=torch.float32, device=x.device)
+        for s, ((n, hop, _), w, (cols, cols_t)) in enumerate(zip(ctx.scales, ctx.windows, ctx.tables)):
+            sums_s = sums[:, s].contiguous()
+            for b0, b1 in _specdist_chunks(B, L, n, hop):
+                for side, (own, other, grad) in enumerate(((x, y, grads[0]), (y, x, grads[1]))):
+                    if grad is None:
+                        continue
+                    O = _mel_of(other[b0:b1], w, n, hop, cols)
+                    S = ops.stft_forward(own[b0:b1], w, n, hop, center=True)
+                    ops.mel_distance_backward(S, O, sums_s[b0:b1], g[b0:b1], cols, cols_t, *ctx.weights, ctx.eps, side)
+                    out = grad[b0:b1] if s == 0 else scratch[:b1 - b0]      # stft_backward overwrites its out
+                    ops.stft_backward(S, w, n, hop, L, out=out)
+                    if s:
+                        grad[b0:b1].add_(out)
+                    del S, O
+        return grads[0], grads[1], None, None, None, None, None, None
 
 
 # ---- the invert side: Magnitude, Polar, Cartesian, polar_to_complex, Normalize -----------------------------------------

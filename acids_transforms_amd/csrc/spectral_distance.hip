@@ -25,6 +25,7 @@
 #include <stdint.h>
 
 #include "../../include/acids_hip.h"
+#include "sd_fold.h"   // sd_block_fold, sd_clip_sums_kernel: shared with mel_distance.hip
 
 namespace at_hip {
 
@@ -33,28 +34,6 @@ constexpr int kSdPerLane = 16;
 constexpr int kSdSlice = kSdThreads * kSdPerLane;   // bins per slice (spectral_distance_cases.py restates it)
 
 __device__ __forceinline__ float sd_abs(float2 v) { return sqrtf(fmaf(v.x, v.x, v.y * v.y)); }
-
-// three sums over the workgroup: xor tree inside a wave, then the waves in order; valid in thread 0
-__device__ __forceinline__ void sd_block_fold(float& a, float& b, float& c) {
-  __shared__ float part[kSdThreads / 64][3];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    a += __shfl_xor(a, o, 64);
-    b += __shfl_xor(b, o, 64);
-    c += __shfl_xor(c, o, 64);
-  }
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) {
-    part[w][0] = a; part[w][1] = b; part[w][2] = c;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int i = 1; i < kSdThreads / 64; ++i) {
-      a += part[i][0]; b += part[i][1]; c += part[i][2];
-    }
-  }
-}
 
 // workgroup blk reduces slice blk % slices of clip blk / slices into partial[blk][3]
 __global__ __launch_bounds__(kSdThreads) void sd_slice_sums_kernel(const float2* __restrict__ X,
@@ -85,24 +64,11 @@ __global__ __launch_bounds__(kSdThreads) void sd_slice_sums_kernel(const float2*
       sl += fabsf(logf(a + eps) - logf(bm + eps));
     }
   }
-  sd_block_fold(sd, sb, sl);
+  sd_block_fold<kSdThreads>(sd, sb, sl);
   if (threadIdx.x == 0) {
     float* dst = partial + 3 * blk;
     dst[0] = sd; dst[1] = sb; dst[2] = sl;
   }
-}
-
-// thread (b, k): sums[b][k] = the clip's partials k in slice order, in double
-__global__ __launch_bounds__(kSdThreads) void sd_clip_sums_kernel(const float* __restrict__ partial, long long B,
-                                                                   long long slices, double* __restrict__ sums) {
-  const long long i = (long long)blockIdx.x * kSdThreads + threadIdx.x;
-  if (i >= 3 * B) return;
-  const long long b = i / 3;
-  const int k = (int)(i - 3 * b);
-  const float* src = partial + 3 * b * slices + k;
-  double s = 0.0;
-  for (long long q = 0; q < slices; ++q) s += (double)src[3 * q];
-  sums[i] = s;
 }
 
 // workgroup blk turns slice blk % slices of clip blk / slices of X (NEED_X) and of Y (NEED_Y) into its gradient
@@ -178,7 +144,7 @@ int at_spectral_distance_sums(const float* X_complex, const float* Y_complex, in
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(sd_slice_sums_kernel, dim3((unsigned)blocks), dim3(kSdThreads), 0, s, (const float2*)X_complex,
                      (const float2*)Y_complex, (long long)n, slices, eps, (float*)workspace);
-  hipLaunchKernelGGL(sd_clip_sums_kernel, dim3((unsigned)((3 * B + kSdThreads - 1) / kSdThreads)), dim3(kSdThreads), 0, s,
+  hipLaunchKernelGGL(sd_clip_sums_kernel<kSdThreads>, dim3((unsigned)((3 * B + kSdThreads - 1) / kSdThreads)), dim3(kSdThreads), 0, s,
                      (const float*)workspace, (long long)B, slices, sums);
   return hipGetLastError() == hipSuccess ? AT_OK : AT_ELAUNCH;
 }

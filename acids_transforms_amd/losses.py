@@ -1,4 +1,5 @@
-"""Losses on MI355X: SpectralDistance, the multi-scale STFT distance a generative-audio model is trained with.
+"""Losses on MI355X: SpectralDistance, the multi-scale STFT distance a generative-audio model is trained with, and
+MelSpectralDistance, the same distance between mel-band magnitudes (csrc/mel_distance.hip).
 
 The transforms of this package make a model differentiable THROUGH a spectrum; this is the distance it is trained
 WITH.  Composed from STFT + Magnitude + torch expressions, every scale keeps its spectrum for the backward; here the
@@ -10,12 +11,15 @@ from torch import nn
 
 from . import ops
 from ._lib import device_scoped, require_device
-from .autograd import SpectralDistanceFunction, specdist_loss, specdist_sums
+from .autograd import (MelSpectralDistanceFunction, SpectralDistanceFunction, _meldist_tables, meldist_loss, meldist_sums,
+                       specdist_loss, specdist_sums)
 from .transforms.stft import MAX_NFFT
+from .utils.melbank import melscale_fbanks
 
-__all__ = ["SpectralDistance"]
+__all__ = ["SpectralDistance", "MelSpectralDistance"]
 
 DEFAULT_SCALES = ((2048, 512), (1024, 256), (512, 128), (256, 64), (128, 32))
+DEFAULT_MEL_SCALES = ((2048, 512, 320), (1024, 256, 160), (512, 128, 80), (256, 64, 40), (128, 32, 20))
 
 
 class SpectralDistance(nn.Module):
@@ -77,6 +81,79 @@ class SpectralDistance(nn.Module):
             per_clip = SpectralDistanceFunction.apply(xb, yb, *args)
         else:
             per_clip = specdist_loss(specdist_sums(xb, yb, args[0], args[1], self.eps), L, *args[1:4])
+        per_clip = per_clip.reshape(x.shape[:-1])
+        if self.reduction == "none":
+            return per_clip
+        return per_clip.sum() if self.reduction == "sum" else per_clip.mean()
+
+
+class MelSpectralDistance(nn.Module):
+    """loss = crit(x, y): x the generated audio, y the target, one shape (..., L), float32, on the GPU.
+
+    A scale is (n_fft, hop, n_mels), with STFT's conventions (periodic window, center=True, reflect padding,
+    T = 1 + L // hop) and the HTK bank W_s = melscale_fbanks(n_fft // 2 + 1, f_min, f_max, n_mels, sr), a constant
+    buffer.  For clip b and scale s, M = |STFT_s(x_b)| @ W_s and Q = |STFT_s(y_b)| @ W_s of n = T_s n_mels cells:
+
+        S_D = sum (M - Q)^2        S_B = sum Q^2        S_L = sum |log(M + eps) - log(Q + eps)|
+        loss_b = sum_s [ lin_weight * S_D / S_B  +  log_weight * S_L / n ]
+
+    An empty filter counts in n and adds 0 to the three sums.  reduction: "none" (shape x.shape[:-1]), "sum" or "mean"
+    over the clips.  A silent target clip (S_B == 0) gives the IEEE result (inf or nan) in that clip only; a clip's
+    value and gradient never depend on the rest of the batch.  f_max None: sr // 2.
+
+    Gradients: for whichever of x and y requires one when grad mode is on (first order only); every other call runs
+    the same kernels without a graph, to the same bits."""
+
+    def __init__(self, scales=DEFAULT_MEL_SCALES, sr: int = 44100, f_min: float = 0.0, f_max=None, window: str = "hann",
+                 lin_weight: float = 1.0, log_weight: float = 1.0, eps: float = torch.finfo(torch.float32).eps,
+                 reduction: str = "mean"):
+        super().__init__()
+        if not hasattr(torch, "%s_window" % window):
+            raise ValueError("Window %s is not known" % window)
+        if reduction not in ("none", "sum", "mean"):
+            raise ValueError("reduction %s not known (none, sum, mean)" % reduction)
+        self.scales = tuple((int(n), int(h), int(m)) for n, h, m in scales)
+        if not self.scales:
+            raise ValueError("at least one (n_fft, hop, n_mels) scale is needed")
+        for n, h, m in self.scales:
+            if not (1 < n <= MAX_NFFT and h > 0):
+                raise ValueError("scale (%d, %d, %d): n_fft must lie in 2 .. %d and hop be positive" % (n, h, m, MAX_NFFT))
+            if m < 1:
+                raise ValueError("scale (%d, %d, %d): n_mels must be at least 1" % (n, h, m))
+        if eps < 0:
+            raise ValueError("eps must not be negative")
+        self.sr, self.f_min = int(sr), float(f_min)
+        self.f_max = float(self.sr // 2 if f_max is None else f_max)
+        self.lin_weight, self.log_weight, self.eps, self.reduction = float(lin_weight), float(log_weight), float(eps), reduction
+        for i, (n, _, m) in enumerate(self.scales):
+            self.register_buffer("window_%d" % i, getattr(torch, "%s_window" % window)(n))
+            self.register_buffer("mel_bank_%d" % i, melscale_fbanks(n // 2 + 1, self.f_min, self.f_max, m, self.sr))
+
+    def __repr__(self):
+        return "MelSpectralDistance(scales=%s, sr=%d, lin_weight=%g, log_weight=%g, reduction=%s)" % (
+            self.scales, self.sr, self.lin_weight, self.log_weight, self.reduction)
+
+    def _windows(self):
+        return tuple(getattr(self, "window_%d" % i) for i in range(len(self.scales)))
+
+    def forward(self, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+        if x.shape != y.shape:
+            raise ValueError("x and y must have one shape, got %s and %s" % (tuple(x.shape), tuple(y.shape)))
+        longest = max(n for n, _, _ in self.scales)
+        if x.dim() < 1 or x.shape[-1] <= longest // 2:
+            raise ValueError("clips of %d samples are too short for n_fft %d (reflect padding needs more than n_fft // 2)"
+                             % (x.shape[-1] if x.dim() else 0, longest))
+        device_scoped(require_device)(x, y)      # no CPU route, and one device for both
+        if self.window_0.device != x.device:
+            self.to(x.device)
+        L = x.shape[-1]
+        # torch's own reshape / float / contiguous: they carry the gradient back to the caller's tensors
+        xb, yb = (ops._no_fp64(t).reshape(-1, L).float().contiguous() for t in (x, y))
+        args = (self._windows(), self.scales, _meldist_tables(self, x.device), self.lin_weight, self.log_weight, self.eps)
+        if torch.is_grad_enabled() and (x.requires_grad or y.requires_grad):
+            per_clip = MelSpectralDistanceFunction.apply(xb, yb, *args)
+        else:
+            per_clip = meldist_loss(meldist_sums(xb, yb, *args[:3], self.eps), L, self.scales, *args[3:5])
         per_clip = per_clip.reshape(x.shape[:-1])
         if self.reduction == "none":
             return per_clip

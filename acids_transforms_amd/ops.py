@@ -813,6 +813,62 @@ def spectral_distance_backward(X, Y, sums, gclip, lin_weight=1.0, log_weight=1.0
     return X, Y
 
 
+def mel_rows(X, bank_cols, out=None):
+    """Mel rows of a spectrum: X (..., K) complex64 -> |X| @ bank, (..., N) float32 (written into `out`, a contiguous
+    float32 tensor of that shape, when given).  bank_cols: utils.banded.bank_columns of the (K, N) bank, on X's device."""
+    require_device(X, out, *bank_cols)
+    X = _c64(X)
+    assert X.is_contiguous(), "X must be contiguous"
+    K, N = X.shape[-1], bank_cols[0].numel()
+    shape = tuple(X.shape[:-1]) + (N,)
+    if out is not None:
+        assert tuple(out.shape) == shape and out.dtype == torch.float32 and out.is_contiguous()
+    M = out if out is not None else torch.empty(shape, dtype=torch.float32, device=X.device)
+    check(lib().at_mel_rows(ptr(X), X.numel() // K, K, N, *_cols_args(bank_cols), ptr(M), stream_ptr()), "at_mel_rows")
+    return M
+
+
+def mel_distance_sums(M, Q, eps=1.1920929e-07, out=None):
+    """Per-clip sums of the mel distance between the mel rows M (generated) and Q (target), both (B, T, N) or (B, n)
+    float32: (B, 3) float64 holding S_D = sum (M - Q)^2, S_B = sum Q^2 and S_L = sum |ln(M + eps) - ln(Q + eps)|
+    (written into `out`, a contiguous (B, 3) float64 tensor, when given).  A clip's bits depend on its own cells only."""
+    require_device(M, Q, out)
+    M, Q = _f32c(M), _f32c(Q)
+    assert M.shape == Q.shape and M.ndim >= 2, "M and Q must be mel rows of one shape (B, ...)"
+    B = M.shape[0]
+    n = M[0].numel() if B else max(M.numel(), 1)
+    if out is not None:
+        assert out.shape == (B, 3) and out.dtype == torch.float64 and out.is_contiguous()
+    sums = out if out is not None else torch.empty((B, 3), dtype=torch.float64, device=M.device)
+    wsb = lib().at_mel_distance_workspace_bytes(B, n)
+    ws = _workspace(wsb, M.device)
+    check(lib().at_mel_distance_sums(ptr(M), ptr(Q), B, n, eps, ptr(sums), ptr(ws), wsb, stream_ptr()),
+          "at_mel_distance_sums")
+    return sums
+
+
+def mel_distance_backward(S, other, sums, gclip, bank_cols, bank_t_cols, lin_weight=1.0, log_weight=1.0,
+                          eps=1.1920929e-07, side=0):
+    """Backward of lin_weight S_D / S_B + log_weight S_L / n with respect to ONE spectrum, IN PLACE: S (B, T, K)
+    complex64 becomes the gradient of its spectrum, in the convention stft_backward takes.  side 0: S is the generated
+    signal's spectrum and `other` (B, T, N) float32 the target's mel rows; side 1: S is the target's spectrum and
+    `other` the generated signal's mel rows.  sums (B, 3) float64: what mel_distance_sums gave; gclip (B,) float32: the
+    gradient of the per-clip loss; bank_cols / bank_t_cols: utils.banded.bank_columns of the (K, N) bank and of its
+    transpose, on S's device.  Returns S."""
+    require_device(S, other, sums, gclip, *bank_cols, *bank_t_cols)
+    assert S.dtype == torch.complex64 and S.is_contiguous() and S.ndim == 3, "in place: a contiguous (B, T, K) complex64"
+    B, T, K = S.shape
+    N = bank_cols[0].numel()
+    assert bank_t_cols[0].numel() == K, "the transposed bank's tables do not match the spectrum"
+    other, gclip = _f32c(other), _f32c(gclip)
+    assert other.numel() == B * T * N, "the other signal's mel rows do not match the spectrum"
+    assert sums.shape == (B, 3) and sums.dtype == torch.float64 and sums.is_contiguous() and gclip.shape == (B,)
+    check(lib().at_mel_distance_backward(ptr(S), ptr(other), B, T, K, N, *_cols_args(bank_cols), *_cols_args(bank_t_cols),
+                                         ptr(sums), ptr(gclip), lin_weight, log_weight, eps, int(side), stream_ptr()),
+          "at_mel_distance_backward")
+    return S
+
+
 def _c64_grad(g):
     """A complex gradient as the kernels read it: complex64, contiguous, 8-byte aligned (a slice of a cat's gradient
     always is: complex64 elements)."""

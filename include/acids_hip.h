@@ -648,6 +648,48 @@ int at_spectral_distance_backward(float *X_complex, float *Y_complex, int64_t B,
                                   const float *gclip, float lin_weight, float log_weight, float eps, int need_x,
                                   int need_y, void *stream);
 
+/* ---- mel-scale spectral distance (mel_distance.hip; losses.MelSpectralDistance, autograd.MelSpectralDistanceFunction) - */
+/* Mel rows of a spectrum: out[r, j] = sum_k |X[r, k]| W[k, j] for X (rows, K) complex64 (8-byte aligned) and the (K x N)
+ * bank W by column (as at_magnitude_backward's f_*: column j holds f_len[j] weights at f_w[f_off[j] ..] for the bins
+ * f_start[j] ..), summed in ascending k.  out: (rows, N) float32.  One wave per row, |X| of the row in LDS, lane l
+ * writes mel l, l + 64, ...; persistent workgroups, the tables staged in LDS once per workgroup when they fit next to
+ * four rows (160 KB), read from global memory otherwise.  8 bytes read per bin, N / K of that written.  AT_OK without
+ * a launch when rows == 0; AT_EINVAL on null pointers, rows < 0, K or N < 1, f_nnz < 1 or X off its 8-byte grid;
+ * AT_EUNSUPPORTED when one row exceeds the LDS budget. */
+int at_mel_rows(const float *X_complex, int64_t rows, int K, int N, const int *f_start, const int *f_len,
+                const int *f_off, const float *f_w, int f_nnz, float *out, void *stream);
+
+/* Per-clip sums of the distance between two arrays of mel rows M (generated) and Q (target), both (B, n) float32 with
+ * n = T N cells per clip:
+ *   sums[b] = { S_D = sum (M - Q)^2,  S_B = sum Q^2,  S_L = sum |ln(M + eps) - ln(Q + eps)| }           (B, 3) float64
+ * from which the caller forms loss_b = lin_weight S_D / S_B + log_weight S_L / n.  The order is
+ * at_spectral_distance_sums's: slices of 4096 cells, one workgroup per slice (fp32 per lane in cell order, a fixed tree
+ * over the lanes), a second kernel adds a clip's slices in order in double; a function of n alone, no atomics.
+ * workspace: 4-byte aligned, at_mel_distance_workspace_bytes(B, n) bytes (AT_EWORKSPACE otherwise).  AT_OK without a
+ * launch when B == 0; AT_EINVAL on null M, Q or sums, B < 0, n < 1 or eps < 0, before any launch. */
+size_t at_mel_distance_workspace_bytes(int64_t B, int64_t n);
+int at_mel_distance_sums(const float *M, const float *Q, int64_t B, int64_t n, float eps, double *sums,
+                         void *workspace, size_t workspace_bytes, void *stream);
+
+/* Backward of the above with respect to ONE spectrum, in place.  S (B, T, K) complex64 is the spectrum of one signal,
+ * other (B T, N) float32 the mel rows of the other one: side 0: S = X, other = Q, S becomes G_X; side 1: S = Y,
+ * other = M, S becomes G_Y.  With sums (B, 3) what at_mel_distance_sums wrote, gclip (B,) float32 the gradient g of
+ * loss_b, n = T N and d = M - Q:
+ *   dM = g (lin_weight 2 d / S_B + log_weight sgn(d) / (n (M + eps)))
+ *   dQ = g (lin_weight (-2 d / S_B - 2 Q S_D / S_B^2) - log_weight sgn(d) / (n (Q + eps)))
+ *   dA[k] = sum_j W[k, j] dM[j],   G_X = dA X / |X| (0 where X == 0);   G_Y likewise from dQ and Y
+ * in the convention at_stft_backward takes (dRe + i dIm); sgn(0) = 0, no logarithm.  The row's own mel values are
+ * recomputed by at_mel_rows's device code, to its bits.  f_*: the bank by column (N columns), t_*: its transpose by
+ * column (K columns), as at_magnitude_backward.  16 bytes moved per bin plus 4 N / K.  Plans as at_mel_rows (both
+ * banks' tables and K + N floats per row).  AT_OK without a launch when B == 0; AT_EINVAL on null pointers, B < 0,
+ * T, K or N < 1, eps < 0, S off its 8-byte grid or side outside {0, 1}; AT_EUNSUPPORTED when one row exceeds the LDS
+ * budget. */
+int at_mel_distance_backward(float *S_complex, const float *other, int64_t B, int64_t T, int K, int N,
+                             const int *f_start, const int *f_len, const int *f_off, const float *f_w, int f_nnz,
+                             const int *t_start, const int *t_len, const int *t_off, const float *t_w, int t_nnz,
+                             const double *sums, const float *gclip, float lin_weight, float log_weight, float eps,
+                             int side, void *stream);
+
 /* ---- audio front end ------------------------------------------------------------------------------------- */
 /* torchaudio.transforms.Resample(orig, new) with default arguments, as utils/misc.py:31-33 uses it (algorithm
  * restated, torchaudio is not in the reference tree).  x: (rows, L); orig/new: the rates divided by their gcd;

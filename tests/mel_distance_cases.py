@@ -1,0 +1,184 @@
+"""Shared by test_mel_distance_cpu.py and test_mel_distance_gpu.py: a float64 numpy model of the three kernels of
+csrc/mel_distance.hip, float64 torch autograd of the stated expression on complex128 spectra (the module's float32
+bank cast to double), the float64 torch.stft chain, the plan rule of the two row kernels restated, and the case tables.
+The chunk rule, the STFT chain and the planted spectra are those of spectral_distance_cases.py; the grid and the row
+loop are those of invert_grad_cases.py (band_launch is one launcher)."""
+import numpy as np
+import torch
+
+import spectral_distance_cases as SD
+from acids_transforms_amd.utils.banded import bank_columns
+from acids_transforms_amd.utils.melbank import melscale_fbanks
+from invert_grad_cases import CUS, LDS_BUDGET, row_loop_trips
+
+EPS = SD.EPS
+SLICE = 4096                    # kMdSlice of mel_distance.hip: cells one workgroup reduces
+SR = 44100
+
+DEFAULT_SCALES = ((2048, 512, 320), (1024, 256, 160), (512, 128, 80), (256, 64, 40), (128, 32, 20))
+DEFAULT_EMPTY = (6, 3, 2, 1, 1)  # all-zero bank columns of the default ladder
+# the module-level sweep: the default five, a mixed-radix size, a hop other than n / 4
+SCALES = DEFAULT_SCALES + ((400, 100, 40), (1024, 128, 128))
+MODULE_B, MODULE_L = 3, 4096
+
+# (B, T, F, n_mels) of the op-level spectra, the smallest that reach every path: one frame, N < 64 and an empty
+# filter; T no multiple of the 4 waves and 5 empty filters; n_fft 400; N > 64 with the row in registers (K <= 576);
+# K > 576, rows from LDS; tables over the LDS budget (global tables); n = 5200 cells per clip: two slices, the last
+# 1104 cells
+OP_SHAPES = ((3, 1, 65, 20), (2, 7, 65, 40), (2, 9, 201, 40), (3, 9, 513, 80), (2, 5, 1025, 160), (1, 2, 8193, 320),
+             (2, 130, 65, 40))
+OP_EMPTY = (1, 5, 0, 0, 0, 0, 5)     # all-zero columns of each op-level bank
+OP_TABLE_FLOATS_8193 = 58119         # both banks' tables at (8193, 320): 232 KB, over the 160 KB budget
+
+
+def many_rows_shape(cus=CUS):
+    """(B, T, 65, 20) whose rows make the busiest workgroup of either row kernel walk its loop three times, the last
+    trip with only some workgroups: 8 workgroups of 4 waves per CU at most (the wave slots bind, not the LDS)."""
+    blocks = 8 * cus
+    groups = 2 * blocks + blocks // 2 + 1
+    T = -(-(4 * groups - 1) // 3)
+    return (3, T, 65, 20)
+
+
+def frames(n_fft, hop, L):
+    return SD.frames(n_fft, hop, L)
+
+
+def slices(n):
+    return (n + SLICE - 1) // SLICE
+
+
+def bank(F, n_mels, sr=SR, f_min=0.0, f_max=None):
+    """The module's bank of one scale: (F, n_mels) float32."""
+    return melscale_fbanks(F, f_min, float(sr // 2 if f_max is None else f_max), n_mels, sr)
+
+
+def empty_filters(W):
+    return int((~(W != 0).any(0)).sum())
+
+
+def spectra(shape, seed):
+    """Two random complex64 spectra of (B, T, F) with spectral_distance_cases' planted zeros (only X, only Y, both),
+    and, when there is more than one frame, a frame that X and Y share in the last clip."""
+    X, Y = SD.spectra(shape[:3], seed)
+    if shape[1] > 1:
+        Y[-1, shape[1] // 2] = X[-1, shape[1] // 2]
+    return X, Y
+
+
+# ---- the plan rule of launch_mel_rows and launch_mel_distance_backward ------------------------------------------------------
+
+def pad64(v):
+    return (v + 63) // 64 * 64
+
+
+def table_floats(K, N, f_nnz, t_nnz=None):
+    """start / len / off and weights of the bank by column (N columns) and, for the backward, of its transpose (K)."""
+    floats = 3 * N + f_nnz + (3 * K + t_nnz if t_nnz is not None else 0)
+    return (floats + 3) // 4 * 4
+
+
+def plan(K, N, f_nnz, t_nnz=None):
+    """(class, waves per workgroup, dynamic LDS bytes, row in registers) of at_mel_rows (t_nnz None) or of
+    at_mel_distance_backward: launch_magnitude_backward's rule."""
+    per_wave = 4 * (pad64(K) + (pad64(N) if t_nnz is not None else 0))
+    tab = 4 * table_floats(K, N, f_nnz, t_nnz)
+    if tab + 4 * per_wave <= LDS_BUDGET:
+        lds = tab + 4 * per_wave
+        return ("lds_big" if lds > 64 * 1024 else "lds"), 4, lds, K <= 576
+    if per_wave > LDS_BUDGET:
+        return "unsupported", 0, 0, False
+    wpb = min(4, LDS_BUDGET // per_wave)
+    return "global_w%d" % wpb, wpb, per_wave * wpb, False
+
+
+def bank_plans(W):
+    """(plan of at_mel_rows, plan of at_mel_distance_backward) for the bank W (K, N), with the nnz the library is handed."""
+    K, N = W.shape
+    f_nnz, t_nnz = bank_columns(W)[3].size, bank_columns(W.t())[3].size
+    return plan(K, N, f_nnz), plan(K, N, f_nnz, t_nnz)
+
+
+def trips(rows, the_plan, cus=CUS):
+    return row_loop_trips(rows, the_plan[1], the_plan[2], cus)
+
+
+# ---- the float64 model of the kernels ---------------------------------------------------------------------------------------
+
+def model_mel_rows(X, W):
+    """What at_mel_rows computes: |X| @ W in float64.  X (..., K) complex, W (K, N)."""
+    return np.abs(X.astype(np.complex128)) @ np.asarray(W, dtype=np.float64)
+
+
+def model_sums(M, Q, eps=EPS):
+    """What at_mel_distance_sums computes: (B, 3) float64 of S_D, S_B, S_L.  M, Q (B, ...) real."""
+    B = M.shape[0]
+    M, Q = M.astype(np.float64).reshape(B, -1), Q.astype(np.float64).reshape(B, -1)
+    return np.stack([((M - Q) ** 2).sum(1), (Q ** 2).sum(1), np.abs(np.log(M + eps) - np.log(Q + eps)).sum(1)], 1)
+
+
+def model_loss(sums, n, lin_weight=1.0, log_weight=1.0):
+    """loss_b of one scale from its sums (B, 3) and its n cells per clip."""
+    return lin_weight * sums[:, 0] / sums[:, 1] + log_weight * sums[:, 2] / n
+
+
+def model_backward(S, O, W, sums, g, lin_weight=1.0, log_weight=1.0, eps=EPS, side=0):
+    """What at_mel_distance_backward writes over S (B, T, K): complex128, dRe + i dIm.  O (B, T, N): the other signal's
+    mel rows; sums (B, 3); g (B,): the gradient of the per-clip loss."""
+    S, W = S.astype(np.complex128), np.asarray(W, dtype=np.float64)
+    B, T, _ = S.shape
+    n = T * W.shape[1]
+    A = np.abs(S)
+    own, O = A @ W, O.astype(np.float64).reshape(B, T, -1)
+    gb, S_D, S_B = (np.asarray(v, dtype=np.float64).reshape(B, 1, 1) for v in (g, sums[:, 0], sums[:, 1]))
+    d = own - O if side == 0 else O - own
+    sg = np.sign(d)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        if side == 0:
+            dm = gb * (lin_weight * 2 * d / S_B + log_weight * sg / (n * (own + eps)))
+        else:
+            dm = gb * (lin_weight * (-2 * d / S_B - 2 * own * S_D / S_B ** 2) - log_weight * sg / (n * (own + eps)))
+        dA = dm @ W.T
+        return np.where(A > 0, dA / np.where(A > 0, A, 1.0), 0.0) * S
+
+
+def model_gradients(X, Y, W, g, lin_weight=1.0, log_weight=1.0, eps=EPS, need_x=True, need_y=True):
+    """(G_X or None, G_Y or None): the three kernels in the order the Function runs them."""
+    M, Q = model_mel_rows(X, W), model_mel_rows(Y, W)
+    sums = model_sums(M, Q, eps)
+    GX = model_backward(X, Q, W, sums, g, lin_weight, log_weight, eps, 0) if need_x else None
+    GY = model_backward(Y, M, W, sums, g, lin_weight, log_weight, eps, 1) if need_y else None
+    return GX, GY
+
+
+# ---- float64 torch autograd of the stated expression --------------------------------------------------------------------------
+
+def torch_loss(Xt, Yt, W, lin_weight=1.0, log_weight=1.0, eps=EPS):
+    """loss_b (B,) of one scale, as stated, on complex128 torch spectra (B, T, K) and the bank W (K, N) cast to double."""
+    B = Xt.shape[0]
+    Wd = torch.as_tensor(W).double()
+    M, Q = (Xt.abs() @ Wd).reshape(B, -1), (Yt.abs() @ Wd).reshape(B, -1)
+    lin = ((M - Q) ** 2).sum(1) / (Q ** 2).sum(1)
+    log = (torch.log(M + eps) - torch.log(Q + eps)).abs().sum(1) / M.shape[1]
+    return lin_weight * lin + log_weight * log
+
+
+def autograd_backward(X, Y, W, g, lin_weight=1.0, log_weight=1.0, eps=EPS):
+    """(G_X, G_Y) complex128 numpy: torch autograd of torch_loss weighted by g (B,), in float64."""
+    Xt = torch.from_numpy(X.astype(np.complex128)).requires_grad_()
+    Yt = torch.from_numpy(Y.astype(np.complex128)).requires_grad_()
+    loss = torch_loss(Xt, Yt, W, lin_weight, log_weight, eps)
+    loss.backward(torch.as_tensor(np.asarray(g, dtype=np.float64)))
+    return Xt.grad.numpy(), Yt.grad.numpy()
+
+
+# ---- the float64 torch.stft chain (the module-level reference) ------------------------------------------------------------------
+
+stft64 = SD.stft64
+stft_adjoint64 = SD.stft_adjoint64
+
+
+def chain_loss(x64, y64, scales, lin_weight=1.0, log_weight=1.0, eps=EPS, sr=SR):
+    """The per-clip multi-scale mel loss (B,) float64 of the torch.stft chain."""
+    return sum(torch_loss(stft64(x64, n, h), stft64(y64, n, h), bank(n // 2 + 1, m, sr), lin_weight, log_weight, eps)
+               for n, h, m in scales)
