@@ -21,6 +21,9 @@ backward (spectral_distance.hip through ops.spectral_distance_backward) rebuilds
 MelSpectralDistanceFunction is its mel-scale sibling (mel_distance.hip through ops.mel_rows / ops.mel_distance_sums /
 ops.mel_distance_backward): to differentiate one signal it rebuilds that signal's spectrum and the other's mel rows.
 
+PqmfFunction and PqmfInvertFunction are PQMF's forward and invert (pqmf.hip): synthesis is n_band x the transpose of
+analysis, so each one's backward is the other's kernel with the transposed scale, and neither saves a tensor.
+
 All backward passes are first-order only (@once_differentiable): create_graph=True raises.
 """
 import torch
@@ -34,7 +37,7 @@ __all__ = ["wants_grad", "StftFunction", "IstftFunction", "IstftPolarFunction", 
            "PhaseScanFunction", "CartesianFunction", "PolarFunction", "PolarIFFunction", "StftPolarFunction",
            "RtStftFunction", "RtIstftFunction", "RtIstftPolarFunction", "OaddFramesFunction", "OaddInvertFunction",
            "SpectralDistanceFunction", "specdist_chunk_clips", "MelSpectralDistanceFunction", "meldist_sums",
-           "meldist_loss"]
+           "meldist_loss", "PqmfFunction", "PqmfInvertFunction"]
 
 
 def wants_grad(x: torch.Tensor) -> bool:
@@ -407,6 +410,38 @@ class MelSpectralDistanceFunction(torch.autograd.Function):
                         grad[b0:b1].add_(out)
                     del S, O
         return grads[0], grads[1], None, None, None, None, None, None
+
+
+# ---- PQMF (transforms.PQMF): analysis and synthesis are each other's transpose up to n_band ---------------------------------
+
+class PqmfFunction(torch.autograd.Function):
+    """PQMF.forward: x (rows, L) float32 -> ops.pqmf_analysis(x) (rows, M, L / M).  Saves nothing but the module's two
+    buffers (prototype, modulation: constants of the graph); the backward is the synthesis kernel with scale 1."""
+
+    @staticmethod
+    def forward(ctx, x, proto, mod):
+        ctx.proto, ctx.mod, ctx.dtype = proto, mod, x.dtype
+        return ops.pqmf_analysis(x, proto, mod, 1.0)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        return ops.pqmf_synthesis(gy, ctx.proto, ctx.mod, 1.0).to(ctx.dtype), None, None
+
+
+class PqmfInvertFunction(torch.autograd.Function):
+    """PQMF.invert: y (rows, M, T) float32 -> ops.pqmf_synthesis(y, scale M) (rows, M T).  Saves nothing but the
+    module's two buffers; the backward is the analysis kernel with scale M."""
+
+    @staticmethod
+    def forward(ctx, y, proto, mod):
+        ctx.proto, ctx.mod, ctx.dtype = proto, mod, y.dtype
+        return ops.pqmf_synthesis(y, proto, mod, float(mod.shape[0]))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gx):
+        return ops.pqmf_analysis(gx, ctx.proto, ctx.mod, float(ctx.mod.shape[0])).to(ctx.dtype), None, None
 
 
 # ---- the invert side: Magnitude, Polar, Cartesian, polar_to_complex, Normalize -----------------------------------------

@@ -869,6 +869,47 @@ def mel_distance_backward(S, other, sums, gclip, bank_cols, bank_t_cols, lin_wei
     return S
 
 
+def pqmf_tile_blocks(n_band, taps):
+    """Blocks t that one workgroup of the PQMF kernels handles at (n_band, taps); AcidsHipError outside their range."""
+    tile = lib().at_pqmf_tile_blocks(int(n_band), int(taps))
+    if tile <= 0:
+        check(tile, "at_pqmf_tile_blocks")
+    return tile
+
+
+def pqmf_analysis(x, proto, mod, scale=1.0):
+    """PQMF analysis: x (rows, L) float32 -> (rows, M, L / M) float32, y[row, k, t] = scale sum_n h_k[n] x[row, tM + n - P]
+    with h_k the bank of the prototype `proto` (N,) and the modulation `mod` (M, 2M) (include/acids_hip.h).  The
+    backward of pqmf_synthesis with respect to its input, too."""
+    require_device(x, proto, mod)
+    x = _f32c(x)
+    assert x.ndim == 2 and proto.dtype == mod.dtype == torch.float32 and proto.is_contiguous() and mod.is_contiguous()
+    M, N = mod.shape[0], proto.numel()
+    rows, L = x.shape
+    if L % M:
+        raise ValueError("the audio length %d is no multiple of n_band = %d" % (L, M))
+    y = torch.empty((rows, M, L // M), dtype=torch.float32, device=x.device)
+    check(lib().at_pqmf_analysis(ptr(x), rows, L, ptr(proto), N, M, ptr(mod), float(scale), ptr(y), stream_ptr()),
+          "at_pqmf_analysis")
+    return y
+
+
+def pqmf_synthesis(y, proto, mod, scale=1.0):
+    """PQMF synthesis: y (rows, M, T) float32 -> (rows, M T) float32, x[row, m] = scale sum_k sum_t h_k[m + P - tM]
+    y[row, k, t]: the transpose of pqmf_analysis, and so the backward of it with respect to its input."""
+    require_device(y, proto, mod)
+    y = _f32c(y)
+    assert y.ndim == 3 and proto.dtype == mod.dtype == torch.float32 and proto.is_contiguous() and mod.is_contiguous()
+    M, N = mod.shape[0], proto.numel()
+    rows, bands, T = y.shape
+    if bands != M:
+        raise ValueError("the band axis holds %d bands, the bank has n_band = %d" % (bands, M))
+    x = torch.empty((rows, M * T), dtype=torch.float32, device=y.device)
+    check(lib().at_pqmf_synthesis(ptr(y), rows, M * T, ptr(proto), N, M, ptr(mod), float(scale), ptr(x), stream_ptr()),
+          "at_pqmf_synthesis")
+    return x
+
+
 def _c64_grad(g):
     """A complex gradient as the kernels read it: complex64, contiguous, 8-byte aligned (a slice of a cat's gradient
     always is: complex64 elements)."""

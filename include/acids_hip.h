@@ -690,6 +690,29 @@ int at_mel_distance_backward(float *S_complex, const float *other, int64_t B, in
                              const double *sums, const float *gclip, float lin_weight, float log_weight, float eps,
                              int side, void *stream);
 
+/* ---- PQMF: multiband analysis and synthesis (pqmf.hip; transforms.PQMF, autograd.PqmfFunction / PqmfInvertFunction) - */
+/* The cosine-modulated pseudo-QMF bank of M = n_band bands on a real prototype h of N = taps (odd) taps, P = (N - 1) / 2:
+ *   h_k[n] = 2 h[n] cos((2k+1) pi / (2M) (n - P) + (-1)^k pi / 4)
+ *   analysis   y[row, k, t] = scale sum_n h_k[n] x[row, tM + n - P]                    x (rows, L) -> y (rows, M, L / M)
+ *   synthesis  x[row, m]    = scale sum_k sum_t h_k[m + P - tM] y[row, k, t]           y (rows, M, L / M) -> x (rows, L)
+ * with x zero outside [0, L) and y outside [0, L / M): synthesis is the transpose of analysis.  PQMF.forward is analysis
+ * with scale 1 and PQMF.invert synthesis with scale M; their backward passes are synthesis with scale 1 and analysis
+ * with scale M.  L is the AUDIO length in both calls.  mod: (M, 2M) float32, mod[k, r] = 2 cos((2k+1) pi / (2M) (r - P)
+ * + (-1)^k pi / 4), computed by the caller (the device evaluates no cosine); the kernels fold the taps that share a
+ * phase, u[r] = sum_j (-1)^j h[r + 2Mj] x[tM + r + 2Mj - P], and modulate, y_k = sum_r mod[k, r] u[r]: N / M + 2M
+ * multiply-adds per sample.  Every sum is one fmaf chain in ascending index order, a function of (M, N) alone: a row's
+ * bits do not depend on the other rows, and away from the edges a shift by M samples is a shift by one block to the bit.
+ * One workgroup per tile of at_pqmf_tile_blocks(M, N) blocks t of one row; rows and tiles share one 64-bit index, so
+ * there is no row limit.  No allocation, no workspace, asynchronous on `stream`.
+ * AT_OK without a launch when rows == 0 or L == 0 (before any pointer check); AT_EINVAL on rows or L < 0, n_band < 1,
+ * L % n_band != 0, even taps, taps < 2 n_band + 1 or a null pointer; AT_EUNSUPPORTED outside n_band 2 .. 64 or taps
+ * <= 4097.  at_pqmf_tile_blocks answers the same two errors, a positive count otherwise. */
+int at_pqmf_tile_blocks(int n_band, int taps);
+int at_pqmf_analysis(const float *x, int64_t rows, int64_t L, const float *proto, int taps, int n_band,
+                     const float *mod, float scale, float *y, void *stream);
+int at_pqmf_synthesis(const float *y, int64_t rows, int64_t L, const float *proto, int taps, int n_band,
+                      const float *mod, float scale, float *x, void *stream);
+
 /* ---- audio front end ------------------------------------------------------------------------------------- */
 /* torchaudio.transforms.Resample(orig, new) with default arguments, as utils/misc.py:31-33 uses it (algorithm
  * restated, torchaudio is not in the reference tree).  x: (rows, L); orig/new: the rates divided by their gcd;
