@@ -116,6 +116,8 @@ _SIGNATURES = {
     "at_pqmf_tile_blocks": [c_int, c_int],
     "at_pqmf_analysis": [c_f, c_i64, c_i64, c_f, c_int, c_int, c_f, c_flt, c_f, c_f],
     "at_pqmf_synthesis": [c_f, c_i64, c_i64, c_f, c_int, c_int, c_f, c_flt, c_f, c_f],
+    "at_pqmf_analysis_stream": [c_f, c_i64, c_i64, c_f, c_f, c_int, c_f, c_int, c_int, c_f, c_flt, c_f, c_f],
+    "at_pqmf_synthesis_stream": [c_f, c_i64, c_i64, c_f, c_f, c_int, c_f, c_int, c_int, c_f, c_flt, c_f, c_f],
 }
 _RESTYPES = {"at_error_string": ctypes.c_char_p, "at_istft_workspace_bytes": c_sz, "at_stats_workspace_bytes": c_sz,
              "at_pghi_offline_workspace_bytes": c_sz, "at_mel_bf16_bank_bytes": c_sz, "at_pghi_rt_workspace_bytes": c_sz,

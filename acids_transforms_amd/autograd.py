@@ -23,6 +23,9 @@ ops.mel_distance_backward): to differentiate one signal it rebuilds that signal'
 
 PqmfFunction and PqmfInvertFunction are PQMF's forward and invert (pqmf.hip): synthesis is n_band x the transpose of
 analysis, so each one's backward is the other's kernel with the transposed scale, and neither saves a tensor.
+PqmfStreamFunction and PqmfStreamInvertFunction are RealtimePQMF's (ops.pqmf_analysis_stream /
+ops.pqmf_synthesis_stream): the causal bank delayed by D blocks forward, the other kernel ADVANCED by D blocks and
+without state backward; the carried filter state is a constant of the graph like every other streaming state.
 
 All backward passes are first-order only (@once_differentiable): create_graph=True raises.
 """
@@ -37,7 +40,7 @@ __all__ = ["wants_grad", "StftFunction", "IstftFunction", "IstftPolarFunction", 
            "PhaseScanFunction", "CartesianFunction", "PolarFunction", "PolarIFFunction", "StftPolarFunction",
            "RtStftFunction", "RtIstftFunction", "RtIstftPolarFunction", "OaddFramesFunction", "OaddInvertFunction",
            "SpectralDistanceFunction", "specdist_chunk_clips", "MelSpectralDistanceFunction", "meldist_sums",
-           "meldist_loss", "PqmfFunction", "PqmfInvertFunction"]
+           "meldist_loss", "PqmfFunction", "PqmfInvertFunction", "PqmfStreamFunction", "PqmfStreamInvertFunction"]
 
 
 def wants_grad(x: torch.Tensor) -> bool:
@@ -442,6 +445,49 @@ class PqmfInvertFunction(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, gx):
         return ops.pqmf_analysis(gx, ctx.proto, ctx.mod, float(ctx.mod.shape[0])).to(ctx.dtype), None, None
+
+
+class PqmfStreamFunction(torch.autograd.Function):
+    """RealtimePQMF.forward: chunk x (rows, C) float32, state (rows, Ha) or None -> (y (rows, M, C / M), new_state
+    (rows, Ha)) by ops.pqmf_analysis_stream.  The state is a constant of the graph and the new state is not
+    differentiable, so the gradient covers the chunk's own samples: y[k, t] = sum_n h_k[n] x[(t - D) M + n - P] gives
+    gx[s] = the offline synthesis of gy (scale 1) at sample s + D M, i.e. the synthesis kernel advanced by D blocks
+    with no state.  Saves no tensor: the two tables hang on the node."""
+
+    @staticmethod
+    def forward(ctx, x, state, proto, mod):
+        ctx.proto, ctx.mod, ctx.dtype = proto, mod, x.dtype
+        y, new_state = ops.pqmf_analysis_stream(x, state, proto, mod, 1.0)
+        ctx.mark_non_differentiable(new_state)
+        return y, new_state
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy, _gstate):
+        D = ops.pqmf_stream_sizes(ctx.mod.shape[0], ctx.proto.numel())[0]
+        gx, _ = ops.pqmf_synthesis_stream(gy, None, ctx.proto, ctx.mod, 1.0, shift=D, want_state=False)
+        return gx.to(ctx.dtype), None, None, None
+
+
+class PqmfStreamInvertFunction(torch.autograd.Function):
+    """RealtimePQMF.invert: chunk y (rows, M, c) float32, state (rows, M, Hs) or None -> (x (rows, M c), new_state) by
+    ops.pqmf_synthesis_stream with scale M.  The backward is the analysis kernel with scale M, advanced by D blocks,
+    over the zero-extended gx and with no state.  Saves no tensor."""
+
+    @staticmethod
+    def forward(ctx, y, state, proto, mod):
+        ctx.proto, ctx.mod, ctx.dtype = proto, mod, y.dtype
+        x, new_state = ops.pqmf_synthesis_stream(y, state, proto, mod, float(mod.shape[0]))
+        ctx.mark_non_differentiable(new_state)
+        return x, new_state
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gx, _gstate):
+        M = ctx.mod.shape[0]
+        D = ops.pqmf_stream_sizes(M, ctx.proto.numel())[0]
+        gy, _ = ops.pqmf_analysis_stream(gx, None, ctx.proto, ctx.mod, float(M), shift=D, want_state=False)
+        return gy.to(ctx.dtype), None, None, None
 
 
 # ---- the invert side: Magnitude, Polar, Cartesian, polar_to_complex, Normalize -----------------------------------------

@@ -64,7 +64,8 @@ extern "C" {
 //    at_phase_scan_backward, at_cartesian_pack_backward, and the streaming path's at_rfft_frames_backward,
 //    at_irfft_frames_backward, at_oadd_forward_backward, at_oadd_invert_backward) and spectral_distance.hip's
 //    at_spectral_distance_sums / _backward and mel_distance.hip's at_mel_rows, at_mel_distance_sums / _backward and
-//    pqmf.hip's at_pqmf_tile_blocks, at_pqmf_analysis, at_pqmf_synthesis: additions only.
+//    pqmf.hip's at_pqmf_tile_blocks, at_pqmf_analysis, at_pqmf_synthesis and their streaming forms
+//    at_pqmf_analysis_stream, at_pqmf_synthesis_stream: additions only.
 int at_abi_version(void) { return 4; }
 
 int at_set_variant(int which, int value) {

@@ -11,6 +11,17 @@
 //               with n0 = (a + P) mod M and c = (a + P) div M
 // x is zero outside [0, L), y outside [0, L / M).
 //
+// Streaming (transforms.RealtimePQMF, autograd.PqmfStreamFunction / PqmfStreamInvertFunction) is the same two kernels
+// with a generalised STAGING, not other arithmetic.  A PqStream says where a call sits: the output grid lies `shift`
+// blocks from the input grid (output block t is the sum above at block t + shift), and the H entries before the input
+// (analysis: samples of the row; synthesis: blocks of every band) come from a state buffer instead of being zero.
+// With D = ceil(P / M): shift -D with state is the causal bank delayed by D blocks (Ha = D M + P samples, Hs = D +
+// floor(P / M) blocks of history are all it reads); shift +D without state is the transpose of the other kernel's
+// delayed form, i.e. the streaming backward passes.  The state of the NEXT call -- the last H entries of
+// [state | input] -- is written into a second buffer by the workgroup of each row's last tile, so that no tile reads
+// what another one overwrites.  The offline entries pass no state and shift 0, and run a copy of the kernels compiled
+// without any of this (template flag ST): run-time loop counts cost them 6 ... 10 % when the code was shared.
+//
 // One workgroup of 256 lanes handles a tile of TB = at_pqmf_tile_blocks(M, N) consecutive blocks t of one row: the
 // signed prototype and C sit in LDS for the workgroup's whole life, the tile's window (analysis: TB M + Np - M samples;
 // synthesis: the M band runs of the TB + ~N / M blocks that reach the tile) is staged with coalesced loads, kPqStage of
@@ -21,7 +32,9 @@
 // Order of the additions.  Every u, y, v and xh is ONE fmaf chain: over j ascending (xh: e = 0 then e = 1), over r
 // ascending, over k ascending.  A lane carries four chains whose blocks are two apart -- they share the window
 // samples and the taps in registers (8 LDS reads for 16 FMAs) -- but each chain is its own.  The order is a function
-// of (M, N) alone: not of the rows, the tile, or the place in the clip.  No atomics.
+// of (M, N) alone: not of the rows, the tile, the place in the clip, or the chunking of a stream.  No atomics.  A
+// streaming tile with fewer than TB blocks left (a short chunk) runs only the groups of chains that hold a live
+// block: which chains run depends on the length, never what a chain adds.
 //
 // LDS layouts (banking is by instruction width): the fold's lanes walk r, so window, prototype and v are read at
 // consecutive dwords; u has the odd row stride 2M + 1 because the modulation's lanes walk t; C is stored (2M, M
@@ -74,6 +87,17 @@ static inline PqPlan pq_plan(int M, int N) {
   return p;
 }
 
+// where a call sits in a stream (the header of this file); every offline call is {nullptr, nullptr, 0, 0}
+struct PqStream {
+  const float* state_in;   // (rows, H) or (rows, M, H): the H entries before the input; nullptr: zeros
+  float* state_out;        // the same shape: the last H entries of [state_in | input]; nullptr: not wanted
+  int H;
+  int shift;               // output block t reads the input as block t + shift of the offline sums
+};
+
+// D = ceil(P / M): the blocks of delay of the causal bank
+__host__ __device__ static inline int pq_delay_blocks(int M, int N) { return ((N - 1) / 2 + M - 1) / M; }
+
 // hs[n] = (-1)^(n div 2M) h[n], zero from N on
 __device__ __forceinline__ void pq_stage_proto(float* hs, const float* __restrict__ proto, int N, int Np, int M2) {
   for (int n = threadIdx.x; n < Np; n += kPqThreads) {
@@ -83,12 +107,14 @@ __device__ __forceinline__ void pq_stage_proto(float* hs, const float* __restric
 }
 
 // MT: the band count as a compile-time constant (LDS offsets become immediates, the divisions shifts), 0: p.M
-template <int MT>
+// ST: the streaming copy reads its PqStream and bounds its loops by the tile's live blocks; the offline copy (ST false)
+// has no state, shift 0 and whole-tile loop counts as constants -- the code it had before there was a streaming form
+template <int MT, bool ST>
 __global__ __launch_bounds__(kPqThreads) void pqmf_analysis_kernel(const float* __restrict__ x, long long L, long long T,
                                                                     long long tiles, long long units,
                                                                     const float* __restrict__ proto,
                                                                     const float* __restrict__ mod, float scale,
-                                                                    float* __restrict__ y, PqPlan p) {
+                                                                    float* __restrict__ y, PqPlan p, PqStream st) {
   extern __shared__ __attribute__((aligned(16))) float pq_lds[];
   const int M = MT ? MT : p.M, M2 = 2 * M, G = p.G, TB = pq_tile_blocks(M), Mp = (M + 3) & ~3, us = 2 * M + 1;
   float* hs = pq_lds;                         // Np (every array starts on a 16-byte boundary)
@@ -105,28 +131,43 @@ __global__ __launch_bounds__(kPqThreads) void pqmf_analysis_kernel(const float* 
     const long long row = unit / tiles;
     const long long t0 = (unit - row * tiles) * TB;
     const float* xr = x + row * L;
-    const long long s0 = t0 * M - p.P;        // clip sample of win[0]
+    const long long s0 = (t0 + (ST ? st.shift : 0)) * M - p.P;        // clip sample of win[0]
+    // the live blocks of the tile, in the groups of eight a pair of fold items carries, and the window they read
+    const int nb = ST && T - t0 < (long long)TB ? (int)(T - t0) : TB;
+    const int nsb = ST ? (nb + 7) >> 3 : TB / 8;
+    const int wlive = ST ? nsb * 8 * M + p.Np - M : p.wlen;
+    const float* state = ST ? st.state_in : nullptr;
     __syncthreads();                          // the tables are staged; the previous tile's u is read
-    // window samples [qlo, qhi) lie inside the clip, the rest is zero
-    const int qlo = s0 < 0 ? (int)-s0 : 0;
-    const int qhi = L - s0 < (long long)p.wlen ? (int)(L - s0) : p.wlen;
+    // window samples [qlo, qhi) lie inside the clip, [qs, qlo) in the carried state, the rest is zero
+    const int nlo = s0 < 0 ? (int)-s0 : 0;
+    const int qlo = ST && nlo > wlive ? wlive : nlo;
+    const int qhi = L - s0 < (long long)wlive ? (int)(L - s0) : wlive;
+    const int qs = !state ? qlo : nlo > st.H ? nlo - st.H : 0;
     const float* xw = xr + s0;
-    for (int q0 = threadIdx.x; q0 < p.wlen; q0 += kPqThreads * kPqStage) {
+    const float* sw = state + (row + 1) * st.H + s0;      // the state's last sample is clip sample -1
+    for (int q0 = threadIdx.x; q0 < wlive; q0 += kPqThreads * kPqStage) {
       float val[kPqStage];
 #pragma unroll
       for (int i = 0; i < kPqStage; ++i) {      // every load of the pass is issued before the first LDS store
         const int q = q0 + i * kPqThreads;
-        val[i] = (q >= qlo && q < qhi) ? xw[q] : 0.f;
+        val[i] = (q >= qlo && q < qhi) ? xw[q] : (q >= qs && q < qlo) ? sw[q] : 0.f;
       }
 #pragma unroll
       for (int i = 0; i < kPqStage; ++i) {
         const int q = q0 + i * kPqThreads;
-        if (q < p.wlen) win[q] = val[i];
+        if (q < wlive) win[q] = val[i];
+      }
+    }
+    if (ST && st.state_out && t0 + TB >= T) {       // the row's last tile: the last H samples of [state | chunk]
+      float* so = st.state_out + row * st.H;
+      for (int i = threadIdx.x; i < st.H; i += kPqThreads) {
+        const long long s = L - st.H + i;
+        so[i] = s >= 0 ? xr[s] : state ? sw[s - s0] : 0.f;
       }
     }
     __syncthreads();
     // fold: item = (r, parity of t, group of four same-parity blocks)
-    const int items = M2 * 2 * (TB / 8);
+    const int items = M2 * 2 * nsb;
     for (int i = threadIdx.x; i < items; i += kPqThreads) {
       const int rest = i / M2, r = i - rest * M2;
       const int tp = rest & 1, sblk = rest >> 1;
@@ -155,7 +196,7 @@ __global__ __launch_bounds__(kPqThreads) void pqmf_analysis_kernel(const float* 
     }
     __syncthreads();
     // modulation: a wave's item = (64 blocks, four bands); lane = block
-    const int kchunks = Mp / 4, mitems = (TB / 64) * kchunks;
+    const int kchunks = Mp / 4, mitems = (ST ? (nb + 63) >> 6 : TB / 64) * kchunks;
     float* yr = y + row * M * T;
     for (int it = wave; it < mitems; it += kPqThreads / 64) {
       const int tc = it / kchunks, k0 = 4 * (it - tc * kchunks);
@@ -181,12 +222,12 @@ __global__ __launch_bounds__(kPqThreads) void pqmf_analysis_kernel(const float* 
   }
 }
 
-template <int MT>
+template <int MT, bool ST>
 __global__ __launch_bounds__(kPqThreads) void pqmf_synthesis_kernel(const float* __restrict__ y, long long L, long long T,
                                                                      long long tiles, long long units,
                                                                      const float* __restrict__ proto,
                                                                      const float* __restrict__ mod, float scale,
-                                                                     float* __restrict__ x, PqPlan p) {
+                                                                     float* __restrict__ x, PqPlan p, PqStream st) {
   extern __shared__ __attribute__((aligned(16))) float pq_lds[];
   const int M = MT ? MT : p.M, M2 = 2 * M, G = p.G, TB = pq_tile_blocks(M), ys = p.ys;
   float* hs = pq_lds;                         // Np (every array starts on a 16-byte boundary)
@@ -199,18 +240,29 @@ __global__ __launch_bounds__(kPqThreads) void pqmf_synthesis_kernel(const float*
     const long long row = unit / tiles;
     const long long t0 = (unit - row * tiles) * TB;
     const float* yr = y + row * M * T;
-    const long long tlo = t0 - p.lo;          // block of v's row 0
+    const long long tlo = t0 + (ST ? st.shift : 0) - p.lo;          // block of v's row 0
+    // the live blocks of the tile, in the groups of eight a pair of accumulation items carries, and the rows of v
+    // they read (a multiple of four: the modulation's items)
+    const int nb = ST && T - t0 < (long long)TB ? (int)(T - t0) : TB;
+    const int nsb = ST ? (nb + 7) >> 3 : TB / 8;
+    const int ysl = ST ? pq_up4(8 * nsb + (M - 1 + p.P) / M + p.lo) : ys;
+    const float* state = ST ? st.state_in : nullptr;
     __syncthreads();                          // the tables are staged; the previous tile's output is stored
-    // v rows [rlo, rhi) lie inside the clip, the rest is zero; (k, tl) of a lane's next element by steps, no division
-    const int rlo = tlo < 0 ? (int)-tlo : 0;
-    const int rhi = T - tlo < (long long)ys ? (int)(T - tlo) : ys;
+    // v rows [rlo, rhi) lie inside the clip, [rs, rlo) in the carried state, the rest is zero; (k, tl) of a lane's
+    // next element by steps, no division
+    const int nlo = tlo < 0 ? (int)-tlo : 0;
+    const int rlo = ST && nlo > ysl ? ysl : nlo;
+    const int rhi = T - tlo < (long long)ysl ? (int)(T - tlo) : ysl;
+    const int rs = !state ? rlo : nlo > st.H ? nlo - st.H : 0;
+    const float* sr = state + row * M * st.H + st.H + tlo;      // a band's last state block is block -1
     const int dk = kPqThreads / ys, dt = kPqThreads - dk * ys;
     int k = threadIdx.x / ys, tl = threadIdx.x - k * ys;
     for (int i0 = threadIdx.x; i0 < M * ys; i0 += kPqThreads * kPqStage) {
       float val[kPqStage];
 #pragma unroll
       for (int q = 0; q < kPqStage; ++q) {      // every load of the pass is issued before the first LDS store
-        val[q] = (k < M && tl >= rlo && tl < rhi) ? yr[(long long)k * T + tlo + tl] : 0.f;
+        val[q] = (k < M && tl >= rlo && tl < rhi) ? yr[(long long)k * T + tlo + tl]
+                 : (ST && k < M && tl >= rs && tl < rlo) ? sr[k * st.H + tl] : 0.f;
         k += dk; tl += dt;
         if (tl >= ys) { tl -= ys; ++k; }
       }
@@ -220,9 +272,17 @@ __global__ __launch_bounds__(kPqThreads) void pqmf_synthesis_kernel(const float*
         if (i < M * ys) yl[i] = val[q];
       }
     }
+    if (ST && st.state_out && t0 + TB >= T) {       // the row's last tile: the last H blocks of every band of [state | chunk]
+      float* so = st.state_out + row * M * st.H;
+      for (int i = threadIdx.x; i < M * st.H; i += kPqThreads) {
+        const int kb = i / st.H;
+        const long long tb = T - st.H + (i - kb * st.H);
+        so[i] = tb >= 0 ? yr[(long long)kb * T + tb] : state ? sr[kb * st.H + (tb - tlo)] : 0.f;
+      }
+    }
     __syncthreads();
     // modulation: item = (r, four blocks)
-    const int vitems = M2 * (ys / 4);
+    const int vitems = M2 * (ysl / 4);
     for (int i = threadIdx.x; i < vitems; i += kPqThreads) {
       const int tg = i / M2, r = i - tg * M2;
       const float* cp = cm + r;
@@ -239,7 +299,7 @@ __global__ __launch_bounds__(kPqThreads) void pqmf_synthesis_kernel(const float*
     }
     __syncthreads();
     // accumulation: item = (a, parity of the block, group of four same-parity blocks); the result goes over yl
-    const int items = M * 2 * (TB / 8);
+    const int items = M * 2 * nsb;
     for (int i = threadIdx.x; i < items; i += kPqThreads) {
       const int rest = i / M, a = i - rest * M;
       const int bp = rest & 1, sblk = rest >> 1;
@@ -294,7 +354,7 @@ static int pq_check(const void* in, int64_t rows, int64_t L, const void* proto, 
 // persistent workgroups: as many as the chip holds at once, at most one per tile
 template <typename Kernel>
 static int pq_launch(Kernel kernel, size_t lds, const float* in, int64_t rows, int64_t L, const float* proto,
-                     const float* mod, float scale, float* out, const PqPlan& p, hipStream_t stream) {
+                     const float* mod, float scale, float* out, const PqPlan& p, const PqStream& st, hipStream_t stream) {
   if (lds > kPqLdsBytes) return AT_EUNSUPPORTED;
   const void* fn = (const void*)kernel;
   if (lds > 64 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
@@ -315,28 +375,30 @@ static int pq_launch(Kernel kernel, size_t lds, const float* in, int64_t rows, i
   long long blocks = (long long)(per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 1);
   if (blocks > units) blocks = units;
   hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(kPqThreads), lds, stream, in, (long long)L, T, tiles, units,
-                     proto, mod, scale, out, p);
+                     proto, mod, scale, out, p, st);
   return hipGetLastError() == hipSuccess ? AT_OK : AT_ELAUNCH;
 }
 
 // the kernel of a band count: a specialisation for the usual counts, the general one otherwise -- same sums, same bits
 #define PQ_DISPATCH(kernel, lds)                                                                      \
   switch (n_band) {                                                                                   \
-    case 4: return pq_launch(kernel<4>, lds, in, rows, L, proto, mod, scale, out, p, s);              \
-    case 8: return pq_launch(kernel<8>, lds, in, rows, L, proto, mod, scale, out, p, s);              \
-    case 16: return pq_launch(kernel<16>, lds, in, rows, L, proto, mod, scale, out, p, s);            \
-    case 32: return pq_launch(kernel<32>, lds, in, rows, L, proto, mod, scale, out, p, s);            \
-    case 64: return pq_launch(kernel<64>, lds, in, rows, L, proto, mod, scale, out, p, s);            \
-    default: return pq_launch(kernel<0>, lds, in, rows, L, proto, mod, scale, out, p, s);             \
+    case 4: return pq_launch(kernel<4, ST>, lds, in, rows, L, proto, mod, scale, out, p, st, s);           \
+    case 8: return pq_launch(kernel<8, ST>, lds, in, rows, L, proto, mod, scale, out, p, st, s);           \
+    case 16: return pq_launch(kernel<16, ST>, lds, in, rows, L, proto, mod, scale, out, p, st, s);         \
+    case 32: return pq_launch(kernel<32, ST>, lds, in, rows, L, proto, mod, scale, out, p, st, s);         \
+    case 64: return pq_launch(kernel<64, ST>, lds, in, rows, L, proto, mod, scale, out, p, st, s);         \
+    default: return pq_launch(kernel<0, ST>, lds, in, rows, L, proto, mod, scale, out, p, st, s);          \
   }
 
+template <bool ST>
 static int pq_analysis(const float* in, int64_t rows, int64_t L, const float* proto, const float* mod, float scale,
-                       float* out, int n_band, const PqPlan& p, hipStream_t s) {
+                       float* out, int n_band, const PqPlan& p, const PqStream& st, hipStream_t s) {
   PQ_DISPATCH(pqmf_analysis_kernel, p.lds_analysis)
 }
 
+template <bool ST>
 static int pq_synthesis(const float* in, int64_t rows, int64_t L, const float* proto, const float* mod, float scale,
-                        float* out, int n_band, const PqPlan& p, hipStream_t s) {
+                        float* out, int n_band, const PqPlan& p, const PqStream& st, hipStream_t s) {
   PQ_DISPATCH(pqmf_synthesis_kernel, p.lds_synthesis)
 }
 #undef PQ_DISPATCH
@@ -360,7 +422,7 @@ int at_pqmf_analysis(const float* x, int64_t rows, int64_t L, const float* proto
   const int rc = pq_check(x, rows, L, proto, taps, n_band, mod, y);
   if (rc) return rc > 0 ? AT_OK : rc;
   const PqPlan p = pq_plan(n_band, taps);
-  return pq_analysis(x, rows, L, proto, mod, scale, y, n_band, p, (hipStream_t)stream);
+  return pq_analysis<false>(x, rows, L, proto, mod, scale, y, n_band, p, PqStream{nullptr, nullptr, 0, 0}, (hipStream_t)stream);
 }
 
 int at_pqmf_synthesis(const float* y, int64_t rows, int64_t L, const float* proto, int taps, int n_band, const float* mod,
@@ -369,7 +431,33 @@ int at_pqmf_synthesis(const float* y, int64_t rows, int64_t L, const float* prot
   const int rc = pq_check(y, rows, L, proto, taps, n_band, mod, x);
   if (rc) return rc > 0 ? AT_OK : rc;
   const PqPlan p = pq_plan(n_band, taps);
-  return pq_synthesis(y, rows, L, proto, mod, scale, x, n_band, p, (hipStream_t)stream);
+  return pq_synthesis<false>(y, rows, L, proto, mod, scale, x, n_band, p, PqStream{nullptr, nullptr, 0, 0}, (hipStream_t)stream);
+}
+
+int at_pqmf_analysis_stream(const float* x, int64_t rows, int64_t L, const float* state_in, float* state_out,
+                            int shift_blocks, const float* proto, int taps, int n_band, const float* mod, float scale,
+                            float* y, void* stream) {
+  using namespace at_hip;
+  const int rc = pq_check(x, rows, L, proto, taps, n_band, mod, y);
+  if (rc) return rc > 0 ? AT_OK : rc;
+  const int D = pq_delay_blocks(n_band, taps);
+  if (shift_blocks < -D || shift_blocks > D || (state_out && state_out == state_in)) return AT_EINVAL;
+  const PqPlan p = pq_plan(n_band, taps);
+  const PqStream st = {state_in, state_out, D * n_band + p.P, shift_blocks};
+  return pq_analysis<true>(x, rows, L, proto, mod, scale, y, n_band, p, st, (hipStream_t)stream);
+}
+
+int at_pqmf_synthesis_stream(const float* y, int64_t rows, int64_t L, const float* state_in, float* state_out,
+                             int shift_blocks, const float* proto, int taps, int n_band, const float* mod, float scale,
+                             float* x, void* stream) {
+  using namespace at_hip;
+  const int rc = pq_check(y, rows, L, proto, taps, n_band, mod, x);
+  if (rc) return rc > 0 ? AT_OK : rc;
+  const int D = pq_delay_blocks(n_band, taps);
+  if (shift_blocks < -D || shift_blocks > D || (state_out && state_out == state_in)) return AT_EINVAL;
+  const PqPlan p = pq_plan(n_band, taps);
+  const PqStream st = {state_in, state_out, D + p.P / n_band, shift_blocks};
+  return pq_synthesis<true>(y, rows, L, proto, mod, scale, x, n_band, p, st, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -910,6 +910,74 @@ def pqmf_synthesis(y, proto, mod, scale=1.0):
     return x
 
 
+def pqmf_stream_sizes(n_band, taps):
+    """(D, Ha, Hs) of the streaming PQMF at (n_band, taps): the blocks of delay D = ceil(P / M), the samples of carried
+    analysis state Ha = D M + P and the blocks per band of carried synthesis state Hs = D + floor(P / M)."""
+    M, P = int(n_band), (int(taps) - 1) // 2
+    D = -(-P // M)
+    return D, D * M + P, D + P // M
+
+
+def _pqmf_state(state, shape, like):
+    if state is None:
+        return None
+    require_device(like, state)
+    state = _f32c(state)
+    assert tuple(state.shape) == shape, "the carried state is %s, the stream needs %s" % (tuple(state.shape), shape)
+    return state
+
+
+def pqmf_analysis_stream(x, state, proto, mod, scale=1.0, shift=None, want_state=True):
+    """PQMF analysis of a chunk of a stream: x (rows, C) float32, state (rows, Ha) float32 -- the samples before the
+    chunk -- or None for zeros -> (y (rows, M, C / M), new_state (rows, Ha) or None), y[row, k, t] = scale sum_n h_k[n]
+    s[row, (t + shift) M + n - P] over s = [state | x | zeros] (include/acids_hip.h).  shift=None is -D, the causal
+    bank delayed by D blocks; shift=+D with state=None and want_state=False is the backward of pqmf_synthesis_stream
+    with respect to its chunk.  new_state is a fresh tensor, the last Ha samples of [state | x], written by the kernel:
+    no torch.cat, one launch.  An empty chunk or batch launches nothing and hands the state back as it came."""
+    require_device(x, proto, mod)
+    x = _f32c(x)
+    assert x.ndim == 2 and proto.dtype == mod.dtype == torch.float32 and proto.is_contiguous() and mod.is_contiguous()
+    M, N = mod.shape[0], proto.numel()
+    rows, C = x.shape
+    if C % M:
+        raise ValueError("the chunk length %d is no multiple of n_band = %d" % (C, M))
+    D, Ha, _ = pqmf_stream_sizes(M, N)
+    state = _pqmf_state(state, (rows, Ha), x)
+    y = torch.empty((rows, M, C // M), dtype=torch.float32, device=x.device)
+    if rows == 0 or C == 0:
+        return y, (state if want_state else None)
+    new_state = torch.empty((rows, Ha), dtype=torch.float32, device=x.device) if want_state else None
+    check(lib().at_pqmf_analysis_stream(ptr(x), rows, C, ptr(state), ptr(new_state), -D if shift is None else int(shift),
+                                        ptr(proto), N, M, ptr(mod), float(scale), ptr(y), stream_ptr()),
+          "at_pqmf_analysis_stream")
+    return y, new_state
+
+
+def pqmf_synthesis_stream(y, state, proto, mod, scale=1.0, shift=None, want_state=True):
+    """PQMF synthesis of a chunk of a stream: y (rows, M, c) float32, state (rows, M, Hs) float32 -- the blocks before
+    the chunk -- or None for zeros -> (x (rows, M c), new_state (rows, M, Hs) or None), x[row, m] = scale sum_k sum_t
+    h_k[m + shift M + P - tM] s[row, k, t] over s = [state | y | zeros] with the chunk's first block at t = 0.
+    shift=None is -D; shift=+D with state=None and want_state=False is the backward of pqmf_analysis_stream with
+    respect to its chunk.  new_state is a fresh tensor, the last Hs blocks of [state | y], written by the kernel."""
+    require_device(y, proto, mod)
+    y = _f32c(y)
+    assert y.ndim == 3 and proto.dtype == mod.dtype == torch.float32 and proto.is_contiguous() and mod.is_contiguous()
+    M, N = mod.shape[0], proto.numel()
+    rows, bands, c = y.shape
+    if bands != M:
+        raise ValueError("the band axis holds %d bands, the bank has n_band = %d" % (bands, M))
+    D, _, Hs = pqmf_stream_sizes(M, N)
+    state = _pqmf_state(state, (rows, M, Hs), y)
+    x = torch.empty((rows, M * c), dtype=torch.float32, device=y.device)
+    if rows == 0 or c == 0:
+        return x, (state if want_state else None)
+    new_state = torch.empty((rows, M, Hs), dtype=torch.float32, device=y.device) if want_state else None
+    check(lib().at_pqmf_synthesis_stream(ptr(y), rows, M * c, ptr(state), ptr(new_state), -D if shift is None else int(shift),
+                                         ptr(proto), N, M, ptr(mod), float(scale), ptr(x), stream_ptr()),
+          "at_pqmf_synthesis_stream")
+    return x, new_state
+
+
 def _c64_grad(g):
     """A complex gradient as the kernels read it: complex64, contiguous, 8-byte aligned (a slice of a cat's gradient
     always is: complex64 elements)."""

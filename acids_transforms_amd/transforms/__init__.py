@@ -10,10 +10,10 @@ from .oadd import OverlapAdd
 from .raw import MuLaw
 from .misc import OneHot
 from .channels import Mono, Stereo, MidSide, Window, Squeeze, Unsqueeze, Transpose
-from .pqmf import PQMF
+from .pqmf import PQMF, RealtimePQMF
 
 __all__ = ["AudioTransform", "ComposeAudioTransform", "NotInvertibleError", "InversionEnumType",
            "apply_transform_to_list", "apply_invert_transform_to_list", "STFT", "RealtimeSTFT", "DGT", "RealtimeDGT", "DGT_INVERSION_MODES",
            "Normalize", "Magnitude", "Real", "Imaginary", "Phase", "IF", "SpectralRepresentation", "Cartesian", "Polar",
            "PolarIF", "MFCC", "OverlapAdd", "MuLaw", "OneHot", "Mono", "Stereo", "MidSide", "Window", "Squeeze", "Unsqueeze", "Transpose",
-           "PQMF"]
+           "PQMF", "RealtimePQMF"]

@@ -27,13 +27,35 @@ Gradients: `forward` and `invert` carry a gradient when grad mode is on and the 
 (autograd.PqmfFunction / PqmfInvertFunction: the same kernels forward, the transposed kernel backward; the graph keeps
 no tensor but the module's two buffers).  First order only.
 
-There is no streaming form: a chunked filterbank needs taps - 1 samples of carried filter state per direction, which is
-not built.  `realtime()` therefore warns and returns the module itself, which filters every chunk as a whole clip (zero
+Streaming: `RealtimePQMF` (also `PQMF.streaming()`) is the same bank made causal by a delay of D = ceil(P / M) whole
+blocks in each direction, with the filter state carried in two module buffers:
+
+    forward  chunk (..., C), C a multiple of M, down to one block -> (..., M, C / M); block t of the stream is
+             y_ext[k, t - D], y_ext[k, t'] = sum_n h_k[n] x[t'M + n - P] with x zero before the stream's start, so the
+             outputs of ANY chunking of x (..., L) concatenate to PQMF.forward(cat([zeros(D M), x], -1))[..., :L / M]
+    invert   chunk (..., M, c), c >= 1 -> (..., c M); sample m of the stream is the offline synthesis sum at m - D M, so
+             the outputs concatenate to PQMF.invert(cat([zeros(..., M, D), y], -1))[..., :T M]
+    state    `input_buffer` (lead..., Ha), the last Ha = D M + P input samples; `band_buffer` (lead..., M, Hs), the last
+             Hs = D + floor(P / M) blocks of every band (input history, not an output tail: every output stays one
+             fmaf chain).  Zeros on a new leading batch shape or device and after `reset()`.
+
+At the defaults (16 bands, 513 taps) D = 16, Ha = 512, Hs = 32: `analysis_delay` = `synthesis_delay` = 256 samples,
+`latency` = 512 = taps - 1 for the round trip.  The kernels are the offline ones with another staging (a tile's window
+comes from the state buffer, then the chunk, then zeros; csrc/pqmf.hip), so for finite input the chunked outputs are
+the bits of the one-call result and of the delayed offline module.  (Finite only: the prototype's zero padding up to a
+multiple of 2M multiplies samples that the stream has not received yet, which streaming reads as zeros.)  The new
+state is written by the kernel into a second buffer that replaces the module's: no torch.cat, one launch per call.
+Gradients (autograd.PqmfStreamFunction / PqmfStreamInvertFunction): the carried state is a constant of the graph and
+is stored detached, so a chunk's gradient covers that chunk's own samples -- truncated back-propagation at chunk
+boundaries, as for OverlapAdd.  The backward is the other kernel advanced by D blocks, without state.
+
+`PQMF.realtime()` itself still warns and returns the offline module, which filters every chunk as a whole clip (zero
 state at both chunk edges, so the P samples on either side of a chunk boundary differ from the offline result); it does
 not raise, because the package's contract -- the reference's own suite, replayed on every transform -- is that
 `realtime()` hands back a working module.  For the same reason the self-test hooks (`test_forward`, `test_inversion`,
-`test_scripted_transform`) drop the last L % n_band samples of their audio, where `forward` itself raises.  Also not
-built: a fast DCT-IV modulation, bf16, optimised non-Kaiser prototypes."""
+`test_scripted_transform`) drop the last L % n_band samples of their audio, where `forward` itself raises.  Not built: a
+hipGraph-captured streaming session (the state buffers change place every call), gradient flow through the carried
+state, a fast DCT-IV modulation, bf16, optimised non-Kaiser prototypes."""
 import math
 import warnings
 from typing import Optional, Union
@@ -42,10 +64,10 @@ import torch
 
 from .. import ops
 from .._lib import device_scoped, require_device
-from ..autograd import PqmfFunction, PqmfInvertFunction, wants_grad
+from ..autograd import PqmfFunction, PqmfInvertFunction, PqmfStreamFunction, PqmfStreamInvertFunction, wants_grad
 from .base import AudioTransform
 
-__all__ = ["PQMF", "MIN_BANDS", "MAX_BANDS", "MAX_TAPS", "CUTOFF_GRID", "kaiser_prototype", "design_cutoff",
+__all__ = ["PQMF", "RealtimePQMF", "MIN_BANDS", "MAX_BANDS", "MAX_TAPS", "CUTOFF_GRID", "kaiser_prototype", "design_cutoff",
            "modulation_matrix"]
 
 MIN_BANDS, MAX_BANDS, MAX_TAPS = 2, 64, 4097      # the range of the kernels (csrc/pqmf.hip)
@@ -134,9 +156,17 @@ class PQMF(AudioTransform):
         return self.n_band
 
     def realtime(self):
-        warnings.warn("PQMF has no streaming form (carried filter state is not built): realtime() returns the offline "
-                      "module, which filters every chunk as a whole clip with zero state at its edges", stacklevel=2)
+        warnings.warn("PQMF has no streaming form of its own: realtime() returns the offline module, which filters every "
+                      "chunk as a whole clip with zero state at its edges; RealtimePQMF (or PQMF.streaming()) carries "
+                      "the filter state across chunks", stacklevel=2)
         return self
+
+    def streaming(self) -> "RealtimePQMF":
+        """The streaming form of this bank: a RealtimePQMF that shares this module's prototype and modulation."""
+        rt = RealtimePQMF(n_band=self.n_band, attenuation=self.attenuation, prototype=self.prototype, sr=self.sr)
+        rt.cutoff = self.cutoff
+        rt._buffers["prototype"], rt._buffers["modulation"] = self.prototype, self.modulation
+        return rt.to(self.prototype.device)
 
     # the self-test hooks of the base class, on audio cut to a whole number of blocks (forward raises otherwise)
     def _whole_blocks(self, x: torch.Tensor) -> torch.Tensor:
@@ -196,3 +226,99 @@ class PQMF(AudioTransform):
         else:
             out = ops.pqmf_synthesis(y3, proto, mod, float(self.n_band))
         return out.reshape(lead + (self.n_band * T,))
+
+
+class RealtimePQMF(PQMF):
+    """The causal PQMF with carried filter state (the module docstring): `forward` and `invert` take the next chunk of
+    a stream and answer the offline bank delayed by `analysis_delay` / `synthesis_delay` samples."""
+
+    def __repr__(self):
+        return "Realtime" + super().__repr__()
+
+    def __init__(self, n_band: int = 16, taps: Optional[int] = None, attenuation: float = 100.0,
+                 prototype: Optional[torch.Tensor] = None, sr: int = 44100) -> None:
+        super().__init__(n_band=n_band, taps=taps, attenuation=attenuation, prototype=prototype, sr=sr)
+        self.delay_blocks, self._keep_in, self._keep_band = ops.pqmf_stream_sizes(self.n_band, self.taps)
+        self.register_buffer("input_buffer", torch.zeros(self._keep_in))
+        self.register_buffer("band_buffer", torch.zeros(self.n_band, self._keep_band))
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        for k in ("input_buffer", "band_buffer"):                 # any batch shape, as OverlapAdd's
+            if prefix + k in state_dict:
+                self._buffers[k] = torch.zeros_like(state_dict[prefix + k])
+        return super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+
+    @property
+    def analysis_delay(self) -> int:
+        """Samples by which `forward` lags the offline bank."""
+        return self.delay_blocks * self.n_band
+
+    @property
+    def synthesis_delay(self) -> int:
+        """Samples by which `invert` lags the offline bank."""
+        return self.delay_blocks * self.n_band
+
+    @property
+    def latency(self) -> int:
+        """Samples by which invert(forward(x)) lags x."""
+        return self.analysis_delay + self.synthesis_delay
+
+    def realtime(self):
+        return self
+
+    def streaming(self) -> "RealtimePQMF":
+        return self
+
+    def reset(self) -> None:
+        """Forget the stream: both states become zeros (of their current shape)."""
+        self.input_buffer = torch.zeros_like(self.input_buffer)
+        self.band_buffer = torch.zeros_like(self.band_buffer)
+
+    def forward_with_time(self, x: torch.Tensor, time: torch.Tensor):
+        return self.forward(x), time - self.analysis_delay / self.sr
+
+    def _state(self, buf: torch.Tensor, lead, tail, x: torch.Tensor):
+        """The carried state as the kernel reads it, (rows,) + tail, or None for zeros: a new leading batch shape or a
+        new device starts a new stream."""
+        if tuple(buf.shape) != tuple(lead) + tail or buf.device != x.device:
+            return None
+        return buf.reshape((math.prod(lead),) + tail)
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if x.ndim < 1 or x.shape[-1] % self.n_band:
+            raise ValueError("RealtimePQMF.forward takes a (..., C) chunk with C a multiple of n_band = %d, got shape %s"
+                             % (self.n_band, tuple(x.shape)))
+        ops._no_fp64(x)
+        device_scoped(require_device)(x)
+        lead, C = tuple(x.shape[:-1]), x.shape[-1]
+        if x.numel() == 0:                                      # nothing arrived: no launch, the state stays
+            return torch.empty(lead + (self.n_band, C // self.n_band), dtype=torch.float32, device=x.device)
+        state = self._state(self.input_buffer, lead, (self._keep_in,), x)
+        proto, mod = self._tables(x)
+        x2 = x.reshape(math.prod(lead), C)
+        if wants_grad(x):
+            y, new_state = PqmfStreamFunction.apply(x2, state, proto, mod)      # the state is a constant of the graph
+        else:
+            y, new_state = ops.pqmf_analysis_stream(x2, state, proto, mod, 1.0)
+        self.input_buffer = new_state.detach().reshape(lead + (self._keep_in,))
+        return y.reshape(lead + (self.n_band, C // self.n_band))
+
+    def invert(self, x: torch.Tensor, inversion_mode: Union[str, None] = None, **kwargs) -> torch.Tensor:
+        if x.ndim < 2 or x.shape[-2] != self.n_band:
+            raise ValueError("RealtimePQMF.invert takes a (..., n_band = %d, c) chunk of sub-band signals, got shape %s"
+                             % (self.n_band, tuple(x.shape)))
+        ops._no_fp64(x)
+        device_scoped(require_device)(x)
+        lead, c = tuple(x.shape[:-2]), x.shape[-1]
+        if x.numel() == 0:
+            return torch.empty(lead + (self.n_band * c,), dtype=torch.float32, device=x.device)
+        tail = (self.n_band, self._keep_band)
+        state = self._state(self.band_buffer, lead, tail, x)
+        proto, mod = self._tables(x)
+        y3 = x.reshape((math.prod(lead), self.n_band, c))
+        if wants_grad(x):
+            out, new_state = PqmfStreamInvertFunction.apply(y3, state, proto, mod)
+        else:
+            out, new_state = ops.pqmf_synthesis_stream(y3, state, proto, mod, float(self.n_band))
+        self.band_buffer = new_state.detach().reshape(lead + tail)
+        return out.reshape(lead + (self.n_band * c,))

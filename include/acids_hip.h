@@ -712,6 +712,27 @@ int at_pqmf_analysis(const float *x, int64_t rows, int64_t L, const float *proto
                      const float *mod, float scale, float *y, void *stream);
 int at_pqmf_synthesis(const float *y, int64_t rows, int64_t L, const float *proto, int taps, int n_band,
                       const float *mod, float scale, float *x, void *stream);
+/* The same two kernels on a chunk of a stream (transforms.RealtimePQMF, autograd.PqmfStreamFunction /
+ * PqmfStreamInvertFunction): only what a tile stages differs, every sum is the chain of the entries above.  With
+ * D = ceil(P / M), output block t is the offline sum at block t + shift_blocks of the signal [state | chunk | zeros]:
+ *   analysis   y[row, k, t] = scale sum_n h_k[n] x[row, (t + shift) M + n - P]      state_in, state_out (rows, D M + P)
+ *   synthesis  x[row, m]    = scale sum_k sum_t h_k[m + shift M + P - tM] y[row, k, t]
+ *                                                                      state_in, state_out (rows, M, D + floor(P / M))
+ * where the entries before the chunk are state_in (the last samples of the row, the last blocks of every band; null:
+ * zeros) and the entries after it are zero.  shift_blocks = -D with the state is the causal bank delayed by D blocks:
+ * no output reads past the chunk, so the outputs of any chunking of a stream are, for finite input, the bits of one
+ * call over the whole stream.  shift_blocks = +D with null state is the transpose of the OTHER kernel's delayed form,
+ * i.e. the backward passes of the streaming forward (synthesis, scale 1) and invert (analysis, scale M) with the state
+ * a constant.  state_out (null: not wanted) receives the last entries of [state_in | chunk], written on the device by
+ * the workgroup of each row's last tile; it must not be state_in (the caller swaps the two buffers).  L is the AUDIO
+ * length of the chunk in both calls.  Everything else as above; additionally AT_EINVAL when |shift_blocks| > D or
+ * state_out == state_in.  Nothing is written, state_out included, when rows == 0 or L == 0. */
+int at_pqmf_analysis_stream(const float *x, int64_t rows, int64_t L, const float *state_in, float *state_out,
+                            int shift_blocks, const float *proto, int taps, int n_band, const float *mod,
+                            float scale, float *y, void *stream);
+int at_pqmf_synthesis_stream(const float *y, int64_t rows, int64_t L, const float *state_in, float *state_out,
+                             int shift_blocks, const float *proto, int taps, int n_band, const float *mod,
+                             float scale, float *x, void *stream);
 
 /* ---- audio front end ------------------------------------------------------------------------------------- */
 /* torchaudio.transforms.Resample(orig, new) with default arguments, as utils/misc.py:31-33 uses it (algorithm
