@@ -80,10 +80,15 @@ def sinebank_realtime(mod, x_fft: torch.Tensor, window: torch.Tensor = None) -> 
     if batch_shape != tuple(mod.random_phase.shape[:-2]):
         mod.random_phase = (2 * torch.pi * torch.rand(batch_shape + (1, F))).to(dev)
     # running clock: the reference keeps `time_index` as an fp32 tensor on the CPU; a host shadow of the buffer
-    # (same fp32 additions) spares the streaming loop a device->host read per chunk
-    now = mod.__dict__.get("_time_index_host")
-    if now is None:
-        now = np.float32(float(mod.time_index))
+    # (same fp32 additions) spares the streaming loop a device->host read per chunk.  The shadow stands for the
+    # tensor this function itself last stored, at the version it had then: a buffer that was replaced (assignment,
+    # .to(), reset()) or written in place (load_state_dict, zero_()) since is read again, one sync
+    buf = mod.time_index
+    shadow = mod.__dict__.get("_time_index_host")
+    if shadow is not None and shadow[0] is buf and shadow[1] == buf._version:
+        now = shadow[2]
+    else:
+        now = np.float32(float(buf))
     tidx = torch.arange(n_fft).unsqueeze(0) + torch.arange(T).unsqueeze(1) * hop
     tau = tidx / mod.sr + torch.tensor(now)                            # (T, n_fft), fp32 like the reference
     c = 2 * torch.pi * torch.linspace(0, mod.sr / 2, int(n_fft / 2 + 1))
@@ -93,6 +98,6 @@ def sinebank_realtime(mod, x_fft: torch.Tensor, window: torch.Tensor = None) -> 
     phi = mod.random_phase.to(dev).reshape(-1, F) if batch_shape else mod.random_phase.to(dev).reshape(1, F)
     y = ops.sinebank_realtime(x_fft.reshape(S, T, F), c.to(dev), tau.to(dev), phi.expand(S, F).contiguous(), window)
     step = (T * hop + n_fft) / mod.sr
-    mod.__dict__["_time_index_host"] = np.float32(now + np.float32(step))
-    mod.time_index = mod.time_index + step
+    mod.time_index = buf + step
+    mod.__dict__["_time_index_host"] = (mod.time_index, mod.time_index._version, np.float32(now + np.float32(step)))
     return y.reshape(batch_shape + (T, n_fft))

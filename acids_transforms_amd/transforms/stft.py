@@ -195,6 +195,7 @@ class STFT(AudioTransform):
         if key in state_dict:
             self._buffers["phase_buffer"] = torch.zeros_like(state_dict[key])
         self.__dict__["_phase_src"] = None
+        self.__dict__.pop("_time_index_host", None)     # the realtime classes' clock shadow: the loaded buffer rules
         out = super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
         self._n_fft = int(self._buffers["n_fft"].item())
         self._hop = int(self._buffers["hop_length"].item())

@@ -1,12 +1,21 @@
 """GPU parity: "sinebank" inversion (at_sinebank_offline / at_sinebank_realtime) against the reference's outputs
 (tests/golden/g13_sinebank.npz, random phases recorded) and the oracle.  The oscillator phase is formed in fp32
 exactly as the reference does; what differs is the summation order over bins (MFMA contraction vs torch.sum)
-and sin()'s last bit -> 1e-5 of the output's largest magnitude (the output is peak-normalised to 1)."""
+and sin()'s last bit -> 1e-5 of the output's largest magnitude (the output is peak-normalised to 1).
+
+The second half runs the cases of sinebank_cases.py, which name the kernel path each one reaches
+(test_sinebank_cases_cpu.py checks that they reach all of them), under the same bar, and pins who owns the stream clock."""
+import copy
+
 import numpy as np
 import pytest
 import torch
 
 import acids_transforms_amd as A
+import sinebank_cases as C
+from acids_transforms_amd import ops
+from acids_transforms_amd._lib import AcidsHipError, variant
+from acids_transforms_amd.transforms.sinebank import _offline_tables
 from conftest import rel_max
 from oracle import oracle as O
 
@@ -108,3 +117,173 @@ def test_full_size_properties(dev):
     a = s.get_sinebank_inversion(m2.to(dev), random_phase=phase)
     b = s.get_sinebank_inversion((m2 * 3.0).to(dev), random_phase=phase)
     assert float((a - b).abs().max()) < 2e-6
+
+
+# ---- every kernel path: the cases of sinebank_cases.py ----------------------------------------------------------------
+def _offline(case, dev, module=None):
+    """The case's clips through STFT.get_sinebank_inversion: (output on the CPU, error against the fp32 oracle)."""
+    B, T, n_fft, hop = case
+    mag, phase = C.offline_inputs(case)
+    s = module if module is not None else A.STFT(n_fft=n_fft, hop_length=hop).to(dev)
+    y = cpu(s.get_sinebank_inversion(mag.to(dev), random_phase=phase))
+    assert y.shape == (B, C.out_len(T, n_fft, hop))
+    return y, rel_max(y.numpy(), C.offline_oracle(case).numpy())
+
+
+@pytest.mark.parametrize("case", C.OFFLINE_CASES, ids=lambda c: "B%d-T%d-n%d-h%d" % c)
+def test_offline_paths(case, dev):
+    y, err = _offline(case, dev)
+    print("sinebank offline %-22s F %4d  n_pass %2d  rel_max %.2e" % (case, C.n_bins(case[2]), C.n_pass(*case[1:]), err))
+    assert err < TOL, (case, err)
+    assert abs(float(y.max()) - 1.0) < 1e-6                           # peak-normalised
+
+
+@pytest.mark.parametrize("case", C.ROW_RUN_CASES, ids=lambda c: "B%d-T%d-n%d-h%d" % c)
+def test_offline_row_runs(case, dev):
+    """DENSE mel_gemm_kernel with 1, 2 and all of its 32-row tiles per workgroup (the double-buffered staging through the
+    block offsets): same bits as the default plan; every clip differs, so a swapped row or a stale tile shows."""
+    mag, _ = C.offline_inputs(case)
+    assert all(not torch.equal(mag[0], mag[b]) for b in range(1, case[0]))
+    y0, err0 = _offline(case, dev)
+    assert err0 < TOL
+    for v in sorted({1, 2, C.row_tiles(case[0])}):
+        with variant("row_run", v):
+            y, err = _offline(case, dev)
+        print("sinebank offline %-18s row_run %d  rel_max %.2e  bit-equal %s" % (case, v, err, torch.equal(y, y0)))
+        assert torch.equal(y, y0), (case, v)
+        assert err < TOL, (case, v, err)
+
+
+def _tables(case):
+    B, T, n_fft, hop = case
+    return _offline_tables(T, C.n_bins(n_fft), n_fft, hop, C.SR)
+
+
+def test_offline_pass_limit(dev):
+    """64 passes, the ABI's limit, pass parity; 70 are refused by the launcher's argument check, and the module goes on."""
+    assert _tables(C.PASS_LIMIT_CASE)[1] == C.PASS_LIMIT
+    _, err = _offline(C.PASS_LIMIT_CASE, dev)
+    print("sinebank offline %-22s n_pass 64  rel_max %.2e" % (C.PASS_LIMIT_CASE, err))
+    assert err < TOL
+    B, T, n_fft, hop = C.OVER_PASS_LIMIT_CASE
+    assert _tables(C.OVER_PASS_LIMIT_CASE)[1] == 70
+    s = A.STFT(n_fft=n_fft, hop_length=hop).to(dev)
+    mag, phase = C.offline_inputs(C.OVER_PASS_LIMIT_CASE)
+    with pytest.raises(AcidsHipError):
+        s.get_sinebank_inversion(mag.to(dev), random_phase=phase)
+    follow = (2, 6, n_fft, hop)                                       # one block, six passes
+    _, err = _offline(follow, dev, module=s)
+    print("sinebank offline %-22s after the refusal  rel_max %.2e" % (follow, err))
+    assert err < TOL
+
+
+def _realtime_module(cls, case, batch, dev):
+    """A fresh module with the case's phases and clock set by the caller."""
+    S, T, n_fft, hop, clock = case
+    mag, phase = C.realtime_inputs(case, batch)
+    r = cls(n_fft=n_fft, hop_length=hop).to(dev)
+    r.random_phase = phase.to(dev)
+    r.time_index = torch.tensor(clock, device=dev)
+    return r, mag
+
+
+@pytest.mark.parametrize("cls", [A.RealtimeSTFT, A.RealtimeDGT], ids=["stft", "dgt"])
+@pytest.mark.parametrize("case", C.REALTIME_CASES, ids=lambda c: "S%d-T%d-n%d-h%d-t%g" % c)
+def test_realtime_paths(case, cls, dev):
+    S, T, n_fft, hop, clock = case
+    for batch in ((S,), (2, 3), ()):
+        want, clock_after = C.realtime_oracle(case, batch)
+        for windowed in (False, True):
+            r, mag = _realtime_module(cls, case, batch, dev)
+            if windowed:
+                y = cpu(r.invert(mag.to(dev), inversion_mode="sinebank"))
+                ref = want * cpu(r.inv_window[:n_fft])
+            else:
+                y = cpu(r.get_sinebank_inversion(mag.to(dev)))
+                ref = want
+            assert y.shape == tuple(batch) + (T, n_fft)
+            err = rel_max(y.numpy(), ref.numpy())
+            print("sinebank realtime %-4s %-28s batch %-6s %-10s rel_max %.2e" % (
+                cls.__name__[8:], case, batch, "windowed" if windowed else "unwindowed", err))
+            assert err < TOL, (case, batch, windowed, err)
+            assert float(r.time_index) == float(clock_after)
+
+
+def test_realtime_limits(dev):
+    """Op level: one step past the grid and the LDS limit is refused by the launcher's argument check (nothing is
+    launched); at the limits the kernel matches the float64 model."""
+    for S, T, F, N in C.REALTIME_REFUSED:
+        z = torch.zeros
+        with pytest.raises(AcidsHipError):
+            ops.sinebank_realtime(z(S, T, F, device=dev), z(F, device=dev), z(T, N, device=dev), z(S, F, device=dev))
+    for lim in C.REALTIME_LIMIT_CASES:
+        x, c, tau, phi = C.realtime_limit_inputs(*lim)
+        y = cpu(ops.sinebank_realtime(x.to(dev), c.to(dev), tau.to(dev), phi.to(dev)))
+        assert y.shape == (lim[0], lim[1], lim[3])
+        err = rel_max(y.numpy(), C.realtime_model_op(x, c, tau, phi).numpy())
+        print("sinebank realtime op S %d T %d F %d N %d  rel_max %.2e against the float64 model" % (lim[:4] + (err,)))
+        assert err < TOL, (lim, err)
+
+
+def test_realtime_long_stream(dev):
+    """200 one-frame chunks at the default size: the buffer's clock stays the oracle's, bit for bit, and the frames at
+    it pass parity."""
+    S, n_fft, hop = C.LONG_STREAM["S"], C.LONG_STREAM["n_fft"], C.LONG_STREAM["hop"]
+    n, every, F = C.LONG_STREAM["chunks"], C.LONG_STREAM["check_every"], C.n_bins(n_fft)
+    gen = torch.Generator().manual_seed(12)
+    mags = torch.rand(n, S, 1, F, generator=gen) ** 2
+    phase = 2 * torch.pi * torch.rand(S, 1, F, generator=gen)
+    r = A.RealtimeSTFT(n_fft=n_fft, hop_length=hop).to(dev)
+    r.random_phase = phase.to(dev)
+    mags_d = mags.to(dev)
+    now = torch.tensor(0.)
+    for i in range(n):
+        y = r.get_sinebank_inversion(mags_d[i])
+        if (i + 1) % every == 0:
+            want, after = O.sinebank_realtime(mags[i], C.SR, n_fft, hop, phase, now)
+            err = rel_max(cpu(y).numpy(), want.numpy())
+            print("sinebank realtime chunk %3d at %.4f s  rel_max %.2e" % (i + 1, float(now), err))
+            assert err < TOL, (i, err)
+            assert float(r.time_index) == float(after), (i, float(r.time_index), float(after))
+            now = after
+        else:
+            now = now + (1 * hop + n_fft) / C.SR                     # the oracle's own advance
+    assert float(now) > 5.0
+
+
+@pytest.mark.parametrize("cls", [A.RealtimeSTFT, A.RealtimeDGT], ids=["stft", "dgt"])
+def test_realtime_clock_ownership(cls, dev):
+    """The registered buffer `time_index` is the clock: a loaded state, an assigned tensor and an in-place write all
+    rule over what the module remembers of its own earlier chunks (the reference reads the buffer on every call)."""
+    n_fft, hop, T = 128, 32, 4
+    gen = torch.Generator().manual_seed(13)
+    chunks = torch.rand(4, 3, T, 65, generator=gen) ** 2
+    phase = 2 * torch.pi * torch.rand(3, 1, 65, generator=gen)
+    step = (T * hop + n_fft) / C.SR
+    r = cls(n_fft=n_fft, hop_length=hop).to(dev)
+    r.random_phase = phase.to(dev)
+
+    def run(i):
+        return cpu(r.get_sinebank_inversion(chunks[i].to(dev)))
+
+    def want(i, t):
+        return O.sinebank_realtime(chunks[i], C.SR, n_fft, hop, phase, torch.tensor(t))[0].numpy()
+
+    y1 = run(0)
+    sd = copy.deepcopy(r.state_dict())
+    y2 = run(1)
+    assert rel_max(y2.numpy(), want(1, step)) < TOL
+    r.load_state_dict(sd)                                             # back to the state after chunk 1
+    assert torch.equal(run(1), y2)
+    t0 = 1234.5
+    r.time_index = torch.tensor(t0, device=dev)                       # a clock set by the caller
+    assert rel_max(run(2).numpy(), want(2, t0)) < TOL
+    assert float(r.time_index) == float(torch.tensor(t0) + step)
+    r.time_index.zero_()                                              # in place
+    assert torch.equal(run(0), y1)
+    assert rel_max(run(1).numpy(), want(1, step)) < TOL               # ... and the shadow follows on from there
+    if cls is A.RealtimeDGT:
+        t = float(r.time_index)
+        r.reset([3])                                                  # the PGHI history only (reference dgt.py)
+        assert float(r.time_index) == t
+        assert rel_max(run(3).numpy(), want(3, t)) < TOL
