@@ -190,11 +190,15 @@ class StftMagnitudeFunction(torch.autograd.Function):
 MFCC_CHUNK_ELEMS = 1 << 26      # complex64 elements of spectrum per chunk of MfccFunction.backward: 512 MiB
 
 
+def _chunk_clips(elems, B, T, n_fft):
+    """The most of B clips whose spectrum (T frames of n_fft // 2 + 1 bins per clip) stays within elems, at least 1."""
+    return min(max(elems // (T * (n_fft // 2 + 1)), 1), B)
+
+
 def mfcc_chunk_clips(B, T, n_fft):
-    """Clips per chunk of MfccFunction.backward: the most whose spectrum (T frames of n_fft // 2 + 1 bins per clip)
-    stays within MFCC_CHUNK_ELEMS, at least 1 (189 at n_fft 1024 / hop 256 and 4 s clips)."""
-    per_clip = T * (n_fft // 2 + 1)
-    return min(max(MFCC_CHUNK_ELEMS // per_clip, 1), B)
+    """Clips per chunk of MfccFunction.backward: _chunk_clips under MFCC_CHUNK_ELEMS as it stands at the call (189 at
+    n_fft 1024 / hop 256 and 4 s clips)."""
+    return _chunk_clips(MFCC_CHUNK_ELEMS, B, T, n_fft)
 
 
 def _mfcc_tables(module, device):
@@ -243,47 +247,93 @@ class MfccFunction(torch.autograd.Function):
         return dx.to(x.dtype), None
 
 
-# ---- the multi-scale spectral distance (losses.SpectralDistance) -----------------------------------------------------------
+# ---- the multi-scale distances (losses.SpectralDistance, losses.MelSpectralDistance) -----------------------------------------
+# One driver for both: a scale is (n_fft, hop) or (n_fft, hop, n_mels), and the two differ in the cells whose distance is
+# taken -- the bins of a spectrum, or its mel rows -- and in which spectra the backward holds together.
 
 SPECDIST_CHUNK_ELEMS = 1 << 26      # complex64 elements of ONE spectrum per chunk: 512 MiB, so x's and y's peak at 1 GiB
 
 
 def specdist_chunk_clips(B, T, n_fft):
-    """Clips per chunk of the spectral distance, forward and backward: the most whose one spectrum (T frames of
-    n_fft // 2 + 1 bins per clip) stays within SPECDIST_CHUNK_ELEMS, at least 1."""
-    per_clip = T * (n_fft // 2 + 1)
-    return min(max(SPECDIST_CHUNK_ELEMS // per_clip, 1), B)
+    """Clips per chunk of both distances, forward and backward: _chunk_clips of ONE spectrum under SPECDIST_CHUNK_ELEMS
+    as it stands at the call."""
+    return _chunk_clips(SPECDIST_CHUNK_ELEMS, B, T, n_fft)
+
+
+def _frames(L, n_fft, hop):
+    return 1 + (L - (n_fft & 1)) // hop
 
 
 def _specdist_chunks(B, L, n_fft, hop):
     """(b0, b1) of every chunk of B clips of L samples at one scale."""
-    chunk = max(specdist_chunk_clips(B, 1 + (L - (n_fft & 1)) // hop, n_fft), 1)
+    chunk = max(specdist_chunk_clips(B, _frames(L, n_fft, hop), n_fft), 1)
     return [(b0, min(b0 + chunk, B)) for b0 in range(0, B, chunk)]
 
 
-def specdist_sums(x, y, windows, scales, eps):
-    """x, y (B, L) float32 -> (B, n_scales, 3) float64, the sums S_D, S_B, S_L of every clip at every scale
-    (ops.spectral_distance_sums on the two spectra of a chunk of clips, which is freed before the next)."""
+def _dist_sums(x, y, scales, cells_of, sums_op, eps):
+    """x, y (B, L) float32 -> (B, n_scales, 3) float64, the sums S_D, S_B, S_L of every clip at every scale: sums_op on
+    cells_of(s, clips) of x's and then of y's rows of a chunk of clips, both freed before the next chunk."""
     B, L = x.shape
     per_scale = []
-    for (n, hop), w in zip(scales, windows):
+    for s, (n, hop, *_) in enumerate(scales):
         out = torch.empty((B, 3), dtype=torch.float64, device=x.device)
         for b0, b1 in _specdist_chunks(B, L, n, hop):
-            X = ops.stft_forward(x[b0:b1], w, n, hop, center=True)
-            Y = ops.stft_forward(y[b0:b1], w, n, hop, center=True)
-            ops.spectral_distance_sums(X, Y, eps, out=out[b0:b1])
+            X = cells_of(s, x[b0:b1])
+            Y = cells_of(s, y[b0:b1])
+            sums_op(X, Y, eps, out=out[b0:b1])
             del X, Y
         per_scale.append(out)
     return torch.stack(per_scale, 1)
 
 
-def specdist_loss(sums, L, scales, lin_weight, log_weight):
-    """The per-clip loss (B,) float32 of the sums: sum over scales of lin_weight S_D / S_B + log_weight S_L / n."""
+def _dist_loss(sums, cells, lin_weight, log_weight):
+    """The per-clip loss (B,) float32 of the sums: sum over scales of lin_weight S_D / S_B + log_weight S_L / n, n the
+    scale's cells per clip."""
     loss = (sums[:, :, 0] / sums[:, :, 1]).sum(1) * lin_weight
-    for s, (n, hop) in enumerate(scales):
-        bins = (1 + (L - (n & 1)) // hop) * (n // 2 + 1)
-        loss = loss + sums[:, s, 2] * (log_weight / bins)
+    for s, n in enumerate(cells):
+        loss = loss + sums[:, s, 2] * (log_weight / n)
     return loss.float()
+
+
+class _DistBackward:
+    """What the two backward passes share.  Allocates the (B, L) gradient of every input that needs one and the
+    (chunk, L) scratch of the later scales; chunks() walks scales and chunks of clips; put() runs the STFT adjoint of one
+    spectrum gradient -- into the result for the first scale, into the scratch that is added to it for every later one.
+    Which spectra are built, alive together and freed is the caller's, between two calls."""
+
+    def __init__(self, x, gclip, need, scales, windows):
+        B, L = x.shape
+        self.B, self.L, self.scales, self.windows = B, L, scales, windows
+        self.g = ops._f32c(gclip)
+        self.grads = [torch.empty((B, L), dtype=torch.float32, device=x.device) if nd else None for nd in need]
+        rows = max([b1 - b0 for n, hop, *_ in scales[1:] for b0, b1 in _specdist_chunks(B, L, n, hop)[:1]], default=0)
+        self.scratch = torch.empty((rows, L), dtype=torch.float32, device=x.device)
+
+    def chunks(self, sums):
+        """(s, b0, b1, the sums and the upstream gradient of clips b0:b1 at scale s) of every scale and chunk of clips."""
+        for s, (n, hop, *_) in enumerate(self.scales):
+            sums_s = sums[:, s].contiguous()
+            for b0, b1 in _specdist_chunks(self.B, self.L, n, hop):
+                yield s, b0, b1, sums_s[b0:b1], self.g[b0:b1]
+
+    def put(self, k, G, s, b0, b1):
+        """Input k's gradient of clips b0:b1 at scale s from the gradient G of their spectrum."""
+        n, hop = self.scales[s][:2]
+        out = self.grads[k][b0:b1] if s == 0 else self.scratch[:b1 - b0]      # stft_backward overwrites its out
+        ops.stft_backward(G, self.windows[s], n, hop, self.L, out=out)
+        if s:
+            self.grads[k][b0:b1].add_(out)
+
+
+def specdist_sums(x, y, windows, scales, eps):
+    """_dist_sums of the two spectra of a chunk of clips (ops.spectral_distance_sums), which are alive together."""
+    return _dist_sums(x, y, scales, lambda s, c: ops.stft_forward(c, windows[s], *scales[s], center=True),
+                      ops.spectral_distance_sums, eps)
+
+
+def specdist_loss(sums, L, scales, lin_weight, log_weight):
+    """_dist_loss with n = T F bins per clip."""
+    return _dist_loss(sums, [_frames(L, n, hop) * (n // 2 + 1) for n, hop in scales], lin_weight, log_weight)
 
 
 class SpectralDistanceFunction(torch.autograd.Function):
@@ -291,8 +341,8 @@ class SpectralDistanceFunction(torch.autograd.Function):
     Saves the two audios and the (B, n_scales, 3) sums, and nothing else: the backward rebuilds both spectra per scale
     and chunk of clips (specdist_chunk_clips), turns them into their own gradients in place
     (ops.spectral_distance_backward) and runs the STFT adjoint -- into the result for the first scale, into a (chunk, L)
-    scratch that is added to it for every later one.  Only the inputs that require a gradient get one; the windows
-    are constants of the graph."""
+    scratch that is added to it for every later one (_DistBackward).  Only the inputs that require a gradient get one;
+    the windows are constants of the graph."""
 
     @staticmethod
     def forward(ctx, x, y, windows, scales, lin_weight, log_weight, eps):
@@ -306,30 +356,18 @@ class SpectralDistanceFunction(torch.autograd.Function):
     def backward(ctx, gclip):
         x, y, sums = ctx.saved_tensors
         need = ctx.needs_input_grad[:2]
-        B, L = x.shape
-        g = ops._f32c(gclip)
-        grads = [torch.empty((B, L), dtype=torch.float32, device=x.device) if nd else None for nd in need]
-        rows = max([b1 - b0 for n, hop in ctx.scales[1:] for b0, b1 in _specdist_chunks(B, L, n, hop)[:1]], default=0)
-        scratch = torch.empty((rows, L), dtype=torch.float32, device=x.device)
-        for s, ((n, hop), w) in enumerate(zip(ctx.scales, ctx.windows)):
-            sums_s = sums[:, s].contiguous()
-            for b0, b1 in _specdist_chunks(B, L, n, hop):
-                X = ops.stft_forward(x[b0:b1], w, n, hop, center=True)
-                Y = ops.stft_forward(y[b0:b1], w, n, hop, center=True)
-                ops.spectral_distance_backward(X, Y, sums_s[b0:b1], g[b0:b1], *ctx.weights, ctx.eps, *need)
-                for G, grad in zip((X, Y), grads):
-                    if grad is None:
-                        continue
-                    out = grad[b0:b1] if s == 0 else scratch[:b1 - b0]      # stft_backward overwrites its out
-                    ops.stft_backward(G, w, n, hop, L, out=out)
-                    if s:
-                        grad[b0:b1].add_(out)
-                del X, Y
-        return grads[0], grads[1], None, None, None, None, None
+        bwd = _DistBackward(x, gclip, need, ctx.scales, ctx.windows)
+        for s, b0, b1, sums_c, g in bwd.chunks(sums):
+            (n, hop), w = ctx.scales[s], ctx.windows[s]
+            X = ops.stft_forward(x[b0:b1], w, n, hop, center=True)
+            Y = ops.stft_forward(y[b0:b1], w, n, hop, center=True)
+            ops.spectral_distance_backward(X, Y, sums_c, g, *ctx.weights, ctx.eps, *need)
+            for k, G in enumerate((X, Y)):
+                if need[k]:
+                    bwd.put(k, G, s, b0, b1)
+            del X, Y
+        return bwd.grads[0], bwd.grads[1], None, None, None, None, None
 
-
-# ---- the multi-scale mel distance (losses.MelSpectralDistance) ---------------------------------------------------------------
-# Chunks are _specdist_chunks: only ONE spectrum of a chunk is alive at a time here, so the peak is 512 MiB.
 
 def _meldist_tables(module, device):
     """Per scale, (bank by column, transposed bank by column) of a MelSpectralDistance's mel_bank_i on `device`: built
@@ -347,29 +385,15 @@ def _mel_of(x, w, n, hop, cols):
 
 
 def meldist_sums(x, y, windows, scales, tables, eps):
-    """x, y (B, L) float32 -> (B, n_scales, 3) float64, the sums S_D, S_B, S_L of every clip at every scale
-    (ops.mel_distance_sums on the two arrays of mel rows of a chunk of clips).  One spectrum is alive at a time."""
-    B, L = x.shape
-    per_scale = []
-    for (n, hop, _), w, (cols, _t) in zip(scales, windows, tables):
-        out = torch.empty((B, 3), dtype=torch.float64, device=x.device)
-        for b0, b1 in _specdist_chunks(B, L, n, hop):
-            M = _mel_of(x[b0:b1], w, n, hop, cols)
-            Q = _mel_of(y[b0:b1], w, n, hop, cols)
-            ops.mel_distance_sums(M, Q, eps, out=out[b0:b1])
-            del M, Q
-        per_scale.append(out)
-    return torch.stack(per_scale, 1)
+    """_dist_sums of the two arrays of mel rows of a chunk of clips (ops.mel_distance_sums).  One spectrum is alive at a
+    time, so the peak is 512 MiB."""
+    return _dist_sums(x, y, scales, lambda s, c: _mel_of(c, windows[s], *scales[s][:2], tables[s][0]),
+                      ops.mel_distance_sums, eps)
 
 
 def meldist_loss(sums, L, scales, lin_weight, log_weight):
-    """The per-clip loss (B,) float32 of the sums: sum over scales of lin_weight S_D / S_B + log_weight S_L / n,
-    n = T n_mels cells."""
-    loss = (sums[:, :, 0] / sums[:, :, 1]).sum(1) * lin_weight
-    for s, (n, hop, n_mels) in enumerate(scales):
-        cells = (1 + (L - (n & 1)) // hop) * n_mels
-        loss = loss + sums[:, s, 2] * (log_weight / cells)
-    return loss.float()
+    """_dist_loss with n = T n_mels cells per clip."""
+    return _dist_loss(sums, [_frames(L, n, hop) * n_mels for n, hop, n_mels in scales], lin_weight, log_weight)
 
 
 class MelSpectralDistanceFunction(torch.autograd.Function):
@@ -377,9 +401,9 @@ class MelSpectralDistanceFunction(torch.autograd.Function):
     Saves the two audios and the (B, n_scales, 3) sums, and nothing else.  Per scale, chunk of clips and input that
     needs a gradient, the backward rebuilds the OTHER signal's mel rows (spectrum, ops.mel_rows, spectrum freed), then
     this signal's spectrum, turns it into its own gradient in place (ops.mel_distance_backward) and runs the STFT
-    adjoint -- into the result for the first scale, into a (chunk, L) scratch that is added to it for every later one.
-    The x-only backward never holds two spectra and never runs a backward kernel over Y.  The windows and the banks
-    are constants of the graph."""
+    adjoint -- into the result for the first scale, into a (chunk, L) scratch that is added to it for every later one
+    (_DistBackward).  The x-only backward never holds two spectra and never runs a backward kernel over Y.  The windows
+    and the banks are constants of the graph."""
 
     @staticmethod
     def forward(ctx, x, y, windows, scales, tables, lin_weight, log_weight, eps):
@@ -393,26 +417,18 @@ class MelSpectralDistanceFunction(torch.autograd.Function):
     def backward(ctx, gclip):
         x, y, sums = ctx.saved_tensors
         need = ctx.needs_input_grad[:2]
-        B, L = x.shape
-        g = ops._f32c(gclip)
-        grads = [torch.empty((B, L), dtype=torch.float32, device=x.device) if nd else None for nd in need]
-        rows = max([b1 - b0 for n, hop, _ in ctx.scales[1:] for b0, b1 in _specdist_chunks(B, L, n, hop)[:1]], default=0)
-        scratch = torch.empty((rows, L), dtype=torch.float32, device=x.device)
-        for s, ((n, hop, _), w, (cols, cols_t)) in enumerate(zip(ctx.scales, ctx.windows, ctx.tables)):
-            sums_s = sums[:, s].contiguous()
-            for b0, b1 in _specdist_chunks(B, L, n, hop):
-                for side, (own, other, grad) in enumerate(((x, y, grads[0]), (y, x, grads[1]))):
-                    if grad is None:
-                        continue
-                    O = _mel_of(other[b0:b1], w, n, hop, cols)
-                    S = ops.stft_forward(own[b0:b1], w, n, hop, center=True)
-                    ops.mel_distance_backward(S, O, sums_s[b0:b1], g[b0:b1], cols, cols_t, *ctx.weights, ctx.eps, side)
-                    out = grad[b0:b1] if s == 0 else scratch[:b1 - b0]      # stft_backward overwrites its out
-                    ops.stft_backward(S, w, n, hop, L, out=out)
-                    if s:
-                        grad[b0:b1].add_(out)
-                    del S, O
-        return grads[0], grads[1], None, None, None, None, None, None
+        bwd = _DistBackward(x, gclip, need, ctx.scales, ctx.windows)
+        for s, b0, b1, sums_c, g in bwd.chunks(sums):
+            (n, hop, _), w, (cols, cols_t) = ctx.scales[s], ctx.windows[s], ctx.tables[s]
+            for side, (own, other) in enumerate(((x, y), (y, x))):
+                if not need[side]:
+                    continue
+                O = _mel_of(other[b0:b1], w, n, hop, cols)
+                S = ops.stft_forward(own[b0:b1], w, n, hop, center=True)
+                ops.mel_distance_backward(S, O, sums_c, g, cols, cols_t, *ctx.weights, ctx.eps, side)
+                bwd.put(side, S, s, b0, b1)
+                del S, O
+        return bwd.grads[0], bwd.grads[1], None, None, None, None, None, None
 
 
 # ---- PQMF (transforms.PQMF): analysis and synthesis are each other's transpose up to n_band ---------------------------------

@@ -351,18 +351,11 @@ int launch_magnitude_backward(const MagBwdParams& p, hipStream_t stream) {
   }
   const int k_pad = pad64(p.K), n_pad = pad64(p.N);
   const size_t per_wave = sizeof(float) * (size_t)(k_pad + n_pad);
-  const long long tab = band_tab_floats(band_cols_floats(p.t) + band_cols_floats(p.f));
-  auto run = [&](auto kernel, int wpb, long long tab_floats) {   // one row group: the wpb rows of a workgroup
-    return band_launch(kernel, wpb, sizeof(float) * tab_floats + wpb * per_wave, (p.rows + wpb - 1) / wpb, stream, p, k_pad,
-                       n_pad, (int)tab_floats);
-  };
-  if (sizeof(float) * tab + 4 * per_wave <= kBandLdsBudget)
-    return p.K <= 9 * 64 ? run(mag_bwd_banded_kernel<true, 9>, 4, tab)    // n_fft <= 1024
-                         : run(mag_bwd_banded_kernel<true, 0>, 4, tab);
-  if (per_wave > kBandLdsBudget) return -2;
-  int wpb = (int)(kBandLdsBudget / per_wave);
-  if (wpb > 4) wpb = 4;
-  return run(mag_bwd_banded_kernel<false, 0>, wpb, 0);
+  const BandPlan pl = band_plan(band_tab_floats(band_cols_floats(p.t) + band_cols_floats(p.f)), per_wave);
+  if (!pl.ok) return -2;
+  auto run = [&](auto kernel) { return band_launch_rows(kernel, pl, p.rows, stream, p, k_pad, n_pad, (int)pl.tab_floats); };
+  if (!pl.tab_lds) return run(mag_bwd_banded_kernel<false, 0>);
+  return p.K <= kBandKit * 64 ? run(mag_bwd_banded_kernel<true, kBandKit>) : run(mag_bwd_banded_kernel<true, 0>);
 }
 
 }  // namespace at_hip

@@ -1,12 +1,14 @@
 // band_cols.h -- what the banded backward kernels share (mag_bwd_banded_kernel of autograd.hip, maginv_bwd_banded_kernel
 // of invert_grad.hip, mfcc_bwd_kernel of mfcc_grad.hip): a bank as bands by column, its staging in LDS, the walk of one
-// column, the row kept in registers, the LDS plan and the launcher.
+// column, the row kept in registers, the LDS plan (band_plan.h) and the launcher.
 //
 // A (K x N) bank by column (utils.banded.bank_columns): column j holds len[j] weights at w[off[j] ..] for the rows
 // start[j] .. start[j] + len[j] - 1.  The transposed bank is the same tables of bank^T (K columns).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
+
+#include "band_plan.h"
 
 namespace at_hip {
 
@@ -16,15 +18,8 @@ struct BandCols {
   int n, nnz;
 };
 
-// ---- LDS plan ---------------------------------------------------------------------------------------------------------
-
-constexpr size_t kBandLdsBudget = 160 * 1024;   // dynamic LDS of one workgroup (the tests' case files restate it)
-
-inline int pad64(int x) { return (x + 63) / 64 * 64; }
 // floats of one bank's tables in LDS
 inline long long band_cols_floats(const BandCols& c) { return 3LL * c.n + c.nnz; }
-// the staged tables end on a float4 boundary
-inline long long band_tab_floats(long long floats) { return (floats + 3) / 4 * 4; }
 
 // ---- device side ------------------------------------------------------------------------------------------------------
 
@@ -99,6 +94,12 @@ int band_launch(Kernel kernel, int wpb, size_t lds, long long units, hipStream_t
   if (blocks > units) blocks = units;
   hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(64 * wpb), lds, stream, args...);
   return hipGetLastError() == hipSuccess ? 0 : -5;
+}
+
+// band_launch of a one-wave-per-row kernel under the plan pl: one work unit is a row group, the wpb rows of a workgroup
+template <typename Kernel, typename... Args>
+int band_launch_rows(Kernel kernel, const BandPlan& pl, long long rows, hipStream_t stream, Args... args) {
+  return band_launch(kernel, pl.wpb, pl.lds, (rows + pl.wpb - 1) / pl.wpb, stream, args...);
 }
 
 }  // namespace at_hip

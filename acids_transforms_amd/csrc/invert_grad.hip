@@ -138,16 +138,10 @@ static int launch_maginv_form(const MagInvBwdParams& p, hipStream_t stream) {
   const int k_pad = pad64(p.K), n_pad = pad64(p.N);
   const size_t per_wave = sizeof(float) * (size_t)(POLAR ? n_pad + 2 * k_pad : n_pad);
   // tables: the transposed bank's and, polar, the bank's
-  const long long tab = band_tab_floats(band_cols_floats(p.t) + (POLAR ? band_cols_floats(p.f) : 0));
-  auto run = [&](auto kernel, int wpb, long long tab_floats) {   // one row group: the wpb rows of a workgroup
-    return band_launch(kernel, wpb, sizeof(float) * tab_floats + wpb * per_wave, (p.rows + wpb - 1) / wpb, stream, p, k_pad,
-                       n_pad, (int)tab_floats);
-  };
-  if (sizeof(float) * tab + 4 * per_wave <= kBandLdsBudget) return run(maginv_bwd_banded_kernel<true, POLAR>, 4, tab);
-  if (per_wave > kBandLdsBudget) return -2;
-  int wpb = (int)(kBandLdsBudget / per_wave);
-  if (wpb > 4) wpb = 4;
-  return run(maginv_bwd_banded_kernel<false, POLAR>, wpb, 0);
+  const BandPlan pl = band_plan(band_tab_floats(band_cols_floats(p.t) + (POLAR ? band_cols_floats(p.f) : 0)), per_wave);
+  if (!pl.ok) return -2;
+  auto run = [&](auto kernel) { return band_launch_rows(kernel, pl, p.rows, stream, p, k_pad, n_pad, (int)pl.tab_floats); };
+  return pl.tab_lds ? run(maginv_bwd_banded_kernel<true, POLAR>) : run(maginv_bwd_banded_kernel<false, POLAR>);
 }
 
 int launch_magnitude_invert_backward(const MagInvBwdParams& p, hipStream_t stream) {

@@ -17,28 +17,14 @@
 // runs -- the recomputed value has the bits of the stored one, so x == y gives an exactly zero d in every cell.
 //
 // Rows: one wave per row, wpb rows per workgroup, persistent workgroups, the bank tables staged in LDS once per
-// workgroup (band_cols.h).  The plan is launch_magnitude_backward's: tables in LDS when tables + 4 waves fit
-// kBandLdsBudget, else tables from global memory with as many waves as fit; the row in registers when K <= 576.
+// workgroup (band_cols.h), under the one row plan of the banded backward kernels (band_plan.h).
 // md_rows_kernel strides its row groups over the grid; md_backward_kernel gives each workgroup a contiguous run of
 // them, so that a clip's constants are formed once per clip and workgroup, not once per row.
-// Sums: spectral_distance.hip's order rule on float cells (sd_fold.h): slices of kMdSlice cells, one workgroup per
-// slice, lane t adds cells t, t + 256, ... in order, fixed xor tree, waves in order, slices added in order in double.
-// The grid is exactly B x ceil(n / kMdSlice); no float atomics.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "../../include/acids_hip.h"
+// Sums, the clip's constants and the per-cell derivatives: distance_core.h, the sums on float cells as stored.
 #include "band_cols.h"
-#include "sd_fold.h"
+#include "distance_core.h"
 
 namespace at_hip {
-
-constexpr int kMdThreads = 256;
-constexpr int kMdPerLane = 16;
-constexpr int kMdSlice = kMdThreads * kMdPerLane;   // cells per slice (mel_distance_cases.py restates it)
-constexpr int kMdKit = 9;                           // 64-bin segments of a row kept in registers: K <= 576
-
-__device__ __forceinline__ float md_abs(float2 v) { return __builtin_amdgcn_sqrtf(fmaf(v.x, v.x, v.y * v.y)); }
 
 // |row| into the wave's LDS slice a; KIT > 0: the row stays in xv.  The one place a magnitude is formed in this file.
 // The register row is band_row_load's, element lane + 64 q in xv[q], but loaded without a branch (the index clamped to
@@ -101,59 +87,14 @@ __global__ void md_rows_kernel(MelRowsParams p, int k_pad, int tab_floats) {
 static int launch_mel_rows(const MelRowsParams& p, hipStream_t stream) {
   const int k_pad = pad64(p.K);
   const size_t per_wave = sizeof(float) * (size_t)k_pad;
-  const long long tab = band_tab_floats(band_cols_floats(p.f));
-  auto run = [&](auto kernel, int wpb, long long tab_floats) {
-    return band_launch(kernel, wpb, sizeof(float) * tab_floats + wpb * per_wave, (p.rows + wpb - 1) / wpb, stream, p, k_pad,
-                       (int)tab_floats);
-  };
-  if (sizeof(float) * tab + 4 * per_wave <= kBandLdsBudget)
-    return p.K <= kMdKit * 64 ? run(md_rows_kernel<true, kMdKit>, 4, tab) : run(md_rows_kernel<true, 0>, 4, tab);
-  if (per_wave > kBandLdsBudget) return AT_EUNSUPPORTED;
-  int wpb = (int)(kBandLdsBudget / per_wave);
-  if (wpb > 4) wpb = 4;
-  return run(md_rows_kernel<false, 0>, wpb, 0);
+  const BandPlan pl = band_plan(band_tab_floats(band_cols_floats(p.f)), per_wave);
+  if (!pl.ok) return AT_EUNSUPPORTED;
+  auto run = [&](auto kernel) { return band_launch_rows(kernel, pl, p.rows, stream, p, k_pad, (int)pl.tab_floats); };
+  if (!pl.tab_lds) return run(md_rows_kernel<false, 0>);
+  return p.K <= kBandKit * 64 ? run(md_rows_kernel<true, kBandKit>) : run(md_rows_kernel<true, 0>);
 }
 
-// ---- 2. sums ----------------------------------------------------------------------------------------------------------
-
-// workgroup blk reduces slice blk % slices of clip blk / slices into partial[blk][3]
-__global__ __launch_bounds__(kMdThreads) void md_slice_sums_kernel(const float* __restrict__ M,
-                                                                    const float* __restrict__ Q, long long n,
-                                                                    long long slices, float eps,
-                                                                    float* __restrict__ partial) {
-  const long long blk = blockIdx.x;
-  const long long b = blk / slices;
-  const long long i0 = (blk - b * slices) * kMdSlice + threadIdx.x;
-  const float* mr = M + b * n;
-  const float* qr = Q + b * n;
-  float sd = 0.f, sb = 0.f, sl = 0.f;
-  float mv[kMdPerLane], qv[kMdPerLane];
-#pragma unroll
-  for (int j = 0; j < kMdPerLane; ++j) {      // every load of the slice is issued before the first use
-    const long long i = i0 + (long long)j * kMdThreads;
-    const bool live = i < n;
-    mv[j] = live ? mr[i] : 0.f;
-    qv[j] = live ? qr[i] : 0.f;
-  }
-#pragma unroll
-  for (int j = 0; j < kMdPerLane; ++j) {
-    if (i0 + (long long)j * kMdThreads < n) {
-      const float d = mv[j] - qv[j];
-      sd = fmaf(d, d, sd);
-      sb = fmaf(qv[j], qv[j], sb);
-      sl += fabsf(logf(mv[j] + eps) - logf(qv[j] + eps));
-    }
-  }
-  sd_block_fold<kMdThreads>(sd, sb, sl);
-  if (threadIdx.x == 0) {
-    float* dst = partial + 3 * blk;
-    dst[0] = sd; dst[1] = sb; dst[2] = sl;
-  }
-}
-
-static inline long long md_slices(long long n) { return (n + kMdSlice - 1) / kMdSlice; }
-
-// ---- 3. backward ------------------------------------------------------------------------------------------------------
+// ---- 2. backward ------------------------------------------------------------------------------------------------------
 
 struct MelDistBwdParams {
   float2* S;              // (B T) x K: the spectrum, overwritten by its gradient
@@ -167,14 +108,6 @@ struct MelDistBwdParams {
   float lin_weight, log_weight, eps;
   int side;               // 0: S = X, O = Q;  1: S = Y, O = M
 };
-
-// dA at bin k of the row -> the gradient of the bin x
-__device__ __forceinline__ float2 md_grad(float dA, float2 x) {
-  const float a = md_abs(x);
-  if (a == 0.f) return make_float2(0.f, 0.f);
-  const float r = dA / a;
-  return make_float2(r * x.x, r * x.y);
-}
 
 template <bool TAB_LDS, int KIT>
 __global__ void md_backward_kernel(MelDistBwdParams p, int k_pad, int n_pad, int tab_floats) {
@@ -208,13 +141,8 @@ __global__ void md_backward_kernel(MelDistBwdParams p, int k_pad, int n_pad, int
     float2 xv[KIT > 0 ? KIT : 1];
     if (live) md_row_abs<KIT>(xv, srow, lane, K, a);
     if (live && row >= clip_end) {
-      // in double: S_B^2 of a loud clip leaves fp32's range
       const long long b = row / p.T;
-      const double g = (double)p.gclip[b], s_d = p.sums[3 * b], inv_sb = 1.0 / p.sums[3 * b + 1];
-      const double lin2 = 2.0 * g * (double)p.lin_weight * inv_sb;
-      c_lin = (float)lin2;                                   // g lin_weight 2 / S_B
-      c_sq = (float)(lin2 * s_d * inv_sb);                   // g lin_weight 2 S_D / S_B^2
-      c_log = (float)(g * (double)p.log_weight / cells);     // g log_weight / n
+      dist_consts((double)p.gclip[b], p.sums[3 * b], p.sums[3 * b + 1], p.lin_weight, p.log_weight, cells, c_lin, c_sq, c_log);
       clip_end = (b + 1) * p.T;
     }
     __syncthreads();
@@ -224,9 +152,9 @@ __global__ void md_backward_kernel(MelDistBwdParams p, int k_pad, int n_pad, int
         const float other = orow[j];                                     // in flight during the walk
         const float own = band_dot(f, j, a);
         const float d = p.side == 0 ? own - other : other - own;         // M - Q
-        const float lg = d > 0.f ? c_log : (d < 0.f ? -c_log : 0.f * d);  // c_log sgn(d); NaN stays NaN
+        const float lg = dist_lg(d, c_log);
         const float lind = c_lin * d;
-        dm[j] = p.side == 0 ? lind + lg / (own + p.eps) : -lind - c_sq * own - lg / (own + p.eps);
+        dm[j] = p.side == 0 ? dist_d_generated(lind, lg, own, p.eps) : dist_d_target(lind, lg, own, c_sq, p.eps);
       }
     }
     __syncthreads();
@@ -235,10 +163,13 @@ __global__ void md_backward_kernel(MelDistBwdParams p, int k_pad, int n_pad, int
 #pragma unroll
         for (int q = 0; q < KIT; ++q) {
           const int k = lane + 64 * q;
-          if (k < K) srow[k] = md_grad(band_dot(t, k, dm), xv[q]);
+          if (k < K) srow[k] = dist_bin_grad(band_dot(t, k, dm), md_abs(xv[q]), xv[q]);
         }
       } else {
-        for (int k = lane; k < K; k += 64) srow[k] = md_grad(band_dot(t, k, dm), srow[k]);
+        for (int k = lane; k < K; k += 64) {
+          const float2 x = srow[k];
+          srow[k] = dist_bin_grad(band_dot(t, k, dm), md_abs(x), x);
+        }
       }
     }
     __syncthreads();
@@ -248,17 +179,11 @@ __global__ void md_backward_kernel(MelDistBwdParams p, int k_pad, int n_pad, int
 static int launch_mel_distance_backward(const MelDistBwdParams& p, hipStream_t stream) {
   const int k_pad = pad64(p.K), n_pad = pad64(p.N);
   const size_t per_wave = sizeof(float) * (size_t)(k_pad + n_pad);
-  const long long tab = band_tab_floats(band_cols_floats(p.t) + band_cols_floats(p.f));
-  auto run = [&](auto kernel, int wpb, long long tab_floats) {   // one row group: the wpb rows of a workgroup
-    return band_launch(kernel, wpb, sizeof(float) * tab_floats + wpb * per_wave, (p.rows + wpb - 1) / wpb, stream, p, k_pad,
-                       n_pad, (int)tab_floats);
-  };
-  if (sizeof(float) * tab + 4 * per_wave <= kBandLdsBudget)
-    return p.K <= kMdKit * 64 ? run(md_backward_kernel<true, kMdKit>, 4, tab) : run(md_backward_kernel<true, 0>, 4, tab);
-  if (per_wave > kBandLdsBudget) return AT_EUNSUPPORTED;
-  int wpb = (int)(kBandLdsBudget / per_wave);
-  if (wpb > 4) wpb = 4;
-  return run(md_backward_kernel<false, 0>, wpb, 0);
+  const BandPlan pl = band_plan(band_tab_floats(band_cols_floats(p.t) + band_cols_floats(p.f)), per_wave);
+  if (!pl.ok) return AT_EUNSUPPORTED;
+  auto run = [&](auto kernel) { return band_launch_rows(kernel, pl, p.rows, stream, p, k_pad, n_pad, (int)pl.tab_floats); };
+  if (!pl.tab_lds) return run(md_backward_kernel<false, 0>);
+  return p.K <= kBandKit * 64 ? run(md_backward_kernel<true, kBandKit>) : run(md_backward_kernel<true, 0>);
 }
 
 static inline bool md_cols_ok(const int* start, const int* len, const int* off, const float* w, int nnz) {
@@ -280,27 +205,14 @@ int at_mel_rows(const float* X_complex, int64_t rows, int K, int N, const int* f
   return launch_mel_rows(p, (hipStream_t)stream);
 }
 
-size_t at_mel_distance_workspace_bytes(int64_t B, int64_t n) {
-  if (B <= 0 || n < 1) return 0;
-  return sizeof(float) * 3 * (size_t)B * (size_t)at_hip::md_slices(n);
-}
+size_t at_mel_distance_workspace_bytes(int64_t B, int64_t n) { return at_hip::dist_workspace_bytes(B, n); }
 
 int at_mel_distance_sums(const float* M, const float* Q, int64_t B, int64_t n, float eps, double* sums, void* workspace,
                          size_t workspace_bytes, void* stream) {
   using namespace at_hip;
-  if (B == 0) return AT_OK;
+  if (B == 0) return AT_OK;                                   // before n and eps, unlike at_spectral_distance_sums
   if (B < 0 || n < 1 || !(eps >= 0.f)) return AT_EINVAL;
-  if (!M || !Q || !sums) return AT_EINVAL;
-  const long long slices = md_slices(n), blocks = (long long)B * slices;
-  if (blocks > 0x7fffffffLL) return AT_EUNSUPPORTED;
-  if (!workspace || (((uintptr_t)workspace) & 3) || workspace_bytes < at_mel_distance_workspace_bytes(B, n))
-    return AT_EWORKSPACE;
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(md_slice_sums_kernel, dim3((unsigned)blocks), dim3(kMdThreads), 0, s, M, Q, (long long)n, slices, eps,
-                     (float*)workspace);
-  hipLaunchKernelGGL(sd_clip_sums_kernel<kMdThreads>, dim3((unsigned)((3 * B + kMdThreads - 1) / kMdThreads)),
-                     dim3(kMdThreads), 0, s, (const float*)workspace, (long long)B, slices, sums);
-  return hipGetLastError() == hipSuccess ? AT_OK : AT_ELAUNCH;
+  return dist_sums(M, Q, B, n, eps, sums, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int at_mel_distance_backward(float* S_complex, const float* other, int64_t B, int64_t T, int K, int N,

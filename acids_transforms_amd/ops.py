@@ -780,20 +780,25 @@ def _sd_spectra(X, Y):
     return X, Y, X.shape[0], n
 
 
+def _distance_sums(workspace_bytes, entry, what, A, Bm, B, n, eps, out):
+    """The library's sums `entry` (named `what`) on the cells A, Bm of B clips of n cells, with its workspace."""
+    if out is not None:
+        assert out.shape == (B, 3) and out.dtype == torch.float64 and out.is_contiguous()
+    sums = out if out is not None else torch.empty((B, 3), dtype=torch.float64, device=A.device)
+    wsb = workspace_bytes(B, n)
+    ws = _workspace(wsb, A.device)
+    check(entry(ptr(A), ptr(Bm), B, n, eps, ptr(sums), ptr(ws), wsb, stream_ptr()), what)
+    return sums
+
+
 def spectral_distance_sums(X, Y, eps=1.1920929e-07, out=None):
     """Per-clip sums of the spectral distance between X (generated) and Y (target), both (B, T, F) or (B, n) complex64:
     (B, 3) float64 holding S_D = sum (|X| - |Y|)^2, S_B = sum |Y|^2 and S_L = sum |ln(|X| + eps) - ln(|Y| + eps)|
     (written into `out`, a contiguous (B, 3) float64 tensor, when given).  A clip's bits depend on its own bins only."""
     require_device(X, Y, out)
     X, Y, B, n = _sd_spectra(X, Y)
-    if out is not None:
-        assert out.shape == (B, 3) and out.dtype == torch.float64 and out.is_contiguous()
-    sums = out if out is not None else torch.empty((B, 3), dtype=torch.float64, device=X.device)
-    wsb = lib().at_spectral_distance_workspace_bytes(B, n)
-    ws = _workspace(wsb, X.device)
-    check(lib().at_spectral_distance_sums(ptr(X), ptr(Y), B, n, eps, ptr(sums), ptr(ws), wsb, stream_ptr()),
-          "at_spectral_distance_sums")
-    return sums
+    return _distance_sums(lib().at_spectral_distance_workspace_bytes, lib().at_spectral_distance_sums,
+                          "at_spectral_distance_sums", X, Y, B, n, eps, out)
 
 
 def spectral_distance_backward(X, Y, sums, gclip, lin_weight=1.0, log_weight=1.0, eps=1.1920929e-07, need_x=True,
@@ -837,14 +842,8 @@ def mel_distance_sums(M, Q, eps=1.1920929e-07, out=None):
     assert M.shape == Q.shape and M.ndim >= 2, "M and Q must be mel rows of one shape (B, ...)"
     B = M.shape[0]
     n = M[0].numel() if B else max(M.numel(), 1)
-    if out is not None:
-        assert out.shape == (B, 3) and out.dtype == torch.float64 and out.is_contiguous()
-    sums = out if out is not None else torch.empty((B, 3), dtype=torch.float64, device=M.device)
-    wsb = lib().at_mel_distance_workspace_bytes(B, n)
-    ws = _workspace(wsb, M.device)
-    check(lib().at_mel_distance_sums(ptr(M), ptr(Q), B, n, eps, ptr(sums), ptr(ws), wsb, stream_ptr()),
-          "at_mel_distance_sums")
-    return sums
+    return _distance_sums(lib().at_mel_distance_workspace_bytes, lib().at_mel_distance_sums, "at_mel_distance_sums",
+                          M, Q, B, n, eps, out)
 
 
 def mel_distance_backward(S, other, sums, gclip, bank_cols, bank_t_cols, lin_weight=1.0, log_weight=1.0,

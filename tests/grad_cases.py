@@ -7,7 +7,7 @@ adj_ola_fold_kernel, launch_magnitude_backward)."""
 
 CHUNK_FLOATS = 1 << 28      # adj_chunk_clips: a chunk's irFFT frames stay within 1 GiB
 GRID_Y = 65535              # launch_adj_ola_fold: rows of blocks, one per clip, at most this many
-LDS_BUDGET = 160 * 1024     # kBandLdsBudget (csrc/band_cols.h)
+LDS_BUDGET = 160 * 1024     # kBandLdsBudget (csrc/band_plan.h)
 
 
 def is_pow2(n):

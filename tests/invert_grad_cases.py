@@ -6,7 +6,7 @@ test_invert_grad_cases_cpu.py checks that the sweep reaches every class named he
 it.  The bank shapes are those of grad_cases.MAG_CASES."""
 import grad_cases as G
 
-LDS_BUDGET = 160 * 1024          # kBandLdsBudget (csrc/band_cols.h)
+LDS_BUDGET = 160 * 1024          # kBandLdsBudget (csrc/band_plan.h)
 LDS_PER_CU = 160 * 1024          # gfx950
 THREADS_PER_CU = 2048            # 8 waves on each of 4 SIMDs
 CUS = 256

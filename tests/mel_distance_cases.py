@@ -12,7 +12,7 @@ from acids_transforms_amd.utils.melbank import melscale_fbanks
 from invert_grad_cases import CUS, LDS_BUDGET, row_loop_trips
 
 EPS = SD.EPS
-SLICE = 4096                    # kMdSlice of mel_distance.hip: cells one workgroup reduces
+SLICE = 4096                    # kDistSlice of csrc/distance_core.h: cells one workgroup reduces
 SR = 44100
 
 DEFAULT_SCALES = ((2048, 512, 320), (1024, 256, 160), (512, 128, 80), (256, 64, 40), (128, 32, 20))
@@ -80,7 +80,7 @@ def table_floats(K, N, f_nnz, t_nnz=None):
 
 def plan(K, N, f_nnz, t_nnz=None):
     """(class, waves per workgroup, dynamic LDS bytes, row in registers) of at_mel_rows (t_nnz None) or of
-    at_mel_distance_backward: launch_magnitude_backward's rule."""
+    at_mel_distance_backward: band_plan's rule (csrc/band_plan.h)."""
     per_wave = 4 * (pad64(K) + (pad64(N) if t_nnz is not None else 0))
     tab = 4 * table_floats(K, N, f_nnz, t_nnz)
     if tab + 4 * per_wave <= LDS_BUDGET:

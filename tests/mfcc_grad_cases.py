@@ -6,7 +6,7 @@ csrc/mfcc_grad.hip (launch_mfcc_backward, mfcc_bwd_kernel), autograd.py (mfcc_ch
 (MFCC._forward_plain)."""
 
 TILE = 32                   # kMfccTile: frames of one clip per workgroup tile
-LDS_BUDGET = 160 * 1024     # kBandLdsBudget (csrc/band_cols.h)
+LDS_BUDGET = 160 * 1024     # kBandLdsBudget (csrc/band_plan.h)
 CHUNK_ELEMS = 1 << 26       # autograd.MFCC_CHUNK_ELEMS: complex64 elements of spectrum per chunk (512 MiB)
 
 

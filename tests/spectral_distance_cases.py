@@ -5,7 +5,7 @@ import numpy as np
 import torch
 
 EPS = float(torch.finfo(torch.float32).eps)
-SLICE = 4096                    # kSdSlice of spectral_distance.hip: bins one workgroup reduces
+SLICE = 4096                    # kDistSlice of csrc/distance_core.h: bins one workgroup reduces
 CHUNK_ELEMS = 1 << 26           # autograd.SPECDIST_CHUNK_ELEMS
 
 DEFAULT_SCALES = ((2048, 512), (1024, 256), (512, 128), (256, 64), (128, 32))

@@ -10,6 +10,7 @@ import torch
 
 import acids_transforms_amd as A
 import mel_distance_cases as C
+from distance_driver_stub import stub_ops
 from acids_transforms_amd import _lib, autograd
 from acids_transforms_amd.utils.banded import bank_columns
 from acids_transforms_amd.utils.melbank import melscale_fbanks
@@ -54,15 +55,20 @@ def test_float64_model_matches_torch_autograd(need_x, need_y, weights):
 
 
 def test_case_tables_and_plan_rule():
-    src = open(os.path.join(ROOT, "acids_transforms_amd", "csrc", "mel_distance.hip")).read()
-    assert re.search(r"kMdThreads = 256;", src) and re.search(r"kMdPerLane = 16;", src) and C.SLICE == 256 * 16
-    assert '#include "sd_fold.h"' in src and '#include "band_cols.h"' in src
-    sd = open(os.path.join(ROOT, "acids_transforms_amd", "csrc", "spectral_distance.hip")).read()
-    fold = open(os.path.join(ROOT, "acids_transforms_amd", "csrc", "sd_fold.h")).read()
-    for name in ("sd_block_fold", "sd_clip_sums_kernel"):             # stated once, in the shared header
-        assert re.search(r"void %s\(" % name, fold)
-        assert not re.search(r"void %s\(" % name, sd) and not re.search(r"void %s\(" % name, src)
+    csrc = os.path.join(ROOT, "acids_transforms_amd", "csrc")
+    src = open(os.path.join(csrc, "mel_distance.hip")).read()
+    sd = open(os.path.join(csrc, "spectral_distance.hip")).read()
+    core = open(os.path.join(csrc, "distance_core.h")).read()
+    assert re.search(r"kDistThreads = 256;", core) and re.search(r"kDistPerLane = 16;", core) and C.SLICE == 256 * 16
+    assert '#include "distance_core.h"' in src and '#include "band_cols.h"' in src and '#include "distance_core.h"' in sd
+    # stated once, in the shared header; both files go through its launcher and its constants
+    for name in ("sd_block_fold", "sd_clip_sums_kernel", "dist_slice_sums_kernel", "dist_consts", "dist_d_generated",
+                 "dist_d_target"):
+        assert re.search(r"(void|float) %s\(" % name, core)
+        assert not re.search(r"(void|float) %s\(" % name, sd) and not re.search(r"(void|float) %s\(" % name, src)
+    for name in ("dist_sums(", "dist_workspace_bytes(", "dist_consts(", "dist_d_generated(", "dist_d_target(", "dist_bin_grad("):
         assert name in sd and name in src
+    assert not re.search(r"k(Sd|Md)(Threads|PerLane|Slice)", sd + src)       # no slice geometry of their own
     # the default ladder's empty filters, and DC / Nyquist rows empty at every scale of the sweep
     assert tuple(C.empty_filters(C.bank(n // 2 + 1, m)) for n, _, m in C.DEFAULT_SCALES) == C.DEFAULT_EMPTY
     for n, _, m in C.SCALES:
@@ -217,3 +223,74 @@ def test_autograd_surface():
     want = 0.5 * (2.0 / 4.0 + 1.0 / 2.0) + 2.0 * (6.0 / (129 * 20) + 3.0 / (65 * 40))
     got = autograd.meldist_loss(sums, 4096, scales, 0.5, 2.0)
     assert got.dtype == torch.float32 and abs(float(got[0]) - want) < 1e-6 * want
+
+
+def test_module_surface_is_unchanged():
+    """state_dict keys, repr and every constructor and call message, as literals."""
+    crit = A.MelSpectralDistance()
+    assert list(crit.state_dict().keys()) == ["window_0", "mel_bank_0", "window_1", "mel_bank_1", "window_2", "mel_bank_2",
+                                              "window_3", "mel_bank_3", "window_4", "mel_bank_4"]
+    assert repr(crit) == ("MelSpectralDistance(scales=((2048, 512, 320), (1024, 256, 160), (512, 128, 80), (256, 64, 40), "
+                          "(128, 32, 20)), sr=44100, lin_weight=1, log_weight=1, reduction=mean)")
+    for kw, msg in ((dict(window="nope"), "Window nope is not known"),
+                    (dict(reduction="median"), "reduction median not known (none, sum, mean)"),
+                    (dict(scales=()), "at least one (n_fft, hop, n_mels) scale is needed"),
+                    (dict(scales=((1, 1, 4),)), "scale (1, 1, 4): n_fft must lie in 2 .. 16384 and hop be positive"),
+                    (dict(scales=((1024, 0, 4),)), "scale (1024, 0, 4): n_fft must lie in 2 .. 16384 and hop be positive"),
+                    (dict(scales=((1024, 256, 0),)), "scale (1024, 256, 0): n_mels must be at least 1"),
+                    (dict(scales=((1024, 256, 4), (1, 1, 0))), "scale (1, 1, 0): n_fft must lie in 2 .. 16384 and hop be positive"),
+                    (dict(eps=-1.0), "eps must not be negative"),
+                    (dict(window="nope", reduction="median", scales=()), "Window nope is not known"),     # the order
+                    (dict(scales=((1024, 256, 0),), eps=-1.0), "scale (1024, 256, 0): n_mels must be at least 1")):
+        with pytest.raises(ValueError) as e:
+            A.MelSpectralDistance(**kw)
+        assert str(e.value) == msg
+    with pytest.raises(ValueError):
+        A.MelSpectralDistance(scales=((1024, 256),))             # a scale is a triple: the unpacking's own error
+    for a, b, msg in ((torch.zeros(2, 4096), torch.zeros(3, 4096), "x and y must have one shape, got (2, 4096) and (3, 4096)"),
+                      (torch.zeros(2, 1024), torch.zeros(2, 1024),
+                       "clips of 1024 samples are too short for n_fft 2048 (reflect padding needs more than n_fft // 2)"),
+                      (torch.zeros(()), torch.zeros(()),
+                       "clips of 0 samples are too short for n_fft 2048 (reflect padding needs more than n_fft // 2)")):
+        with pytest.raises(ValueError) as e:
+            crit(a, b)
+        assert str(e.value) == msg
+
+
+@pytest.mark.parametrize("need", [(True, False), (False, True), (True, True)])
+def test_function_goes_through_the_shared_driver(monkeypatch, need):
+    """With ops stubbed: the sums driver and the backward helper are SpectralDistanceFunction's, the chunks follow the
+    patched constant, one spectrum is built per mel_rows call, and only the sides that need a gradient run."""
+    log = stub_ops(monkeypatch, autograd)
+    scales = ((128, 32, 20), (64, 32, 8), (64, 64, 40))
+    B, L = 5, 1024
+    elems = 2 * C.SD.bins(128, 32, L)
+    monkeypatch.setattr(autograd, "SPECDIST_CHUNK_ELEMS", elems)                        # 2, 3 and 5 clips per chunk
+    monkeypatch.setattr(autograd, "MFCC_CHUNK_ELEMS", 1)                                # not this one
+    cuts = [C.SD.chunks(B, C.frames(n, h, L), n, elems=elems) for n, h, _ in scales]
+    assert cuts == [[2, 2, 1], [3, 2], [5]]
+    x, y = (torch.zeros(B, L, requires_grad=nd) for nd in need)
+    windows = tuple(torch.hann_window(n) for n, _, _ in scales)
+    tables = tuple(((torch.zeros(m, dtype=torch.int32),) * 4,) * 2 for _, _, m in scales)
+    loss = autograd.MelSpectralDistanceFunction.apply(x, y, windows, scales, tables, 0.5, 2.0, C.EPS)
+    want = 0.5 * 3 * (1.0 / 2.0) + 2.0 * sum(3.0 / (C.frames(n, h, L) * m) for n, h, m in scales)
+    assert loss.shape == (B,) and loss.dtype == torch.float32 and torch.allclose(loss, torch.full((B,), want))
+    assert [e[0] for e in log].count("_dist_sums") == 1 and ("_DistBackward", None) not in log
+    assert [e[1] for e in log if e[0] == "mel_distance_sums"] == [(c, C.frames(n, h, L), m)
+                                                                 for (n, h, m), cut in zip(scales, cuts) for c in cut]
+    names = [e[0] for e in log if e[0] in ("stft_forward", "mel_rows", "mel_distance_sums")]
+    assert names == ["stft_forward", "mel_rows", "stft_forward", "mel_rows", "mel_distance_sums"] * 6
+    del log[:]
+    loss.sum().backward()
+    assert [e[0] for e in log].count("_DistBackward") == 1
+    sides = [s for s in (0, 1) if need[s]]
+    assert [e[1] for e in log if e[0] == "mel_distance_backward"] == [(c, s) for cut in cuts for c in cut for s in sides]
+    per_side = ["stft_forward", "mel_rows", "stft_forward", "mel_distance_backward", "stft_backward"]
+    assert [e[0] for e in log if e[0] != "_DistBackward"] == per_side * (6 * len(sides))
+    for t, nd in zip((x, y), need):
+        assert (t.grad is None) == (not nd)
+        if nd:
+            assert torch.equal(t.grad, torch.full((B, L), 128.0 + 64.0 + 64.0))        # written once, added twice
+    outs = [e[1] for e in log if e[0] == "stft_backward"]
+    later = {o[2] for o in outs if o[1] != 128}
+    assert len(later) == 1 and not later & {o[2] for o in outs if o[1] == 128}          # one scratch

@@ -89,7 +89,7 @@ def test_chunk_and_tile_restatement():
     assert C.tiles(690) == (22, 18) and C.tiles(64) == (2, 32) and C.tiles(1) == (1, 1) and C.tiles(33) == (2, 1)
     csrc = os.path.join(ROOT, "acids_transforms_amd", "csrc")
     assert re.search(r"kMfccTile = %d;" % C.TILE, open(os.path.join(csrc, "mfcc_grad.hip")).read())
-    assert re.search(r"kBandLdsBudget = 160 \* 1024;", open(os.path.join(csrc, "band_cols.h")).read())
+    assert re.search(r"kBandLdsBudget = 160 \* 1024;", open(os.path.join(csrc, "band_plan.h")).read())
 
 
 def _sweep():

@@ -10,6 +10,7 @@ import torch
 
 import acids_transforms_amd as A
 import spectral_distance_cases as C
+from distance_driver_stub import stub_ops
 from acids_transforms_amd import _lib, autograd
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -63,8 +64,9 @@ def test_chunk_rule():
     # the 2 + 2 + 1 cut of the GPU chunk test holds at every default scale
     for n, hop in C.DEFAULT_SCALES:
         assert C.chunks(5, C.frames(n, hop, C.MODULE_L), n, elems=20000) == [2, 2, 1]
-    src = open(os.path.join(ROOT, "acids_transforms_amd", "csrc", "spectral_distance.hip")).read()
-    assert re.search(r"kSdThreads = 256;", src) and re.search(r"kSdPerLane = 16;", src) and C.SLICE == 256 * 16
+    src = open(os.path.join(ROOT, "acids_transforms_amd", "csrc", "distance_core.h")).read()
+    assert re.search(r"kDistThreads = 256;", src) and re.search(r"kDistPerLane = 16;", src) and C.SLICE == 256 * 16
+    assert re.search(r"kDistSlice = kDistThreads \* kDistPerLane;", src)
     assert [C.slices(T * F) for _, T, F in C.OP_SHAPES] == [1, 1, 3, 87]
 
 
@@ -140,3 +142,76 @@ def test_module_on_the_cpu():
 def test_autograd_surface():
     assert "SpectralDistanceFunction" in autograd.__all__ and "specdist_chunk_clips" in autograd.__all__
     assert issubclass(autograd.SpectralDistanceFunction, torch.autograd.Function)
+
+
+def test_module_surface_is_unchanged():
+    """state_dict keys, repr and every constructor and call message, as literals."""
+    crit = A.SpectralDistance()
+    assert list(crit.state_dict().keys()) == ["window_0", "window_1", "window_2", "window_3", "window_4"]
+    assert repr(crit) == ("SpectralDistance(scales=((2048, 512), (1024, 256), (512, 128), (256, 64), (128, 32)), "
+                          "lin_weight=1, log_weight=1, reduction=mean)")
+    for kw, msg in ((dict(window="nope"), "Window nope is not known"),
+                    (dict(reduction="median"), "reduction median not known (none, sum, mean)"),
+                    (dict(scales=()), "at least one (n_fft, hop) scale is needed"),
+                    (dict(scales=((1, 1),)), "scale (1, 1): n_fft must lie in 2 .. 16384 and hop be positive"),
+                    (dict(scales=((1024, 0),)), "scale (1024, 0): n_fft must lie in 2 .. 16384 and hop be positive"),
+                    (dict(eps=-1.0), "eps must not be negative"),
+                    (dict(window="nope", reduction="median", scales=()), "Window nope is not known"),     # the order
+                    (dict(reduction="median", scales=()), "reduction median not known (none, sum, mean)")):
+        with pytest.raises(ValueError) as e:
+            A.SpectralDistance(**kw)
+        assert str(e.value) == msg
+    with pytest.raises(ValueError):
+        A.SpectralDistance(scales=((1024, 256, 80),))           # a scale is a pair: the unpacking's own error
+    for a, b, msg in ((torch.zeros(2, 4096), torch.zeros(3, 4096), "x and y must have one shape, got (2, 4096) and (3, 4096)"),
+                      (torch.zeros(2, 1024), torch.zeros(2, 1024),
+                       "clips of 1024 samples are too short for n_fft 2048 (reflect padding needs more than n_fft // 2)"),
+                      (torch.zeros(()), torch.zeros(()),
+                       "clips of 0 samples are too short for n_fft 2048 (reflect padding needs more than n_fft // 2)")):
+        with pytest.raises(ValueError) as e:
+            crit(a, b)
+        assert str(e.value) == msg
+
+
+def test_chunk_constants_are_read_at_the_call(monkeypatch):
+    assert autograd.mfcc_chunk_clips(5, 33, 128) == 5 == autograd.specdist_chunk_clips(5, 33, 128)
+    monkeypatch.setattr(autograd, "SPECDIST_CHUNK_ELEMS", 2 * 33 * 65)
+    assert autograd.specdist_chunk_clips(5, 33, 128) == 2 and autograd.mfcc_chunk_clips(5, 33, 128) == 5
+    assert autograd._specdist_chunks(5, 1024, 128, 32) == [(0, 2), (2, 4), (4, 5)]
+    monkeypatch.setattr(autograd, "MFCC_CHUNK_ELEMS", 3 * 33 * 65 + 1)
+    assert autograd.specdist_chunk_clips(5, 33, 128) == 2 and autograd.mfcc_chunk_clips(5, 33, 128) == 3
+    assert autograd._chunk_clips(33 * 65 - 1, 5, 33, 128) == 1          # one clip over the budget: a chunk of one
+
+
+@pytest.mark.parametrize("need", [(True, False), (False, True), (True, True)])
+def test_function_goes_through_the_shared_driver(monkeypatch, need):
+    """With ops stubbed: the sums driver and the backward helper are the shared ones, the chunks follow the patched
+    constant, and the first scale writes into the result while later scales go through the scratch and are added."""
+    log = stub_ops(monkeypatch, autograd)
+    scales = ((128, 32), (64, 32), (64, 64))
+    B, L = 5, 1024
+    monkeypatch.setattr(autograd, "SPECDIST_CHUNK_ELEMS", 2 * C.bins(128, 32, L))       # 2, 3 and 5 clips per chunk
+    cuts = [C.chunks(B, C.frames(n, h, L), n, elems=2 * C.bins(128, 32, L)) for n, h in scales]
+    assert cuts == [[2, 2, 1], [3, 2], [5]]
+    x, y = (torch.zeros(B, L, requires_grad=nd) for nd in need)
+    windows = tuple(torch.hann_window(n) for n, _ in scales)
+    loss = autograd.SpectralDistanceFunction.apply(x, y, windows, scales, 0.5, 2.0, C.EPS)
+    want = 0.5 * 3 * (1.0 / 2.0) + 2.0 * sum(3.0 / C.bins(n, h, L) for n, h in scales)
+    assert loss.shape == (B,) and loss.dtype == torch.float32 and torch.allclose(loss, torch.full((B,), want))
+    assert [e[0] for e in log].count("_dist_sums") == 1 and ("_DistBackward", None) not in log
+    assert [e[1] for e in log if e[0] == "spectral_distance_sums"] == [(c, C.frames(n, h, L), n // 2 + 1)
+                                                                      for (n, h), cut in zip(scales, cuts) for c in cut]
+    del log[:]
+    loss.sum().backward()
+    assert [e[0] for e in log].count("_DistBackward") == 1
+    assert [e[1] for e in log if e[0] == "stft_forward"] == [(c, n, h) for (n, h), cut in zip(scales, cuts) for c in cut
+                                                            for _ in (0, 1)]
+    assert [e[1] for e in log if e[0] == "spectral_distance_backward"] == [(c, need[1]) for cut in cuts for c in cut]
+    for t, nd in zip((x, y), need):
+        assert (t.grad is None) == (not nd)
+        if nd:
+            assert torch.equal(t.grad, torch.full((B, L), 128.0 + 64.0 + 64.0))        # written once, added twice
+    outs = [e[1] for e in log if e[0] == "stft_backward"]
+    first, later = [o for o in outs if o[1] == 128], [o for o in outs if o[1] != 128]
+    assert len(first) == 3 * sum(need) and len(later) == 3 * sum(need)
+    assert len({o[2] for o in later}) == 1 and not {o[2] for o in later} & {o[2] for o in first}      # one scratch
