@@ -27,6 +27,10 @@ PqmfStreamFunction and PqmfStreamInvertFunction are RealtimePQMF's (ops.pqmf_ana
 ops.pqmf_synthesis_stream): the causal bank delayed by D blocks forward, the other kernel ADVANCED by D blocks and
 without state backward; the carried filter state is a constant of the graph like every other streaming state.
 
+ResampleFunction and ResampleStreamFunction are utils.Resample's and utils.RealtimeResample's (resample.hip): sample-rate
+conversion is linear, so both backward passes are one kernel, the transposed polyphase filter (ops.resample_sinc_backward),
+which the streaming form calls with the state's length as the lead of its window; neither saves a tensor.
+
 All backward passes are first-order only (@once_differentiable): create_graph=True raises.
 """
 import torch
@@ -40,7 +44,8 @@ __all__ = ["wants_grad", "StftFunction", "IstftFunction", "IstftPolarFunction", 
            "PhaseScanFunction", "CartesianFunction", "PolarFunction", "PolarIFFunction", "StftPolarFunction",
            "RtStftFunction", "RtIstftFunction", "RtIstftPolarFunction", "OaddFramesFunction", "OaddInvertFunction",
            "SpectralDistanceFunction", "specdist_chunk_clips", "MelSpectralDistanceFunction", "meldist_sums",
-           "meldist_loss", "PqmfFunction", "PqmfInvertFunction", "PqmfStreamFunction", "PqmfStreamInvertFunction"]
+           "meldist_loss", "PqmfFunction", "PqmfInvertFunction", "PqmfStreamFunction", "PqmfStreamInvertFunction",
+           "ResampleFunction", "ResampleStreamFunction"]
 
 
 def wants_grad(x: torch.Tensor) -> bool:
@@ -504,6 +509,46 @@ class PqmfStreamInvertFunction(torch.autograd.Function):
         D = ops.pqmf_stream_sizes(M, ctx.proto.numel())[0]
         gy, _ = ops.pqmf_analysis_stream(gx, None, ctx.proto, ctx.mod, float(M), shift=D, want_state=False)
         return gy.to(ctx.dtype), None, None, None
+
+
+# ---- Resample (utils.Resample / RealtimeResample): the backward is the transposed polyphase filter ------------------------
+
+class ResampleFunction(torch.autograd.Function):
+    """Resample.forward: x (rows, L) float32 -> ops.resample_sinc(x) (rows, ceil(new L / orig)).  Saves no tensor: L,
+    the three integers and the module's bank (a constant of the graph) hang on the node; the backward is
+    ops.resample_sinc_backward with lead = width."""
+
+    @staticmethod
+    def forward(ctx, x, bank, orig, new, width):
+        ctx.bank, ctx.orig, ctx.new, ctx.width, ctx.L, ctx.dtype = bank, orig, new, width, x.shape[-1], x.dtype
+        return ops.resample_sinc(x, orig, new, width, bank)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        gx = ops.resample_sinc_backward(gy, ctx.L, ctx.orig, ctx.new, 2 * ctx.width + ctx.orig, ctx.width, ctx.bank)
+        return gx.to(ctx.dtype), None, None, None, None
+
+
+class ResampleStreamFunction(torch.autograd.Function):
+    """RealtimeResample.forward: chunk x (rows, C) float32, state (rows, Ha) or None -> (y (rows, C new / orig),
+    new_state (rows, Ha)) by ops.resample_sinc_stream.  The state is a constant of the graph and the new state is not
+    differentiable, so the gradient covers the chunk's own samples: output block t reads chunk sample n at tap n + Ha -
+    t orig, which is ops.resample_sinc_backward with lead = Ha over the chunk's own output blocks.  Saves no tensor."""
+
+    @staticmethod
+    def forward(ctx, x, state, bank, orig, new, width):
+        ctx.bank, ctx.orig, ctx.new, ctx.width, ctx.C, ctx.dtype = bank, orig, new, width, x.shape[-1], x.dtype
+        y, new_state = ops.resample_sinc_stream(x, state, orig, new, width, bank)
+        ctx.mark_non_differentiable(new_state)
+        return y, new_state
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy, _gstate):
+        Ha = ops.resample_stream_sizes(ctx.orig, ctx.width)[1]
+        gx = ops.resample_sinc_backward(gy, ctx.C, ctx.orig, ctx.new, 2 * ctx.width + ctx.orig, Ha, ctx.bank)
+        return gx.to(ctx.dtype), None, None, None, None, None
 
 
 # ---- the invert side: Magnitude, Polar, Cartesian, polar_to_complex, Normalize -----------------------------------------

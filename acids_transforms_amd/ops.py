@@ -1282,6 +1282,64 @@ def resample_sinc(x, orig, new, width, filters):
     return out
 
 
+def resample_backward_plan(orig, new, taps, lead):
+    """(tile_blocks, bank_in_lds) of at_resample_sinc_backward at a shape: the whole input blocks one workgroup handles,
+    and whether the bank sits in LDS beside the window of g or is read through L1 / L2.  Reads no device state."""
+    import ctypes
+    tile, in_lds = ctypes.c_int(0), ctypes.c_int(0)
+    check(lib().at_resample_backward_plan(int(orig), int(new), int(taps), int(lead), ctypes.byref(tile),
+                                          ctypes.byref(in_lds)), "at_resample_backward_plan")
+    return tile.value, bool(in_lds.value)
+
+
+def resample_sinc_backward(g, L, orig, new, taps, lead, filters):
+    """The adjoint of resample_sinc with respect to its input: g (rows, out_len) -> gx (rows, L), gx[n] = sum over the
+    output samples o = i new + j that read input n of filters[j][n - i orig + lead] g[o] (include/acids_hip.h).  lead =
+    width is the offline converter's; lead = Ha over a chunk's own output blocks is resample_sinc_stream's."""
+    require_device(g, filters)
+    g, filters = _f32c(g), _f32c(filters)
+    assert g.ndim == 2 and tuple(filters.shape) == (new, taps)
+    rows, out_len = g.shape
+    gx = torch.empty((rows, int(L)), dtype=torch.float32, device=g.device)
+    check(lib().at_resample_sinc_backward(ptr(g), rows, int(L), orig, new, taps, lead, ptr(filters), out_len, ptr(gx),
+                                          stream_ptr()), "at_resample_sinc_backward")
+    return gx
+
+
+def resample_stream_sizes(orig, width):
+    """(D, Ha) of the streaming converter: the blocks of delay D = ceil(width / orig) and the samples of carried state
+    Ha = D orig + width."""
+    D = -(-int(width) // int(orig))
+    return D, D * int(orig) + int(width)
+
+
+def resample_sinc_stream(x, state, orig, new, width, filters, want_state=True):
+    """Sample-rate conversion of a chunk of a stream: x (rows, C) float32, C a multiple of orig, state (rows, Ha)
+    float32 -- the samples before the chunk -- or None for zeros -> (y (rows, C new / orig), new_state (rows, Ha) or
+    None): resample_sinc's chain over [state | x], delayed by D blocks (include/acids_hip.h).  new_state is a fresh
+    tensor, the last Ha samples of [state | x], written by the same launch: no torch.cat.  An empty chunk or batch
+    launches nothing and hands the state back as it came."""
+    require_device(x, filters)
+    x, filters = _f32c(x), _f32c(filters)
+    assert x.ndim == 2 and tuple(filters.shape) == (new, 2 * width + orig)
+    rows, C = x.shape
+    if C % orig:
+        raise ValueError("the chunk length %d is no multiple of orig = %d" % (C, orig))
+    _, Ha = resample_stream_sizes(orig, width)
+    if state is not None:
+        require_device(x, state)
+        state = _f32c(state)
+        assert tuple(state.shape) == (rows, Ha), "the carried state is %s, the stream needs %s" % (tuple(state.shape),
+                                                                                                   (rows, Ha))
+    y = torch.empty((rows, C // orig * new), dtype=torch.float32, device=x.device)
+    if rows == 0 or C == 0:
+        return y, (state if want_state else None)
+    new_state = torch.empty((rows, Ha), dtype=torch.float32, device=x.device) if want_state else None
+    check(lib().at_resample_sinc_stream(ptr(x), rows, C, ptr(state), ptr(new_state), orig, new, width, ptr(filters),
+                                        ptr(y), stream_ptr()), "at_resample_sinc_stream")
+    return y, new_state
+
+
 def stft_polar_forward(x, window, band, contrast=None, mag_offset=None, mag_scale=None, eps=1.1920929e-07,
                        phase_offset=None, phase_scale=None):
     """Compose(STFT -> Polar) in one kernel: x (B, L) -> (B, T, 2, F): [.., 0, :] = normalise(contrast(|X| @ bank)),

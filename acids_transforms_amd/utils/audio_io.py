@@ -19,8 +19,10 @@ import numpy as np
 import torch
 
 from .. import ops
+from .._lib import device_scoped, require_device
+from ..autograd import ResampleFunction, ResampleStreamFunction, wants_grad
 
-__all__ = ["Resample", "resample", "import_data", "load_wav"]
+__all__ = ["Resample", "RealtimeResample", "resample", "import_data", "load_wav"]
 
 
 def sinc_filter_bank(orig_freq: int, new_freq: int, lowpass_filter_width: int = 6, rolloff: float = 0.99):
@@ -39,12 +41,17 @@ def sinc_filter_bank(orig_freq: int, new_freq: int, lowpass_filter_width: int = 
 
 
 class Resample(torch.nn.Module):
-    """torchaudio.transforms.Resample(orig_freq, new_freq) with its default interpolation."""
+    """torchaudio.transforms.Resample(orig_freq, new_freq) with its default interpolation.
+
+    Differentiable: when grad mode is on and the waveform requires grad the call goes through
+    autograd.ResampleFunction -- the same forward kernel, to the bit, and the transposed polyphase filter backward
+    (at_resample_sinc_backward; first order only, the graph keeps no tensor).  `streaming()` is the causal form."""
 
     def __init__(self, orig_freq: int = 16000, new_freq: int = 16000, lowpass_filter_width: int = 6,
                  rolloff: float = 0.99):
         super().__init__()
         self.orig_freq, self.new_freq = int(orig_freq), int(new_freq)
+        self.lowpass_filter_width, self.rolloff = lowpass_filter_width, rolloff
         g = math.gcd(self.orig_freq, self.new_freq)
         self.orig, self.new = self.orig_freq // g, self.new_freq // g
         if self.orig != self.new:
@@ -56,8 +63,98 @@ class Resample(torch.nn.Module):
             return waveform
         lead = waveform.shape[:-1]
         x = waveform.reshape(-1, waveform.shape[-1])
-        y = ops.resample_sinc(x, self.orig, self.new, self.width, self.kernel.to(x.device))
-        return y.reshape(tuple(lead) + (y.shape[-1],))
+        if wants_grad(waveform):
+            y = ResampleFunction.apply(x, self.kernel.to(x.device), self.orig, self.new, self.width)
+        else:
+            y = ops.resample_sinc(x, self.orig, self.new, self.width, self.kernel.to(x.device))
+        # (rows, L) audio gets the node itself back (its grad_fn names ResampleFunction), not a view of it
+        return y if waveform.ndim == 2 else y.reshape(tuple(lead) + (y.shape[-1],))
+
+    def streaming(self) -> "RealtimeResample":
+        """The causal form of this converter: a RealtimeResample that shares this module's bank."""
+        rt = RealtimeResample(self.orig_freq, self.new_freq, self.lowpass_filter_width, self.rolloff)
+        if self.orig != self.new:
+            rt._buffers["kernel"] = self.kernel
+            rt = rt.to(self.kernel.device)
+        return rt
+
+
+class RealtimeResample(Resample):
+    """The converter made causal by a delay of D = ceil(width / orig) whole blocks, with the last Ha = D orig + width
+    input samples carried in `input_buffer` (lead..., Ha).
+
+    `forward` takes the next (..., C) chunk of a stream, C a multiple of `orig` down to one block, and returns
+    (..., C new / orig): out[t new + j] = sum_k h[j][k] v[t orig + k] over v = [input_buffer | chunk].  Output block t of
+    the stream is offline block t - D with zeros before the stream's start, so the outputs of ANY chunking of x (..., L)
+    concatenate to Resample(cat([zeros(D orig), x], -1))[..., :L new / orig] -- for finite input to the bit: the kernel
+    is the offline chain reading another source, and the offline call's zero padding behind the clip is never reached
+    (D orig >= width).  The next state is written by the same launch into a second buffer that replaces the module's:
+    no torch.cat, one launch per call.  The state is zeros on a new leading batch shape or device and after `reset()`.
+
+    `delay` is D orig input samples (`output_delay` = D new output samples), `ratio` = new / orig.
+
+    Gradients (autograd.ResampleStreamFunction): the carried state is a constant of the graph and is stored detached, so
+    a chunk's gradient covers that chunk's own samples -- truncated back-propagation at chunk boundaries, as for
+    OverlapAdd and RealtimePQMF.  Not built: chunks that are not whole blocks, gradient through the carried state, a
+    hipGraph-captured session (the state buffer changes place every call)."""
+
+    def __init__(self, orig_freq: int = 16000, new_freq: int = 16000, lowpass_filter_width: int = 6,
+                 rolloff: float = 0.99):
+        super().__init__(orig_freq, new_freq, lowpass_filter_width, rolloff)
+        self.delay_blocks, self._keep = (0, 0) if self.orig == self.new else ops.resample_stream_sizes(self.orig, self.width)
+        self.register_buffer("input_buffer", torch.zeros(self._keep))
+
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        if prefix + "input_buffer" in state_dict:                 # any batch shape, as OverlapAdd's
+            self._buffers["input_buffer"] = torch.zeros_like(state_dict[prefix + "input_buffer"])
+        return super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+
+    @property
+    def delay(self) -> int:
+        """Input samples by which `forward` lags the offline converter."""
+        return self.delay_blocks * self.orig
+
+    @property
+    def output_delay(self) -> int:
+        """The same delay in output samples."""
+        return self.delay_blocks * self.new
+
+    @property
+    def ratio(self) -> float:
+        return self.new / self.orig
+
+    def streaming(self) -> "RealtimeResample":
+        return self
+
+    def reset(self) -> None:
+        """Forget the stream: the state becomes zeros (of its current shape)."""
+        self.input_buffer = torch.zeros_like(self.input_buffer)
+
+    def forward(self, waveform: torch.Tensor) -> torch.Tensor:
+        if waveform.ndim < 1 or waveform.shape[-1] % self.orig:
+            raise ValueError("RealtimeResample.forward takes a (..., C) chunk with C a multiple of orig = %d, got shape %s"
+                             % (self.orig, tuple(waveform.shape)))
+        if self.orig == self.new:
+            return waveform
+        ops._no_fp64(waveform)
+        device_scoped(require_device)(waveform)
+        lead, C = tuple(waveform.shape[:-1]), waveform.shape[-1]
+        out_c = C // self.orig * self.new
+        if waveform.numel() == 0:                                 # nothing arrived: no launch, the state stays
+            return torch.empty(lead + (out_c,), dtype=torch.float32, device=waveform.device)
+        rows = math.prod(lead)
+        buf = self.input_buffer
+        state = None                                              # a new leading shape or device starts a new stream
+        if tuple(buf.shape) == lead + (self._keep,) and buf.device == waveform.device:
+            state = buf.reshape(rows, self._keep)
+        bank = self.kernel.to(waveform.device)
+        x = waveform.reshape(rows, C)
+        if wants_grad(waveform):
+            y, new_state = ResampleStreamFunction.apply(x, state, bank, self.orig, self.new, self.width)
+        else:
+            y, new_state = ops.resample_sinc_stream(x, state, self.orig, self.new, self.width, bank)
+        self.input_buffer = new_state.detach().reshape(lead + (self._keep,))
+        return y if waveform.ndim == 2 else y.reshape(lead + (out_c,))
 
 
 def resample(waveform: torch.Tensor, orig_freq: int, new_freq: int) -> torch.Tensor:

@@ -741,6 +741,31 @@ int at_pqmf_synthesis_stream(const float *y, int64_t rows, int64_t L, const floa
 int at_resample_sinc(const float *x, int64_t rows, int64_t L, int orig, int new_, int width, const float *filters,
                      int64_t out_len, float *out, void *stream);
 
+/* The adjoint of at_resample_sinc with respect to x (autograd.ResampleFunction): g (rows, out_len) -> gx (rows, L),
+ *   gx[n] = sum over (i, j) with o = i new + j < out_len and 0 <= k = n - i orig + lead < taps of filters[j][k] g[o],
+ * lead = width and taps = 2 width + orig for the offline converter; at_resample_sinc_stream's gradient with respect to
+ * its chunk is the same sum with lead = Ha over the chunk's own output blocks (L = C, out_len = C / orig * new), which is
+ * why lead and taps are separate arguments.  Each gx[n] is one fmaf chain from +0 over o ascending: no atomics, and the
+ * bits of a row depend on neither its batch nor the tiling.  One workgroup per tile of *tile_blocks whole input blocks
+ * of one row, the window of g it reads in LDS, the bank in LDS too when it fits beside it (*bank_in_lds), read through
+ * L1 / L2 otherwise: at_resample_backward_plan answers both for a shape; it is a pure function of its arguments.
+ * AT_EINVAL: null pointers, negative sizes, out_len != ceil(new L / orig) when lead == width (taps == 2 lead + orig).
+ * AT_OK without a launch when rows == 0 or L == 0.  AT_EUNSUPPORTED: rows > 65535 (at_resample_sinc's limit), or a bank
+ * so wide that the window of a one-block tile exceeds the LDS. */
+int at_resample_backward_plan(int orig, int new_, int taps, int lead, int *tile_blocks, int *bank_in_lds);
+int at_resample_sinc_backward(const float *g, int64_t rows, int64_t L, int orig, int new_, int taps, int lead,
+                              const float *filters, int64_t out_len, float *gx, void *stream);
+
+/* The causal converter (utils.RealtimeResample): the next chunk x (rows, C), C a multiple of orig, of a stream whose
+ * last Ha = D orig + width samples are state_in (rows, Ha) (null: zeros), D = ceil(width / orig) -> out (rows, C / orig *
+ * new), out[t new + j] = sum_k filters[j][k] v[t orig + k] over v = [state_in | x]: at_resample_sinc's chain, delayed
+ * by D blocks, so for finite input the bits of at_resample_sinc on the stream with D orig zeros in front.  state_out
+ * (null: not wanted; never state_in) receives the last Ha samples of v from the same launch.  AT_EINVAL: negative sizes,
+ * C % orig != 0, state_out == state_in, null x / filters / out; AT_OK without a launch (state_out untouched) when rows
+ * == 0 or C == 0; AT_EUNSUPPORTED: rows > 65535. */
+int at_resample_sinc_stream(const float *x, int64_t rows, int64_t C, const float *state_in, float *state_out, int orig,
+                            int new_, int width, const float *filters, float *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
