@@ -31,6 +31,10 @@ ResampleFunction and ResampleStreamFunction are utils.Resample's and utils.Realt
 conversion is linear, so both backward passes are one kernel, the transposed polyphase filter (ops.resample_sinc_backward),
 which the streaming form calls with the state's length as the lead of its window; neither saves a tensor.
 
+PhaseVocoderFunction is transforms.TimeStretch's (phase_vocoder.hip): the forward also hands back the phasor after its last
+step, and the backward (ops.phase_vocoder_backward) walks the steps downwards from it; the graph keeps the spectrum and
+that (..., F) phasor.
+
 All backward passes are first-order only (@once_differentiable): create_graph=True raises.
 """
 import torch
@@ -45,7 +49,7 @@ __all__ = ["wants_grad", "StftFunction", "IstftFunction", "IstftPolarFunction", 
            "RtStftFunction", "RtIstftFunction", "RtIstftPolarFunction", "OaddFramesFunction", "OaddInvertFunction",
            "SpectralDistanceFunction", "specdist_chunk_clips", "MelSpectralDistanceFunction", "meldist_sums",
            "meldist_loss", "PqmfFunction", "PqmfInvertFunction", "PqmfStreamFunction", "PqmfStreamInvertFunction",
-           "ResampleFunction", "ResampleStreamFunction"]
+           "ResampleFunction", "ResampleStreamFunction", "PhaseVocoderFunction"]
 
 
 def wants_grad(x: torch.Tensor) -> bool:
@@ -549,6 +553,28 @@ class ResampleStreamFunction(torch.autograd.Function):
         Ha = ops.resample_stream_sizes(ctx.orig, ctx.width)[1]
         gx = ops.resample_sinc_backward(gy, ctx.C, ctx.orig, ctx.new, 2 * ctx.width + ctx.orig, Ha, ctx.bank)
         return gx.to(ctx.dtype), None, None, None, None, None
+
+
+# ---- TimeStretch: the phase vocoder, a scan up the steps forward and down them backward -------------------------------------
+
+class PhaseVocoderFunction(torch.autograd.Function):
+    """ops.phase_vocoder of a complex spectrum X (..., T, F) at `rate` -> (..., N, F), with its backward
+    (ops.phase_vocoder_backward).  Saves X and the (..., F) phasor after the last step; the step table is a constant of
+    the graph.  The forward values are the plain route's: the same kernel, which writes the phasor on the side."""
+
+    @staticmethod
+    def forward(ctx, X, rate):
+        ctx.rate = float(rate)
+        out, fin = ops.phase_vocoder(X, rate, want_phasor=True)
+        ctx.save_for_backward(X, fin)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        X, fin = ctx.saved_tensors
+        gX = ops.phase_vocoder_backward(X, g, ctx.rate, fin)
+        return gX.reshape(X.shape).to(X.dtype), None
 
 
 # ---- the invert side: Magnitude, Polar, Cartesian, polar_to_complex, Normalize -----------------------------------------

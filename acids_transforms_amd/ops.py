@@ -1340,6 +1340,93 @@ def resample_sinc_stream(x, state, orig, new, width, filters, want_state=True):
     return y, new_state
 
 
+# ----------------------------------------------------------------------------------------------
+# time stretching (phase_vocoder.hip)
+# ----------------------------------------------------------------------------------------------
+PV_MAX_ROWS = 2 ** 31 - 1 - 8      # at_phase_vocoder's int row indices, a batch of rows ahead included
+
+
+def phase_vocoder_steps(T, rate):
+    """The step table of the phase vocoder on the host, in float64: s_j = j * rate for j = 0, 1, ... while s_j < T ->
+    (idx int32 (N,), alpha float32 (N,)) CPU tensors, idx_j = floor(s_j), alpha_j = s_j - idx_j rounded to float32.  N is
+    ceil(T / rate) except for rounding at the edge; idx_j + 1 may be T, the frame of zeros.  ValueError: a rate that is not
+    finite and > 0, a negative T, more rows than the kernel's index range (PV_MAX_ROWS)."""
+    import math
+    rate, T = float(rate), int(T)
+    if not (math.isfinite(rate) and rate > 0.0):
+        raise ValueError("rate must be finite and > 0, got %r" % (rate,))
+    if T < 0:
+        raise ValueError("a clip has T >= 0 frames, got %d" % T)
+    if T / rate > PV_MAX_ROWS:
+        raise ValueError("%d frames at rate %g are more than %d output frames" % (T, rate, PV_MAX_ROWS))
+    s = torch.arange(int(math.ceil(T / rate)) + 2, dtype=torch.float64) * rate      # monotone in j
+    s = s[:int((s < T).sum())]
+    idx = s.floor()
+    return idx.to(torch.int32), (s - idx).to(torch.float32)
+
+
+_pv_tables = {}
+
+
+def _pv_table(T, rate, device):
+    """phase_vocoder_steps on `device`; the last few tables stay (one upload per shape, rate and device)."""
+    key = (int(T), float(rate), str(device))
+    hit = _pv_tables.get(key)
+    if hit is None:
+        idx, alpha = phase_vocoder_steps(T, rate)
+        if len(_pv_tables) >= 16:
+            _pv_tables.pop(next(iter(_pv_tables)))
+        hit = _pv_tables[key] = (idx.to(device), alpha.to(device))
+    return hit
+
+
+def _pv_spectrum(x, rate):
+    rate = float(rate)
+    if not (rate == rate and 0.0 < rate < float("inf")):
+        raise ValueError("rate must be finite and > 0, got %r" % (rate,))
+    if not x.is_complex():
+        raise ValueError("the phase vocoder stretches a complex spectrum (..., frames, bins), got %s"
+                         % str(x.dtype).replace("torch.", ""))
+    require_device(x)
+    x = _c64(x)
+    return x if x.is_contiguous() else x.contiguous()
+
+
+def phase_vocoder(x, rate, want_phasor=False):
+    """Time-stretch the complex spectrum x (..., T, F) by `rate` (> 1: shorter) along dim -2: the phase vocoder of
+    torchaudio.functional.phase_vocoder in the package's time-major layout, as a running product of unit phasors
+    (include/acids_hip.h, at_phase_vocoder; hop_length cancels).  Returns complex64 (..., N, F), N rows of
+    phase_vocoder_steps(T, rate); with want_phasor=True also the phasor after the last step (..., F), which
+    phase_vocoder_backward starts from.  Zero bins come out as zeros; -0 + 0i counts as zero, where torch.angle says pi."""
+    x = _pv_spectrum(x, rate)
+    B, T, F = _btf(x)
+    idx, alpha = _pv_table(T, rate, x.device)
+    N = idx.numel()
+    out = torch.empty(x.shape[:-2] + (N, F), dtype=torch.complex64, device=x.device)
+    fin = torch.empty(x.shape[:-2] + (F,), dtype=torch.complex64, device=x.device) if want_phasor else None
+    check(lib().at_phase_vocoder(ptr(x), B, T, F, ptr(idx), ptr(alpha), N, ptr(out), ptr(fin), stream_ptr()),
+          "at_phase_vocoder")
+    return (out, fin) if want_phasor else out
+
+
+def phase_vocoder_backward(x, g, rate, phasor):
+    """Gradient of phase_vocoder(x, rate) with respect to x (..., T, F) complex64, given g (..., N, F), the gradient of
+    its output, and the final phasor (..., F) the forward handed back (include/acids_hip.h, at_phase_vocoder_backward).
+    Returns complex64 of x's shape: zeros where x == 0 and in frames no step reads."""
+    x = _pv_spectrum(x, rate)
+    require_device(x, g, phasor)
+    B, T, F = _btf(x)
+    idx, alpha = _pv_table(T, rate, x.device)
+    N = idx.numel()
+    g, phasor = _c64_grad(g), _c64_grad(phasor)
+    assert tuple(g.shape) == tuple(x.shape[:-2]) + (N, F), "g does not match the forward's output"
+    assert tuple(phasor.shape) == tuple(x.shape[:-2]) + (F,), "the phasor does not match the forward's"
+    gx = torch.empty_like(x)
+    check(lib().at_phase_vocoder_backward(ptr(x), ptr(g), ptr(idx), ptr(alpha), ptr(phasor), B, T, F, N, ptr(gx),
+                                          stream_ptr()), "at_phase_vocoder_backward")
+    return gx
+
+
 def stft_polar_forward(x, window, band, contrast=None, mag_offset=None, mag_scale=None, eps=1.1920929e-07,
                        phase_offset=None, phase_scale=None):
     """Compose(STFT -> Polar) in one kernel: x (B, L) -> (B, T, 2, F): [.., 0, :] = normalise(contrast(|X| @ bank)),

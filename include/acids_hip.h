@@ -766,6 +766,41 @@ int at_resample_sinc_backward(const float *g, int64_t rows, int64_t L, int orig,
 int at_resample_sinc_stream(const float *x, int64_t rows, int64_t C, const float *state_in, float *state_out, int orig,
                             int new_, int width, const float *filters, float *out, void *stream);
 
+/* ---- time stretching ------------------------------------------------------------------------------------- */
+/* The phase vocoder of torchaudio.functional.phase_vocoder / torchaudio.transforms.TimeStretch (algorithm restated,
+ * torchaudio is not in the reference tree) on a time-major spectrum: X (B, T, F) complex64 -> out (B, N, F) complex64.
+ * The step table is the caller's (ops.phase_vocoder_steps makes it on the host in float64): idx (N int32, device), alpha
+ * (N float32, device), idx_j = floor(j rate), alpha_j = j rate - idx_j for every j with j rate < T; idx_0 = 0, idx never
+ * decreases, idx_j + 1 may be T, and frame T is a frame of zeros.  The textbook phase increment wrap(a1 - a0 - adv) + adv
+ * is congruent to a1 - a0 and only meets exp(i .), so the expected advance -- and hop_length -- cancels and the
+ * accumulated phase is a running product of unit phasors:
+ *   u(z) = z / |z| (1 where z == 0),  p_0 = u(X[0]),  p_{j+1} = p_j u(X[idx_j + 1]) conj(u(X[idx_j])),
+ *   out[j] = (alpha_j |X[idx_j + 1]| + (1 - alpha_j) |X[idx_j]|) p_j.
+ * One thread per (clip, bin) column walks j upwards; a column's bits depend neither on the batch nor on the layout (flat
+ * columns, or one block per clip where rows are no whole 64-byte segments: AT_VARIANT_SCAN_LAYOUT = 1 forces the flat
+ * one), and a NaN stays in its column.  Zero bins give magnitude 0 and u = 1; -0 + 0i counts as zero, where torch.angle
+ * answers pi (the one divergence).  final_phasor (B, F) complex64 or NULL receives p_N, which the backward starts from.
+ * An idx outside [0, T - 1] is read as the nearest frame inside: no table makes the kernel read out of bounds.
+ * AT_EINVAL (no device is touched): negative sizes, N == 0 with T > 0 or the reverse, null X / idx / alpha / out, out ==
+ * X, misalignment (8 bytes for the complex tensors, 4 for the table).  AT_OK and nothing touched when B T F == 0.
+ * AT_EUNSUPPORTED: T or N beyond the int range of the row indices (N > INT_MAX - 8), or more columns than a grid holds. */
+int at_phase_vocoder(const float *X_complex, int64_t B, int64_t T, int64_t F, const int *idx, const float *alpha, int64_t N,
+                     float *out_complex, float *final_phasor, void *stream);
+
+/* Gradient of at_phase_vocoder with respect to X: g (B, N, F) complex64 = dL/dout -> gX (B, T, F) complex64.  With
+ * Z_j = out[j] = m_j p_j:  gphi_j = Im(conj(Z_j) g_j),  gm_j = Re(conj(p_j) g_j),  S_j = sum over j' >= j of gphi_j',
+ *   G_abs[idx_j] += (1 - alpha_j) gm_j,  G_abs[idx_j + 1] += alpha_j gm_j,
+ *   G_ang[0] += S_0,  and for j + 1 < N:  G_ang[idx_j + 1] += S_{j+1},  G_ang[idx_j] -= S_{j+1},
+ *   gX[i] = G_abs[i] X[i] / |X[i]| + G_ang[i] (-Im X[i] + i Re X[i]) / |X[i]|^2,  0 where X[i] == 0;
+ * the share of the frame of zeros T is dropped, frames no step reads get zeros.  One thread per column walks j downwards:
+ * p_j comes back from final_phasor (B, F), what the forward wrote, by the conjugate step; a frame's gradient is written
+ * when idx moves past it -- a gather, no atomics, no (B, N, F) intermediate, every element of gX written once.  First
+ * order only.  Flat columns: a column's bits do not depend on the batch.  Return codes as at_phase_vocoder, with
+ * final_phasor required and gX distinct from X and g. */
+int at_phase_vocoder_backward(const float *X_complex, const float *g_complex, const int *idx, const float *alpha,
+                              const float *final_phasor, int64_t B, int64_t T, int64_t F, int64_t N, float *gX_complex,
+                              void *stream);
+
 #ifdef __cplusplus
 }
 #endif
