@@ -387,6 +387,55 @@ __device__ __forceinline__ void mirror_regs(const v2f (&v)[Q], v2f (&p)[Q], int 
   mirror_regs_rot<Q>(v, p, lane, 0, lane);
 }
 
+// The inverse real transforms of n_fft = 128 Q (Q = 4, 16, 32: stft512.hip, stft2048.hip, stft4096.hip) start with the
+// same two steps, generic in Q.
+// One frame's one-sided spectrum into registers: v[m] = X[lane + 64 m], nyq_re = Re X[64 Q].  The frame's row starts `e`
+// elements into X (complex) or into mag and phase (POLAR: X = mag (cos phase + i sin phase)).
+template <int Q, bool POLAR>
+__device__ __forceinline__ void load_spectrum_row(const float2* X, const float* mag, const float* phase, long long e,
+                                                  int lane, v2f (&v)[Q], float& nyq_re) {
+  if (POLAR) {
+    const float* mrow = mag + e;
+    const float* prow = phase + e;
+#pragma unroll
+    for (int m = 0; m < Q; ++m) {
+      float sn, cs;
+      const float a = mrow[lane + 64 * m];
+      fast_sincosf(prow[lane + 64 * m], sn, cs);
+      v[m] = (v2f){a * cs, a * sn};
+    }
+    float sn, cs;
+    fast_sincosf(prow[64 * Q], sn, cs);
+    nyq_re = mrow[64 * Q] * cs;
+  } else {
+    const float2* row = X + e;
+#pragma unroll
+    for (int m = 0; m < Q; ++m) v[m] = to_v(row[lane + 64 * m]);
+    nyq_re = row[64 * Q].x;
+  }
+}
+// The inverse of the real split: from x[m] = X[k], z[m] = Z[k] = E + i O with E = X[k] + conj X', O = (X[k] - conj X') conj(W^k),
+// X' = X[64 Q - k], k = lane + 64 m (twice the true value: the callers fold the half into their 1 / n_fft).
+// w[WS m] = W_{128 Q}^k: a register array (WS = 1) or this lane's column of an LDS table (WS = 64).
+// Out of place on purpose: written in place through the caller's array, the compiler finishes all row loads before the
+// first pair (irfft2048_frames_kernel<true>: 132 VGPRs instead of 100 and a resident wave per SIMD less;
+// profiles/nfft_cores.md).
+template <int Q, int WS>
+__device__ __forceinline__ void irfft_presplit(const v2f (&x)[Q], float nyq_re, int lane, const v2f* w, v2f (&z)[Q]) {
+  v2f v[Q], pm[Q];
+#pragma unroll
+  for (int m = 0; m < Q; ++m) v[m] = x[m];
+  if (lane == 0) v[0].y = 0.0f;                       // c2r ignores the imaginary parts of DC and Nyquist
+  mirror_regs<Q>(v, pm, lane);
+  if (lane == 0) pm[0] = (v2f){nyq_re, 0.0f};         // partner of k = 0 is X[64 Q]
+#pragma unroll
+  for (int m = 0; m < Q; ++m) {
+    const v2f e = add_conj(v[m], pm[m]);
+    const v2f d = cmul_conj_v(sub_conj(v[m], pm[m]), w[WS * m]);
+    z[m] = add_pi(e, d);
+  }
+}
+
 // real-FFT merge after the forward complex FFT:
 //   X[k] = (Z[k] + conj Z[512-k])/2 - (i/2) W1024^k (Z[k] - conj Z[512-k]),  k = lane + 64 m
 // returns X[512] (Nyquist) in `nyq` (meaningful on lane 0 only).  `tw.getr` = W1024^k / 2 (forward tables).

@@ -17,6 +17,10 @@
 // The mirror partner Z[1024-k] lives in lane 64-lane, register 15-m (lane 0: its own register 16-m).  The inverse
 // runs the same steps backwards.  One wave = one frame at a time, frames of a block interleaved over its four
 // waves, the next frame's loads issued before the current frame's FFTs.
+//
+// Each direction's arithmetic is written once: fwd_core2k (two FFTs, radix-2, mirror, merge; plain or with rotated
+// output columns) serves the frame, run and mel kernels, inv_core2k (radix-2 backwards, two FFTs) behind fft512.h's
+// load_spectrum_row / irfft_presplit serves the frames and the fused overlap-add kernel (ola_window.h).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -25,6 +29,7 @@
 #include "fft512.h"
 #include "band_bank.h"
 #include "mel_gemm.h"   // C_* contrast codes
+#include "ola_window.h"
 #include "run_plan.h"
 #include "stft_launch.h"
 #include "variants.h"
@@ -51,11 +56,12 @@ struct P2k {
 };
 
 // q[j] = x[s + 4 (lane + 64 j) .. + 3] of frame f (reflect padding with center, zero padding without)
-__device__ __forceinline__ void load_frame2k(const P2k& p, long long f, int lane, float4 (&q)[8]) {
-  const long long b = f / p.T, t = f - b * p.T;
-  const float* clip = p.x + b * p.clip_stride;
-  const long long start = t * (long long)p.hop - (p.center ? N2K / 2 : 0);
-  const bool interior = (start >= 0) && (start + N2K <= p.L);
+__device__ __forceinline__ void load_frame2k(const float* x, long long clip_stride, long long L, long long T, int hop,
+                                             int center, long long f, int lane, float4 (&q)[8]) {
+  const long long b = f / T, t = f - b * T;
+  const float* clip = x + b * clip_stride;
+  const long long start = t * (long long)hop - (center ? N2K / 2 : 0);
+  const bool interior = (start >= 0) && (start + N2K <= L);
   if (interior && ((((uintptr_t)(clip + start)) & 15) == 0)) {
     const float4* src = reinterpret_cast<const float4*>(clip + start);
 #pragma unroll
@@ -75,21 +81,70 @@ __device__ __forceinline__ void load_frame2k(const P2k& p, long long f, int lane
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
         const long long i = i0 + c;
-        if (p.center) v[c] = clip[reflect_index(i, p.L)];
-        else v[c] = (i >= 0 && i < p.L) ? clip[i] : 0.0f;     // zero padding past the end (utils/misc.py:156)
+        if (center) v[c] = clip[reflect_index(i, L)];
+        else v[c] = (i >= 0 && i < L) ? clip[i] : 0.0f;     // zero padding past the end (utils/misc.py:156)
       }
       q[j] = make_float4(v[0], v[1], v[2], v[3]);
     }
   }
 }
 
-// Both kernels keep the constant tables in LDS, shared by the block's four waves and read at the point of use (the
-// fft512 twiddles: 11 KB; W2048^k: 8 KB): held in registers they cost 76 VGPRs and leave one wave per SIMD.
-template <bool INV>
-__device__ __forceinline__ void stage_tables2k(const P2k& p, float2* tab, float2* w2tab) {
-  for (int i = threadIdx.x; i < kTwiddleCount; i += 64 * W2K) tab[i] = twiddle_for_lds<INV>(p.tw, i);
-  for (int i = threadIdx.x; i < 1024; i += 64 * W2K) w2tab[i] = p.tw2k[i];
+// All kernels keep the constant tables in LDS, shared by the block's waves and read at the point of use (the fft512
+// twiddles: 11 KB; W2048^k: 8 KB): held in registers they cost 76 VGPRs and leave one wave per SIMD.  Ends with the
+// block's __syncthreads(): a kernel that stages more (a window, a bank) does so first.
+template <bool INV, int THREADS>
+__device__ __forceinline__ void stage_tables2k(const float2* tw, const float2* tw2k, float2* tab, float2* w2tab) {
+  for (int i = threadIdx.x; i < kTwiddleCount; i += THREADS) tab[i] = twiddle_for_lds<INV>(tw, i);
+  for (int i = threadIdx.x; i < 1024; i += THREADS) w2tab[i] = tw2k[i];
   __syncthreads();
+}
+
+// a frame's raw samples times the window (global memory or LDS) -> the inputs of the two 512-point FFTs
+__device__ __forceinline__ void window2k(const float4 (&q)[8], const float4* win, int lane, v2f (&ze)[8], v2f (&zo)[8]) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const float4 w = win[lane + 64 * j];
+    ze[j] = (v2f){q[j].x * w.x, q[j].y * w.y};
+    zo[j] = (v2f){q[j].z * w.z, q[j].w * w.w};
+  }
+}
+
+// The forward core: the windowed even / odd complex samples -> out(m, X[col + 64 m]), m = 0 .. 15, in that order; returns
+// X[1024] (real; meaningful on the lane whose column is 0).  ROT: the output columns are rotated over the lanes, this lane
+// holds column col = (lane - rot) & 63 (the run kernel; the radix-2 stage is lane-local and does not care, the twiddles
+// W1024^k / 2 and W2048^k and the mirror lane follow the column); otherwise rot = 0, col = lane.  The rotated form reads
+// W2048^k one ds_read_b64 at a time, as its fft512 twiddles are; the plain form leaves the pairing of those reads to the
+// compiler.  The bins go to a consumer, not to an array: a kernel that stores or reduces them does so inside the merge
+// loop, as the kernels did before they shared this core -- through an array stft2048_mel_kernel<2, false> took 174 VGPRs
+// instead of 168 and lost a resident wave per SIMD (profiles/nfft_cores.md).
+template <bool ROT, typename OUT>
+__device__ __forceinline__ float fwd_core2k(v2f (&ze)[8], v2f (&zo)[8], const float2* tab, float2* lds, int lane, int rot,
+                                            int col, OUT&& out) {
+  v2f z[16];
+  const LdsTwiddles<false> tw = {tab, lane}, twc = {tab, col};     // getr(m) = W1024^(. + 64 m) / 2
+  const v2f hh = {0.5f, 0.5f};
+  fft512<false>(ze, tw, lds, lane, col);
+  fft512<false>(zo, tw, lds, lane, col);
+  // radix-2: H = Z / 2 (the real split wants the half): H[k] = Ze/2 + (W1024^k / 2) Zo, H[k+512] = Ze/2 - ...
+#pragma unroll
+  for (int m = 0; m < 8; ++m) {
+    const v2f t = cmul_v(zo[m], twc.getr(m));
+    const v2f e = ze[m] * hh;
+    z[m] = e + t;
+    z[m + 8] = e - t;
+  }
+  v2f pm[16];
+  mirror_regs_rot<16>(z, pm, lane, rot, col);
+  // X[k] = (H[k] + conj H') - i W2048^k (H[k] - conj H'),  H = Z / 2,  H' = H[1024 - k]  (k = 0: H' = H[0], X[0] real)
+  const float nyq = 2.0f * (z[0].x - z[0].y);                     // X[1024] = Re Z[0] - Im Z[0]
+  const v2f* w2 = reinterpret_cast<const v2f*>(tab + kTwiddleCount) + col;     // w2[64 m] = W2048^(col + 64 m)
+#pragma unroll
+  for (int m = 0; m < 16; ++m) {
+    const v2f e = add_conj(z[m], pm[m]);
+    const v2f d = sub_conj(z[m], pm[m]);
+    out(m, add_mi(e, cmul_v(d, ROT ? lds_read_single(w2 + 64 * m) : w2[64 * m])));      // e - i W d
+  }
+  return nyq;
 }
 
 template <bool WRITE_PHASE>
@@ -97,56 +152,29 @@ __global__ __launch_bounds__(64 * W2K, 3) void stft2048_fwd_kernel(P2k p) {
   __shared__ float2 lds_all[W2K * kFftLdsFloat2PerWave + kTwiddleCount + 1024];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // uniform: run bookkeeping on the scalar unit
   float2* lds = lds_all + wave * kFftLdsFloat2PerWave;
-  float2* tab = lds_all + W2K * kFftLdsFloat2PerWave;
-  const v2f* w2 = reinterpret_cast<const v2f*>(tab + kTwiddleCount) + lane;     // w2[64 m] = W2048^(lane + 64 m)
-  stage_tables2k<false>(p, tab, tab + kTwiddleCount);
-  const LdsTwiddles<false> tw = {tab, lane};     // tw.getr(m) = W1024^(lane + 64 m) / 2
+  float2* tab = lds_all + W2K * kFftLdsFloat2PerWave;      // the fft512 twiddles, W2048^k behind them
+  stage_tables2k<false, 64 * W2K>(p.tw, p.tw2k, tab, tab + kTwiddleCount);
   const long long f_begin = (long long)blockIdx.x * p.frames_per_block;
   long long f_end = f_begin + p.frames_per_block;
   if (f_end > p.total_frames) f_end = p.total_frames;
-  const float4* win4 = reinterpret_cast<const float4*>(p.window);
-  const v2f hh = {0.5f, 0.5f};
+  const float4* win4 = reinterpret_cast<const float4*>(p.window);    // L1/L2-resident (8 KB), re-read per frame instead of 32 VGPRs
 
   long long f = f_begin + wave;
   float4 nxt[8];
-  if (f < f_end) load_frame2k(p, f, lane, nxt);
+  if (f < f_end) load_frame2k(p.x, p.clip_stride, p.L, p.T, p.hop, p.center, f, lane, nxt);
   for (; f < f_end; f += W2K) {
     v2f ze[8], zo[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float4 w = win4[lane + 64 * j];   // L1/L2-resident (8 KB), re-read per frame instead of 32 VGPRs
-      ze[j] = (v2f){nxt[j].x * w.x, nxt[j].y * w.y};
-      zo[j] = (v2f){nxt[j].z * w.z, nxt[j].w * w.w};
-    }
-    if (f + W2K < f_end) load_frame2k(p, f + W2K, lane, nxt);
-    fft512<false>(ze, tw, lds, lane);
-    fft512<false>(zo, tw, lds, lane);
-    // radix-2: H = Z / 2 (the real split wants the half): H[k] = Ze/2 + (W1024^k / 2) Zo, H[k+512] = Ze/2 - ...
-    v2f z[16];
-#pragma unroll
-    for (int m = 0; m < 8; ++m) {
-      const v2f t = cmul_v(zo[m], tw.getr(m));
-      const v2f e = ze[m] * hh;
-      z[m] = e + t;
-      z[m + 8] = e - t;
-    }
-    v2f pm[16];
-    mirror_regs<16>(z, pm, lane);
-    // X[k] = (H[k] + conj H') - i W2048^k (H[k] - conj H'),  H = Z / 2,  H' = H[1024 - k]  (k = 0: H' = H[0], X[0] real)
-    const float2 nyq = make_float2(2.0f * (z[0].x - z[0].y), 0.0f);    // X[1024] = Re Z[0] - Im Z[0] (lane 0)
+    window2k(nxt, win4, lane, ze, zo);
+    if (f + W2K < f_end) load_frame2k(p.x, p.clip_stride, p.L, p.T, p.hop, p.center, f + W2K, lane, nxt);
     float2* row = p.X + f * F2K;
     float* prow = WRITE_PHASE ? p.phase_out + f * F2K : nullptr;
-#pragma unroll
-    for (int m = 0; m < 16; ++m) {
-      const v2f e = add_conj(z[m], pm[m]);
-      const v2f d = sub_conj(z[m], pm[m]);
-      const v2f xk = add_mi(e, cmul_v(d, w2[64 * m]));      // e - i W d
+    const float nyq = fwd_core2k<false>(ze, zo, tab, lds, lane, 0, lane, [&](int m, v2f xk) {
       row[lane + 64 * m] = to_f2(xk);
       if (WRITE_PHASE) prow[lane + 64 * m] = fast_atan2f(xk.y, xk.x);
-    }
+    });
     if (lane == 0) {
-      row[1024] = nyq;
-      if (WRITE_PHASE) prow[1024] = fast_atan2f(nyq.y, nyq.x);
+      row[1024] = make_float2(nyq, 0.0f);
+      if (WRITE_PHASE) prow[1024] = fast_atan2f(0.0f, nyq);
     }
   }
 }
@@ -188,12 +216,9 @@ __global__ __launch_bounds__(64 * W2KR, 4) void stft2048_run_fwd_kernel(P2kRun p
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   float2* lds = lds_all + wave * kFftLdsFloat2PerWave;
   float2* tab = lds_all + W2KR * kFftLdsFloat2PerWave;
-  float2* w2tab = tab + kTwiddleCount;
-  float4* wintab = reinterpret_cast<float4*>(w2tab + 1024);          // analysis window, 512 float4
-  for (int i = threadIdx.x; i < kTwiddleCount; i += 64 * W2KR) tab[i] = twiddle_for_lds<false>(p.tw, i);
-  for (int i = threadIdx.x; i < 1024; i += 64 * W2KR) w2tab[i] = p.tw2k[i];
+  float4* wintab = reinterpret_cast<float4*>(tab + kTwiddleCount + 1024);          // analysis window, 512 float4
   for (int i = threadIdx.x; i < 512; i += 64 * W2KR) wintab[i] = reinterpret_cast<const float4*>(p.window)[i];
-  __syncthreads();
+  stage_tables2k<false, 64 * W2KR>(p.tw, p.tw2k, tab, tab + kTwiddleCount);
 
   const long long run = (long long)blockIdx.x * W2KR + wave;
   const long long b = run / p.runs_per_clip;
@@ -205,8 +230,6 @@ __global__ __launch_bounds__(64 * W2KR, 4) void stft2048_run_fwd_kernel(P2kRun p
   if (t0 >= t1) return;
   const float* clip = p.x + b * p.clip_stride;
   const long long L = p.L;
-  const LdsTwiddles<false> tw = {tab, lane};
-  const v2f hh = {0.5f, 0.5f};
 
   float4 raw[8];
 #pragma unroll
@@ -223,39 +246,13 @@ __global__ __launch_bounds__(64 * W2KR, 4) void stft2048_run_fwd_kernel(P2kRun p
 
   auto frame_body = [&](const float4 (&fresh)[2]) {
     wave_priority<3>();        // transform > stores, as in stft1024.hip
-    v2f ze[8], zo[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float4 w = wintab[lane + 64 * j];
-      ze[j] = (v2f){raw[j].x * w.x, raw[j].y * w.y};
-      zo[j] = (v2f){raw[j].z * w.z, raw[j].w * w.w};
-    }
+    v2f ze[8], zo[8], z[16];
+    window2k(raw, wintab, lane, ze, zo);
 #pragma unroll
     for (int j = 0; j < 6; ++j) raw[j] = raw[j + 2];
     raw[6] = fresh[0];
     raw[7] = fresh[1];
-    const int col = (lane - rot) & 63;
-    fft512<false>(ze, tw, lds, lane, col);
-    fft512<false>(zo, tw, lds, lane, col);
-    const LdsTwiddles<false> twc = {tab, col};
-    v2f z[16];
-#pragma unroll
-    for (int m = 0; m < 8; ++m) {
-      const v2f t = cmul_v(zo[m], twc.getr(m));
-      const v2f e = ze[m] * hh;
-      z[m] = e + t;
-      z[m + 8] = e - t;
-    }
-    v2f pm[16];
-    mirror_regs_rot<16>(z, pm, lane, rot, col);
-    const v2f nyq = {2.0f * (z[0].x - z[0].y), 0.0f};          // X[1024], meaningful on the lane whose column is 0
-    const v2f* w2 = reinterpret_cast<const v2f*>(w2tab) + col;
-#pragma unroll
-    for (int m = 0; m < 16; ++m) {
-      const v2f e = add_conj(z[m], pm[m]);
-      const v2f d = sub_conj(z[m], pm[m]);
-      z[m] = add_mi(e, cmul_v(d, lds_read_single(w2 + 64 * m)));
-    }
+    const v2f nyq = {fwd_core2k<true>(ze, zo, tab, lds, lane, rot, (lane - rot) & 63, [&](int m, v2f xk) { z[m] = xk; }), 0.0f};
     wave_priority<1>();
     const bool lo = lane < rot;
     const v2f s0 = lo ? carry : z[0];
@@ -303,6 +300,20 @@ __global__ __launch_bounds__(64 * W2KR, 4) void stft2048_run_fwd_kernel(P2kRun p
   if (lane < rot) put(sp, carry);
 }
 
+// The inverse core: v[m] = Z[lane + 64 m] of irfft_presplit<16> (fft512.h) -> the unnormalised time samples,
+// (y[0][j], y[1][j]) = x[4 n .. 4 n + 3], n = lane + 64 j -- the radix-2 stage backwards and the two 512-point FFTs.
+__device__ __forceinline__ void inv_core2k(const v2f (&v)[16], const LdsTwiddles<true>& tw, float2* lds, int lane,
+                                           v2f (&y)[2][8]) {
+  // radix-2 backwards: even samples from Z[k] + Z[k+512], odd ones from (Z[k] - Z[k+512]) conj(W1024^k)
+#pragma unroll
+  for (int m = 0; m < 8; ++m) {
+    y[0][m] = v[m] + v[m + 8];
+    y[1][m] = cmul_conj_v(v[m] - v[m + 8], tw.getr(m));
+  }
+  fft512<true>(y[0], tw, lds, lane);
+  fft512<true>(y[1], tw, lds, lane);
+}
+
 // irfft(X) * window, frames out (the overlap-add is stft_generic.hip's gather): complex or polar input
 template <bool POLAR>
 __global__ __launch_bounds__(64 * W2K, 3) void irfft2048_frames_kernel(P2k p) {
@@ -310,122 +321,51 @@ __global__ __launch_bounds__(64 * W2K, 3) void irfft2048_frames_kernel(P2k p) {
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // uniform: run bookkeeping on the scalar unit
   float2* lds = lds_all + wave * kFftLdsFloat2PerWave;
   float2* tab = lds_all + W2K * kFftLdsFloat2PerWave;
-  const v2f* w2 = reinterpret_cast<const v2f*>(tab + kTwiddleCount) + lane;
-  stage_tables2k<true>(p, tab, tab + kTwiddleCount);
+  const v2f* w2 = reinterpret_cast<const v2f*>(tab + kTwiddleCount) + lane;     // w2[64 m] = W2048^(lane + 64 m)
+  stage_tables2k<true, 64 * W2K>(p.tw, p.tw2k, tab, tab + kTwiddleCount);
   const LdsTwiddles<true> tw = {tab, lane};      // tw.getr(m) = W1024^(lane + 64 m)
   const long long f_begin = (long long)blockIdx.x * p.frames_per_block;
   long long f_end = f_begin + p.frames_per_block;
   if (f_end > p.total_frames) f_end = p.total_frames;
   const float4* win4 = reinterpret_cast<const float4*>(p.window);
-  const float scale = 1.0f / 2048.0f;
+  const float scale = 1.0f / 2048.0f;             // the split's factor 2 is in here
   for (long long f = f_begin + wave; f < f_end; f += W2K) {
-    v2f v[16];
+    v2f v[16], z[16], y[2][8];
     float nyq_re;
-    if (POLAR) {
-      const float* mrow = p.mag + f * F2K;
-      const float* prow = p.phase + f * F2K;
-#pragma unroll
-      for (int m = 0; m < 16; ++m) {
-        float sn, cs;
-        const float a = mrow[lane + 64 * m];
-        fast_sincosf(prow[lane + 64 * m], sn, cs);
-        v[m] = (v2f){a * cs, a * sn};
-      }
-      float sn, cs;
-      fast_sincosf(prow[1024], sn, cs);
-      nyq_re = mrow[1024] * cs;
-    } else {
-      const float2* row = p.X + f * F2K;
-#pragma unroll
-      for (int m = 0; m < 16; ++m) v[m] = to_v(row[lane + 64 * m]);
-      nyq_re = row[1024].x;
-    }
-    if (lane == 0) v[0].y = 0.0f;                       // c2r ignores the imaginary parts of DC and Nyquist
-    v2f pm[16];
-    mirror_regs<16>(v, pm, lane);
-    if (lane == 0) pm[0] = (v2f){nyq_re, 0.0f};         // partner of k = 0 is X[1024]
-    // Z = E + i O,  E = X + conj X',  O = (X - conj X') conj(W2048^k)   (twice the true value: folded into `scale`)
-#pragma unroll
-    for (int m = 0; m < 16; ++m) {
-      const v2f e = add_conj(v[m], pm[m]);
-      const v2f d = cmul_conj_v(sub_conj(v[m], pm[m]), w2[64 * m]);
-      v[m] = add_pi(e, d);
-    }
-    // radix-2 backwards: even samples from Z[k] + Z[k+512], odd ones from (Z[k] - Z[k+512]) conj(W1024^k)
-    v2f ze[8], zo[8];
-#pragma unroll
-    for (int m = 0; m < 8; ++m) {
-      ze[m] = v[m] + v[m + 8];
-      zo[m] = cmul_conj_v(v[m] - v[m + 8], tw.getr(m));
-    }
-    fft512<true>(ze, tw, lds, lane);
-    fft512<true>(zo, tw, lds, lane);
+    load_spectrum_row<16, POLAR>(p.X, p.mag, p.phase, f * F2K, lane, v, nyq_re);
+    irfft_presplit<16, 64>(v, nyq_re, lane, w2, z);
+    inv_core2k(z, tw, lds, lane, y);
     float4* dst = reinterpret_cast<float4*>(p.y + f * N2K);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const float4 w = win4[lane + 64 * j];
-      dst[lane + 64 * j] = make_float4(ze[j].x * (w.x * scale), ze[j].y * (w.y * scale), zo[j].x * (w.z * scale),
-                                       zo[j].y * (w.w * scale));
+      dst[lane + 64 * j] = make_float4(y[0][j].x * (w.x * scale), y[0][j].y * (w.y * scale), y[1][j].x * (w.z * scale),
+                                       y[1][j].y * (w.w * scale));
     }
   }
 }
 
 // ---------------------------------------------------------------------------
 // torch.istft for n_fft = 2048, hop = 256 / 512 / 1024 in one kernel: irfft + window + overlap-add + envelope
-// (reference stft.py:120-128, dgt.py:86-93; polar input: stft.py:157-161, dgt.py:152-154).
-// A wave walks consecutive frames of one clip.  A frame is 8 register slots of 256 samples (float4 per lane); a hop
-// is HS = hop / 256 slots, so the R = 8 / HS frames that overlap a hop are summed in registers: after frame t has
-// been added, block t of the padded signal (samples [t hop, (t + 1) hop)) is complete -- it is divided by the window
-// envelope of the frames that exist around it (the 2^R x hop table of at_istft_envelope_table) and stored once.
-// Output sample s is padded sample s + 1024 (center = True trims n_fft / 2 at both ends): block c is output hop
-// c - 1024 / hop.  A run of blocks [c0, c1) starts R - 1 frames early (warm-up) to have its first block complete.
+// (reference stft.py:120-128, dgt.py:86-93; polar input: stft.py:157-161, dgt.py:152-154).  The inverse core above into
+// the register window of ola_window.h, one float4 per lane and 256-sample slot.
 // ---------------------------------------------------------------------------
-struct P2kOla {
-  const float2* X;       // (B*T, 1025) complex64, or null
-  const float* mag;      // polar input
-  const float* phase;
-  const float* window;   // 2048 synthesis window samples
-  const float* env;      // 2^R x hop
-  const float2* tw;
-  const float2* tw2k;
-  float* y;              // (B, hop (T - 1))
-  long long B, T, runs_per_clip, blocks_per_run;
-};
-
 template <bool POLAR, int HS>
-__global__ __launch_bounds__(64 * W2K, 2) void istft2048_ola_kernel(P2kOla p) {
+__global__ __launch_bounds__(64 * W2K, 2) void istft2048_ola_kernel(POla p) {
   constexpr int HOP = 256 * HS, R = 8 / HS, LEAD = 1024 / HOP;      // LEAD: blocks trimmed at the front
   __shared__ float2 lds_all[W2K * kFftLdsFloat2PerWave + kTwiddleCount + 1024 + 1024];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // uniform: run bookkeeping on the scalar unit
   float2* lds = lds_all + wave * kFftLdsFloat2PerWave;
   float2* tab = lds_all + W2K * kFftLdsFloat2PerWave;
   const v2f* w2 = reinterpret_cast<const v2f*>(tab + kTwiddleCount) + lane;
-  for (int i = threadIdx.x; i < kTwiddleCount; i += 64 * W2K) tab[i] = twiddle_for_lds<true>(p.tw, i);
-  for (int i = threadIdx.x; i < 1024; i += 64 * W2K) tab[kTwiddleCount + i] = p.tw2k[i];
-  // the synthesis window with the transform's 1/2048 folded in, shared by the block's waves: read from global memory
-  // per frame it was as many bytes through the vector-memory path as the spectrum row itself
   float4* wintab = reinterpret_cast<float4*>(tab + kTwiddleCount + 1024);
-  for (int i = threadIdx.x; i < 512; i += 64 * W2K) {
-    const float4 w = reinterpret_cast<const float4*>(p.window)[i];
-    const float sc = 1.0f / 2048.0f;
-    wintab[i] = make_float4(w.x * sc, w.y * sc, w.z * sc, w.w * sc);
-  }
-  __syncthreads();
+  stage_ola_window<N2K, 64 * W2K>(p.window, wintab);
+  stage_tables2k<true, 64 * W2K>(p.tw, p.tw_n, tab, tab + kTwiddleCount);
   const LdsTwiddles<true> tw = {tab, lane};
-  const long long run = (long long)blockIdx.x * W2K + wave;
-  const long long b = run / p.runs_per_clip;
-  if (b >= p.B) return;
-  const long long r = run - b * p.runs_per_clip;
+  long long b, c0, c1;
+  if (!ola_run_blocks(p, (long long)blockIdx.x * W2K + wave, LEAD, b, c0, c1)) return;
   const long long T = p.T;
-  // output hops q = 0 .. T - 2 are blocks c = q + LEAD
-  const long long c0 = LEAD + r * p.blocks_per_run;
-  long long c1 = c0 + p.blocks_per_run;
-  if (c1 > LEAD + T - 1) c1 = LEAD + T - 1;
-  if (c0 >= c1) return;
   const float4* env4 = reinterpret_cast<const float4*>(p.env);
-  float4 acc[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) acc[j] = make_float4(0.f, 0.f, 0.f, 0.f);
   float* yclip = p.y + b * (HOP * (T - 1));
 
   // Complex input: the next frame's row is requested before the current one is transformed (one frame = 8 KB per wave
@@ -441,16 +381,11 @@ __global__ __launch_bounds__(64 * W2K, 2) void istft2048_ola_kernel(P2kOla p) {
     nxt_nyq = reinterpret_cast<const float*>(row + 1024)[0];
   };
   if constexpr (!POLAR) request(c0 - (R - 1));
-  // reciprocal of the fully overlapped envelope: one division per wave instead of four per hop (<= 1 ulp from acc / e)
-  float4 rcp_full[HS];
-#pragma unroll
-  for (int j = 0; j < HS; ++j) {
-    const float4 e = env4[(size_t)((1 << R) - 1) * (HOP / 4) + lane + 64 * j];
-    rcp_full[j] = make_float4(1.0f / e.x, 1.0f / e.y, 1.0f / e.z, 1.0f / e.w);
-  }
+  OlaWindow<HS, 1> ola;
+  ola.init(env4, lane);
 
   for (long long t = c0 - (R - 1); t < c1; ++t) {
-    v2f cur[16];
+    v2f cur[16], z[16], y[2][8];
     float cur_nyq = 0.f;
     if constexpr (!POLAR) {
 #pragma unroll
@@ -459,86 +394,14 @@ __global__ __launch_bounds__(64 * W2K, 2) void istft2048_ola_kernel(P2kOla p) {
       request(t + 1);
     }
     if (t >= 0 && t < T) {
-      const long long f = b * T + t;
-      v2f v[16];
-      float nyq_re;
-      if (POLAR) {
-        const float* mrow = p.mag + f * F2K;
-        const float* prow = p.phase + f * F2K;
-#pragma unroll
-        for (int m = 0; m < 16; ++m) {
-          float sn, cs;
-          const float a = mrow[lane + 64 * m];
-          fast_sincosf(prow[lane + 64 * m], sn, cs);
-          v[m] = (v2f){a * cs, a * sn};
-        }
-        float sn, cs;
-        fast_sincosf(prow[1024], sn, cs);
-        nyq_re = mrow[1024] * cs;
-      } else {
-#pragma unroll
-        for (int m = 0; m < 16; ++m) v[m] = cur[m];
-        nyq_re = cur_nyq;
-        (void)f;
-      }
-      if (lane == 0) v[0].y = 0.0f;
-      v2f pm[16];
-      mirror_regs<16>(v, pm, lane);
-      if (lane == 0) pm[0] = (v2f){nyq_re, 0.0f};
-#pragma unroll
-      for (int m = 0; m < 16; ++m) {
-        const v2f e = add_conj(v[m], pm[m]);
-        const v2f d = cmul_conj_v(sub_conj(v[m], pm[m]), w2[64 * m]);
-        v[m] = add_pi(e, d);
-      }
-      v2f ze[8], zo[8];
-#pragma unroll
-      for (int m = 0; m < 8; ++m) {
-        ze[m] = v[m] + v[m + 8];
-        zo[m] = cmul_conj_v(v[m] - v[m + 8], tw.getr(m));
-      }
-      fft512<true>(ze, tw, lds, lane);
-      fft512<true>(zo, tw, lds, lane);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float4 w = wintab[lane + 64 * j];
-        acc[j].x += ze[j].x * w.x;
-        acc[j].y += ze[j].y * w.y;
-        acc[j].z += zo[j].x * w.z;
-        acc[j].w += zo[j].y * w.w;
-      }
+      if constexpr (POLAR) load_spectrum_row<16, true>(nullptr, p.mag, p.phase, (b * T + t) * F2K, lane, cur, cur_nyq);
+      irfft_presplit<16, 64>(cur, cur_nyq, lane, w2, z);
+      inv_core2k(z, tw, lds, lane, y);
+      ola.add_frame(y, wintab, lane);
     }
     // block t is complete: frames t - R + 1 .. t are all that cover it
-    if (t >= c0) {
-      int mask = 0;
-#pragma unroll
-      for (int q = 0; q < R; ++q) {
-        const long long ft = t - (R - 1) + q;          // bit q: oldest frame first (at_istft_envelope_table)
-        if (ft >= 0 && ft < T) mask |= 1 << q;
-      }
-      float* dst = yclip + (t - LEAD) * HOP;
-      typedef float v4f __attribute__((ext_vector_type(4)));
-      if (mask == (1 << R) - 1) {
-        // a hop's value must not depend on how the launch cut the clip into runs: every fully overlapped hop takes
-        // the reciprocal form, whichever run emits it
-#pragma unroll
-        for (int j = 0; j < HS; ++j)
-          __builtin_nontemporal_store((v4f){acc[j].x * rcp_full[j].x, acc[j].y * rcp_full[j].y, acc[j].z * rcp_full[j].z,
-                                            acc[j].w * rcp_full[j].w},
-                                      reinterpret_cast<v4f*>(dst + 4 * (lane + 64 * j)));
-      } else {
-#pragma unroll
-        for (int j = 0; j < HS; ++j) {
-          const float4 e = env4[(size_t)mask * (HOP / 4) + lane + 64 * j];
-          *reinterpret_cast<float4*>(dst + 4 * (lane + 64 * j)) =
-              make_float4(acc[j].x / e.x, acc[j].y / e.y, acc[j].z / e.z, acc[j].w / e.w);
-        }
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 8 - HS; ++j) acc[j] = acc[j + HS];
-#pragma unroll
-    for (int j = 8 - HS; j < 8; ++j) acc[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (t >= c0) ola.emit(yclip + (t - LEAD) * HOP, env4, ola.frame_mask(t, T), lane);
+    ola.slide();
   }
 }
 
@@ -566,6 +429,34 @@ struct P2kMel {
   float eps;
 };
 
+// One pass of the band walk: this lane's filter over `quads` float4 of the |X|^p row from `a` on, its weights at w[64 j]
+// (the pass's block of the lane-interleaved table); moves w past the block and returns the sum.
+__device__ __forceinline__ float band_walk2k(const float* a, const float4*& w, int quads) {
+  const float4* a4 = reinterpret_cast<const float4*>(a);
+  v2f acc2 = {0.f, 0.f};
+  int j = 0;
+  for (; j + 4 <= quads; j += 4) {          // four steps' reads ahead of the multiply-adds
+    float4 av[4], wv[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      av[u] = a4[j + u];
+      wv[u] = w[(j + u) * 64];
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      acc2 = __builtin_elementwise_fma((v2f){av[u].x, av[u].y}, (v2f){wv[u].x, wv[u].y}, acc2);
+      acc2 = __builtin_elementwise_fma((v2f){av[u].z, av[u].w}, (v2f){wv[u].z, wv[u].w}, acc2);
+    }
+  }
+  for (; j < quads; ++j) {
+    const float4 av = a4[j], wv = w[j * 64];
+    acc2 = __builtin_elementwise_fma((v2f){av.x, av.y}, (v2f){wv.x, wv.y}, acc2);
+    acc2 = __builtin_elementwise_fma((v2f){av.z, av.w}, (v2f){wv.z, wv.w}, acc2);
+  }
+  w += quads * 64;
+  return acc2.x + acc2.y;
+}
+
 // CMW 1 / 2: channel-major output of a bank with that many passes (register window); 0: anything else.  WINLDS: the
 // analysis window staged in LDS (when the bank's tables leave 8 KB of the two-blocks-per-CU budget).
 template <int CMW, bool WINLDS>
@@ -574,13 +465,10 @@ __global__ __launch_bounds__(64 * W2K, 2) void stft2048_mel_kernel(P2kMel p) {
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // uniform: run bookkeeping on the scalar unit
   float2* lds = lds_all + wave * kFftLdsFloat2PerWave;
   float2* tab = lds_all + W2K * kFftLdsFloat2PerWave;
-  const v2f* w2 = reinterpret_cast<const v2f*>(tab + kTwiddleCount) + lane;
   float* rows = reinterpret_cast<float*>(tab + kTwiddleCount + 1024);
   float* absrow = rows + wave * p.row_floats;
   float* wlds = rows + W2K * p.row_floats;
   int* lane_tab = reinterpret_cast<int*>(wlds + p.table_floats);
-  for (int i = threadIdx.x; i < kTwiddleCount; i += 64 * W2K) tab[i] = twiddle_for_lds<false>(p.tw, i);
-  for (int i = threadIdx.x; i < 1024; i += 64 * W2K) tab[kTwiddleCount + i] = p.tw2k[i];
   for (int i = threadIdx.x; i < p.table_floats; i += 64 * W2K) wlds[i] = p.bank.weights[i];
   for (int i = threadIdx.x; i < 64 * p.bank.n_passes; i += 64 * W2K) {
     lane_tab[i] = p.bank.lane_start[i];
@@ -593,21 +481,16 @@ __global__ __launch_bounds__(64 * W2K, 2) void stft2048_mel_kernel(P2kMel p) {
   if constexpr (WINLDS)
     for (int i = threadIdx.x; i < 512; i += 64 * W2K) wintab[i] = reinterpret_cast<const float4*>(p.window)[i];
   const float4* win4 = reinterpret_cast<const float4*>(p.window);
-  __syncthreads();
-  const LdsTwiddles<false> tw = {tab, lane};
+  stage_tables2k<false, 64 * W2K>(p.tw, p.tw2k, tab, tab + kTwiddleCount);
   const long long f_begin = ((long long)blockIdx.x * W2K + wave) * p.frames_per_wave;
   long long f_end = f_begin + p.frames_per_wave;
   if (f_end > p.total_frames) f_end = p.total_frames;
   if (f_begin >= f_end) return;
-  const v2f hh = {0.5f, 0.5f};
   float off = 0.f, sc = 1.f;
   if (p.offset) {
     off = *p.offset;
     sc = *p.scale;
   }
-  // forward kernel's frame loader on this struct's fields
-  P2k lp = {};
-  lp.x = p.x; lp.L = p.L; lp.clip_stride = p.clip_stride; lp.T = p.T; lp.hop = p.hop; lp.center = 1;
 
   float cm[CMW > 0 ? CMW : 1][8];
   long long e_next[CMW > 0 ? CMW : 1];
@@ -623,38 +506,17 @@ __global__ __launch_bounds__(64 * W2K, 2) void stft2048_mel_kernel(P2kMel p) {
   long long cb = f_begin / p.T, ct = f_begin - cb * p.T;
 
   float4 nxt[8];
-  load_frame2k(lp, f_begin, lane, nxt);
+  load_frame2k(p.x, p.clip_stride, p.L, p.T, p.hop, 1, f_begin, lane, nxt);
   for (long long f = f_begin; f < f_end; ++f) {
     wave_priority<3>();        // transform > epilogue
     v2f ze[8], zo[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float4 w = WINLDS ? wintab[lane + 64 * j] : win4[lane + 64 * j];
-      ze[j] = (v2f){nxt[j].x * w.x, nxt[j].y * w.y};
-      zo[j] = (v2f){nxt[j].z * w.z, nxt[j].w * w.w};
-    }
-    if (f + 1 < f_end) load_frame2k(lp, f + 1, lane, nxt);
-    fft512<false>(ze, tw, lds, lane);
-    fft512<false>(zo, tw, lds, lane);
-    v2f z[16];
-#pragma unroll
-    for (int m = 0; m < 8; ++m) {
-      const v2f t = cmul_v(zo[m], tw.getr(m));
-      const v2f e = ze[m] * hh;
-      z[m] = e + t;
-      z[m + 8] = e - t;
-    }
-    v2f pm[16];
-    mirror_regs<16>(z, pm, lane);
-    const float nyq = 2.0f * (z[0].x - z[0].y);          // X[1024] (lane 0), real
-#pragma unroll
-    for (int m = 0; m < 16; ++m) {
-      const v2f e = add_conj(z[m], pm[m]);
-      const v2f d = sub_conj(z[m], pm[m]);
-      const v2f xk = add_mi(e, cmul_v(d, w2[64 * m]));
+    if constexpr (WINLDS) window2k(nxt, wintab, lane, ze, zo);
+    else window2k(nxt, win4, lane, ze, zo);
+    if (f + 1 < f_end) load_frame2k(p.x, p.clip_stride, p.L, p.T, p.hop, 1, f + 1, lane, nxt);
+    const float nyq = fwd_core2k<false>(ze, zo, tab, lds, lane, 0, lane, [&](int m, v2f xk) {
       const float s2 = fmaf(xk.x, xk.x, xk.y * xk.y);
       absrow[lane + 64 * m] = p.power2 ? s2 : __builtin_amdgcn_sqrtf(s2);
-    }
+    });                                                  // X[1024] (lane 0), real
     if (lane == 0) absrow[1024] = p.power2 ? nyq * nyq : fabsf(nyq);
     wave_lds_sync();
     wave_priority<0>();
@@ -671,30 +533,7 @@ __global__ __launch_bounds__(64 * W2K, 2) void stft2048_mel_kernel(P2kMel p) {
 #pragma unroll
       for (int q = 0; q < CMW; ++q) {
         fq[q] = lane_tab[(CMW + q) * 64 + lane];
-        const float4* a = reinterpret_cast<const float4*>(absrow + lane_tab[q * 64 + lane]);
-        v2f acc2 = {0.f, 0.f};
-        const int quads = p.bank.pass_len[q] >> 2;
-        int j = 0;
-        for (; j + 4 <= quads; j += 4) {          // four steps' reads ahead of the multiply-adds
-          float4 av[4], wv[4];
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            av[u] = a[j + u];
-            wv[u] = w[(j + u) * 64];
-          }
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            acc2 = __builtin_elementwise_fma((v2f){av[u].x, av[u].y}, (v2f){wv[u].x, wv[u].y}, acc2);
-            acc2 = __builtin_elementwise_fma((v2f){av[u].z, av[u].w}, (v2f){wv[u].z, wv[u].w}, acc2);
-          }
-        }
-        for (; j < quads; ++j) {
-          const float4 av = a[j], wv = w[j * 64];
-          acc2 = __builtin_elementwise_fma((v2f){av.x, av.y}, (v2f){wv.x, wv.y}, acc2);
-          acc2 = __builtin_elementwise_fma((v2f){av.z, av.w}, (v2f){wv.z, wv.w}, acc2);
-        }
-        w += quads * 64;
-        float acc = contrast_fwd(acc2.x + acc2.y, p.contrast, p.eps);
+        float acc = contrast_fwd(band_walk2k(absrow + lane_tab[q * 64 + lane], w, p.bank.pass_len[q] >> 2), p.contrast, p.eps);
         if (p.offset) acc = (acc - off) / sc;
 #pragma unroll
         for (int k = 0; k < 7; ++k) cm[q][k] = cm[q][k + 1];
@@ -729,31 +568,9 @@ __global__ __launch_bounds__(64 * W2K, 2) void stft2048_mel_kernel(P2kMel p) {
     } else {
       for (int q = 0; q < p.bank.n_passes; ++q) {
         const int filt = lane_tab[(p.bank.n_passes + q) * 64 + lane];
-        const float4* a = reinterpret_cast<const float4*>(absrow + lane_tab[q * 64 + lane]);
-        v2f acc2 = {0.f, 0.f};
-        const int quads = p.bank.pass_len[q] >> 2;
-        int j = 0;
-        for (; j + 4 <= quads; j += 4) {          // four steps' reads ahead of the multiply-adds
-          float4 av[4], wv[4];
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            av[u] = a[j + u];
-            wv[u] = w[(j + u) * 64];
-          }
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            acc2 = __builtin_elementwise_fma((v2f){av[u].x, av[u].y}, (v2f){wv[u].x, wv[u].y}, acc2);
-            acc2 = __builtin_elementwise_fma((v2f){av[u].z, av[u].w}, (v2f){wv[u].z, wv[u].w}, acc2);
-          }
-        }
-        for (; j < quads; ++j) {
-          const float4 av = a[j], wv = w[j * 64];
-          acc2 = __builtin_elementwise_fma((v2f){av.x, av.y}, (v2f){wv.x, wv.y}, acc2);
-          acc2 = __builtin_elementwise_fma((v2f){av.z, av.w}, (v2f){wv.z, wv.w}, acc2);
-        }
-        w += quads * 64;
+        const float sum = band_walk2k(absrow + lane_tab[q * 64 + lane], w, p.bank.pass_len[q] >> 2);
         if (filt >= 0) {
-          float acc = contrast_fwd(acc2.x + acc2.y, p.contrast, p.eps);
+          float acc = contrast_fwd(sum, p.contrast, p.eps);
           if (p.offset) acc = (acc - off) / sc;
           if (p.channel_major) p.feat[(b * p.bank.n_filters + filt) * p.T + t] = acc;
           else p.feat[f * p.bank.n_filters + filt] = acc;
@@ -812,21 +629,10 @@ int launch_stft2048_mel(const float* x, long long B, long long L, long long clip
 int launch_istft2048_ola(const float2* X, const float* mag, const float* phase, long long B, long long T, int hop,
                          const float* window, const float* env, const float2* tw, const float2* tw2k, float* y,
                          hipStream_t stream) {
-  if (B == 0 || T <= 1) return 0;
-  P2kOla p = {X, mag, phase, window, env, tw, tw2k, y, B, T, 0, 0};
-  const long long blocks = T - 1;                        // output hops per clip
-  p.blocks_per_run = plan_ola_runs(B, blocks, 2048, 8);
-  p.runs_per_clip = (blocks + p.blocks_per_run - 1) / p.blocks_per_run;
-  const long long waves = B * p.runs_per_clip;
-  const unsigned grid = (unsigned)((waves + W2K - 1) / W2K);
-#define OLA2K(POLAR_, HS_) hipLaunchKernelGGL((istft2048_ola_kernel<POLAR_, HS_>), dim3(grid), dim3(64 * W2K), 0, stream, p)
-  const bool polar = (X == nullptr);
-  if (hop == 256) { if (polar) OLA2K(true, 1); else OLA2K(false, 1); }
-  else if (hop == 512) { if (polar) OLA2K(true, 2); else OLA2K(false, 2); }
-  else if (hop == 1024) { if (polar) OLA2K(true, 4); else OLA2K(false, 4); }
-  else return -2;
-#undef OLA2K
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  static void (*const kernels[2][3])(POla) = {
+      {istft2048_ola_kernel<false, 1>, istft2048_ola_kernel<false, 2>, istft2048_ola_kernel<false, 4>},
+      {istft2048_ola_kernel<true, 1>, istft2048_ola_kernel<true, 2>, istft2048_ola_kernel<true, 4>}};
+  return launch_istft_ola(kernels, N2K, W2K, X, mag, phase, B, T, hop, window, env, tw, tw2k, y, stream);
 }
 
 int launch_stft2048_fwd(const float* x, long long B, long long L, long long clip_stride, long long T, int hop, int center,

@@ -16,12 +16,17 @@
 //   X[k] = (Z[k] + conj Z[2048-k])/2 - (i/2) W4096^k (Z[k] - conj Z[2048-k]),  k = 0 .. 2048
 // The mirror partner Z[2048-k] lives in lane 64-lane, register 31-m (lane 0: its own register 32-m).  The inverse
 // runs the same steps backwards.  One wave = one frame at a time, frames of a block interleaved over its four waves.
+//
+// Each direction's arithmetic is written once: fwd_core4k (four FFTs, radix-4, mirror, merge; plain or with rotated
+// output columns) serves the frame and the run kernel, inv_core4k (radix-4 backwards, four FFTs) behind fft512.h's
+// load_spectrum_row / irfft_presplit serves the frames and the fused overlap-add kernel (ola_window.h).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/acids_hip.h"
 #include "fastmath.h"
 #include "fft512.h"
+#include "ola_window.h"
 #include "run_plan.h"
 #include "stft_launch.h"
 #include "variants.h"
@@ -101,6 +106,60 @@ __device__ __forceinline__ void stage_tables4k(const float2* tw, const float2* t
 
 constexpr int kLds4k = W4K * kFftLdsFloat2PerWave + kTwiddleCount + kTab4k;
 
+// a frame's raw samples times the window (global memory or LDS) -> the inputs y[r] of the four 512-point FFTs
+__device__ __forceinline__ void window4k(const float4 (&qa)[8], const float4 (&qb)[8], const float4* win, int lane,
+                                         v2f (&y)[4][8]) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const float4 wa = win[2 * (lane + 64 * j)];
+    const float4 wb = win[2 * (lane + 64 * j) + 1];
+    y[0][j] = (v2f){qa[j].x * wa.x, qa[j].y * wa.y};
+    y[1][j] = (v2f){qa[j].z * wa.z, qa[j].w * wa.w};
+    y[2][j] = (v2f){qb[j].x * wb.x, qb[j].y * wb.y};
+    y[3][j] = (v2f){qb[j].z * wb.z, qb[j].w * wb.w};
+  }
+}
+
+// The forward core: the windowed samples y[r][m] = z[4 (lane + 64 m) + r] -> out(m, X[col + 64 m]), m = 0 .. 31, in that
+// order; returns X[2048] (real; meaningful on the lane whose column is 0).  t4: the staged n_fft-4096 tables.  The run
+// kernel rotates the output columns over the lanes: this lane holds column col = (lane - rot) & 63 (the radix-4 stage is
+// lane-local; its twiddles, the merge's and the mirror lane follow the column); the frame kernel passes rot = 0, col = lane.
+// The bins go to a consumer, not to an array: a kernel that stores or reduces them does so inside the merge loop, as the
+// kernels did before they shared this core, and keeps their register count (profiles/nfft_cores.md).
+template <typename OUT>
+__device__ __forceinline__ float fwd_core4k(v2f (&y)[4][8], const LdsTwiddles<false>& tw, const float2* t4, float2* lds,
+                                            int lane, int rot, int col, OUT&& out) {
+  const v2f hh = {0.5f, 0.5f};
+#pragma unroll
+  for (int r = 0; r < 4; ++r) fft512<false>(y[r], tw, lds, lane, col);
+  const v2f* wh = reinterpret_cast<const v2f*>(t4) + col;            // wh[64 m] = W4096^(col + 64 m) / 2
+  const v2f* wr = reinterpret_cast<const v2f*>(t4 + 2048) + col;     // wr[(r - 1) 512 + 64 m] = W2048^(r (col + 64 m))
+  // radix-4: registers m, m + 8, m + 16, m + 24 hold Z[k], Z[k + 512], Z[k + 1024], Z[k + 1536]
+  v2f z[32];
+#pragma unroll
+  for (int m = 0; m < 8; ++m) {
+    const v2f t1 = cmul_v(y[1][m], wr[64 * m]);
+    const v2f t2 = cmul_v(y[2][m], wr[512 + 64 * m]);
+    const v2f t3 = cmul_v(y[3][m], wr[1024 + 64 * m]);
+    const v2f a = y[0][m] + t2, b = y[0][m] - t2, c = t1 + t3, d = t1 - t3;
+    z[m] = a + c;
+    z[m + 16] = a - c;
+    z[m + 8] = add_mi(b, d);        // b - i d
+    z[m + 24] = add_pi(b, d);       // b + i d
+  }
+  v2f pm[32];
+  mirror_regs_rot<32>(z, pm, lane, rot, col);
+  // X[k] = (Z[k] + conj Z')/2 - i (W4096^k / 2) (Z[k] - conj Z'),  Z' = Z[2048 - k]  (k = 0: Z' = Z[0], X[0] real)
+  const float nyq = z[0].x - z[0].y;                                // X[2048] = Re Z[0] - Im Z[0]
+#pragma unroll
+  for (int m = 0; m < 32; ++m) {
+    const v2f e = add_conj(z[m], pm[m]);
+    const v2f d = sub_conj(z[m], pm[m]);
+    out(m, scale_add_mi(e, hh, cmul_v(d, wh[64 * m])));             // e / 2 - i (W / 2) d
+  }
+  return nyq;
+}
+
 template <bool WRITE_PHASE>
 __global__ __launch_bounds__(64 * W4K, 2) void stft4096_fwd_kernel(P4k p) {
   __shared__ float2 lds_all[kLds4k];
@@ -108,65 +167,29 @@ __global__ __launch_bounds__(64 * W4K, 2) void stft4096_fwd_kernel(P4k p) {
   float2* lds = lds_all + wave * kFftLdsFloat2PerWave;
   float2* tab = lds_all + W4K * kFftLdsFloat2PerWave;
   float2* t4 = tab + kTwiddleCount;
-  const v2f* wh = reinterpret_cast<const v2f*>(t4) + lane;            // wh[64 m] = W4096^(lane + 64 m) / 2
-  const v2f* wr = reinterpret_cast<const v2f*>(t4 + 2048) + lane;     // wr[(r - 1) * 512 + 64 m] = W2048^(r (lane + 64 m))
   stage_tables4k<false>(p.tw, p.tw4k, tab, t4);
   const LdsTwiddles<false> tw = {tab, lane};
   const long long f_begin = (long long)blockIdx.x * p.frames_per_block;
   long long f_end = f_begin + p.frames_per_block;
   if (f_end > p.total_frames) f_end = p.total_frames;
-  const float4* win4 = reinterpret_cast<const float4*>(p.window);
-  const v2f hh = {0.5f, 0.5f};
+  const float4* win4 = reinterpret_cast<const float4*>(p.window);     // L2-resident (16 KB), re-read per frame
 
   long long f = f_begin + wave;
   float4 na[8], nb[8];
   if (f < f_end) load_frame4k(p, f, lane, na, nb);
   for (; f < f_end; f += W4K) {
-    v2f z0[8], z1[8], z2[8], z3[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float4 wa = win4[2 * (lane + 64 * j)];   // L2-resident (16 KB), re-read per frame
-      const float4 wb = win4[2 * (lane + 64 * j) + 1];
-      z0[j] = (v2f){na[j].x * wa.x, na[j].y * wa.y};
-      z1[j] = (v2f){na[j].z * wa.z, na[j].w * wa.w};
-      z2[j] = (v2f){nb[j].x * wb.x, nb[j].y * wb.y};
-      z3[j] = (v2f){nb[j].z * wb.z, nb[j].w * wb.w};
-    }
+    v2f y[4][8];
+    window4k(na, nb, win4, lane, y);
     if (f + W4K < f_end) load_frame4k(p, f + W4K, lane, na, nb);
-    fft512<false>(z0, tw, lds, lane);
-    fft512<false>(z1, tw, lds, lane);
-    fft512<false>(z2, tw, lds, lane);
-    fft512<false>(z3, tw, lds, lane);
-    // radix-4: registers m, m + 8, m + 16, m + 24 hold Z[k], Z[k + 512], Z[k + 1024], Z[k + 1536]
-    v2f z[32];
-#pragma unroll
-    for (int m = 0; m < 8; ++m) {
-      const v2f t1 = cmul_v(z1[m], wr[64 * m]);
-      const v2f t2 = cmul_v(z2[m], wr[512 + 64 * m]);
-      const v2f t3 = cmul_v(z3[m], wr[1024 + 64 * m]);
-      const v2f a = z0[m] + t2, b = z0[m] - t2, c = t1 + t3, d = t1 - t3;
-      z[m] = a + c;
-      z[m + 16] = a - c;
-      z[m + 8] = add_mi(b, d);        // b - i d
-      z[m + 24] = add_pi(b, d);       // b + i d
-    }
-    v2f pm[32];
-    mirror_regs<32>(z, pm, lane);
-    // X[k] = (Z[k] + conj Z')/2 - i (W4096^k / 2) (Z[k] - conj Z'),  Z' = Z[2048 - k]  (k = 0: Z' = Z[0], X[0] real)
-    const float2 nyq = make_float2(z[0].x - z[0].y, 0.0f);      // X[2048] = Re Z[0] - Im Z[0] (lane 0)
     float2* row = p.X + f * F4K;
     float* prow = WRITE_PHASE ? p.phase_out + f * F4K : nullptr;
-#pragma unroll
-    for (int m = 0; m < 32; ++m) {
-      const v2f e = add_conj(z[m], pm[m]);
-      const v2f d = sub_conj(z[m], pm[m]);
-      const v2f xk = scale_add_mi(e, hh, cmul_v(d, wh[64 * m]));      // e / 2 - i (W / 2) d
+    const float nyq = fwd_core4k(y, tw, t4, lds, lane, 0, lane, [&](int m, v2f xk) {
       row[lane + 64 * m] = to_f2(xk);
       if (WRITE_PHASE) prow[lane + 64 * m] = fast_atan2f(xk.y, xk.x);
-    }
+    });
     if (lane == 0) {
-      row[2048] = nyq;
-      if (WRITE_PHASE) prow[2048] = fast_atan2f(nyq.y, nyq.x);
+      row[2048] = make_float2(nyq, 0.0f);
+      if (WRITE_PHASE) prow[2048] = fast_atan2f(0.0f, nyq);
     }
   }
 }
@@ -230,7 +253,6 @@ __global__ __launch_bounds__(64 * W4K, 2) void stft4096_run_fwd_kernel(P4kRun p)
   const float* clip = p.x + b * p.clip_stride;
   const long long L = p.L;
   const LdsTwiddles<false> tw = {tab, lane};
-  const v2f hh = {0.5f, 0.5f};
 
   float4 ra[8], rb[8];
 #pragma unroll
@@ -250,16 +272,8 @@ __global__ __launch_bounds__(64 * W4K, 2) void stft4096_run_fwd_kernel(P4kRun p)
 
   auto frame_body = [&](const float4 (&fa)[2], const float4 (&fb)[2]) {
     wave_priority<3>();        // transform > stores, as in stft1024.hip
-    v2f z0[8], z1[8], z2[8], z3[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float4 wa = wintab[2 * (lane + 64 * j)];
-      const float4 wb = wintab[2 * (lane + 64 * j) + 1];
-      z0[j] = (v2f){ra[j].x * wa.x, ra[j].y * wa.y};
-      z1[j] = (v2f){ra[j].z * wa.z, ra[j].w * wa.w};
-      z2[j] = (v2f){rb[j].x * wb.x, rb[j].y * wb.y};
-      z3[j] = (v2f){rb[j].z * wb.z, rb[j].w * wb.w};
-    }
+    v2f y[4][8], z[32];
+    window4k(ra, rb, wintab, lane, y);
 #pragma unroll
     for (int j = 0; j < 6; ++j) {
       ra[j] = ra[j + 2];
@@ -267,34 +281,7 @@ __global__ __launch_bounds__(64 * W4K, 2) void stft4096_run_fwd_kernel(P4kRun p)
     }
     ra[6] = fa[0]; rb[6] = fb[0];
     ra[7] = fa[1]; rb[7] = fb[1];
-    const int col = (lane - rot) & 63;
-    fft512<false>(z0, tw, lds, lane, col);
-    fft512<false>(z1, tw, lds, lane, col);
-    fft512<false>(z2, tw, lds, lane, col);
-    fft512<false>(z3, tw, lds, lane, col);
-    const v2f* wh = reinterpret_cast<const v2f*>(t4) + col;            // wh[64 m] = W4096^(col + 64 m) / 2
-    const v2f* wr = reinterpret_cast<const v2f*>(t4 + 2048) + col;     // wr[(r - 1) 512 + 64 m] = W2048^(r (col + 64 m))
-    v2f z[32];
-#pragma unroll
-    for (int m = 0; m < 8; ++m) {
-      const v2f t1 = cmul_v(z1[m], wr[64 * m]);
-      const v2f t2 = cmul_v(z2[m], wr[512 + 64 * m]);
-      const v2f t3 = cmul_v(z3[m], wr[1024 + 64 * m]);
-      const v2f a = z0[m] + t2, bb = z0[m] - t2, c = t1 + t3, d = t1 - t3;
-      z[m] = a + c;
-      z[m + 16] = a - c;
-      z[m + 8] = add_mi(bb, d);
-      z[m + 24] = add_pi(bb, d);
-    }
-    v2f pm[32];
-    mirror_regs_rot<32>(z, pm, lane, rot, col);
-    const v2f nyq = {z[0].x - z[0].y, 0.0f};                           // X[2048], on the lane whose column is 0
-#pragma unroll
-    for (int m = 0; m < 32; ++m) {
-      const v2f e = add_conj(z[m], pm[m]);
-      const v2f d = sub_conj(z[m], pm[m]);
-      z[m] = scale_add_mi(e, hh, cmul_v(d, wh[64 * m]));
-    }
+    const v2f nyq = {fwd_core4k(y, tw, t4, lds, lane, rot, (lane - rot) & 63, [&](int m, v2f xk) { z[m] = xk; }), 0.0f};
     wave_priority<1>();
     const bool lo = lane < rot;
     const v2f s0 = lo ? carry : z[0];
@@ -343,52 +330,22 @@ __global__ __launch_bounds__(64 * W4K, 2) void stft4096_run_fwd_kernel(P4kRun p)
   if (lane < rot) put(sp, carry);
 }
 
-// one-sided spectrum of frame f -> the four sub-transform inputs, ready for fft512<true> (shared by the frames kernel)
-template <bool POLAR>
-__device__ __forceinline__ void spectrum_to_subffts4k(const float2* X, const float* mag, const float* phase, long long f,
-                                                      int lane, const v2f* w4, const v2f* wr, v2f (&y0)[8], v2f (&y1)[8],
-                                                      v2f (&y2)[8], v2f (&y3)[8]) {
-  v2f v[32];
-  float nyq_re;
-  if (POLAR) {
-    const float* mrow = mag + f * F4K;
-    const float* prow = phase + f * F4K;
-#pragma unroll
-    for (int m = 0; m < 32; ++m) {
-      float sn, cs;
-      const float a = mrow[lane + 64 * m];
-      fast_sincosf(prow[lane + 64 * m], sn, cs);
-      v[m] = (v2f){a * cs, a * sn};
-    }
-    float sn, cs;
-    fast_sincosf(prow[2048], sn, cs);
-    nyq_re = mrow[2048] * cs;
-  } else {
-    const float2* row = X + f * F4K;
-#pragma unroll
-    for (int m = 0; m < 32; ++m) v[m] = to_v(row[lane + 64 * m]);
-    nyq_re = row[2048].x;
-  }
-  if (lane == 0) v[0].y = 0.0f;                       // c2r ignores the imaginary parts of DC and Nyquist
-  v2f pm[32];
-  mirror_regs<32>(v, pm, lane);
-  if (lane == 0) pm[0] = (v2f){nyq_re, 0.0f};         // partner of k = 0 is X[2048]
-  // Z = E + i O,  E = X + conj X',  O = (X - conj X') conj(W4096^k)   (twice the true value: folded into the scale)
-#pragma unroll
-  for (int m = 0; m < 32; ++m) {
-    const v2f e = add_conj(v[m], pm[m]);
-    const v2f d = cmul_conj_v(sub_conj(v[m], pm[m]), w4[64 * m]);
-    v[m] = add_pi(e, d);
-  }
+// The inverse core: v[m] = Z[lane + 64 m] of irfft_presplit<32> (fft512.h) -> the unnormalised time samples,
+// (y[0][j], .., y[3][j]) = x[8 n .. 8 n + 7], n = lane + 64 j -- the radix-4 stage backwards and the four 512-point FFTs.
+// wr[(r - 1) 512 + 64 m] = W2048^(r (lane + 64 m)).
+__device__ __forceinline__ void inv_core4k(const v2f (&v)[32], const LdsTwiddles<true>& tw, const v2f* wr, float2* lds,
+                                           int lane, v2f (&y)[4][8]) {
   // radix-4 backwards: y_r[k] = conj(W2048^(r k)) sum_q (+i)^(r q) Z[k + 512 q]
 #pragma unroll
   for (int m = 0; m < 8; ++m) {
     const v2f a = v[m] + v[m + 16], b = v[m] - v[m + 16], c = v[m + 8] + v[m + 24], d = v[m + 8] - v[m + 24];
-    y0[m] = a + c;
-    y2[m] = cmul_conj_v(a - c, wr[512 + 64 * m]);
-    y1[m] = cmul_conj_v(add_pi(b, d), wr[64 * m]);          // b + i d
-    y3[m] = cmul_conj_v(add_mi(b, d), wr[1024 + 64 * m]);   // b - i d
+    y[0][m] = a + c;
+    y[2][m] = cmul_conj_v(a - c, wr[512 + 64 * m]);
+    y[1][m] = cmul_conj_v(add_pi(b, d), wr[64 * m]);          // b + i d
+    y[3][m] = cmul_conj_v(add_mi(b, d), wr[1024 + 64 * m]);   // b - i d
   }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) fft512<true>(y[r], tw, lds, lane);
 }
 
 // irfft(X) * window, frames out (the overlap-add is stft_generic.hip's gather): complex or polar input
@@ -399,7 +356,7 @@ __global__ __launch_bounds__(64 * W4K, 2) void irfft4096_frames_kernel(P4k p) {
   float2* lds = lds_all + wave * kFftLdsFloat2PerWave;
   float2* tab = lds_all + W4K * kFftLdsFloat2PerWave;
   float2* t4 = tab + kTwiddleCount;
-  const v2f* w4 = reinterpret_cast<const v2f*>(t4) + lane;
+  const v2f* w4 = reinterpret_cast<const v2f*>(t4) + lane;            // w4[64 m] = W4096^(lane + 64 m)
   const v2f* wr = reinterpret_cast<const v2f*>(t4 + 2048) + lane;
   stage_tables4k<true>(p.tw, p.tw4k, tab, t4);
   const LdsTwiddles<true> tw = {tab, lane};
@@ -407,49 +364,33 @@ __global__ __launch_bounds__(64 * W4K, 2) void irfft4096_frames_kernel(P4k p) {
   long long f_end = f_begin + p.frames_per_block;
   if (f_end > p.total_frames) f_end = p.total_frames;
   const float4* win4 = reinterpret_cast<const float4*>(p.window);
-  const float scale = 1.0f / 4096.0f;
+  const float scale = 1.0f / 4096.0f;             // the split's factor 2 is in here
   for (long long f = f_begin + wave; f < f_end; f += W4K) {
-    v2f y0[8], y1[8], y2[8], y3[8];
-    spectrum_to_subffts4k<POLAR>(p.X, p.mag, p.phase, f, lane, w4, wr, y0, y1, y2, y3);
-    fft512<true>(y0, tw, lds, lane);
-    fft512<true>(y1, tw, lds, lane);
-    fft512<true>(y2, tw, lds, lane);
-    fft512<true>(y3, tw, lds, lane);
+    v2f v[32], z[32], y[4][8];
+    float nyq_re;
+    load_spectrum_row<32, POLAR>(p.X, p.mag, p.phase, f * F4K, lane, v, nyq_re);
+    irfft_presplit<32, 64>(v, nyq_re, lane, w4, z);
+    inv_core4k(z, tw, wr, lds, lane, y);
     float4* dst = reinterpret_cast<float4*>(p.y + f * N4K);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const float4 wa = win4[2 * (lane + 64 * j)];
       const float4 wb = win4[2 * (lane + 64 * j) + 1];
-      dst[2 * (lane + 64 * j)] = make_float4(y0[j].x * (wa.x * scale), y0[j].y * (wa.y * scale), y1[j].x * (wa.z * scale),
-                                             y1[j].y * (wa.w * scale));
-      dst[2 * (lane + 64 * j) + 1] = make_float4(y2[j].x * (wb.x * scale), y2[j].y * (wb.y * scale),
-                                                 y3[j].x * (wb.z * scale), y3[j].y * (wb.w * scale));
+      dst[2 * (lane + 64 * j)] = make_float4(y[0][j].x * (wa.x * scale), y[0][j].y * (wa.y * scale),
+                                             y[1][j].x * (wa.z * scale), y[1][j].y * (wa.w * scale));
+      dst[2 * (lane + 64 * j) + 1] = make_float4(y[2][j].x * (wb.x * scale), y[2][j].y * (wb.y * scale),
+                                                 y[3][j].x * (wb.z * scale), y[3][j].y * (wb.w * scale));
     }
   }
 }
 
 // ---------------------------------------------------------------------------
 // torch.istft for n_fft = 4096, hop = 512 / 1024 / 2048 in one kernel: irfft + window + overlap-add + envelope
-// (reference stft.py:120-128, dgt.py:86-93; polar input: stft.py:157-161, dgt.py:152-154).  The scheme of
-// istft2048_ola_kernel with 512-sample register slots (two float4 per lane): a hop is HS = hop / 512 slots, the
-// R = 8 / HS frames that overlap a hop are summed in registers, a completed block is divided by the window envelope of
-// the frames that exist around it (at_istft_envelope_table) and stored once.  Output sample s is padded sample
-// s + 2048: block c is output hop c - 2048 / hop.
+// (reference stft.py:120-128, dgt.py:86-93; polar input: stft.py:157-161, dgt.py:152-154).  The inverse core above into
+// the register window of ola_window.h, two float4 per lane and 512-sample slot.
 // ---------------------------------------------------------------------------
-struct P4kOla {
-  const float2* X;       // (B*T, 2049) complex64, or null
-  const float* mag;      // polar input
-  const float* phase;
-  const float* window;   // 4096 synthesis window samples
-  const float* env;      // 2^R x hop
-  const float2* tw;
-  const float2* tw4k;
-  float* y;              // (B, hop (T - 1))
-  long long B, T, runs_per_clip, blocks_per_run;
-};
-
 template <bool POLAR, int HS>
-__global__ __launch_bounds__(64 * W4K, 2) void istft4096_ola_kernel(P4kOla p) {
+__global__ __launch_bounds__(64 * W4K, 2) void istft4096_ola_kernel(POla p) {
   constexpr int HOP = 512 * HS, R = 8 / HS, LEAD = 2048 / HOP;      // LEAD: blocks trimmed at the front
   __shared__ float2 lds_all[kLds4k + 2048];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // uniform: run bookkeeping on the scalar unit
@@ -458,120 +399,40 @@ __global__ __launch_bounds__(64 * W4K, 2) void istft4096_ola_kernel(P4kOla p) {
   float2* t4 = tab + kTwiddleCount;
   const v2f* w4 = reinterpret_cast<const v2f*>(t4) + lane;
   const v2f* wr = reinterpret_cast<const v2f*>(t4 + 2048) + lane;
-  // the synthesis window with the transform's 1/4096 folded in, shared by the block's waves (16 KB): read from global
-  // memory per frame it was as many bytes through the vector-memory path as the spectrum row itself
-  float4* wintab = reinterpret_cast<float4*>(t4 + kTab4k);
-  for (int i = threadIdx.x; i < 1024; i += 64 * W4K) {
-    const float4 w = reinterpret_cast<const float4*>(p.window)[i];
-    const float sc = 1.0f / 4096.0f;
-    wintab[i] = make_float4(w.x * sc, w.y * sc, w.z * sc, w.w * sc);
-  }
-  stage_tables4k<true>(p.tw, p.tw4k, tab, t4);
+  float4* wintab = reinterpret_cast<float4*>(t4 + kTab4k);            // 16 KB
+  stage_ola_window<N4K, 64 * W4K>(p.window, wintab);
+  stage_tables4k<true>(p.tw, p.tw_n, tab, t4);
   const LdsTwiddles<true> tw = {tab, lane};
-  const long long run = (long long)blockIdx.x * W4K + wave;
-  const long long b = run / p.runs_per_clip;
-  if (b >= p.B) return;
-  const long long r = run - b * p.runs_per_clip;
+  long long b, c0, c1;
+  if (!ola_run_blocks(p, (long long)blockIdx.x * W4K + wave, LEAD, b, c0, c1)) return;
   const long long T = p.T;
-  const long long c0 = LEAD + r * p.blocks_per_run;      // output hops q = 0 .. T - 2 are blocks c = q + LEAD
-  long long c1 = c0 + p.blocks_per_run;
-  if (c1 > LEAD + T - 1) c1 = LEAD + T - 1;
-  if (c0 >= c1) return;
   const float4* env4 = reinterpret_cast<const float4*>(p.env);
-  // reciprocal of the fully overlapped envelope: one division per wave instead of eight per hop (<= 1 ulp from acc / e)
-  float4 rcpa[HS], rcpb[HS];
-#pragma unroll
-  for (int j = 0; j < HS; ++j) {
-    const float4 ea = env4[(size_t)((1 << R) - 1) * (HOP / 4) + 2 * (lane + 64 * j)];
-    const float4 eb = env4[(size_t)((1 << R) - 1) * (HOP / 4) + 2 * (lane + 64 * j) + 1];
-    rcpa[j] = make_float4(1.0f / ea.x, 1.0f / ea.y, 1.0f / ea.z, 1.0f / ea.w);
-    rcpb[j] = make_float4(1.0f / eb.x, 1.0f / eb.y, 1.0f / eb.z, 1.0f / eb.w);
-  }
-  float4 acca[8], accb[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) acca[j] = accb[j] = make_float4(0.f, 0.f, 0.f, 0.f);
   float* yclip = p.y + b * (HOP * (T - 1));
+  OlaWindow<HS, 2> ola;
+  ola.init(env4, lane);
 
   for (long long t = c0 - (R - 1); t < c1; ++t) {
     if (t >= 0 && t < T) {
-      v2f y0[8], y1[8], y2[8], y3[8];
-      spectrum_to_subffts4k<POLAR>(p.X, p.mag, p.phase, b * T + t, lane, w4, wr, y0, y1, y2, y3);
-      fft512<true>(y0, tw, lds, lane);
-      fft512<true>(y1, tw, lds, lane);
-      fft512<true>(y2, tw, lds, lane);
-      fft512<true>(y3, tw, lds, lane);
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const float4 wa = wintab[2 * (lane + 64 * j)];
-        const float4 wb = wintab[2 * (lane + 64 * j) + 1];
-        acca[j].x += y0[j].x * wa.x;
-        acca[j].y += y0[j].y * wa.y;
-        acca[j].z += y1[j].x * wa.z;
-        acca[j].w += y1[j].y * wa.w;
-        accb[j].x += y2[j].x * wb.x;
-        accb[j].y += y2[j].y * wb.y;
-        accb[j].z += y3[j].x * wb.z;
-        accb[j].w += y3[j].y * wb.w;
-      }
+      v2f v[32], z[32], y[4][8];
+      float nyq_re;
+      load_spectrum_row<32, POLAR>(p.X, p.mag, p.phase, (b * T + t) * F4K, lane, v, nyq_re);
+      irfft_presplit<32, 64>(v, nyq_re, lane, w4, z);
+      inv_core4k(z, tw, wr, lds, lane, y);
+      ola.add_frame(y, wintab, lane);
     }
     // block t is complete: frames t - R + 1 .. t are all that cover it
-    if (t >= c0) {
-      int mask = 0;
-#pragma unroll
-      for (int q = 0; q < R; ++q) {
-        const long long ft = t - (R - 1) + q;          // bit q: oldest frame first (at_istft_envelope_table)
-        if (ft >= 0 && ft < T) mask |= 1 << q;
-      }
-      float* dst = yclip + (t - LEAD) * HOP;
-      typedef float v4f __attribute__((ext_vector_type(4)));
-      if (mask == (1 << R) - 1) {       // every fully overlapped hop takes the reciprocal form, whichever run emits it
-#pragma unroll
-        for (int j = 0; j < HS; ++j) {
-          v4f* d4 = reinterpret_cast<v4f*>(dst + 8 * (lane + 64 * j));
-          __builtin_nontemporal_store((v4f){acca[j].x * rcpa[j].x, acca[j].y * rcpa[j].y, acca[j].z * rcpa[j].z,
-                                            acca[j].w * rcpa[j].w}, d4);
-          __builtin_nontemporal_store((v4f){accb[j].x * rcpb[j].x, accb[j].y * rcpb[j].y, accb[j].z * rcpb[j].z,
-                                            accb[j].w * rcpb[j].w}, d4 + 1);
-        }
-      } else {
-#pragma unroll
-        for (int j = 0; j < HS; ++j) {
-          const float4 ea = env4[(size_t)mask * (HOP / 4) + 2 * (lane + 64 * j)];
-          const float4 eb = env4[(size_t)mask * (HOP / 4) + 2 * (lane + 64 * j) + 1];
-          float4* d4 = reinterpret_cast<float4*>(dst + 8 * (lane + 64 * j));
-          d4[0] = make_float4(acca[j].x / ea.x, acca[j].y / ea.y, acca[j].z / ea.z, acca[j].w / ea.w);
-          d4[1] = make_float4(accb[j].x / eb.x, accb[j].y / eb.y, accb[j].z / eb.z, accb[j].w / eb.w);
-        }
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 8 - HS; ++j) {
-      acca[j] = acca[j + HS];
-      accb[j] = accb[j + HS];
-    }
-#pragma unroll
-    for (int j = 8 - HS; j < 8; ++j) acca[j] = accb[j] = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (t >= c0) ola.emit(yclip + (t - LEAD) * HOP, env4, ola.frame_mask(t, T), lane);
+    ola.slide();
   }
 }
 
 int launch_istft4096_ola(const float2* X, const float* mag, const float* phase, long long B, long long T, int hop,
                          const float* window, const float* env, const float2* tw, const float2* tw4k, float* y,
                          hipStream_t stream) {
-  if (B == 0 || T <= 1) return 0;
-  P4kOla p = {X, mag, phase, window, env, tw, tw4k, y, B, T, 0, 0};
-  const long long blocks = T - 1;                        // output hops per clip
-  p.blocks_per_run = plan_ola_runs(B, blocks, 2048, 8);
-  p.runs_per_clip = (blocks + p.blocks_per_run - 1) / p.blocks_per_run;
-  const long long waves = B * p.runs_per_clip;
-  const unsigned grid = (unsigned)((waves + W4K - 1) / W4K);
-#define OLA4K(POLAR_, HS_) hipLaunchKernelGGL((istft4096_ola_kernel<POLAR_, HS_>), dim3(grid), dim3(64 * W4K), 0, stream, p)
-  const bool polar = (X == nullptr);
-  if (hop == 512) { if (polar) OLA4K(true, 1); else OLA4K(false, 1); }
-  else if (hop == 1024) { if (polar) OLA4K(true, 2); else OLA4K(false, 2); }
-  else if (hop == 2048) { if (polar) OLA4K(true, 4); else OLA4K(false, 4); }
-  else return -2;
-#undef OLA4K
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  static void (*const kernels[2][3])(POla) = {
+      {istft4096_ola_kernel<false, 1>, istft4096_ola_kernel<false, 2>, istft4096_ola_kernel<false, 4>},
+      {istft4096_ola_kernel<true, 1>, istft4096_ola_kernel<true, 2>, istft4096_ola_kernel<true, 4>}};
+  return launch_istft_ola(kernels, N4K, W4K, X, mag, phase, B, T, hop, window, env, tw, tw4k, y, stream);
 }
 
 int launch_stft4096_fwd(const float* x, long long B, long long L, long long clip_stride, long long T, int hop, int center,

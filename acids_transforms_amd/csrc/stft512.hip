@@ -16,6 +16,11 @@
 // lanes frame B (y[lane + 64 j] = a or b [(lane >> 1) + 32 j]).  Then the real split of each,
 //   X[k] = (A[k] + conj A[256-k])/2 - (i/2) W512^k (A[k] - conj A[256-k]),  k = 0 .. 256,
 // with the mirror partner in lane 64 - lane, register 3 - m.  The inverse runs the same steps backwards.
+//
+// Each direction's arithmetic is written once: fwd_core5 (one FFT, the un-mixing of the pair, mirror and merge of both
+// frames; plain or with rotated output columns) serves the frame, run and mel kernels, inv_core5 (the pair's mix, one
+// FFT) behind load_split5 -- fft512.h's load_spectrum_row / irfft_presplit -- serves the frames and the fused
+// overlap-add kernel.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -49,6 +54,38 @@ struct P5 {
   int hop, center;
 };
 
+// The forward core: the windowed samples of a frame pair (even lanes frame A, odd lanes frame B) -> both spectra,
+// xa[m] = X_A[col + 64 m], xb[m] = X_B[col + 64 m], m = 0 .. 3, and na = X_A[256], nb = X_B[256] (real; meaningful on the
+// lane whose column is 0).  ROT: the output columns are rotated over the lanes, this lane holds column
+// col = (lane - rot) & 63 and w5 is the LDS table W512^k (the run kernel: twiddle and mirror lane follow the column);
+// otherwise rot = 0, col = lane and w5 is this lane's register array W512^(lane + 64 m).
+template <bool ROT>
+__device__ __forceinline__ void fwd_core5(v2f (&y)[8], const Twiddles& tw, float2* lds, const v2f* w5, int lane, int rot,
+                                          int col, v2f (&xa)[4], v2f (&xb)[4], float& na, float& nb) {
+  const v2f hh = {0.5f, 0.5f};
+  fft512<false>(y, tw, lds, lane, col);
+  // unpack the two 256-point spectra (halved: the real split wants A/2): HA = (Y[k] + Y[k+256]) / 4 ...
+  v2f ha[4], hb[4], wk[4];
+#pragma unroll
+  for (int m = 0; m < 4; ++m) {
+    wk[m] = ROT ? lds_read_single(w5 + col + 64 * m) : w5[m];
+    const v2f s = (y[m] + y[m + 4]) * hh;              // A[k]
+    const v2f d = (y[m] - y[m + 4]) * hh;              // W512^k B[k]
+    ha[m] = s * hh;                                     // A / 2
+    hb[m] = cmul_conj_v(d, wk[m]) * hh;                 // B / 2
+  }
+  v2f pa[4], pb[4];
+  mirror_regs_rot<4>(ha, pa, lane, rot, col);
+  mirror_regs_rot<4>(hb, pb, lane, rot, col);
+#pragma unroll
+  for (int m = 0; m < 4; ++m) {
+    xa[m] = add_mi(add_conj(ha[m], pa[m]), cmul_v(sub_conj(ha[m], pa[m]), wk[m]));
+    xb[m] = add_mi(add_conj(hb[m], pb[m]), cmul_v(sub_conj(hb[m], pb[m]), wk[m]));
+  }
+  na = 2.0f * (ha[0].x - ha[0].y);                      // X[256] = Re A[0] - Im A[0]
+  nb = 2.0f * (hb[0].x - hb[0].y);
+}
+
 template <bool WRITE_PHASE>
 __global__ __launch_bounds__(64 * W5) void stft512_fwd_kernel(P5 p) {
   __shared__ float2 lds_all[W5 * kFftLdsFloat2PerWave];
@@ -69,7 +106,6 @@ __global__ __launch_bounds__(64 * W5) void stft512_fwd_kernel(P5 p) {
   const long long pr_begin = (long long)blockIdx.x * p.pairs_per_block;
   long long pr_end = pr_begin + p.pairs_per_block;
   if (pr_end > n_pairs) pr_end = n_pairs;
-  const v2f hh = {0.5f, 0.5f};
 
   // pair pr is frames 2 i, 2 i + 1 of clip b, pr = b pairs_per_clip + i
   auto load_pair = [&](long long q, float2 (&dst)[8]) {
@@ -84,19 +120,9 @@ __global__ __launch_bounds__(64 * W5) void stft512_fwd_kernel(P5 p) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) y[j] = (v2f){nxt[j].x * win[j].x, nxt[j].y * win[j].y};
     if (pr + W5 < pr_end) load_pair(pr + W5, nxt);
-    fft512<false>(y, tw, lds, lane);
-    // unpack the two 256-point spectra (halved: the real split wants A/2): HA = (Y[k] + Y[k+256]) / 4 ...
-    v2f ha[4], hb[4];
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-      const v2f s = (y[m] + y[m + 4]) * hh;              // A[k]
-      const v2f d = (y[m] - y[m + 4]) * hh;              // W512^k B[k]
-      ha[m] = s * hh;                                     // A / 2
-      hb[m] = cmul_conj_v(d, w5[m]) * hh;                 // B / 2
-    }
-    v2f pa[4], pb[4];
-    mirror_regs<4>(ha, pa, lane);
-    mirror_regs<4>(hb, pb, lane);
+    v2f xa[4], xb[4];
+    float na, nb;
+    fwd_core5<false>(y, tw, lds, w5, lane, 0, lane, xa, xb, na, nb);
     const long long cb = pr / p.pairs_per_clip;
     const long long ta = 2 * (pr - cb * p.pairs_per_clip);
     const long long fa = cb * p.T + ta, fb = fa + 1;
@@ -105,17 +131,14 @@ __global__ __launch_bounds__(64 * W5) void stft512_fwd_kernel(P5 p) {
     const bool has_b = ta + 1 < p.T;
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
-      const v2f xa = add_mi(add_conj(ha[m], pa[m]), cmul_v(sub_conj(ha[m], pa[m]), w5[m]));
-      const v2f xb = add_mi(add_conj(hb[m], pb[m]), cmul_v(sub_conj(hb[m], pb[m]), w5[m]));
-      rowa[lane + 64 * m] = to_f2(xa);
-      if (has_b) rowb[lane + 64 * m] = to_f2(xb);
+      rowa[lane + 64 * m] = to_f2(xa[m]);
+      if (has_b) rowb[lane + 64 * m] = to_f2(xb[m]);
       if (WRITE_PHASE) {
-        p.phase_out[fa * F5 + lane + 64 * m] = fast_atan2f(xa.y, xa.x);
-        if (has_b) p.phase_out[fb * F5 + lane + 64 * m] = fast_atan2f(xb.y, xb.x);
+        p.phase_out[fa * F5 + lane + 64 * m] = fast_atan2f(xa[m].y, xa[m].x);
+        if (has_b) p.phase_out[fb * F5 + lane + 64 * m] = fast_atan2f(xb[m].y, xb[m].x);
       }
     }
     if (lane == 0) {
-      const float na = 2.0f * (ha[0].x - ha[0].y), nb = 2.0f * (hb[0].x - hb[0].y);   // X[256] = Re A[0] - Im A[0]
       rowa[256] = make_float2(na, 0.0f);
       if (has_b) rowb[256] = make_float2(nb, 0.0f);
       if (WRITE_PHASE) {
@@ -181,7 +204,6 @@ __global__ __launch_bounds__(64 * W5R, 4) void stft512_run_fwd_kernel(P5Run p) {
   if (i1 > n_pairs) i1 = n_pairs;
   if (i0 >= i1) return;
   const float* clip = p.x + b * p.clip_stride;
-  const v2f hh = {0.5f, 0.5f};
 
   // this lane's frame of pair i: f = 2 i + par, starting at original sample 128 f - 256; slot j = samples 64 j .. + 63.
   // The missing frame f = T of a half pair (odd T) holds what the steady state carries into it from the pair before --
@@ -239,29 +261,10 @@ __global__ __launch_bounds__(64 * W5R, 4) void stft512_run_fwd_kernel(P5Run p) {
     for (int j = 0; j < 4; ++j) raw[j] = raw[j + 4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) raw[4 + j] = fresh[j];
-    const int col = (lane - rot) & 63;
-    fft512<false>(y, tw, lds, lane, col);
-    const v2f* w5 = reinterpret_cast<const v2f*>(w5tab) + col;             // w5[64 m] = W512^(col + 64 m)
-    v2f ha[4], hb[4], wk[4];
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-      wk[m] = lds_read_single(w5 + 64 * m);
-      const v2f sm = (y[m] + y[m + 4]) * hh;              // A[k]
-      const v2f d = (y[m] - y[m + 4]) * hh;               // W512^k B[k]
-      ha[m] = sm * hh;                                     // A / 2
-      hb[m] = cmul_conj_v(d, wk[m]) * hh;                  // B / 2
-    }
-    v2f pa[4], pb[4];
-    mirror_regs_rot<4>(ha, pa, lane, rot, col);
-    mirror_regs_rot<4>(hb, pb, lane, rot, col);
     v2f xa[4], xb[4];
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-      xa[m] = add_mi(add_conj(ha[m], pa[m]), cmul_v(sub_conj(ha[m], pa[m]), wk[m]));
-      xb[m] = add_mi(add_conj(hb[m], pb[m]), cmul_v(sub_conj(hb[m], pb[m]), wk[m]));
-    }
-    const v2f na = {2.0f * (ha[0].x - ha[0].y), 0.0f};     // X_A[256], on the lane whose column is 0 (= lane rot)
-    const float nbx = 2.0f * (hb[0].x - hb[0].y);
+    float nax, nbx;
+    fwd_core5<true>(y, tw, lds, reinterpret_cast<const v2f*>(w5tab), lane, rot, (lane - rot) & 63, xa, xb, nax, nbx);
+    const v2f na = {nax, 0.0f};                            // X_A[256], on the lane whose column is 0 (= lane rot)
     wave_priority<1>();
     emit_frame(xa, na);
     if (has_b) {
@@ -319,8 +322,8 @@ __global__ __launch_bounds__(64 * W5R, 4) void stft512_run_fwd_kernel(P5Run p) {
 
 // one frame's one-sided spectrum -> A[k] * 2 (k = lane + 64 m, m = 0..3): E + i O of the inverse split
 template <bool POLAR>
-__device__ __forceinline__ void load_split5(const P5& p, long long f, bool exists, int lane, const v2f (&w5)[4],
-                                            v2f (&a)[4]) {
+__device__ __forceinline__ void load_split5(const float2* X, const float* mag, const float* phase, long long f, bool exists,
+                                            int lane, const v2f (&w5)[4], v2f (&a)[4]) {
   if (!exists) {              // wave-uniform: a missing frame contributes a zero spectrum
 #pragma unroll
     for (int m = 0; m < 4; ++m) a[m] = (v2f){0.f, 0.f};
@@ -328,35 +331,22 @@ __device__ __forceinline__ void load_split5(const P5& p, long long f, bool exist
   }
   v2f v[4];
   float nyq_re;
-  if (POLAR) {
-    const float* mrow = p.mag + f * F5;
-    const float* prow = p.phase + f * F5;
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-      float sn, cs;
-      const float g = mrow[lane + 64 * m];
-      fast_sincosf(prow[lane + 64 * m], sn, cs);
-      v[m] = (v2f){g * cs, g * sn};
-    }
-    float sn, cs;
-    fast_sincosf(prow[256], sn, cs);
-    nyq_re = mrow[256] * cs;
-  } else {
-    const float2* row = p.X + f * F5;
-#pragma unroll
-    for (int m = 0; m < 4; ++m) v[m] = to_v(row[lane + 64 * m]);
-    nyq_re = row[256].x;
-  }
-  if (lane == 0) v[0].y = 0.0f;                 // c2r ignores the imaginary parts of DC and Nyquist
-  v2f pm[4];
-  mirror_regs<4>(v, pm, lane);
-  if (lane == 0) pm[0] = (v2f){nyq_re, 0.0f};   // partner of k = 0 is X[256]
+  load_spectrum_row<4, POLAR>(X, mag, phase, f * F5, lane, v, nyq_re);
+  irfft_presplit<4, 1>(v, nyq_re, lane, w5, a);
+}
+
+// The inverse core: 2 A[k], 2 B[k] of a frame pair -> y[lane + 64 j], the pair's unnormalised time samples: even lanes
+// hold frame A's complex sample (lane >> 1) + 32 j, odd lanes frame B's
+__device__ __forceinline__ void inv_core5(const v2f (&a)[4], const v2f (&b)[4], const v2f (&w5)[4], const Twiddles& tw,
+                                          float2* lds, int lane, v2f (&y)[8]) {
+  // Y[k] = A + W512^k B, Y[k+256] = A - W512^k B
 #pragma unroll
   for (int m = 0; m < 4; ++m) {
-    const v2f e = add_conj(v[m], pm[m]);
-    const v2f d = cmul_conj_v(sub_conj(v[m], pm[m]), w5[m]);
-    a[m] = add_pi(e, d);                         // 2 A[k]
+    const v2f t = cmul_v(b[m], w5[m]);
+    y[m] = a[m] + t;
+    y[m + 4] = a[m] - t;
   }
+  fft512<true>(y, tw, lds, lane);
 }
 
 // irfft(X) * window for frame pairs, frames out (overlap-add: stft_generic.hip's gather)
@@ -386,19 +376,10 @@ __global__ __launch_bounds__(64 * W5) void irfft512_frames_kernel(P5 p) {
     const long long cb = pr / p.pairs_per_clip;
     const long long ta = 2 * (pr - cb * p.pairs_per_clip);
     const long long fa = cb * p.T + ta;
-    v2f a[4], b[4];
-    load_split5<POLAR>(p, fa, true, lane, w5, a);
-    load_split5<POLAR>(p, fa + 1, ta + 1 < p.T, lane, w5, b);
-    // Y[k] = A + W512^k B, Y[k+256] = A - W512^k B
-    v2f y[8];
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-      const v2f t = cmul_v(b[m], w5[m]);
-      y[m] = a[m] + t;
-      y[m + 4] = a[m] - t;
-    }
-    fft512<true>(y, tw, lds, lane);
-    // y[lane + 64 j]: even lanes hold frame A's complex sample (lane >> 1) + 32 j, odd lanes frame B's
+    v2f a[4], b[4], y[8];
+    load_split5<POLAR>(p.X, p.mag, p.phase, fa, true, lane, w5, a);
+    load_split5<POLAR>(p.X, p.mag, p.phase, fa + 1, ta + 1 < p.T, lane, w5, b);
+    inv_core5(a, b, w5, tw, lds, lane, y);
     const long long f = fa + (lane & 1);
     if (ta + (lane & 1) < p.T) {
       float2* dst = reinterpret_cast<float2*>(p.y + f * N5);
@@ -471,9 +452,6 @@ __global__ __launch_bounds__(64 * W5) void istft512_ola_kernel(P5Ola p) {
   const long long i_end = (c_hi + 1) / 2;                                  // first pair with no valid block
   if (i1 > i_end) i1 = i_end;
   if (i0 >= i1) return;
-  // P5 view for the shared spectrum loader
-  P5 q5 = {};
-  q5.X = const_cast<float2*>(p.X); q5.mag = p.mag; q5.phase = p.phase;
   const float2* env2 = reinterpret_cast<const float2*>(p.env);
   float* yclip = p.y + b * (HOP * (T - 1));
   v2f acc[8], carry[HS];
@@ -499,17 +477,10 @@ __global__ __launch_bounds__(64 * W5) void istft512_ola_kernel(P5Ola p) {
     for (int j = 0; j < 8; ++j) acc[j] = (j + 2 * HS < 8) ? acc[j + 2 * HS] : (v2f){0.f, 0.f};
     const long long ta = 2 * i, tb = 2 * i + 1;
     if (tb >= 0 && ta < T) {                     // at least one frame of the pair exists (wave-uniform)
-      v2f a[4], bb[4];                           // frames outside [0, T) of THIS clip read as zero spectra
-      load_split5<POLAR>(q5, b * T + ta, ta >= 0 && ta < T, lane, w5, a);
-      load_split5<POLAR>(q5, b * T + tb, tb >= 0 && tb < T, lane, w5, bb);
-      v2f y[8];
-#pragma unroll
-      for (int m = 0; m < 4; ++m) {
-        const v2f t = cmul_v(bb[m], w5[m]);
-        y[m] = a[m] + t;
-        y[m + 4] = a[m] - t;
-      }
-      fft512<true>(y, tw, lds, lane);
+      v2f a[4], bb[4], y[8];                     // frames outside [0, T) of THIS clip read as zero spectra
+      load_split5<POLAR>(p.X, p.mag, p.phase, b * T + ta, ta >= 0 && ta < T, lane, w5, a);
+      load_split5<POLAR>(p.X, p.mag, p.phase, b * T + tb, tb >= 0 && tb < T, lane, w5, bb);
+      inv_core5(a, bb, w5, tw, lds, lane, y);
 #pragma unroll
       for (int j = 0; j < 8; ++j) acc[j] += (v2f){y[j].x * win[j].x, y[j].y * win[j].y};
     }
@@ -633,7 +604,6 @@ __global__ __launch_bounds__(64 * W5) void stft512_mel_kernel(P5Mel p) {
   long long pr_end = pr_begin + p.pairs_per_wave;
   if (pr_end > n_pairs) pr_end = n_pairs;
   if (pr_begin >= pr_end) return;
-  const v2f hh = {0.5f, 0.5f};
   float off = 0.f, sc = 1.f;
   if (p.offset) {
     off = *p.offset;
@@ -737,28 +707,16 @@ __global__ __launch_bounds__(64 * W5) void stft512_mel_kernel(P5Mel p) {
 #pragma unroll
     for (int j = 0; j < 8; ++j) y[j] = (v2f){nxt[j].x * win[j].x, nxt[j].y * win[j].y};
     if (pr + 1 < pr_end) load_shared_frame<2>(lp, pb, 2 * pi + (lane & 1), lane, nxt);
-    fft512<false>(y, tw, lds, lane);
-    v2f ha[4], hb[4];
+    v2f xa[4], xb[4];
+    float na, nb;
+    fwd_core5<false>(y, tw, lds, w5, lane, 0, lane, xa, xb, na, nb);
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
-      const v2f s = (y[m] + y[m + 4]) * hh;
-      const v2f d = (y[m] - y[m + 4]) * hh;
-      ha[m] = s * hh;
-      hb[m] = cmul_conj_v(d, w5[m]) * hh;
-    }
-    v2f pa[4], pb[4];
-    mirror_regs<4>(ha, pa, lane);
-    mirror_regs<4>(hb, pb, lane);
-#pragma unroll
-    for (int m = 0; m < 4; ++m) {
-      const v2f xa = add_mi(add_conj(ha[m], pa[m]), cmul_v(sub_conj(ha[m], pa[m]), w5[m]));
-      const v2f xb = add_mi(add_conj(hb[m], pb[m]), cmul_v(sub_conj(hb[m], pb[m]), w5[m]));
-      const float sa = fmaf(xa.x, xa.x, xa.y * xa.y), sb = fmaf(xb.x, xb.x, xb.y * xb.y);
+      const float sa = fmaf(xa[m].x, xa[m].x, xa[m].y * xa[m].y), sb = fmaf(xb[m].x, xb[m].x, xb[m].y * xb[m].y);
       rowa[lane + 64 * m] = p.power2 ? sa : __builtin_amdgcn_sqrtf(sa);
       rowb[lane + 64 * m] = p.power2 ? sb : __builtin_amdgcn_sqrtf(sb);
     }
     if (lane == 0) {
-      const float na = 2.0f * (ha[0].x - ha[0].y), nb = 2.0f * (hb[0].x - hb[0].y);
       rowa[256] = p.power2 ? na * na : fabsf(na);
       rowb[256] = p.power2 ? nb * nb : fabsf(nb);
     }

@@ -331,9 +331,13 @@ def fused(x, w, band, n_fft, hop, T, cm, power, contrast, off, sc):
     return fn
 
 
-# n_fft, n_mels, channel-major, sample rate (a one-pass bank at 2048 that the fused kernel takes: 64 mels at 16 kHz)
+# n_fft, n_mels, channel-major, sample rate (a one-pass bank at 2048 that the fused kernel takes: 64 mels at 16 kHz).
+# At 2048 the analysis window joins the bank in LDS when 8 KB are left (launch_stft2048_mel): the bands of 60 mels at
+# 4 kHz and of 128 at 44.1 kHz leave them, those of 64 at 16 kHz and of 100 at 44.1 kHz do not -- each of the register
+# windows (one pass, two passes, none) with the window in LDS and without.
 FUSED = [(512, 40, True, 44100), (512, 128, True, 44100), (512, 128, False, 44100), (2048, 64, True, 16000),
-         (2048, 128, True, 44100), (2048, 100, False, 44100)]
+         (2048, 128, True, 44100), (2048, 100, False, 44100), (2048, 60, True, 4000), (2048, 100, True, 44100),
+         (2048, 128, False, 44100)]
 
 
 @pytest.mark.parametrize("n_fft,n_mels,cm,sr", FUSED, ids=["%d_%d_%s" % (a, b, "cm" if c else "rows") for a, b, c, _ in
