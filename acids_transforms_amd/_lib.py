@@ -53,6 +53,8 @@ _SIGNATURES = {
     "at_resample_backward_plan": [c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)],
     "at_resample_sinc_backward": [c_f, c_i64, c_i64, c_int, c_int, c_int, c_int, c_f, c_i64, c_f, c_f],
     "at_resample_sinc_stream": [c_f, c_i64, c_i64, c_f, c_f, c_int, c_int, c_int, c_f, c_f, c_f],
+    "at_sinc_interp_plan": [c_int, c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)],
+    "at_sinc_interp": [c_f, c_i64, c_i64, c_int, c_int, c_f, c_int, c_i64, c_f, c_f],
     "at_phase_vocoder": [c_f, c_i64, c_i64, c_i64, c_f, c_f, c_i64, c_f, c_f, c_f],
     "at_phase_vocoder_backward": [c_f, c_f, c_f, c_f, c_f, c_i64, c_i64, c_i64, c_i64, c_f, c_f],
     "at_sinebank_workspace_bytes": [c_i64, c_int, c_i64, c_int],

@@ -30,6 +30,8 @@ without state backward; the carried filter state is a constant of the graph like
 ResampleFunction and ResampleStreamFunction are utils.Resample's and utils.RealtimeResample's (resample.hip): sample-rate
 conversion is linear, so both backward passes are one kernel, the transposed polyphase filter (ops.resample_sinc_backward),
 which the streaming form calls with the state's length as the lead of its window; neither saves a tensor.
+ResampleDirectFunction is the bankless route (sinc_interp.hip) of Resample(direct=True) and PitchShift: forward and backward
+are one kernel with the two rates exchanged.
 
 PhaseVocoderFunction is transforms.TimeStretch's (phase_vocoder.hip): the forward also hands back the phasor after its last
 step, and the backward (ops.phase_vocoder_backward) walks the steps downwards from it; the graph keeps the spectrum and
@@ -49,7 +51,7 @@ __all__ = ["wants_grad", "StftFunction", "IstftFunction", "IstftPolarFunction", 
            "RtStftFunction", "RtIstftFunction", "RtIstftPolarFunction", "OaddFramesFunction", "OaddInvertFunction",
            "SpectralDistanceFunction", "specdist_chunk_clips", "MelSpectralDistanceFunction", "meldist_sums",
            "meldist_loss", "PqmfFunction", "PqmfInvertFunction", "PqmfStreamFunction", "PqmfStreamInvertFunction",
-           "ResampleFunction", "ResampleStreamFunction", "PhaseVocoderFunction"]
+           "ResampleFunction", "ResampleStreamFunction", "ResampleDirectFunction", "PhaseVocoderFunction"]
 
 
 def wants_grad(x: torch.Tensor) -> bool:
@@ -553,6 +555,24 @@ class ResampleStreamFunction(torch.autograd.Function):
         Ha = ops.resample_stream_sizes(ctx.orig, ctx.width)[1]
         gx = ops.resample_sinc_backward(gy, ctx.C, ctx.orig, ctx.new, 2 * ctx.width + ctx.orig, Ha, ctx.bank)
         return gx.to(ctx.dtype), None, None, None, None, None
+
+
+class ResampleDirectFunction(torch.autograd.Function):
+    """Resample(direct=True).forward and PitchShift's last stage: x (rows, L) float32 -> ops.sinc_interp(x, orig, new)
+    (rows, ceil(new L / orig)) through the converter's half-table (sinc_interp.hip), no bank.  Saves no tensor: L, the
+    three integers and the table (a constant of the graph) hang on the node; the backward is the same kernel with the
+    rates exchanged."""
+
+    @staticmethod
+    def forward(ctx, x, table, Qi, orig, new):
+        ctx.table, ctx.Qi, ctx.orig, ctx.new, ctx.L, ctx.dtype = table, Qi, orig, new, x.shape[-1], x.dtype
+        return ops.sinc_interp(x, orig, new, table, Qi, -(-new * x.shape[-1] // orig))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        gx = ops.sinc_interp(gy, ctx.new, ctx.orig, ctx.table, ctx.Qi, ctx.L)
+        return gx.to(ctx.dtype), None, None, None, None
 
 
 # ---- TimeStretch: the phase vocoder, a scan up the steps forward and down them backward -------------------------------------

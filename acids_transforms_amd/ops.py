@@ -4,6 +4,8 @@ Each function takes ROCm-device tensors, allocates the output with torch
 (device memory + stream plumbing only) and launches the HIP kernels on the
 current torch stream.  No arithmetic happens in Python.
 """
+import math
+
 import torch
 
 from ._lib import AT_EUNSUPPORTED, AcidsHipError, check, device_scoped, lib, ptr, require_device, stream_ptr
@@ -1338,6 +1340,116 @@ def resample_sinc_stream(x, state, orig, new, width, filters, want_state=True):
     check(lib().at_resample_sinc_stream(ptr(x), rows, C, ptr(state), ptr(new_state), orig, new, width, ptr(filters),
                                         ptr(y), stream_ptr()), "at_resample_sinc_stream")
     return y, new_state
+
+
+# ----------------------------------------------------------------------------------------------
+# sample-rate conversion without the bank (sinc_interp.hip)
+# ----------------------------------------------------------------------------------------------
+SINC_TABLE_MAX = 2 ** 24           # entries of a half-table: 64 MB, rates up to about 2.7 million after the gcd
+
+
+def _reduced_rates(orig_freq, new_freq):
+    orig_freq, new_freq = int(orig_freq), int(new_freq)
+    if orig_freq < 1 or new_freq < 1:
+        raise ValueError("sample rates must be >= 1, got %d and %d" % (orig_freq, new_freq))
+    g = math.gcd(orig_freq, new_freq)
+    return orig_freq // g, new_freq // g
+
+
+def sinc_table(orig, new, lowpass_filter_width=6, rolloff=0.99):
+    """The half-table of the converter orig -> new (reduced by their gcd here): (table float32 (Qi + 1,) on the CPU, Qi).
+    An entry h[j][k] of utils.audio_io.sinc_filter_bank depends only on q = n new - o orig:
+        table[q] = (min(orig, new) rolloff / orig) sinc(pi q rho) cos^2(pi q rho / (2 lpw)),   rho = rolloff / max(orig, new)
+    in float64 with sinc(0) = 1, rounded to float32; Qi is the largest integer < lpw / rho, beyond which the bank is
+    exactly 0.  ValueError: rates < 1, lpw < 1, a rolloff outside (0, 1], more than SINC_TABLE_MAX entries."""
+    orig, new = _reduced_rates(orig, new)
+    lpw, rolloff = int(lowpass_filter_width), float(rolloff)
+    if lpw < 1 or not 0.0 < rolloff <= 1.0:
+        raise ValueError("lowpass_filter_width must be >= 1 and rolloff in (0, 1], got %r and %r"
+                         % (lowpass_filter_width, rolloff))
+    base_freq = min(orig, new) * rolloff
+    edge = lpw * orig * new / base_freq                   # lpw / rho
+    Qi = math.ceil(edge) - 1
+    if Qi + 1 > SINC_TABLE_MAX:
+        raise ValueError("the converter %d -> %d needs a table of %d entries, more than %d" % (orig, new, Qi + 1,
+                                                                                              SINC_TABLE_MAX))
+    t = torch.arange(0, Qi + 1, dtype=torch.float64) / orig / new
+    t = (t * base_freq).clamp_(-lpw, lpw)
+    window = torch.cos(t * math.pi / lpw / 2) ** 2
+    t = t * math.pi
+    kernels = torch.where(t == 0, torch.tensor(1.0, dtype=torch.float64), t.sin() / t)
+    return (kernels * window * (base_freq / orig)).to(torch.float32).contiguous(), Qi
+
+
+_sinc_tables = {}
+
+
+def _sinc_table_on(device, orig, new, lowpass_filter_width=6, rolloff=0.99):
+    """sinc_table on `device`, for reduced rates; the last few tables stay (one upload per converter and device)."""
+    key = (str(device), int(orig), int(new), int(lowpass_filter_width), float(rolloff))
+    hit = _sinc_tables.get(key)
+    if hit is None:
+        table, Qi = sinc_table(orig, new, lowpass_filter_width, rolloff)
+        if len(_sinc_tables) >= 16:
+            _sinc_tables.pop(next(iter(_sinc_tables)))
+        hit = _sinc_tables[key] = (table.to(device), Qi)
+    return hit
+
+
+def sinc_interp_plan(a, b, Qi):
+    """(tile_outputs, table_in_lds) of at_sinc_interp at a shape: the consecutive outputs one workgroup handles, and
+    whether the table sits in LDS beside the input window or is read from global memory.  Reads no device state."""
+    import ctypes
+    tile, in_lds = ctypes.c_int(0), ctypes.c_int(0)
+    check(lib().at_sinc_interp_plan(int(a), int(b), int(Qi), ctypes.byref(tile), ctypes.byref(in_lds)),
+          "at_sinc_interp_plan")
+    return tile.value, bool(in_lds.value)
+
+
+def sinc_interp(x, a, b, table, Qi, out_len):
+    """x (rows, in_len) -> (rows, out_len), out[r][o] = sum over n ascending with |n b - o a| <= Qi of
+    table[|n b - o a|] x[r][n] (include/acids_hip.h, at_sinc_interp): the converter with (a, b) = (orig, new) and its
+    adjoint with (a, b) = (new, orig)."""
+    require_device(x, table)
+    x, table = _f32c(x), _f32c(table)
+    assert x.ndim == 2 and table.ndim == 1 and table.numel() == int(Qi) + 1
+    rows, in_len = x.shape
+    out = torch.empty((rows, int(out_len)), dtype=torch.float32, device=x.device)
+    check(lib().at_sinc_interp(ptr(x), rows, in_len, int(a), int(b), ptr(table), int(Qi), int(out_len), ptr(out),
+                               stream_ptr()), "at_sinc_interp")
+    return out
+
+
+def resample_direct(x, orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99):
+    """torchaudio.functional.resample with its default interpolation, for any pair of rates: x (..., L) -> (...,
+    ceil(new L / orig)) through the half-table of the converter, no bank (sinc_interp.hip).  For finite input the bits
+    of utils.Resample.  Equal rates return x itself.  No graph: autograd.ResampleDirectFunction is the differentiable
+    form."""
+    orig, new = _reduced_rates(orig_freq, new_freq)
+    if orig == new:
+        return x
+    require_device(x)
+    _no_fp64(x)
+    table, Qi = _sinc_table_on(x.device, orig, new, lowpass_filter_width, rolloff)
+    lead, L = tuple(x.shape[:-1]), x.shape[-1]
+    out_len = -(-new * L // orig)
+    y = sinc_interp(x.reshape(math.prod(lead), L), orig, new, table, Qi, out_len)
+    return y.reshape(lead + (out_len,))
+
+
+def resample_direct_backward(g, L, orig_freq, new_freq, lowpass_filter_width=6, rolloff=0.99):
+    """The adjoint of resample_direct with respect to its input: g (..., ceil(new L / orig)) -> gx (..., L), the same
+    kernel with the two rates exchanged.  For finite g the bits of resample_sinc_backward."""
+    orig, new = _reduced_rates(orig_freq, new_freq)
+    if orig == new:
+        return g
+    require_device(g)
+    _no_fp64(g, "gradient")
+    lead, out_len = tuple(g.shape[:-1]), g.shape[-1]
+    assert out_len == -(-new * int(L) // orig), "g does not match the forward's output"
+    table, Qi = _sinc_table_on(g.device, orig, new, lowpass_filter_width, rolloff)
+    gx = sinc_interp(g.reshape(math.prod(lead), out_len), new, orig, table, Qi, int(L))
+    return gx.reshape(lead + (int(L),))
 
 
 # ----------------------------------------------------------------------------------------------

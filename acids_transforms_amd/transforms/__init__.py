@@ -11,10 +11,10 @@ from .raw import MuLaw
 from .misc import OneHot
 from .channels import Mono, Stereo, MidSide, Window, Squeeze, Unsqueeze, Transpose
 from .pqmf import PQMF, RealtimePQMF
-from .stretch import TimeStretch
+from .stretch import TimeStretch, PitchShift
 
 __all__ = ["AudioTransform", "ComposeAudioTransform", "NotInvertibleError", "InversionEnumType",
            "apply_transform_to_list", "apply_invert_transform_to_list", "STFT", "RealtimeSTFT", "DGT", "RealtimeDGT", "DGT_INVERSION_MODES",
            "Normalize", "Magnitude", "Real", "Imaginary", "Phase", "IF", "SpectralRepresentation", "Cartesian", "Polar",
            "PolarIF", "MFCC", "OverlapAdd", "MuLaw", "OneHot", "Mono", "Stereo", "MidSide", "Window", "Squeeze", "Unsqueeze", "Transpose",
-           "PQMF", "RealtimePQMF", "TimeStretch"]
+           "PQMF", "RealtimePQMF", "TimeStretch", "PitchShift"]

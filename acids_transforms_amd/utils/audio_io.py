@@ -20,7 +20,7 @@ import torch
 
 from .. import ops
 from .._lib import device_scoped, require_device
-from ..autograd import ResampleFunction, ResampleStreamFunction, wants_grad
+from ..autograd import ResampleDirectFunction, ResampleFunction, ResampleStreamFunction, wants_grad
 
 __all__ = ["Resample", "RealtimeResample", "resample", "import_data", "load_wav"]
 
@@ -45,22 +45,43 @@ class Resample(torch.nn.Module):
 
     Differentiable: when grad mode is on and the waveform requires grad the call goes through
     autograd.ResampleFunction -- the same forward kernel, to the bit, and the transposed polyphase filter backward
-    (at_resample_sinc_backward; first order only, the graph keeps no tensor).  `streaming()` is the causal form."""
+    (at_resample_sinc_backward; first order only, the graph keeps no tensor).  `streaming()` is the causal form.
+
+    `direct=True` builds no bank: the module keeps the converter's half-table (`table`, ops.sinc_table: a few KB where
+    the bank has new x (2 width + orig) entries, so any pair of rates is affordable) and both passes are sinc_interp.hip,
+    which walks only the taps of a bank row that are not zero -- for finite input the same bits, forward and backward.
+    It has no streaming form."""
 
     def __init__(self, orig_freq: int = 16000, new_freq: int = 16000, lowpass_filter_width: int = 6,
-                 rolloff: float = 0.99):
+                 rolloff: float = 0.99, direct: bool = False):
         super().__init__()
         self.orig_freq, self.new_freq = int(orig_freq), int(new_freq)
         self.lowpass_filter_width, self.rolloff = lowpass_filter_width, rolloff
+        self.direct = bool(direct)
         g = math.gcd(self.orig_freq, self.new_freq)
         self.orig, self.new = self.orig_freq // g, self.new_freq // g
-        if self.orig != self.new:
+        if self.orig != self.new and self.direct:
+            table, self.Qi = ops.sinc_table(self.orig, self.new, lowpass_filter_width, rolloff)
+            self.register_buffer("table", table, persistent=False)
+        elif self.orig != self.new:
             bank, self.width = sinc_filter_bank(self.orig, self.new, lowpass_filter_width, rolloff)
             self.register_buffer("kernel", bank, persistent=False)
+
+    def _forward_direct(self, waveform: torch.Tensor) -> torch.Tensor:
+        lead, L = tuple(waveform.shape[:-1]), waveform.shape[-1]
+        x = waveform.reshape(math.prod(lead), L)
+        out_len = -(-self.new * L // self.orig)
+        if wants_grad(waveform):
+            y = ResampleDirectFunction.apply(x, self.table.to(x.device), self.Qi, self.orig, self.new)
+        else:
+            y = ops.sinc_interp(x, self.orig, self.new, self.table.to(x.device), self.Qi, out_len)
+        return y if waveform.ndim == 2 else y.reshape(lead + (out_len,))
 
     def forward(self, waveform: torch.Tensor) -> torch.Tensor:
         if self.orig == self.new:
             return waveform
+        if self.direct:
+            return self._forward_direct(waveform)
         lead = waveform.shape[:-1]
         x = waveform.reshape(-1, waveform.shape[-1])
         if wants_grad(waveform):
@@ -72,6 +93,8 @@ class Resample(torch.nn.Module):
 
     def streaming(self) -> "RealtimeResample":
         """The causal form of this converter: a RealtimeResample that shares this module's bank."""
+        if self.direct:
+            raise ValueError("Resample(direct=True) has no streaming form: build the module with direct=False")
         rt = RealtimeResample(self.orig_freq, self.new_freq, self.lowpass_filter_width, self.rolloff)
         if self.orig != self.new:
             rt._buffers["kernel"] = self.kernel
@@ -99,7 +122,9 @@ class RealtimeResample(Resample):
     hipGraph-captured session (the state buffer changes place every call)."""
 
     def __init__(self, orig_freq: int = 16000, new_freq: int = 16000, lowpass_filter_width: int = 6,
-                 rolloff: float = 0.99):
+                 rolloff: float = 0.99, direct: bool = False):
+        if direct:
+            raise ValueError("RealtimeResample has no direct (bankless) form: the streaming kernel reads the bank")
         super().__init__(orig_freq, new_freq, lowpass_filter_width, rolloff)
         self.delay_blocks, self._keep = (0, 0) if self.orig == self.new else ops.resample_stream_sizes(self.orig, self.width)
         self.register_buffer("input_buffer", torch.zeros(self._keep))

@@ -766,6 +766,24 @@ int at_resample_sinc_backward(const float *g, int64_t rows, int64_t L, int orig,
 int at_resample_sinc_stream(const float *x, int64_t rows, int64_t C, const float *state_in, float *state_out, int orig,
                             int new_, int width, const float *filters, float *out, void *stream);
 
+/* Sample-rate conversion without the bank (ops.resample_direct, PitchShift).  An entry of the polyphase bank depends only
+ * on q = n new - o orig through one even function that is exactly 0 in float32 beyond |q| = Qi; table is its half,
+ * table[0 .. Qi] (ops.sinc_table).  in: (rows, in_len) -> out: (rows, out_len),
+ *   out[r][o] = sum over n ascending, max(0, ceil((o a - Qi) / b)) <= n <= min(in_len - 1, floor((o a + Qi) / b)),
+ *               of table[|n b - o a|] in[r][n]
+ * The converter is (in = x, a = orig, b = new, out_len = ceil(new L / orig)); its adjoint is the same routine with
+ * (in = g, in_len = out_len, a = new, b = orig, out_len = L).  Each output is one fmaf chain from +0: a function of (a,
+ * b, Qi, o, in_len) alone, so the bits of a row depend on neither its batch, the tile, the grid nor the place of the
+ * table, and for finite input they are the bits of the bank routes above, which add only zero terms to the same chain.
+ * One workgroup per tile of *tile_outputs consecutive outputs of one row, the input window they reach in LDS, the table in
+ * LDS too when it fits beside it (*table_in_lds), read from global memory otherwise: the plan routine answers both for
+ * a shape and is a pure function of its arguments.  Rows and tiles share one 64-bit index: no limit on the rows.
+ * AT_EINVAL: null pointers, negative sizes, a or b < 1, Qi < 0.  AT_OK without a launch when rows == 0 or out_len == 0.
+ * AT_EUNSUPPORTED: rates so far apart that one output's window exceeds the LDS, or sizes beyond 64-bit indexing. */
+int at_sinc_interp_plan(int a, int b, int Qi, int *tile_outputs, int *table_in_lds);
+int at_sinc_interp(const float *in, int64_t rows, int64_t in_len, int a, int b, const float *table, int Qi,
+                   int64_t out_len, float *out, void *stream);
+
 /* ---- time stretching ------------------------------------------------------------------------------------- */
 /* The phase vocoder of torchaudio.functional.phase_vocoder / torchaudio.transforms.TimeStretch (algorithm restated,
  * torchaudio is not in the reference tree) on a time-major spectrum: X (B, T, F) complex64 -> out (B, N, F) complex64.

@@ -1,0 +1,87 @@
+"""GPU side of transforms.PitchShift: the module against its definition -- the hand-written chain of the public pieces,
+STFT -> TimeStretch -> STFT.invert -> crop or pad -> the bankless converter -> crop or pad -- to the bit, forward and
+gradient; the direction of the shift on a sine; shapes, composition and the self-test hooks."""
+import numpy as np
+import pytest
+import torch
+
+import acids_transforms_amd as A
+import sinc_interp_cases as C
+from acids_transforms_amd import ops
+
+pytestmark = pytest.mark.gpu
+SR = 44100
+LENGTHS = (2048, 8191)
+STEPS = (4, -3, 12, -12)
+
+
+def _fit(y, n):
+    if y.shape[-1] >= n:
+        return y[..., :n]
+    return torch.nn.functional.pad(y, (0, n - y.shape[-1]))
+
+
+def _chain(x, n_steps, n_fft=512):
+    """torchaudio.functional.pitch_shift written out with the package's public pieces."""
+    rate, orig_freq = C.pitch_rates(SR, n_steps)
+    L = x.shape[-1]
+    stft = A.STFT(SR, n_fft, n_fft // 4).to(x.device)
+    y = stft.invert(A.TimeStretch(rate)(stft(x)))
+    y = _fit(y, int(round(L / rate)))
+    if x.requires_grad:
+        y = A.Resample(orig_freq, SR, direct=True).to(x.device)(y)
+    else:
+        y = ops.resample_direct(y, orig_freq, SR)
+    return _fit(y, L)
+
+
+@pytest.mark.parametrize("n_steps", STEPS)
+@pytest.mark.parametrize("L", LENGTHS)
+def test_the_module_is_its_definition(dev, L, n_steps):
+    x = C.audio((2, L), 100 + L).float().to(dev)
+    ps = A.PitchShift(SR, n_steps).to(dev)
+    y = ps(x)
+    assert y.shape == x.shape and y.dtype == torch.float32 and y.grad_fn is None
+    assert bool(torch.isfinite(y).all()) and bool(y.any())
+    assert torch.equal(y, _chain(x, n_steps))
+    g = C.audio((2, L), 200 + L).float().to(dev)
+    xa, xb = x.clone().requires_grad_(), x.clone().requires_grad_()
+    ya = ps(xa)
+    assert ya.grad_fn is not None and torch.equal(ya.detach(), y)                       # the same bits under autograd
+    (ya * g).sum().backward()
+    (_chain(xb, n_steps) * g).sum().backward()
+    assert xa.grad.shape == x.shape and bool(torch.isfinite(xa.grad).all()) and bool(xa.grad.any())
+    assert torch.equal(xa.grad, xb.grad)
+
+
+@pytest.mark.parametrize("n_steps,want", ((12, 2000.0), (-12, 500.0)))
+def test_a_sine_moves_the_right_way(dev, n_steps, want):
+    t = torch.arange(8192, dtype=torch.float64) / SR
+    x = torch.sin(2 * np.pi * 1000.0 * t).float().to(dev)[None]
+    y = A.PitchShift(SR, n_steps).to(dev)(x)
+    assert y.shape == x.shape
+    mid = y[0, 2048:6144].double().cpu()
+    peak = int(torch.fft.rfft(mid).abs().argmax())
+    hz = SR / 4096
+    print("n_steps %d: peak at bin %d = %.1f Hz" % (n_steps, peak, peak * hz))
+    assert abs(peak * hz - want) <= hz
+
+
+def test_shapes_composition_and_hooks(dev):
+    for lead in C.LEADS:
+        x = C.audio(lead + (3000,), 300).float().to(dev)
+        assert A.PitchShift(SR, 4).to(dev)(x).shape == x.shape
+        assert A.PitchShift(SR, -5, bins_per_octave=24, n_fft=1024).to(dev)(x).shape == x.shape
+    x = C.audio((3, 2, 3000), 301).float().to(dev)
+    chain = (A.Mono() + A.PitchShift(n_steps=4)).to(dev)
+    y = chain(x)
+    assert torch.equal(y, A.PitchShift(n_steps=4).to(dev)(A.Mono()(x)))
+    ps = A.PitchShift().to(dev)                                      # n_steps = 0: the argument itself, the hooks still shift
+    assert ps(x) is x
+    out = ps.test_forward(x)
+    assert out.shape == x.shape and not torch.equal(out, x) and torch.equal(out, A.PitchShift(n_steps=4).to(dev)(x))
+    out, tm = ps.test_forward(x, torch.zeros(3, 2, device=dev))
+    assert out.shape == x.shape and tm.shape == (3, 2)
+    A.PitchShift.test_scripted_transform(ps, invert=False)
+    y, tm = A.PitchShift(n_steps=2).to(dev).forward_with_time(x, torch.ones(3, 2, device=dev))
+    assert y.shape == x.shape and torch.equal(tm, torch.ones(3, 2, device=dev))
