@@ -57,6 +57,8 @@ _SIGNATURES = {
     "at_sinc_interp": [c_f, c_i64, c_i64, c_int, c_int, c_f, c_int, c_i64, c_f, c_f],
     "at_phase_vocoder": [c_f, c_i64, c_i64, c_i64, c_f, c_f, c_i64, c_f, c_f, c_f],
     "at_phase_vocoder_backward": [c_f, c_f, c_f, c_f, c_f, c_i64, c_i64, c_i64, c_i64, c_f, c_f],
+    "at_sos_filter_plan": [c_i64, c_i64, c_int, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), ctypes.POINTER(c_int)],
+    "at_sos_filter": [c_f, c_i64, c_i64, c_f, c_int, c_int, c_f, c_f, c_f, c_f],
     "at_sinebank_workspace_bytes": [c_i64, c_int, c_i64, c_int],
     "at_sinebank_offline": [c_f, c_i64, c_i64, c_int, c_f, c_f, c_f, c_i64, c_int, c_f, c_f, c_f, c_f, c_f, c_sz, c_f],
     "at_sinebank_realtime": [c_f, c_i64, c_int, c_int, c_int, c_f, c_f, c_f, c_f, c_f, c_f],

@@ -37,6 +37,10 @@ PhaseVocoderFunction is transforms.TimeStretch's (phase_vocoder.hip): the forwar
 step, and the backward (ops.phase_vocoder_backward) walks the steps downwards from it; the graph keeps the spectrum and
 that (..., F) phasor.
 
+SosFilterFunction and SosFilterStreamFunction are transforms.SOSFilter's and RealtimeSOSFilter's (sos_filter.hip): the
+adjoint of a recursive filter with zero state is the same filter run backwards in time, so the backward is the forward
+kernel with its direction flag flipped; coefficients and carried state are constants of the graph, and neither saves a tensor.
+
 All backward passes are first-order only (@once_differentiable): create_graph=True raises.
 """
 import torch
@@ -51,7 +55,8 @@ __all__ = ["wants_grad", "StftFunction", "IstftFunction", "IstftPolarFunction", 
            "RtStftFunction", "RtIstftFunction", "RtIstftPolarFunction", "OaddFramesFunction", "OaddInvertFunction",
            "SpectralDistanceFunction", "specdist_chunk_clips", "MelSpectralDistanceFunction", "meldist_sums",
            "meldist_loss", "PqmfFunction", "PqmfInvertFunction", "PqmfStreamFunction", "PqmfStreamInvertFunction",
-           "ResampleFunction", "ResampleStreamFunction", "ResampleDirectFunction", "PhaseVocoderFunction"]
+           "ResampleFunction", "ResampleStreamFunction", "ResampleDirectFunction", "PhaseVocoderFunction",
+           "SosFilterFunction", "SosFilterStreamFunction"]
 
 
 def wants_grad(x: torch.Tensor) -> bool:
@@ -595,6 +600,42 @@ class PhaseVocoderFunction(torch.autograd.Function):
         X, fin = ctx.saved_tensors
         gX = ops.phase_vocoder_backward(X, g, ctx.rate, fin)
         return gX.reshape(X.shape).to(X.dtype), None
+
+
+# ---- SOSFilter / RealtimeSOSFilter: the adjoint is the same cascade run the other way in time ---------------------------------
+
+class SosFilterFunction(torch.autograd.Function):
+    """ops.sos_filter(x, sos, reverse=reverse) with zero state, x (..., L) -> (..., L).  The backward is the same op with
+    `reverse` flipped (gx = flip(H flip(g))), so forward followed by reverse -- zero-phase filtering -- is its own backward.
+    Saves no tensor: the checked coefficients (a constant of the graph) and the flag hang on the node."""
+
+    @staticmethod
+    def forward(ctx, x, sos, reverse):
+        ctx.sos, ctx.reverse, ctx.dtype = ops.sos_coefficients(sos), bool(reverse), x.dtype
+        return ops.sos_filter(x, ctx.sos, reverse=ctx.reverse)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy):
+        return ops.sos_filter(gy, ctx.sos, reverse=not ctx.reverse).to(ctx.dtype), None, None
+
+
+class SosFilterStreamFunction(torch.autograd.Function):
+    """RealtimeSOSFilter.forward: chunk x (..., C), state zi (..., n_sections, 2) float64 or None -> (y (..., C), zf) by
+    ops.sos_filter.  The state is a constant of the graph and the new state is not differentiable, so the gradient covers
+    the chunk's own samples: the zero-state adjoint over the chunk, ops.sos_filter(g, reverse=True).  Saves no tensor."""
+
+    @staticmethod
+    def forward(ctx, x, zi, sos):
+        ctx.sos, ctx.dtype = ops.sos_coefficients(sos), x.dtype
+        y, zf = ops.sos_filter(x, ctx.sos, zi=zi, return_state=True)
+        ctx.mark_non_differentiable(zf)
+        return y, zf
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gy, _gstate):
+        return ops.sos_filter(gy, ctx.sos, reverse=True).to(ctx.dtype), None, None
 
 
 # ---- the invert side: Magnitude, Polar, Cartesian, polar_to_complex, Normalize -----------------------------------------

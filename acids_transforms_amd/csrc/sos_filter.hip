@@ -1,0 +1,318 @@
+// sos_filter.hip -- recursive (IIR) filtering by a cascade of second-order sections (scipy.signal.sosfilt's recurrence and
+// state layout, restated), forwards or backwards in time, as one scan along each row of a (rows, L) tensor.
+//
+// Section k filters the output v of section k - 1 in the transposed direct form II,
+//     y = b0 v + z1,   z1' = b1 v - a1 y + z2,   z2' = b2 v - a2 y           (a0 == 1),
+// which is linear in its state s = (z1, z2):  s' = A s + Bv v,  y = b0 v + s[0],  A = [[-a1, 1], [-a2, 0]].  A lane that
+// owns S consecutive samples runs them from a ZERO state in registers and gets outputs y_zs[i] and an end state e; with
+// the true state s_in at the lane's first sample
+//     y[i] = y_zs[i] + (A^i s_in)[0],        s_in(next lane) = A^S s_in + e,
+// and since every lane uses the same matrices the second relation is a scan whose only constants are powers of A^S.
+//
+// One workgroup of 256 lanes owns a row and walks it in tiles of 256 x 16 samples.  A tile is requested with coalesced
+// loads one tile ahead (16 floats per lane in registers), goes through LDS with a stride of 17 floats per lane so that a
+// lane can pick up its 16 consecutive samples without bank conflicts, and leaves the same way.  Per section: the
+// zero-state recurrence; an inclusive Hillis-Steele scan of the end states inside each wavefront (__shfl_up on the two
+// doubles, constants (A^S)^(2^m)); the four wave totals meet in LDS, where every lane chains them onto the tile's incoming
+// state in one order; the lane's own s_in = (A^S)^lane s_wave + (what the lanes below it in the wave add: the scan's value
+// one lane down, an EXCLUSIVE prefix); the fix-up above, as the homogeneous recurrence from s_in.  The tile's outgoing state goes to the next tile through LDS.
+// A lane's s_in is built from lanes before it only, and values are selected, never multiplied by a zero mask: a NaN at
+// sample n cannot reach a sample before n.
+//
+// Everything but the audio is double: the state, the coefficients (kernel arguments, by value) and the signal between
+// sections, which is rounded to float once, after the last section.  An fp32 state, or fp32 coefficients, are 1e-4 off on
+// a 20 Hz high-pass at 44.1 kHz.  Each workgroup computes the powers it needs into LDS in one fixed order (square and
+// multiply, an entry per lane), so y[r][n] is a function of (sos, L, n, reverse) and row r's samples alone: the tile and the
+// samples per lane are constants, there is one dispatch, and neither the batch nor the grid enters.  Built with
+// -ffp-contract=off and every fma written out.
+//
+// reverse = 1 is the same walk over the row read and written back to front (logical sample m is x[L - 1 - m]), the tiling
+// anchored at the row's last sample: bit for bit flip -> forward -> flip.  It is the adjoint of the forward filter with
+// zero state, so this one kernel is the forward, the backward and both halves of zero-phase filtering.
+//
+// No workgroup ever waits for another one.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+#include <type_traits>
+
+#include "../../include/acids_hip.h"
+
+namespace at_hip {
+
+constexpr int kSosLanes = 256;
+constexpr int kSosPerLane = 16;                          // S
+constexpr int kSosTile = kSosLanes * kSosPerLane;
+constexpr int kSosStride = kSosPerLane + 1;              // floats per lane in LDS: 17 is odd, so 64 lanes hit 64 banks
+constexpr int kSosWaves = kSosLanes / 64;
+constexpr int kSosMaxSections = 16;
+constexpr int kSosMaxGrid = 2048;                        // persistent workgroups: rows past the grid are walked in turn
+// a section's table of 2 x 2 matrices in LDS: (A^S)^0 .. (A^S)^64
+constexpr int kSosEntries = 65;
+
+struct SosCoef {
+  double c[kSosMaxSections][5];                          // b0 b1 b2 a1 a2
+};
+
+struct SosMat {
+  double a, b, c, d;                                     // [[a, b], [c, d]]
+};
+
+__device__ __forceinline__ SosMat sos_mul(const SosMat& x, const SosMat& y) {
+  SosMat r;
+  r.a = fma(x.a, y.a, x.b * y.c);
+  r.b = fma(x.a, y.b, x.b * y.d);
+  r.c = fma(x.c, y.a, x.d * y.c);
+  r.d = fma(x.c, y.b, x.d * y.d);
+  return r;
+}
+__device__ __forceinline__ void sos_put(double* t, const SosMat& m) {
+  t[0] = m.a;
+  t[1] = m.b;
+  t[2] = m.c;
+  t[3] = m.d;
+}
+__device__ __forceinline__ SosMat sos_get(const double* t) {
+  SosMat m;
+  m.a = t[0];
+  m.b = t[1];
+  m.c = t[2];
+  m.d = t[3];
+  return m;
+}
+// m s + t
+__device__ __forceinline__ void sos_step(const SosMat& m, double s0, double s1, double t0, double t1, double& r0, double& r1) {
+  r0 = fma(m.a, s0, fma(m.b, s1, t0));
+  r1 = fma(m.c, s0, fma(m.d, s1, t1));
+}
+// The lane's index as a value the compiler takes for new: what is derived from it (addresses, bound masks of sixteen loads)
+// is worked out where it is used, not once before all loops and kept in registers across them (64 of them, an occupancy step)
+__device__ __forceinline__ int sos_fresh(int tid) {
+  asm volatile("" : "+v"(tid));
+  return tid;
+}
+// where a tile's sample q 256 + tid sits in the staging buffer: t + t / S, written so that q is an immediate offset
+__device__ __forceinline__ int sos_slot(int q, int tid) {
+  return (tid + tid / kSosPerLane) + q * (kSosLanes + kSosLanes / kSosPerLane);
+}
+
+template <bool REV>
+__global__ __launch_bounds__(kSosLanes) void sos_filter_kernel(const float* __restrict__ x, float* __restrict__ y,
+                                                               const double* __restrict__ zi, double* __restrict__ zf,
+                                                               long long rows, long long L, SosCoef co, int n) {
+  extern __shared__ double sos_tab[];                    // n x kSosEntries matrices
+  __shared__ float stage[kSosLanes * kSosStride];
+  __shared__ double wtot[kSosMaxSections][kSosWaves][2];
+  __shared__ double carry[2][kSosMaxSections][2];        // the tile's incoming state, and the next tile's
+  __shared__ double aside[kSosPerLane];                  // one lane's: see `owner`
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+
+  // (A^S)^l for l = 0 .. 64 and every section: A^S by four squarings, then lane l raises it to its own power, bit by bit
+  // from the top -- each entry in one fixed order, whatever the launch
+  for (int k = 0; k < n; ++k) {
+    SosMat P;
+    P.a = -co.c[k][3];
+    P.b = 1.0;
+    P.c = -co.c[k][4];
+    P.d = 0.0;
+#pragma unroll
+    for (int i = 1; i < kSosPerLane; i *= 2) P = sos_mul(P, P);
+    if (tid <= 64) {
+      SosMat Q = {1.0, 0.0, 0.0, 1.0};
+      for (int bit = 6; bit >= 0; --bit) {
+        Q = sos_mul(Q, Q);
+        if ((tid >> bit) & 1) Q = sos_mul(P, Q);
+      }
+      sos_put(sos_tab + ((size_t)k * kSosEntries + tid) * 4, Q);
+    }
+  }
+
+  for (long long r = blockIdx.x; r < rows; r += gridDim.x) {
+    const float* xr = x + r * L;
+    float* yr = y + r * L;
+    if (tid < n) {
+      carry[0][tid][0] = zi ? zi[(r * n + tid) * 2] : 0.0;
+      carry[0][tid][1] = zi ? zi[(r * n + tid) * 2 + 1] : 0.0;
+    }
+    float pf[kSosPerLane];                               // the tile to come, as it was read: sample q 256 + tid
+    auto request = [&](long long t0) {                   // logical sample t is x[L - 1 - t] when REV
+      const int tid = sos_fresh(threadIdx.x);
+      const float* p = REV ? xr + (L - 1 - t0 - tid) : xr + (t0 + tid);
+      if (L - t0 >= kSosTile) {
+#pragma unroll
+        for (int q = 0; q < kSosPerLane; ++q) pf[q] = p[REV ? -q * kSosLanes : q * kSosLanes];
+      } else {
+        const int left = (int)(L - t0);                  // samples past L are zeros
+#pragma unroll
+        for (int q = 0; q < kSosPerLane; ++q) pf[q] = tid < left - q * kSosLanes ? p[REV ? -q * kSosLanes : q * kSosLanes] : 0.0f;
+      }
+    };
+    request(0);
+    int par = 0;
+    auto tile = [&](auto tail, long long t0) {
+      constexpr bool TAIL = decltype(tail)::value;       // the row's last tile: partial stores, and the final state
+      const int rem = TAIL ? (int)(L - t0) : kSosTile;   // 1 .. kSosTile
+#pragma unroll
+      for (int q = 0; q < kSosPerLane; ++q) stage[sos_slot(q, tid)] = pf[q];
+      __syncthreads();                                   // (also: the tables, and carry[0] at a row's first tile)
+      double v[kSosPerLane];
+#pragma unroll
+      for (int i = 0; i < kSosPerLane; ++i) v[i] = (double)stage[tid * kSosStride + i];
+      if (!TAIL) request(t0 + kSosTile);
+      // the lane of the row's last sample hands out the final state: it keeps each section's input to its cnt samples
+      // aside and, once it knows its s_in, runs the recurrence itself over them
+      const bool owner = TAIL && zf && tid == (rem - 1) / kSosPerLane;
+      const int cnt = rem - tid * kSosPerLane;           // 1 .. S for the owner
+      for (int k = 0; k < n; ++k) {
+        const double b0 = co.c[k][0], b1 = co.c[k][1], b2 = co.c[k][2], na1 = -co.c[k][3], na2 = -co.c[k][4];
+        const double* T = sos_tab + (size_t)k * kSosEntries * 4;
+        double z1 = 0.0, z2 = 0.0;
+        if (owner) {
+#pragma unroll
+          for (int i = 0; i < kSosPerLane; ++i) aside[i] = v[i];
+        }
+#pragma unroll
+        for (int i = 0; i < kSosPerLane; ++i) {
+          const double u = v[i];
+          const double w = fma(b0, u, z1);
+          z1 = fma(b1, u, fma(na1, w, z2));
+          z2 = fma(b2, u, na2 * w);
+          v[i] = w;
+        }
+        double e0 = z1, e1 = z2;
+#pragma unroll 1
+        for (int m = 0; m < 6; ++m) {
+          const int d = 1 << m;
+          const double u0 = __shfl_up(e0, d), u1 = __shfl_up(e1, d);
+          const SosMat M = sos_get(T + d * 4);
+          double f0, f1;
+          sos_step(M, u0, u1, e0, e1, f0, f1);
+          if (lane >= d) {
+            e0 = f0;
+            e1 = f1;
+          }
+        }
+        if (lane == 63) {
+          wtot[k][wave][0] = e0;
+          wtot[k][wave][1] = e1;
+        }
+        double x0 = __shfl_up(e0, 1), x1 = __shfl_up(e1, 1);
+        if (lane == 0) x0 = x1 = 0.0;
+        __syncthreads();
+        double g0 = carry[par][k][0], g1 = carry[par][k][1], h0 = g0, h1 = g1;
+        const SosMat M64 = sos_get(T + 64 * 4);
+#pragma unroll
+        for (int w = 0; w < kSosWaves; ++w) {
+          if (w == wave) {
+            h0 = g0;
+            h1 = g1;
+          }
+          sos_step(M64, g0, g1, wtot[k][w][0], wtot[k][w][1], g0, g1);
+        }
+        if (tid == 0) {
+          carry[par ^ 1][k][0] = g0;
+          carry[par ^ 1][k][1] = g1;
+        }
+        double s0, s1;
+        sos_step(sos_get(T + lane * 4), h0, h1, x0, x1, s0, s1);
+        if (owner) {
+          double q1 = s0, q2 = s1;
+#pragma unroll 1
+          for (int i = 0; i < cnt; ++i) {
+            const double u = aside[i];
+            const double w = fma(b0, u, q1);
+            q1 = fma(b1, u, fma(na1, w, q2));
+            q2 = fma(b2, u, na2 * w);
+          }
+          zf[(r * n + k) * 2] = q1;
+          zf[(r * n + k) * 2 + 1] = q2;
+        }
+        // the fix-up: y[i] += (A^i s_in)[0], the homogeneous recurrence from s_in
+#pragma unroll
+        for (int i = 0; i < kSosPerLane; ++i) {
+          v[i] = v[i] + s0;
+          const double t = fma(na1, s0, s1);
+          s1 = na2 * s0;
+          s0 = t;
+        }
+      }
+#pragma unroll
+      for (int i = 0; i < kSosPerLane; ++i) stage[tid * kSosStride + i] = (float)v[i] + 0.0f;     // -0 -> +0
+      __syncthreads();
+      const int tid = sos_fresh(threadIdx.x);
+      float* p = REV ? yr + (L - 1 - t0 - tid) : yr + (t0 + tid);
+#pragma unroll
+      for (int q = 0; q < kSosPerLane; ++q) {
+        if (!TAIL || tid < rem - q * kSosLanes) p[REV ? -q * kSosLanes : q * kSosLanes] = stage[sos_slot(q, tid)];
+      }
+      __syncthreads();
+      par ^= 1;
+    };
+    long long t0 = 0;
+    for (; t0 + kSosTile < L; t0 += kSosTile) tile(std::false_type(), t0);
+    tile(std::true_type(), t0);
+  }
+}
+
+static int sos_check_shape(int64_t rows, int64_t L, int n_sections) {
+  if (rows < 0 || L < 0 || n_sections < 1) return AT_EINVAL;
+  if (n_sections > kSosMaxSections) return AT_EUNSUPPORTED;
+  if (rows > 0 && L > INT64_MAX / 8 / rows) return AT_EUNSUPPORTED;        // 64-bit byte offsets
+  return AT_OK;
+}
+
+}  // namespace at_hip
+
+using namespace at_hip;
+
+extern "C" {
+
+int at_sos_filter_plan(int64_t rows, int64_t L, int n_sections, int64_t* tile, int64_t* per_lane, int* dispatch) {
+  if (!tile || !per_lane || !dispatch) return AT_EINVAL;
+  const int rc = sos_check_shape(rows, L, n_sections);
+  if (rc != AT_OK) return rc;
+  *tile = kSosTile;
+  *per_lane = kSosPerLane;
+  *dispatch = 0;                                         // one dispatch: a workgroup per row
+  return AT_OK;
+}
+
+int at_sos_filter(const float* x, int64_t rows, int64_t L, const double* sos, int n_sections, int reverse, const double* zi,
+                  double* zf, float* y, void* stream) {
+  const int rc = sos_check_shape(rows, L, n_sections);
+  if (rc != AT_OK) return rc;
+  if (!sos || (reverse != 0 && reverse != 1) || (reverse && (zi || zf))) return AT_EINVAL;
+  SosCoef co;
+  for (int k = 0; k < kSosMaxSections; ++k)
+    for (int j = 0; j < 5; ++j) co.c[k][j] = 0.0;
+  for (int k = 0; k < n_sections; ++k) {
+    const double* s = sos + k * 6;
+    for (int j = 0; j < 6; ++j)
+      if (!isfinite(s[j])) return AT_EINVAL;
+    if (s[3] != 1.0) return AT_EINVAL;
+    co.c[k][0] = s[0];
+    co.c[k][1] = s[1];
+    co.c[k][2] = s[2];
+    co.c[k][3] = s[4];
+    co.c[k][4] = s[5];
+  }
+  if (((uintptr_t)zi | (uintptr_t)zf) & 7) return AT_EINVAL;
+  if (zf && zf == zi) return AT_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  if (rows == 0) return AT_OK;
+  if (L == 0) {                                          // nothing to filter: the state passes through
+    if (!zf) return AT_OK;
+    const size_t bytes = (size_t)rows * n_sections * 2 * sizeof(double);
+    const hipError_t e = zi ? hipMemcpyAsync(zf, zi, bytes, hipMemcpyDeviceToDevice, st) : hipMemsetAsync(zf, 0, bytes, st);
+    return e == hipSuccess ? AT_OK : AT_ELAUNCH;
+  }
+  if (!x || !y) return AT_EINVAL;
+  if (((uintptr_t)x | (uintptr_t)y) & 3) return AT_EINVAL;
+  const dim3 grid((unsigned)(rows < kSosMaxGrid ? rows : kSosMaxGrid)), block(kSosLanes);
+  const size_t lds = (size_t)n_sections * kSosEntries * 4 * sizeof(double);
+  if (reverse) hipLaunchKernelGGL(sos_filter_kernel<true>, grid, block, lds, st, x, y, zi, zf, (long long)rows, (long long)L, co, n_sections);
+  else hipLaunchKernelGGL(sos_filter_kernel<false>, grid, block, lds, st, x, y, zi, zf, (long long)rows, (long long)L, co, n_sections);
+  return hipGetLastError() == hipSuccess ? AT_OK : AT_ELAUNCH;
+}
+
+}  // extern "C"

@@ -1539,6 +1539,87 @@ def phase_vocoder_backward(x, g, rate, phasor):
     return gx
 
 
+# ----------------------------------------------------------------------------------------------
+# recursive filters (sos_filter.hip)
+# ----------------------------------------------------------------------------------------------
+SOS_MAX_SECTIONS = 16
+
+
+class _Sos:
+    """Coefficients that sos_coefficients has checked: (n, 6) float64 on the host, C order, a0 == 1."""
+
+    def __init__(self, array):
+        import ctypes
+        self.array = array
+        self.n = array.shape[0]
+        self.ptr = ctypes.c_void_p(array.ctypes.data)
+
+
+def sos_coefficients(sos):
+    """Anything array-like of shape (n, 6) -- b0 b1 b2 a0 a1 a2 per section, scipy's layout -> the float64 host array the
+    kernel takes, each section divided by its a0.  ValueError: a shape that is not (n >= 1, 6), a0 == 0, a non-finite
+    entry.  (More than SOS_MAX_SECTIONS sections are the library's AT_EUNSUPPORTED.)"""
+    import numpy as np
+    if isinstance(sos, _Sos):
+        return sos
+    if isinstance(sos, torch.Tensor):
+        sos = sos.detach().cpu().numpy()
+    a = np.array(sos, dtype=np.float64, order="C", ndmin=1)
+    if a.ndim != 2 or a.shape[1] != 6 or a.shape[0] < 1:
+        raise ValueError("sos must have shape (n_sections >= 1, 6), got %s" % (tuple(a.shape),))
+    if not np.isfinite(a).all():
+        raise ValueError("sos has non-finite entries")
+    if (a[:, 3] == 0.0).any():
+        raise ValueError("a section of sos has a0 == 0")
+    a = np.ascontiguousarray(a / a[:, 3:4])
+    if not np.isfinite(a).all():
+        raise ValueError("sos has non-finite entries after the division by a0")
+    a[:, 3] = 1.0
+    return _Sos(a)
+
+
+def sos_filter_plan(rows, L, n_sections):
+    """(tile, per_lane, dispatch) of at_sos_filter at a shape: the samples a workgroup handles per step of its walk along a
+    row, the consecutive samples of one lane, and which dispatch runs (there is one: 0).  Reads no device state."""
+    import ctypes
+    tile, per_lane, dispatch = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int(0)
+    check(lib().at_sos_filter_plan(int(rows), int(L), int(n_sections), ctypes.byref(tile), ctypes.byref(per_lane),
+                                   ctypes.byref(dispatch)), "at_sos_filter_plan")
+    return tile.value, per_lane.value, dispatch.value
+
+
+def sos_filter(x, sos, zi=None, reverse=False, return_state=False):
+    """A cascade of second-order sections along the last axis of x (..., L) float32 -> (..., L) float32: scipy.signal.sosfilt's
+    recurrence and state layout, computed in double and rounded once (include/acids_hip.h, at_sos_filter).  sos: see
+    sos_coefficients.  zi (..., n_sections, 2) FLOAT64 on x's device is the state before the first sample (None: zeros);
+    with return_state=True the result is (y, zf), zf the float64 state after the last sample, written by the same launch.
+    reverse=True filters from the last sample to the first with zero state -- the adjoint of the forward filter, bit for
+    bit flip -> forward -> flip -- and takes neither zi nor return_state (ValueError)."""
+    import math
+    co = sos_coefficients(sos)
+    if reverse and (zi is not None or return_state):
+        raise ValueError("reverse filtering starts from zero state and hands none back: no zi, no return_state")
+    if x.ndim < 1:
+        raise ValueError("sos_filter takes (..., L), got a scalar")
+    require_device(x, zi)
+    x = _f32c(x)
+    lead, L = tuple(x.shape[:-1]), x.shape[-1]
+    rows = math.prod(lead)
+    state_shape = lead + (co.n, 2)
+    if zi is not None:
+        if zi.dtype != torch.float64:
+            raise AcidsHipError("zi is %s: the filter state is float64 (it is no audio: nothing narrows it)"
+                                % str(zi.dtype).replace("torch.", ""))
+        if tuple(zi.shape) != state_shape:
+            raise ValueError("zi is %s, x %s with %d sections needs %s" % (tuple(zi.shape), tuple(x.shape), co.n, state_shape))
+        zi = zi if zi.is_contiguous() else zi.contiguous()
+    y = torch.empty_like(x)
+    zf = torch.empty(state_shape, dtype=torch.float64, device=x.device) if return_state else None
+    check(lib().at_sos_filter(ptr(x), rows, L, co.ptr, co.n, int(bool(reverse)), ptr(zi), ptr(zf), ptr(y),
+                              stream_ptr()), "at_sos_filter")
+    return (y, zf) if return_state else y
+
+
 def stft_polar_forward(x, window, band, contrast=None, mag_offset=None, mag_scale=None, eps=1.1920929e-07,
                        phase_offset=None, phase_scale=None):
     """Compose(STFT -> Polar) in one kernel: x (B, L) -> (B, T, 2, F): [.., 0, :] = normalise(contrast(|X| @ bank)),

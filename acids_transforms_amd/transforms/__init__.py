@@ -12,9 +12,10 @@ from .misc import OneHot
 from .channels import Mono, Stereo, MidSide, Window, Squeeze, Unsqueeze, Transpose
 from .pqmf import PQMF, RealtimePQMF
 from .stretch import TimeStretch, PitchShift
+from .filters import SOSFilter, RealtimeSOSFilter, Preemphasis
 
 __all__ = ["AudioTransform", "ComposeAudioTransform", "NotInvertibleError", "InversionEnumType",
            "apply_transform_to_list", "apply_invert_transform_to_list", "STFT", "RealtimeSTFT", "DGT", "RealtimeDGT", "DGT_INVERSION_MODES",
            "Normalize", "Magnitude", "Real", "Imaginary", "Phase", "IF", "SpectralRepresentation", "Cartesian", "Polar",
            "PolarIF", "MFCC", "OverlapAdd", "MuLaw", "OneHot", "Mono", "Stereo", "MidSide", "Window", "Squeeze", "Unsqueeze", "Transpose",
-           "PQMF", "RealtimePQMF", "TimeStretch", "PitchShift"]
+           "PQMF", "RealtimePQMF", "TimeStretch", "PitchShift", "SOSFilter", "RealtimeSOSFilter", "Preemphasis"]

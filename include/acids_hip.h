@@ -819,6 +819,31 @@ int at_phase_vocoder_backward(const float *X_complex, const float *g_complex, co
                               const float *final_phasor, int64_t B, int64_t T, int64_t F, int64_t N, float *gX_complex,
                               void *stream);
 
+/* ---- recursive filters ----------------------------------------------------------------------------------- */
+/* A cascade of second-order sections (scipy.signal.sosfilt's recurrence and state layout, restated; no reference
+ * counterpart) along each row of x (rows, L) float32 -> y (rows, L) float32.  sos_host: n_sections x 6 doubles ON THE HOST,
+ * b0 b1 b2 a0 a1 a2 per section with a0 == 1; they travel to the kernel by value.  Section k filters the output v of
+ * section k - 1 by
+ *   y = b0 v + z1,   z1' = b1 v - a1 y + z2,   z2' = b2 v - a2 y,
+ * all in double; the signal between sections is not rounded, the last section's output is rounded to float once.  zi
+ * (rows, n_sections, 2) doubles on the device, or NULL for zeros, is the state (z1, z2) before sample 0; zf (same shape, or
+ * NULL; never zi) receives the state after sample L - 1, from the same launch.  reverse = 1 runs n from L - 1 down to 0
+ * with zero state (the adjoint of the forward filter): bit for bit flip -> forward -> flip; it takes neither zi nor zf.
+ * One workgroup of 256 lanes walks a row in tiles of *tile = 256 x *per_lane samples: a lane runs its samples from a zero
+ * state, the lanes' end states are scanned (exclusive: a NaN at sample n leaves y[: n] bit-identical, and other rows
+ * untouched), and y[i] += (A^i s_in)[0] with A = [[-a1, 1], [-a2, 0]].  y[r][n] is a function of (sos, L, n, reverse) and
+ * row r's samples alone: there is one dispatch (*dispatch = 0), a constant tile, and no dependence on the batch or the
+ * grid; the plan routine says so without a device.  Rows past the grid go to persistent workgroups: no limit on the rows.
+ * All-zero input with zero state gives +0.  Stability is the caller's: an unstable section overflows as its recurrence
+ * does (and a section whose A^1024 overflows a double gives NaN from the first tile).
+ * AT_EINVAL (no device is touched): negative sizes, n_sections < 1, null sos_host or plan outputs, null x / y with rows L >
+ * 0, a non-finite coefficient, a0 != 1, reverse outside {0, 1} or with zi / zf, zf == zi, misalignment (4 bytes audio, 8
+ * state).  AT_EUNSUPPORTED: more than 16 sections.  AT_OK without a kernel when rows == 0 or L == 0 (with L == 0 and rows >
+ * 0, zf receives zi, or zeros). */
+int at_sos_filter_plan(int64_t rows, int64_t L, int n_sections, int64_t *tile, int64_t *per_lane, int *dispatch);
+int at_sos_filter(const float *x, int64_t rows, int64_t L, const double *sos_host, int n_sections, int reverse,
+                  const double *zi, double *zf, float *y, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
