@@ -59,6 +59,11 @@ _SIGNATURES = {
     "at_phase_vocoder_backward": [c_f, c_f, c_f, c_f, c_f, c_i64, c_i64, c_i64, c_i64, c_f, c_f],
     "at_sos_filter_plan": [c_i64, c_i64, c_int, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), ctypes.POINTER(c_int)],
     "at_sos_filter": [c_f, c_i64, c_i64, c_f, c_int, c_int, c_f, c_f, c_f, c_f],
+    "at_fft_convolve_plan": [c_i64, c_i64, c_int, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), ctypes.POINTER(c_i64),
+                             ctypes.POINTER(c_int), ctypes.POINTER(c_i64)],
+    "at_spectral_fir": [c_f, c_i64, c_f, c_i64, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_f, c_f],
+    "at_spectral_fir_corr_workspace_bytes": [c_i64, c_i64, c_i64, c_int, c_int],
+    "at_spectral_fir_corr": [c_f, c_i64, c_f, c_i64, c_i64, c_i64, c_int, c_int, c_f, c_f, c_sz, c_f],
     "at_sinebank_workspace_bytes": [c_i64, c_int, c_i64, c_int],
     "at_sinebank_offline": [c_f, c_i64, c_i64, c_int, c_f, c_f, c_f, c_i64, c_int, c_f, c_f, c_f, c_f, c_f, c_sz, c_f],
     "at_sinebank_realtime": [c_f, c_i64, c_int, c_int, c_int, c_f, c_f, c_f, c_f, c_f, c_f],
@@ -133,7 +138,7 @@ _RESTYPES = {"at_error_string": ctypes.c_char_p, "at_istft_workspace_bytes": c_s
              "at_sinebank_workspace_bytes": c_sz, "at_stft_backward_workspace_bytes": c_sz,
              "at_istft_backward_workspace_bytes": c_sz, "at_rfft_frames_backward_workspace_bytes": c_sz,
              "at_irfft_frames_backward_workspace_bytes": c_sz, "at_spectral_distance_workspace_bytes": c_sz,
-             "at_mel_distance_workspace_bytes": c_sz}
+             "at_mel_distance_workspace_bytes": c_sz, "at_spectral_fir_corr_workspace_bytes": c_sz}
 
 
 class AcidsHipError(RuntimeError):

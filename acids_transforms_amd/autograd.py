@@ -41,6 +41,10 @@ SosFilterFunction and SosFilterStreamFunction are transforms.SOSFilter's and Rea
 adjoint of a recursive filter with zero state is the same filter run backwards in time, so the backward is the forward
 kernel with its direction flag flipped; coefficients and carried state are constants of the graph, and neither saves a tensor.
 
+FFTConvolveFunction is ops.fft_convolve's (fft_convolve.hip), the one Function here with two differentiable inputs that are
+both audio-like: it saves x and h and nothing else, and the backward (ops.fft_convolve_backward) rebuilds the spectra chunk
+by chunk and computes only the gradients that are asked for.
+
 All backward passes are first-order only (@once_differentiable): create_graph=True raises.
 """
 import torch
@@ -56,7 +60,7 @@ __all__ = ["wants_grad", "StftFunction", "IstftFunction", "IstftPolarFunction", 
            "SpectralDistanceFunction", "specdist_chunk_clips", "MelSpectralDistanceFunction", "meldist_sums",
            "meldist_loss", "PqmfFunction", "PqmfInvertFunction", "PqmfStreamFunction", "PqmfStreamInvertFunction",
            "ResampleFunction", "ResampleStreamFunction", "ResampleDirectFunction", "PhaseVocoderFunction",
-           "SosFilterFunction", "SosFilterStreamFunction"]
+           "SosFilterFunction", "SosFilterStreamFunction", "FFTConvolveFunction"]
 
 
 def wants_grad(x: torch.Tensor) -> bool:
@@ -636,6 +640,29 @@ class SosFilterStreamFunction(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, gy, _gstate):
         return ops.sos_filter(gy, ctx.sos, reverse=True).to(ctx.dtype), None, None
+
+
+class FFTConvolveFunction(torch.autograd.Function):
+    """ops.fft_convolve(x, h, mode, block): x (..., L), h (K,) shared or with x's leading shape -> (..., n).  The forward is
+    the plain route, bit for bit.  Saves x and h and nothing else: the backward rebuilds the spectra per chunk of rows and
+    computes gx (conj H, anticausal, then the adjoint of framing + rfft) and gh (at_spectral_fir_corr, a shared filter's
+    chunks added in ascending order in double) only where needed."""
+
+    @staticmethod
+    def forward(ctx, x, h, mode, block):
+        ctx.mode, ctx.block = mode, block
+        ctx.save_for_backward(x, h)
+        return ops.fft_convolve(x, h, mode, block)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        x, h = ctx.saved_tensors
+        need_x, need_h = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_x or need_h):
+            return None, None, None, None
+        gx, gh = ops.fft_convolve_backward(x, h, g, ctx.mode, ctx.block, need_x=need_x, need_h=need_h)
+        return (gx.to(x.dtype) if need_x else None), (gh.to(h.dtype) if need_h else None), None, None
 
 
 # ---- the invert side: Magnitude, Polar, Cartesian, polar_to_complex, Normalize -----------------------------------------

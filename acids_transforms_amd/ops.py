@@ -4,6 +4,7 @@ Each function takes ROCm-device tensors, allocates the output with torch
 (device memory + stream plumbing only) and launches the HIP kernels on the
 current torch stream.  No arithmetic happens in Python.
 """
+import ctypes
 import math
 
 import torch
@@ -1618,6 +1619,254 @@ def sos_filter(x, sos, zi=None, reverse=False, return_state=False):
     check(lib().at_sos_filter(ptr(x), rows, L, co.ptr, co.n, int(bool(reverse)), ptr(zi), ptr(zf), ptr(y),
                               stream_ptr()), "at_sos_filter")
     return (y, zf) if return_state else y
+
+
+# ----------------------------------------------------------------------------------------------
+# long-filter convolution (fft_convolve.hip): uniformly partitioned overlap-save
+# ----------------------------------------------------------------------------------------------
+FFT_CONVOLVE_BLOCKS = (128, 256, 512, 1024, 2048)
+FFT_CONVOLVE_MODES = ("full", "same", "valid")
+
+
+def fft_convolve_plan(L, K, block=None):
+    """(B, T, P, frame_tile, chunk_rows) of a convolution of L samples with K taps: the block (None: the smallest of
+    512, 1024, 2048 with ceil(K / B) <= 4, else 2048; 128 and 256 only by request), the frames ceil((L + K - 1) / B), the partitions ceil(K / B),
+    the output frames a lane of at_spectral_fir holds, and the rows of one chunk (one spectrum within 2^26 complex64
+    elements, at least one row).  Reads no device state.  ValueError: L < 1, K < 1, a block outside the ladder."""
+    if int(L) < 1 or int(K) < 1:
+        raise ValueError("fft_convolve needs at least one sample and one tap, got L = %d, K = %d" % (L, K))
+    if block is not None and (isinstance(block, bool) or int(block) != block or int(block) not in FFT_CONVOLVE_BLOCKS):
+        raise ValueError("block must be one of %s or None, got %r" % (FFT_CONVOLVE_BLOCKS, block))
+    B, T, P, tile, chunk = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int(0), ctypes.c_int64(0)
+    check(lib().at_fft_convolve_plan(int(L), int(K), 0 if block is None else int(block), ctypes.byref(B), ctypes.byref(T),
+                                     ctypes.byref(P), ctypes.byref(tile), ctypes.byref(chunk)), "at_fft_convolve_plan")
+    return B.value, T.value, P.value, tile.value, chunk.value
+
+
+def fft_convolve_cut(L, K, mode):
+    """(offset, length) of torchaudio's `mode` inside the full result of L + K - 1 samples."""
+    if mode == "full":
+        return 0, L + K - 1
+    if mode == "same":
+        return (K - 1) // 2, L
+    if mode == "valid":
+        return min(L, K) - 1, max(L, K) - min(L, K) + 1
+    raise ValueError("mode must be one of %s, got %r" % (FFT_CONVOLVE_MODES, mode))
+
+
+def spectral_fir(X, H, anticausal=False, conj=False, T=None):
+    """Y[r, t, f] = sum_p Hc[p, f] X[r, s, f], s = t - p or (anticausal) t + p inside [0, T), Hc = H or (conj) its conjugate
+    (include/acids_hip.h, at_spectral_fir).  X (rows, >= T, F) complex64 whose rows may be a slice along the frame axis (T
+    defaults to all its frames), H (P, F) shared or (rows, P, F) -> (rows, T, F) complex64."""
+    require_device(X, H)
+    X, H = _c64(X), _c64_grad(H)
+    if X.dim() != 3 or H.dim() not in (2, 3) or H.shape[-1] != X.shape[-1] or (H.dim() == 3 and H.shape[0] != X.shape[0]):
+        raise ValueError("spectral_fir takes X (rows, T, F) and H (P, F) or (rows, P, F), got %s and %s"
+                         % (tuple(X.shape), tuple(H.shape)))
+    rows, F = X.shape[0], X.shape[2]
+    T = X.shape[1] if T is None else int(T)
+    if X.stride(2) != 1 or X.stride(1) != F or T > X.shape[1] or (rows > 1 and X.stride(0) < T * F):
+        X = X[:, :T].contiguous()
+    stride = X.stride(0) if rows > 1 else max(T * F, 1)
+    P = H.shape[-2]
+    Y = torch.empty((rows, T, F), dtype=torch.complex64, device=X.device)
+    check(lib().at_spectral_fir(ptr(X), stride, ptr(H), P * F if H.dim() == 3 else 0, rows, T, P, F, int(bool(anticausal)),
+                                int(bool(conj)), ptr(Y), stream_ptr()), "at_spectral_fir")
+    return Y
+
+
+def spectral_fir_corr(X, gY, P, shared):
+    """gH[rh, p, f] = sum_r sum_{t >= p} conj(X[r, t - p, f]) gY[r, t, f] (at_spectral_fir_corr): X (rows, >= T, F) as in
+    spectral_fir, gY (rows, T, F) -> (P, F) with the rows added in ascending order (shared) or (rows, P, F)."""
+    require_device(X, gY)
+    X, gY = _c64(X), _c64_grad(gY)
+    if X.dim() != 3 or gY.dim() != 3 or X.shape[0] != gY.shape[0] or X.shape[2] != gY.shape[2] or X.shape[1] < gY.shape[1]:
+        raise ValueError("spectral_fir_corr takes X (rows, >= T, F) and gY (rows, T, F), got %s and %s"
+                         % (tuple(X.shape), tuple(gY.shape)))
+    rows, T, F = gY.shape
+    if X.stride(2) != 1 or X.stride(1) != F or (rows > 1 and X.stride(0) < T * F):
+        X = X[:, :T].contiguous()
+    stride = X.stride(0) if rows > 1 else max(T * F, 1)
+    P, shared = int(P), bool(shared)
+    gH = torch.empty((P, F) if shared else (rows, P, F), dtype=torch.complex64, device=X.device)
+    wsb = lib().at_spectral_fir_corr_workspace_bytes(rows, T, P, F, int(shared))
+    ws = _workspace(max(wsb, 8), X.device)
+    check(lib().at_spectral_fir_corr(ptr(X), stride, ptr(gY), rows, T, P, F, int(shared), ptr(gH), ptr(ws), wsb,
+                                     stream_ptr()), "at_spectral_fir_corr")
+    return gH
+
+
+def _conv_ones(N, device):
+    """The rectangular window of the convolution's transforms."""
+    return torch.ones(N, dtype=torch.float32, device=device)
+
+
+def _conv_streams(B, n):
+    """Frames per stream of the convolution's transforms: at n_fft 256 / 512 the register FFTs share a transform among
+    the frames of a stream, which would carry a frame's NaN to blocks the convolution does not reach -- one frame each."""
+    return 1 if 2 * B <= 512 else max(int(n), 1)
+
+
+def _conv_signal_spectrum(x, B, T):
+    """x (rows, L) float32 contiguous -> X[r, t] = rfft(x[r, tB - B : tB + B], zero outside [0, L)), t < T, as a (rows, T, F)
+    view (at n_fft 256 / 512 of a (rows, T + 1, F) tensor: every frame is a clip of its own there, see _conv_streams, and
+    the frame that straddles two rows is never read)."""
+    rows, L = x.shape
+    N, F = 2 * B, B + 1
+    ones = _conv_ones(N, x.device)
+    if _conv_streams(B, T) == 1:
+        buf = torch.zeros(rows * (T + 1) * B + B, dtype=torch.float32, device=x.device)
+        buf[:rows * (T + 1) * B].view(rows, (T + 1) * B)[:, B:B + L] = x
+        out = torch.empty((rows, T + 1, F), dtype=torch.complex64, device=x.device)
+        check(lib().at_stft_forward(ptr(buf), rows * (T + 1), N, B, 1, N, B, 0, ptr(ones), ptr(out), ptr(None),
+                                    stream_ptr()), "at_stft_forward")
+        return out[:, :T]
+    buf = torch.nn.functional.pad(x, (B, 0))
+    return stft_forward(buf, ones, N, B, center=False, T=T, clip_stride=B + L, L=B + L, B=rows)
+
+
+def _conv_filter_spectrum(h, B, P):
+    """h (rows_h, K) float32 -> H[r, p] = rfft(h[r, pB : pB + B] then B zeros), (rows_h, P, F): each partition is a clip of B
+    samples and one frame, which at_stft_forward pads with zeros."""
+    rows, K = h.shape
+    N, F = 2 * B, B + 1
+    if P * B != K:
+        h = torch.nn.functional.pad(h, (0, P * B - K))
+    h = h.contiguous()
+    out = torch.empty((rows, P, F), dtype=torch.complex64, device=h.device)
+    check(lib().at_stft_forward(ptr(h), rows * P, B, B, 1, N, B, 0, ptr(_conv_ones(N, h.device)), ptr(out), ptr(None),
+                                stream_ptr()), "at_stft_forward")
+    return out
+
+
+def _conv_blocks(Y, B):
+    """Y (rows, T, F) -> (rows, T B): the last B samples of irfft(Y[r, t]), block after block."""
+    rows, T, F = Y.shape
+    N = 2 * B
+    frames = torch.empty((rows, T, N), dtype=torch.float32, device=Y.device)
+    check(lib().at_irfft_frames_streams(ptr(Y), ptr(None), ptr(None), rows * T, _conv_streams(B, T), N,
+                                        ptr(_conv_ones(N, Y.device)), ptr(frames), stream_ptr()), "at_irfft_frames_streams")
+    return frames[..., B:].reshape(rows, T * B)
+
+
+def _conv_blocks_adjoint(g, B):
+    """g (rows, T B) float32 -> gY (rows, T, F): the adjoint of _conv_blocks."""
+    rows, T = g.shape[0], g.shape[1] // B
+    N, F = 2 * B, B + 1
+    gframes = torch.zeros((rows, T, N), dtype=torch.float32, device=g.device)
+    gframes[..., B:] = g.view(rows, T, B)
+    out = torch.empty((rows, T, F), dtype=torch.complex64, device=g.device)
+    per_stream = _conv_streams(B, T)
+    wsb = lib().at_irfft_frames_backward_workspace_bytes(rows * T, per_stream, N, 0)
+    ws = _workspace(wsb, g.device)
+    check(lib().at_irfft_frames_backward(ptr(gframes), ptr(None), rows * T, per_stream, N, ptr(_conv_ones(N, g.device)),
+                                         ptr(out), ptr(ws), wsb, stream_ptr()), "at_irfft_frames_backward")
+    return out
+
+
+def _conv_rfft_adjoint(G, B):
+    """G (rows, n, F) complex64 -> (rows, n, N) float32: the adjoint of the frames' rfft."""
+    rows, n, F = G.shape
+    N = 2 * B
+    out = torch.empty((rows, n, N), dtype=torch.float32, device=G.device)
+    wsb = lib().at_rfft_frames_backward_workspace_bytes(rows * n, N)
+    ws = _workspace(wsb, G.device)
+    check(lib().at_rfft_frames_backward(ptr(G), rows * n, _conv_streams(B, n), N, ptr(_conv_ones(N, G.device)), ptr(out),
+                                        ptr(ws), wsb, stream_ptr()), "at_rfft_frames_backward")
+    return out
+
+
+def _conv_operands(x, h, mode):
+    """Shapes of fft_convolve: -> (x2 (rows, L), h2 (K,) shared or (rows, K), lead, shared), checked before any device is
+    touched."""
+    if mode not in FFT_CONVOLVE_MODES:
+        raise ValueError("mode must be one of %s, got %r" % (FFT_CONVOLVE_MODES, mode))
+    if x.dim() < 1 or h.dim() < 1 or x.shape[-1] < 1 or h.shape[-1] < 1:
+        raise ValueError("fft_convolve takes x (..., L >= 1) and h (..., K >= 1), got %s and %s" % (tuple(x.shape), tuple(h.shape)))
+    shared = h.dim() == 1
+    lead = tuple(x.shape[:-1])
+    if not shared:
+        try:
+            lead = tuple(torch.broadcast_shapes(x.shape[:-1], h.shape[:-1]))
+        except RuntimeError:
+            raise ValueError("the leading shapes of x %s and h %s do not broadcast" % (tuple(x.shape), tuple(h.shape))) from None
+    return lead, shared
+
+
+@device_scoped
+def fft_convolve(x, h, mode="full", block=None):
+    """torchaudio.functional.fftconvolve(x, h, mode) by partitioned overlap-save (include/acids_hip.h, at_spectral_fir): x
+    (..., L) float32, h (K,) -- one filter for every row -- or h with x's leading shape (any other broadcastable leading
+    shape is expanded first).  "full": L + K - 1 samples; "same": L samples from (K - 1) // 2; "valid": max(L, K) - min(L, K)
+    + 1 samples from min(L, K) - 1.  block: see fft_convolve_plan.  Rows go through in chunks of the plan's chunk_rows, so
+    peak memory does not grow with the batch; a shared filter is transformed once per call."""
+    lead, shared = _conv_operands(x, h, mode)
+    L, K = x.shape[-1], h.shape[-1]
+    B, T, P, _tile, chunk = fft_convolve_plan(L, K, block)
+    off, n = fft_convolve_cut(L, K, mode)
+    require_device(x, h)
+    x2 = _f32c(x.expand(lead + (L,))).reshape(-1, L)
+    h2 = _f32c(h if shared else h.expand(lead + (K,))).reshape(-1, K)
+    rows = x2.shape[0]
+    out = torch.empty((rows, n), dtype=torch.float32, device=x.device)
+    H = _conv_filter_spectrum(h2, B, P) if shared else None
+    for r0 in range(0, rows, chunk):
+        r1 = min(rows, r0 + chunk)
+        X = _conv_signal_spectrum(x2[r0:r1], B, T)
+        Hc = H[0] if shared else _conv_filter_spectrum(h2[r0:r1], B, P)
+        out[r0:r1] = _conv_blocks(spectral_fir(X, Hc), B)[:, off:off + n]
+    return out.reshape(lead + (n,))
+
+
+@device_scoped
+def fft_convolve_backward(x, h, g, mode="full", block=None, need_x=True, need_h=True):
+    """The gradients of fft_convolve(x, h, mode, block) given g, the gradient of its result: (gx like x or None, gh like h
+    or None).  The spectra are rebuilt chunk by chunk; gx = framing^T rfft^T (conj H . gY, anticausal), gh = the first B
+    samples of rfft^T of at_spectral_fir_corr(X, gY), a shared filter's chunks added in ascending order in double."""
+    lead, shared = _conv_operands(x, h, mode)
+    L, K = x.shape[-1], h.shape[-1]
+    B, T, P, _tile, chunk = fft_convolve_plan(L, K, block)
+    off, n = fft_convolve_cut(L, K, mode)
+    require_device(x, h, g)
+    if tuple(g.shape) != lead + (n,):
+        raise ValueError("g is %s, the result of fft_convolve is %s" % (tuple(g.shape), lead + (n,)))
+    x2 = _f32c(x.expand(lead + (L,))).reshape(-1, L)
+    h2 = _f32c(h if shared else h.expand(lead + (K,))).reshape(-1, K)
+    g2 = _f32c(g).reshape(-1, n)
+    rows = x2.shape[0]
+    gx = torch.empty((rows, L), dtype=torch.float32, device=x.device) if need_x else None
+    gh = torch.empty((rows, K), dtype=torch.float32, device=x.device) if need_h and not shared else None
+    gH_sum = None
+    H = _conv_filter_spectrum(h2, B, P) if shared and need_x else None
+    for r0 in range(0, rows, chunk):
+        r1 = min(rows, r0 + chunk)
+        gfull = torch.zeros((r1 - r0, T * B), dtype=torch.float32, device=x.device)
+        gfull[:, off:off + n] = g2[r0:r1]
+        gY = _conv_blocks_adjoint(gfull, B)
+        if need_x:
+            Hc = H[0] if shared else _conv_filter_spectrum(h2[r0:r1], B, P)
+            gfr = _conv_rfft_adjoint(spectral_fir(gY, Hc, anticausal=True, conj=True), B)
+            acc = torch.zeros((r1 - r0, T + 1, B), dtype=torch.float32, device=x.device)
+            acc[:, :T] = gfr[..., :B]                    # the two frames that cover a sample
+            acc[:, 1:] += gfr[..., B:]
+            gx[r0:r1] = acc.view(r1 - r0, -1)[:, B:B + L]
+        if need_h:
+            gH = spectral_fir_corr(_conv_signal_spectrum(x2[r0:r1], B, T), gY, P, shared)
+            if shared:
+                gH_sum = gH.to(torch.complex128) if gH_sum is None else gH_sum + gH
+            else:
+                gh[r0:r1] = _conv_rfft_adjoint(gH, B)[..., :B].reshape(r1 - r0, P * B)[:, :K]
+    if need_h and shared:
+        gh = _conv_rfft_adjoint(gH_sum.to(torch.complex64).unsqueeze(0), B)[0, :, :B].reshape(P * B)[:K]
+    if need_x:
+        gx = gx.reshape(lead + (L,))
+        if tuple(x.shape) != lead + (L,):
+            gx = gx.sum_to_size(x.shape)
+    if need_h and not shared:
+        gh = gh.reshape(lead + (K,))
+        if tuple(h.shape) != lead + (K,):
+            gh = gh.sum_to_size(h.shape)
+    return gx, gh
 
 
 def stft_polar_forward(x, window, band, contrast=None, mag_offset=None, mag_scale=None, eps=1.1920929e-07,

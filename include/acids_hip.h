@@ -844,6 +844,50 @@ int at_sos_filter_plan(int64_t rows, int64_t L, int n_sections, int64_t *tile, i
 int at_sos_filter(const float *x, int64_t rows, int64_t L, const double *sos_host, int n_sections, int reverse,
                   const double *zi, double *zf, float *y, void *stream);
 
+/* ---- long-filter convolution (fft_convolve.hip; ops.fft_convolve, autograd.FFTConvolveFunction) -------------------- */
+/* Uniformly partitioned overlap-save convolution of a row of L samples with K taps (torchaudio.functional.fftconvolve,
+ * restated; no reference counterpart): block B, n_fft N = 2 B, F = B + 1, M = L + K - 1, T = ceil(M / B) frames,
+ * P = ceil(K / B) partitions.  X[t] = rfft(x[tB - B, tB + B)), H[p] = rfft(h[pB, pB + B) then B zeros), Y[t] = sum_{p <=
+ * min(t, P - 1)} H[p] X[t - p]; block t of the result is the last B samples of irfft(Y[t]).  The transforms are
+ * at_stft_forward (center = 0, hop = B, a window of ones), at_irfft_frames_streams and, for the backward,
+ * at_rfft_frames_backward / at_irfft_frames_backward; the two calls below are the part in between.
+ *
+ * at_fft_convolve_plan answers, on the host and without a device: *B (block = 0: the smallest of 512, 1024, 2048
+ * with ceil(K / B) <= 4, else 2048; block = 128, 256 or a member of that ladder: that block), *T, *P, *frame_tile (the output frames a
+ * lane of at_spectral_fir keeps in registers) and *chunk_rows (the most rows whose one spectrum T F stays within 2^26
+ * complex64 elements, at least 1).  AT_EINVAL: L < 1, K < 1, a block outside the ladder, a null output. */
+int at_fft_convolve_plan(int64_t L, int64_t K, int block, int64_t *B, int64_t *T, int64_t *P, int *frame_tile,
+                         int64_t *chunk_rows);
+
+/* Y[r][t][f] = sum_{p < P} Hc[p][f] X[r][s][f],  s = t - p (anticausal = 0) or t + p (anticausal = 1), terms with s outside
+ * [0, T) skipped; Hc = H[r] (conj = 0) or its conjugate (conj = 1).  X: rows of T x F complex64, row r at x_row_stride
+ * complex elements (>= T F: the frames of a row may be followed by others); H: (rows or 1, P, F) complex64, h_row_stride = P F
+ * for one filter per row, 0 for one filter shared by all rows; Y: (rows, T, F) complex64, dense.  (0, 0) is the forward,
+ * (1, 1) the backward with respect to X.  One lane per bin, *frame_tile consecutive frames per lane, the window of X in
+ * registers: one load of X and one of H per (p, tile).  Rows x tiles x bin chunks on one 64-bit index, persistent
+ * workgroups past 8192: no limit on the rows.  Every output element is one chain from +0 over p ascending, four fmaf per
+ * complex multiply-add: a function of (T, P, t, direction) alone -- never of the batch, the tile or the grid; zeros give +0;
+ * a NaN in X[r][s][f] stays in column (r, f).  P == 0 gives zeros.
+ * AT_EINVAL: negative sizes or strides, F < 1, a flag outside {0, 1}, null X / Y (H with P > 0) where there is work, a
+ * stride shorter than a row, a pointer that is not 8-byte aligned.  AT_OK without a launch when rows == 0 or T == 0. */
+int at_spectral_fir(const float *X_complex, int64_t x_row_stride, const float *H_complex, int64_t h_row_stride, int64_t rows,
+                    int64_t T, int64_t P, int F, int anticausal, int conj, float *Y_complex, void *stream);
+
+/* gH[rh][p][f] = sum_r sum_{t = p .. T - 1} conj(X[r][t - p][f]) gY[r][t][f]: the backward of the causal FIR with respect
+ * to H.  shared = 0: rh = r, gH (rows, P, F), no sum over rows; shared = 1: gH (1, P, F), rows added in ascending order.  X
+ * as above, gY (rows, T, F) dense.  A row's frames are cut into slices of 64: within a slice fp32 fmaf chains from +0, t
+ * ascending; slices (and, shared, rows) are added in double in ascending order, in groups of consecutive (row, slice)
+ * units that leave one complex double per (p, f) in the workspace, and a second kernel adds the groups in order and rounds
+ * once.  The grouping is a function of (rows, T, P, F) alone and there are no atomics: the same call gives the same bits;
+ * with shared = 0 a row is its own group and its gradient does not depend on the batch.  workspace: 16-byte aligned,
+ * at_spectral_fir_corr_workspace_bytes (AT_EWORKSPACE otherwise): at most 256 groups of P F complex doubles for a shared
+ * filter, one per row otherwise.  AT_EINVAL as above; AT_OK without a launch when rows == 0 or P == 0; T == 0 gives zeros
+ * (a memset, no workspace: at_spectral_fir_corr_workspace_bytes is 0 then). */
+size_t at_spectral_fir_corr_workspace_bytes(int64_t rows, int64_t T, int64_t P, int F, int shared);
+int at_spectral_fir_corr(const float *X_complex, int64_t x_row_stride, const float *gY_complex, int64_t rows, int64_t T,
+                         int64_t P, int F, int shared, float *gH_complex, void *workspace, size_t workspace_bytes,
+                         void *stream);
+
 #ifdef __cplusplus
 }
 #endif
