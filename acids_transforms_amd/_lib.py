@@ -64,6 +64,9 @@ _SIGNATURES = {
     "at_spectral_fir": [c_f, c_i64, c_f, c_i64, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_f, c_f],
     "at_spectral_fir_corr_workspace_bytes": [c_i64, c_i64, c_i64, c_int, c_int],
     "at_spectral_fir_corr": [c_f, c_i64, c_f, c_i64, c_i64, c_i64, c_int, c_int, c_f, c_f, c_sz, c_f],
+    "at_fft_convolve_stream_plan": [c_i64, c_int, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), ctypes.POINTER(c_i64),
+                                    ctypes.POINTER(c_i64)],
+    "at_spectral_fir_stream": [c_f, c_i64, c_f, c_f, c_i64, c_i64, c_i64, c_i64, c_i64, c_int, c_f, c_f],
     "at_sinebank_workspace_bytes": [c_i64, c_int, c_i64, c_int],
     "at_sinebank_offline": [c_f, c_i64, c_i64, c_int, c_f, c_f, c_f, c_i64, c_int, c_f, c_f, c_f, c_f, c_f, c_sz, c_f],
     "at_sinebank_realtime": [c_f, c_i64, c_int, c_int, c_int, c_f, c_f, c_f, c_f, c_f, c_f],

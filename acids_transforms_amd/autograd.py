@@ -45,6 +45,11 @@ FFTConvolveFunction is ops.fft_convolve's (fft_convolve.hip), the one Function h
 both audio-like: it saves x and h and nothing else, and the backward (ops.fft_convolve_backward) rebuilds the spectra chunk
 by chunk and computes only the gradients that are asked for.
 
+ImpulseResponseStreamFunction is transforms.RealtimeImpulseResponse's: one chunk of a stream through
+ops.fft_convolve_stream.  The carried state (the tail of the input and the ring of spectra) is a constant of the graph;
+the graph keeps the filter's spectrum and, only when the response requires grad, the chunk's frames and a copy of the
+P - 1 history frames, taken out of the ring before the launch overwrites anything.
+
 All backward passes are first-order only (@once_differentiable): create_graph=True raises.
 """
 import torch
@@ -60,7 +65,7 @@ __all__ = ["wants_grad", "StftFunction", "IstftFunction", "IstftPolarFunction", 
            "SpectralDistanceFunction", "specdist_chunk_clips", "MelSpectralDistanceFunction", "meldist_sums",
            "meldist_loss", "PqmfFunction", "PqmfInvertFunction", "PqmfStreamFunction", "PqmfStreamInvertFunction",
            "ResampleFunction", "ResampleStreamFunction", "ResampleDirectFunction", "PhaseVocoderFunction",
-           "SosFilterFunction", "SosFilterStreamFunction", "FFTConvolveFunction"]
+           "SosFilterFunction", "SosFilterStreamFunction", "FFTConvolveFunction", "ImpulseResponseStreamFunction"]
 
 
 def wants_grad(x: torch.Tensor) -> bool:
@@ -663,6 +668,35 @@ class FFTConvolveFunction(torch.autograd.Function):
             return None, None, None, None
         gx, gh = ops.fft_convolve_backward(x, h, g, ctx.mode, ctx.block, need_x=need_x, need_h=need_h)
         return (gx.to(x.dtype) if need_x else None), (gh.to(h.dtype) if need_h else None), None, None
+
+
+class ImpulseResponseStreamFunction(torch.autograd.Function):
+    """RealtimeImpulseResponse.forward: chunk x (rows, n B), response ir (K,), its spectrum H (P, F), and the carried state --
+    tail (rows, B), ring (rows, R, F) (updated in place), head -- -> (y (rows, n B), new_tail) by ops.fft_convolve_stream, bit
+    for bit the plain route.  The state is a constant of the graph and the new state is not differentiable: gx is the
+    offline formula over the chunk's own frames with the part that falls on the tail dropped, gh the correlation of
+    [history | the chunk's frames] with gY (ops.fft_convolve_stream_backward).  Saves H; when ir requires grad also the
+    chunk's frames, rows n F 8 bytes, and the history, rows (P - 1) F 8 bytes."""
+
+    @staticmethod
+    def forward(ctx, x, ir, H, tail, ring, head, B):
+        need_h = ctx.needs_input_grad[1]
+        ctx.B, ctx.K, ctx.x_dtype, ctx.ir_dtype = B, ir.shape[-1], x.dtype, ir.dtype
+        history = ops.ring_history(ring, head, H.shape[0] - 1) if need_h else None
+        res = ops.fft_convolve_stream(x, tail, ring, head, H, B, keep_spectra=need_h)
+        ctx.save_for_backward(H, history, res[3] if need_h else None)
+        ctx.mark_non_differentiable(res[1])
+        return res[0], res[1]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g, _gtail):
+        H, history, X = ctx.saved_tensors
+        need_x, need_h = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_x or need_h):
+            return (None,) * 7
+        gx, gh = ops.fft_convolve_stream_backward(g, H, ctx.B, ctx.K, history, X, need_x=need_x, need_h=need_h)
+        return (gx.to(ctx.x_dtype) if need_x else None), (gh.to(ctx.ir_dtype) if need_h else None), None, None, None, None, None
 
 
 # ---- the invert side: Magnitude, Polar, Cartesian, polar_to_complex, Normalize -----------------------------------------

@@ -10,6 +10,8 @@
 //                                        s outside [0, T) skipped, Hc = H or conj(H): the forward is (causal, H), the
 //                                        signal's backward (anticausal, conj H)
 //   at_spectral_fir_corr   gH[rh][p][f] = sum_r sum_{t >= p} conj(X[r][t - p][f]) gY[r][t][f]
+//   at_spectral_fir_stream the causal forward over one chunk of a stream, the P - 1 frames before it read from a ring of
+//                          spectra that the same launch then updates in place (below)
 //
 // spectral_fir.  A lane owns ONE bin and kFirTile consecutive output frames in registers, so a wavefront reads and writes
 // 64 consecutive bins (512 bytes) of a frame.  The kFirTile frames of X that the tile needs at partition p are the ones it
@@ -23,6 +25,16 @@
 // (built with -ffp-contract=off), a skipped term leaves the chain as it is (a select, never a product with zero).  The
 // chain is a function of (T, P, t, direction) alone: the tile, the grid and the batch do not enter; zeros give +0; a lane
 // never looks at another lane's values, so a NaN in X[r][s][f] stays in column (r, f).
+//
+// spectral_fir_stream.  Per row a ring of R >= P - 1 + Tc spectrum frames and a host integer `head`, the slot of the next
+// frame to arrive; a chunk brings Tc <= kFirTile frames.  A lane owns one bin of one row and ALL Tc output frames (one frame
+// tile per row), so the window slides through registers exactly as in fir_step with t0 = 0: frame s < 0 is ring slot
+// (head + s) mod R.  The slots written, [head, head + Tc), are never among the slots read, [head - (P - 1), head), and a lane
+// touches the column (row, bin) alone: the ring is updated in place by the launch that reads it, with no order between
+// workgroups and no barrier.  No term is skipped -- a frame the stream has not received yet is a frame of zeros in the
+// ring, and fmaf(h, +-0, acc) leaves a chain that started at +0 as it is for finite h -- so every output is the chain of
+// at_spectral_fir on the linearised history, to the bit, and a function of (P, t) alone: head, R, the grid and the batch
+// do not enter.
 //
 // spectral_fir_corr.  A lane owns one bin and kFirTile consecutive partitions; a row's frames are cut into slices of
 // kCorrSlice = 64 (t ascending), the unit of work is (row, slice), units ordered by row, then slice.  Within a unit every
@@ -133,6 +145,68 @@ __global__ __launch_bounds__(kFirLanes) void spectral_fir_kernel(const float2* _
 #pragma unroll
     for (int i = 0; i < kFirTile; ++i)
       if (t0 + i < T) Yc[(t0 + i) * F] = acc[i];
+  }
+}
+
+// One partition step of the streaming FIR: fir_step<false, Q> at t0 = 0 with every term present.  Frame -p comes from the
+// ring and replaces frame kFirTile - p in the window.
+template <int Q>
+struct StreamSteps {
+  static __device__ __forceinline__ void run(float2 (&acc)[kFirTile], float2 (&win)[kFirTile], const float2* __restrict__ ring,
+                                             const float2* __restrict__ Hc, long long F, long long R, long long head,
+                                             long long p0, long long P) {
+    constexpr int M = kFirTile - 1;
+    const long long p = p0 + Q;
+    if (p >= P) return;
+    if (p > 0) {                                         // p = 0: the window is the chunk itself
+      long long slot = head - p;                         // p <= P - 1 <= R - Tc: one wrap at the most
+      if (slot < 0) slot += R;
+      win[(kFirTile - Q) & M] = ring[slot * F];
+    }
+    const float2 h = Hc[p * F];
+#pragma unroll
+    for (int i = 0; i < kFirTile; ++i) acc[i] = cmla(acc[i], h, win[(i - Q) & M]);
+    StreamSteps<Q + 1>::run(acc, win, ring, Hc, F, R, head, p0, P);
+  }
+};
+template <>
+struct StreamSteps<kFirTile> {
+  static __device__ __forceinline__ void run(float2 (&)[kFirTile], float2 (&)[kFirTile], const float2* __restrict__,
+                                             const float2* __restrict__, long long, long long, long long, long long, long long) {}
+};
+
+// X: rows of Tc frames at x_row_stride; ring: (rows, R, F), read at [head - (P - 1), head) and written at [head, head + Tc)
+// modulo R; Y: (rows, Tc, F).  Accumulators past Tc run on zeros and are not stored.
+__global__ __launch_bounds__(kFirLanes) void spectral_fir_stream_kernel(const float2* __restrict__ X, long long x_row_stride,
+                                                                        float2* ring, const float2* __restrict__ H,
+                                                                        float2* __restrict__ Y, long long rows, int Tc,
+                                                                        long long P, long long R, long long head,
+                                                                        long long F) {
+  const long long chunks = (F + kFirLanes - 1) / kFirLanes;
+  const long long items = rows * chunks;
+  for (long long item = blockIdx.x; item < items; item += gridDim.x) {
+    const long long c = item % chunks, r = item / chunks;
+    const long long f = c * kFirLanes + threadIdx.x;
+    if (f >= F) continue;                                // no barrier in this kernel: a lane without a bin just leaves
+    const float2* Xc = X + r * x_row_stride + f;
+    const float2* Hc = H + f;
+    float2* ring_c = ring + r * R * F + f;
+    float2 acc[kFirTile], win[kFirTile], in[kFirTile];
+#pragma unroll
+    for (int i = 0; i < kFirTile; ++i) {
+      acc[i] = make_float2(0.f, 0.f);
+      win[i] = in[i] = (i < Tc) ? Xc[i * F] : make_float2(0.f, 0.f);
+    }
+    for (long long p0 = 0; p0 < P; p0 += kFirTile) StreamSteps<0>::run(acc, win, ring_c, Hc, F, R, head, p0, P);
+    float2* Yc = Y + r * Tc * F + f;
+#pragma unroll
+    for (int i = 0; i < kFirTile; ++i)
+      if (i < Tc) {
+        Yc[i * F] = acc[i];
+        long long slot = head + i;
+        if (slot >= R) slot -= R;
+        ring_c[slot * F] = in[i];                        // after every read of this column: the slots differ anyway
+      }
   }
 }
 
@@ -279,6 +353,18 @@ static int fir_check_shape(int64_t rows, int64_t T, int64_t P, int F) {
 
 static unsigned fir_grid(long long items) { return (unsigned)(items < kFirMaxGrid ? items : kFirMaxGrid); }
 
+// the block of K taps: block = 0 is the shipped rule, any other value must be a member of the ladder (0: it is not)
+static int64_t conv_block(int64_t K, int block) {
+  if (block == 0) {
+    for (int i = kConvFirstRuleBlock; i < 5; ++i)
+      if ((K + kConvBlocks[i] - 1) / kConvBlocks[i] <= kConvMaxPartitions) return kConvBlocks[i];
+    return kConvBlocks[4];
+  }
+  for (int i = 0; i < 5; ++i)
+    if (block == kConvBlocks[i]) return block;
+  return 0;
+}
+
 }  // namespace at_hip
 
 using namespace at_hip;
@@ -290,19 +376,8 @@ int at_fft_convolve_plan(int64_t L, int64_t K, int block, int64_t* B, int64_t* T
   if (!B || !T || !P || !frame_tile || !chunk_rows) return AT_EINVAL;
   if (L < 1 || K < 1 || block < 0) return AT_EINVAL;
   if (L > INT64_MAX / 4 - K) return AT_EUNSUPPORTED;
-  int64_t b = 0;
-  if (block == 0) {
-    b = kConvBlocks[4];
-    for (int i = kConvFirstRuleBlock; i < 5; ++i)
-      if ((K + kConvBlocks[i] - 1) / kConvBlocks[i] <= kConvMaxPartitions) {
-        b = kConvBlocks[i];
-        break;
-      }
-  } else {
-    for (int i = 0; i < 5; ++i)
-      if (block == kConvBlocks[i]) b = block;
-    if (b == 0) return AT_EINVAL;
-  }
+  const int64_t b = conv_block(K, block);
+  if (b == 0) return AT_EINVAL;
   const int64_t M = L + K - 1;
   *B = b;
   *T = (M + b - 1) / b;
@@ -334,6 +409,37 @@ int at_spectral_fir(const float* X_complex, int64_t x_row_stride, const float* H
     hipLaunchKernelGGL(spectral_fir_kernel<false>, grid, block, 0, st, (const float2*)X_complex, (long long)x_row_stride,
                        (const float2*)H_complex, (long long)h_row_stride, (float2*)Y_complex, (long long)rows, (long long)T,
                        (long long)P, (long long)F, conj);
+  return hipGetLastError() == hipSuccess ? AT_OK : AT_ELAUNCH;
+}
+
+int at_fft_convolve_stream_plan(int64_t K, int block, int64_t* B, int64_t* P, int64_t* R, int64_t* max_frames) {
+  if (!B || !P || !R || !max_frames) return AT_EINVAL;
+  if (K < 1 || block < 0) return AT_EINVAL;
+  if (K > INT64_MAX / 4) return AT_EUNSUPPORTED;
+  const int64_t b = conv_block(K, block);
+  if (b == 0) return AT_EINVAL;
+  *B = b;
+  *P = (K + b - 1) / b;
+  *R = *P - 1 + kFirTile;
+  *max_frames = kFirTile;
+  return AT_OK;
+}
+
+int at_spectral_fir_stream(const float* X_complex, int64_t x_row_stride, float* ring_complex, const float* H_complex,
+                           int64_t rows, int64_t Tc, int64_t P, int64_t R, int64_t head, int F, float* Y_complex,
+                           void* stream) {
+  if (rows < 0 || Tc < 0 || Tc > kFirTile || P < 1 || F < 1 || x_row_stride < 0) return AT_EINVAL;
+  if (R < P - 1 + Tc || head < 0 || head >= R) return AT_EINVAL;
+  if (rows > 0 && R > INT64_MAX / 16 / F / rows) return AT_EUNSUPPORTED;               // 64-bit byte offsets
+  if (rows > 0 && x_row_stride > INT64_MAX / 16 / rows) return AT_EUNSUPPORTED;
+  if (rows == 0 || Tc == 0) return AT_OK;                // nothing arrived: the ring stays as it is
+  if (!X_complex || !ring_complex || !H_complex || !Y_complex) return AT_EINVAL;
+  if (x_row_stride < Tc * F) return AT_EINVAL;
+  if (((uintptr_t)X_complex | (uintptr_t)ring_complex | (uintptr_t)H_complex | (uintptr_t)Y_complex) & 7) return AT_EINVAL;
+  const long long items = (long long)rows * ((F + kFirLanes - 1) / kFirLanes);
+  hipLaunchKernelGGL(spectral_fir_stream_kernel, dim3(fir_grid(items)), dim3(kFirLanes), 0, (hipStream_t)stream,
+                     (const float2*)X_complex, (long long)x_row_stride, (float2*)ring_complex, (const float2*)H_complex,
+                     (float2*)Y_complex, (long long)rows, (int)Tc, (long long)P, (long long)R, (long long)head, (long long)F);
   return hipGetLastError() == hipSuccess ? AT_OK : AT_ELAUNCH;
 }
 

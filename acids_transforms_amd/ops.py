@@ -1869,6 +1869,151 @@ def fft_convolve_backward(x, h, g, mode="full", block=None, need_x=True, need_h=
     return gx, gh
 
 
+# ---- the streaming form: a ring of spectra per stream (at_spectral_fir_stream) ----------------------------------------------
+def fft_convolve_stream_plan(K, block=None):
+    """(B, P, R, max_frames) of a stream convolved with K taps: the block (None: fft_convolve_plan's rule; 128 and 256 by
+    request), the partitions ceil(K / B), the slots of the ring of spectra P - 1 + max_frames, and the most frames one launch
+    of at_spectral_fir_stream takes.  Reads no device state.  ValueError: K < 1, a block outside the ladder."""
+    if int(K) < 1:
+        raise ValueError("a streaming convolution needs at least one tap, got K = %d" % K)
+    if block is not None and (isinstance(block, bool) or int(block) != block or int(block) not in FFT_CONVOLVE_BLOCKS):
+        raise ValueError("block must be one of %s or None, got %r" % (FFT_CONVOLVE_BLOCKS, block))
+    B, P, R, n = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int64(0)
+    check(lib().at_fft_convolve_stream_plan(int(K), 0 if block is None else int(block), ctypes.byref(B), ctypes.byref(P),
+                                            ctypes.byref(R), ctypes.byref(n)), "at_fft_convolve_stream_plan")
+    return B.value, P.value, R.value, n.value
+
+
+def spectral_fir_stream(Xc, ring, head, H):
+    """Y[r, t, f] = sum_p H[p, f] V[r, t - p, f] over a chunk of a stream (include/acids_hip.h, at_spectral_fir_stream): Xc
+    (rows, Tc, F) complex64, the chunk's frames (its rows may be a slice along the frame axis of a longer tensor), ring
+    (rows, R, F) complex64 contiguous, head the slot of the next frame, H (P, F) -> Y (rows, Tc, F).  MUTATES ring: slots
+    head .. head + Tc - 1 (modulo R) receive Xc.  The caller owns head and advances it by Tc modulo R."""
+    if (Xc.dim() != 3 or ring.dim() != 3 or H.dim() != 2 or ring.shape[0] != Xc.shape[0] or ring.shape[2] != Xc.shape[2]
+            or H.shape[1] != Xc.shape[2]):
+        raise ValueError("spectral_fir_stream takes Xc (rows, Tc, F), ring (rows, R, F) and H (P, F), got %s, %s and %s"
+                         % (tuple(Xc.shape), tuple(ring.shape), tuple(H.shape)))
+    if ring.dtype != torch.complex64 or not ring.is_contiguous():
+        raise ValueError("ring must be a contiguous complex64 tensor (it is updated in place), got %s%s"
+                         % (str(ring.dtype).replace("torch.", ""), "" if ring.is_contiguous() else ", not contiguous"))
+    require_device(Xc, ring, H)
+    Xc, H = _c64(Xc), _c64(H)
+    rows, Tc, F = Xc.shape
+    if Xc.stride(2) != 1 or Xc.stride(1) != F or (rows > 1 and Xc.stride(0) < Tc * F):
+        Xc = Xc.contiguous()
+    stride = Xc.stride(0) if rows > 1 else max(Tc * F, 1)
+    H = H if H.is_contiguous() else H.contiguous()
+    Y = torch.empty((rows, Tc, F), dtype=torch.complex64, device=Xc.device)
+    check(lib().at_spectral_fir_stream(ptr(Xc), stride, ptr(ring), ptr(H), rows, Tc, H.shape[0], ring.shape[1], int(head), F,
+                                       ptr(Y), stream_ptr()), "at_spectral_fir_stream")
+    return Y
+
+
+def _conv_stream_spectrum(tail, x, B):
+    """tail (rows, B) and x (rows, Tc B) float32 -> (stage, Xc): stage (rows, (Tc + 1) B) = [tail | x] and Xc[r, t] =
+    rfft(stage[r, tB : tB + 2 B]), t < Tc, as a (rows, Tc, F) view (at n_fft 256 / 512 of a (rows, Tc + 1, F) tensor: one
+    frame per clip, see _conv_streams; the frame that straddles two rows is never read)."""
+    rows, Tc = x.shape[0], x.shape[1] // B
+    N, F = 2 * B, B + 1
+    ones = _conv_ones(N, x.device)
+    n = rows * (Tc + 1) * B
+    # + B: the last row's straddling frame stays inside the buffer (those B samples are never set: nobody reads that frame)
+    buf = torch.empty(n + B, dtype=torch.float32, device=x.device)
+    stage = buf[:n].view(rows, (Tc + 1) * B)
+    stage[:, :B] = tail
+    stage[:, B:] = x
+    if _conv_streams(B, Tc) == 1:
+        out = torch.empty((rows, Tc + 1, F), dtype=torch.complex64, device=x.device)
+        check(lib().at_stft_forward(ptr(buf), rows * (Tc + 1), N, B, 1, N, B, 0, ptr(ones), ptr(out), ptr(None),
+                                    stream_ptr()), "at_stft_forward")
+        return stage, out[:, :Tc]
+    return stage, stft_forward(stage, ones, N, B, center=False, T=Tc, clip_stride=(Tc + 1) * B, L=(Tc + 1) * B, B=rows)
+
+
+@device_scoped
+def fft_convolve_stream(x, tail, ring, head, H, B, keep_spectra=False):
+    """The next chunk of a stream through the partitioned convolution: x (rows, n B) float32, n >= 1, tail (rows, B) the B
+    samples before it, ring (rows, R, F) and head as in spectral_fir_stream, H (P, F) the filter's spectrum -> (y (rows, n B),
+    new_tail (rows, B), new_head[, X (rows, n, F)]).  The chunk is walked in sub-chunks of at most max_frames blocks: [tail |
+    blocks] -> frames (at_stft_forward, a window of ones, center = 0), at_spectral_fir_stream, the last halves of the inverse
+    transforms.  MUTATES ring; tail is left alone.  keep_spectra: also the chunk's own frames, for the filter's gradient."""
+    rows, C = x.shape
+    P, F = H.shape
+    R = ring.shape[1]
+    step = R - (P - 1)
+    if C < B or C % B or step < 1 or F != B + 1 or tuple(tail.shape) != (rows, B) or tuple(ring.shape) != (rows, R, F):
+        raise ValueError("fft_convolve_stream takes x (rows, n B), tail (rows, B), ring (rows, R >= P, B + 1), H (P, B + 1); got "
+                         "%s, %s, %s, %s at B = %d" % (tuple(x.shape), tuple(tail.shape), tuple(ring.shape), tuple(H.shape), B))
+    require_device(x, tail, ring, H)
+    x, tail = _f32c(x), _f32c(tail)
+    step = min(step, lib_max_stream_frames())
+    n = C // B
+    out = torch.empty((rows, C), dtype=torch.float32, device=x.device) if n > step else None
+    spectra = []
+    for b0 in range(0, n, step):
+        b1 = min(n, b0 + step)
+        stage, Xc = _conv_stream_spectrum(tail, x[:, b0 * B:b1 * B], B)
+        y = _conv_blocks(spectral_fir_stream(Xc, ring, head, H), B)
+        head = (head + (b1 - b0)) % R
+        tail = stage[:, (b1 - b0) * B:]
+        if keep_spectra:
+            spectra.append(Xc)
+        if out is None:
+            out = y
+        else:
+            out[:, b0 * B:b1 * B] = y
+    res = (out, tail.contiguous(), head)
+    if keep_spectra:
+        res += (spectra[0] if len(spectra) == 1 else torch.cat(spectra, dim=1),)
+    return res
+
+
+_MAX_STREAM_FRAMES = None
+
+
+def lib_max_stream_frames():
+    """max_frames of at_fft_convolve_stream_plan (a constant of the library)."""
+    global _MAX_STREAM_FRAMES
+    if _MAX_STREAM_FRAMES is None:
+        _MAX_STREAM_FRAMES = fft_convolve_stream_plan(1)[3]
+    return _MAX_STREAM_FRAMES
+
+
+def ring_history(ring, head, n):
+    """The n frames before slot head of ring (rows, R, F), oldest first, as a new tensor (the ring in ring order)."""
+    R = ring.shape[1]
+    start = (head - n) % R
+    if start + n <= R:
+        return ring[:, start:start + n].clone()
+    return torch.cat([ring[:, start:], ring[:, :start + n - R]], dim=1)     # the range wraps: two pieces
+
+
+@device_scoped
+def fft_convolve_stream_backward(g, H, B, K, history=None, X=None, need_x=True, need_h=False):
+    """The gradients of one chunk of fft_convolve_stream with the carried state a constant: g (rows, n B), H (P, F) ->
+    (gx (rows, n B) or None, gh (K,) or None).  gx is the offline formula over the chunk's own n frames (the part that falls
+    on the tail is dropped); gh is at_spectral_fir_corr of [history | X] (history (rows, P - 1, F): ring_history before the
+    forward's launch; X: the chunk's frames) against gY preceded by P - 1 frames of zeros, then rfft^T and the cut to K taps."""
+    require_device(g, H)
+    g = _f32c(g)
+    rows, C = g.shape
+    n, P = C // B, H.shape[0]
+    gY = _conv_blocks_adjoint(g, B)
+    gx = gh = None
+    if need_x:
+        gfr = _conv_rfft_adjoint(spectral_fir(gY, H, anticausal=True, conj=True), B)
+        acc = torch.zeros((rows, n + 1, B), dtype=torch.float32, device=g.device)
+        acc[:, :n] = gfr[..., :B]                        # the two frames that cover a sample
+        acc[:, 1:] += gfr[..., B:]
+        gx = acc.view(rows, -1)[:, B:]
+    if need_h:
+        Xall = torch.cat([history, X], dim=1) if P > 1 else X
+        gYall = torch.cat([torch.zeros_like(history), gY], dim=1) if P > 1 else gY
+        gH = spectral_fir_corr(Xall, gYall, P, True)
+        gh = _conv_rfft_adjoint(gH.unsqueeze(0), B)[0, :, :B].reshape(P * B)[:K]
+    return gx, gh
+
+
 def stft_polar_forward(x, window, band, contrast=None, mag_offset=None, mag_scale=None, eps=1.1920929e-07,
                        phase_offset=None, phase_scale=None):
     """Compose(STFT -> Polar) in one kernel: x (B, L) -> (B, T, 2, F): [.., 0, :] = normalise(contrast(|X| @ bank)),

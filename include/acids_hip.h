@@ -888,6 +888,25 @@ int at_spectral_fir_corr(const float *X_complex, int64_t x_row_stride, const flo
                          int64_t P, int F, int shared, float *gH_complex, void *workspace, size_t workspace_bytes,
                          void *stream);
 
+/* The causal FIR over a STREAM: per row a ring of R >= P - 1 + Tc spectrum frames, (rows, R, F) complex64, and `head`, the
+ * slot of the next frame to arrive, kept by the caller on the host.  One launch takes a chunk of Tc <= *max_frames (8) new
+ * frames X (rows of Tc x F at x_row_stride complex elements) and ONE filter H (P, F) for every row:
+ *   Y[r][t][f] = sum_{p < P, ascending} H[p][f] V[r][t - p][f],   V[r][s] = X[r][s] (s >= 0) or ring[r][(head + s) mod R] (s < 0),
+ * and then ring[r][(head + t) mod R] = X[r][t], t < Tc: the slots written are never among the P - 1 slots read, so the ring
+ * is updated in place by the same launch; the caller then advances head by Tc modulo R.  A ring of zeros is a stream
+ * that has not begun.  One lane per (row, bin) holds all Tc output frames; no term is skipped, every output is one chain
+ * from +0 of four fmaf per term, a function of (P, t) alone -- never of head, R, the grid or the batch -- and for finite
+ * input it has the bits of at_spectral_fir (causal) on the linearised history [ring in order | X].  Rows x bin chunks on one
+ * 64-bit index, persistent workgroups past 8192.  at_fft_convolve_stream_plan answers on the host, without a device: *B as
+ * at_fft_convolve_plan (block = 0: the shipped rule), *P = ceil(K / B), *R = P - 1 + 8, *max_frames = 8.
+ * AT_EINVAL: a null pointer, negative sizes, Tc > 8, P < 1, F < 1, R < P - 1 + Tc, head outside [0, R), a stride shorter
+ * than Tc F, a pointer that is not 8-byte aligned; for the plan K < 1, a block outside the ladder, a null output.  AT_OK
+ * without a launch, the ring untouched, when rows == 0 or Tc == 0. */
+int at_fft_convolve_stream_plan(int64_t K, int block, int64_t *B, int64_t *P, int64_t *R, int64_t *max_frames);
+int at_spectral_fir_stream(const float *X_complex, int64_t x_row_stride, float *ring_complex, const float *H_complex,
+                           int64_t rows, int64_t Tc, int64_t P, int64_t R, int64_t head, int F, float *Y_complex,
+                           void *stream);
+
 #ifdef __cplusplus
 }
 #endif
