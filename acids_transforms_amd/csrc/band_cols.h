@@ -1,6 +1,6 @@
 // band_cols.h -- what the banded backward kernels share (mag_bwd_banded_kernel of autograd.hip, maginv_bwd_banded_kernel
 // of invert_grad.hip, mfcc_bwd_kernel of mfcc_grad.hip): a bank as bands by column, its staging in LDS, the walk of one
-// column, the row kept in registers, the LDS plan (band_plan.h) and the launcher.
+// column, the row kept in registers, the LDS plan (band_plan.h) and the launch of a row plan (persistent_launch.h).
 //
 // A (K x N) bank by column (utils.banded.bank_columns): column j holds len[j] weights at w[off[j] ..] for the rows
 // start[j] .. start[j] + len[j] - 1.  The transposed bank is the same tables of bank^T (K columns).
@@ -9,6 +9,7 @@
 #include <stddef.h>
 
 #include "band_plan.h"
+#include "persistent_launch.h"
 
 namespace at_hip {
 
@@ -72,34 +73,11 @@ __device__ __forceinline__ void band_row_load(float2 (&xv)[KIT > 0 ? KIT : 1], c
 
 // ---- launcher ---------------------------------------------------------------------------------------------------------
 
-// Launches kernel(args...) with wpb waves per workgroup and lds bytes of dynamic LDS on as many workgroups as the chip
-// holds at once (the tables are staged once per workgroup), at most one per work unit (a row group, a tile).  The device
-// is asked on every call: the current one, on a host with several.  0, or -5.
-template <typename Kernel, typename... Args>
-int band_launch(Kernel kernel, int wpb, size_t lds, long long units, hipStream_t stream, Args... args) {
-  const void* fn = (const void*)kernel;
-  if (lds > 64 * 1024 &&
-      hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-    (void)hipGetLastError();
-    return -5;
-  }
-  int per_cu = 0, cus = 0, dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, 64 * wpb, lds) != hipSuccess) {
-    (void)hipGetLastError();
-    return -5;
-  }
-  long long blocks = (long long)(per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 1);
-  if (blocks > units) blocks = units;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(64 * wpb), lds, stream, args...);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
-}
-
-// band_launch of a one-wave-per-row kernel under the plan pl: one work unit is a row group, the wpb rows of a workgroup
+// persistent_launch of a one-wave-per-row kernel under the plan pl (the tables are staged once per workgroup): one work
+// unit is a row group, the wpb rows of a workgroup
 template <typename Kernel, typename... Args>
 int band_launch_rows(Kernel kernel, const BandPlan& pl, long long rows, hipStream_t stream, Args... args) {
-  return band_launch(kernel, pl.wpb, pl.lds, (rows + pl.wpb - 1) / pl.wpb, stream, args...);
+  return persistent_launch(kernel, 64 * pl.wpb, pl.lds, (rows + pl.wpb - 1) / pl.wpb, stream, args...);
 }
 
 }  // namespace at_hip

@@ -74,50 +74,68 @@ __device__ __forceinline__ float2 cmla(float2 acc, float2 h, float2 x) {
   return acc;
 }
 
+// Where a step's frames of one (row, bin) column come from.  load(s): frame s; whole(lo, hi) and has(s): do frames lo .. hi,
+// does frame s, exist -- the term of a frame that does not is skipped.
+struct ClipFrames {                                      // the frames [0, T) of a clip
+  const float2* __restrict__ Xc;
+  long long F, T;
+  __device__ __forceinline__ bool has(long long s) const { return s >= 0 && s < T; }
+  __device__ __forceinline__ bool whole(long long lo, long long hi) const { return lo >= 0 && hi < T; }
+  __device__ __forceinline__ float2 load(long long s) const { return has(s) ? Xc[s * F] : make_float2(0.f, 0.f); }
+};
+struct RingFrames {                                      // the frames s < 0 before a stream's chunk: ring slot (head + s) mod R
+  const float2* ring;
+  long long F, R, head;
+  // every frame exists (one the stream has not received yet is a frame of zeros): a constant, so that no term is skipped
+  static constexpr __device__ bool has(long long) { return true; }
+  static constexpr __device__ bool whole(long long, long long) { return true; }
+  __device__ __forceinline__ float2 load(long long s) const {
+    long long slot = head + s;                           // -s <= P - 1 <= R - Tc: one wrap at the most
+    if (slot < 0) slot += R;
+    return ring[slot * F];
+  }
+};
+
 // One partition step of the FIR.  Q = p mod kFirTile is a constant, so that the slot of every frame is one.
 // Causal: output i reads X[t0 + i - p] from slot (i - Q) mod tile; the new frame X[t0 - p] replaces X[t0 + tile - p].
 // Anticausal: output i reads X[t0 + i + p] from slot (i + Q) mod tile; the new frame X[t0 + tile - 1 + p] replaces X[t0 + p - 1].
-template <bool ANTI, int Q>
-__device__ __forceinline__ void fir_step(float2 (&acc)[kFirTile], float2 (&win)[kFirTile], const float2* __restrict__ Xc,
-                                         const float2* __restrict__ Hc, long long F, long long T, long long t0, long long p,
-                                         bool conj) {
+template <typename Frames, bool ANTI, int Q>
+__device__ __forceinline__ void fir_step(float2 (&acc)[kFirTile], float2 (&win)[kFirTile], const Frames& src,
+                                         const float2* __restrict__ Hc, long long F, long long t0, long long p, bool conj) {
   constexpr int M = kFirTile - 1;
   if (p > 0) {                                           // p = 0: the window was loaded whole
-    const long long s = ANTI ? t0 + M + p : t0 - p;
     constexpr int slot = ANTI ? ((M + Q) & M) : ((kFirTile - Q) & M);
-    win[slot] = (s >= 0 && s < T) ? Xc[s * F] : make_float2(0.f, 0.f);
+    win[slot] = src.load(ANTI ? t0 + M + p : t0 - p);
   }
   float2 h = Hc[p * F];
   if (conj) h.y = -h.y;
   const long long lo = ANTI ? t0 + p : t0 - p, hi = lo + M;          // the frames of X this step reads
-  if (lo >= 0 && hi < T) {
+  if (src.whole(lo, hi)) {
 #pragma unroll
     for (int i = 0; i < kFirTile; ++i) acc[i] = cmla(acc[i], h, win[ANTI ? ((i + Q) & M) : ((i - Q) & M)]);
   } else {
 #pragma unroll
     for (int i = 0; i < kFirTile; ++i) {
-      const long long s = lo + i;
       const float2 v = cmla(acc[i], h, win[ANTI ? ((i + Q) & M) : ((i - Q) & M)]);
-      if (s >= 0 && s < T) acc[i] = v;                   // a skipped term leaves the chain untouched
+      if (src.has(lo + i)) acc[i] = v;                   // a skipped term leaves the chain untouched
     }
   }
 }
 
-template <bool ANTI, int Q>
+template <typename Frames, bool ANTI, int Q>
 struct FirSteps {
-  static __device__ __forceinline__ void run(float2 (&acc)[kFirTile], float2 (&win)[kFirTile], const float2* __restrict__ Xc,
-                                             const float2* __restrict__ Hc, long long F, long long T, long long t0, long long p0,
+  static __device__ __forceinline__ void run(float2 (&acc)[kFirTile], float2 (&win)[kFirTile], const Frames& src,
+                                             const float2* __restrict__ Hc, long long F, long long t0, long long p0,
                                              long long P, bool conj) {
     if (p0 + Q >= P) return;
-    fir_step<ANTI, Q>(acc, win, Xc, Hc, F, T, t0, p0 + Q, conj);
-    FirSteps<ANTI, Q + 1>::run(acc, win, Xc, Hc, F, T, t0, p0, P, conj);
+    fir_step<Frames, ANTI, Q>(acc, win, src, Hc, F, t0, p0 + Q, conj);
+    FirSteps<Frames, ANTI, Q + 1>::run(acc, win, src, Hc, F, t0, p0, P, conj);
   }
 };
-template <bool ANTI>
-struct FirSteps<ANTI, kFirTile> {
-  static __device__ __forceinline__ void run(float2 (&)[kFirTile], float2 (&)[kFirTile], const float2* __restrict__,
-                                             const float2* __restrict__, long long, long long, long long, long long, long long,
-                                             bool) {}
+template <typename Frames, bool ANTI>
+struct FirSteps<Frames, ANTI, kFirTile> {
+  static __device__ __forceinline__ void run(float2 (&)[kFirTile], float2 (&)[kFirTile], const Frames&,
+                                             const float2* __restrict__, long long, long long, long long, long long, bool) {}
 };
 
 template <bool ANTI>
@@ -140,7 +158,9 @@ __global__ __launch_bounds__(kFirLanes) void spectral_fir_kernel(const float2* _
       acc[i] = make_float2(0.f, 0.f);
       win[i] = (t0 + i < T) ? Xc[(t0 + i) * F] : make_float2(0.f, 0.f);
     }
-    for (long long p0 = 0; p0 < P; p0 += kFirTile) FirSteps<ANTI, 0>::run(acc, win, Xc, Hc, F, T, t0, p0, P, conj != 0);
+    const ClipFrames src = {Xc, F, T};
+    for (long long p0 = 0; p0 < P; p0 += kFirTile)
+      FirSteps<ClipFrames, ANTI, 0>::run(acc, win, src, Hc, F, t0, p0, P, conj != 0);
     float2* Yc = Y + r * T * F + f;
 #pragma unroll
     for (int i = 0; i < kFirTile; ++i)
@@ -148,33 +168,7 @@ __global__ __launch_bounds__(kFirLanes) void spectral_fir_kernel(const float2* _
   }
 }
 
-// One partition step of the streaming FIR: fir_step<false, Q> at t0 = 0 with every term present.  Frame -p comes from the
-// ring and replaces frame kFirTile - p in the window.
-template <int Q>
-struct StreamSteps {
-  static __device__ __forceinline__ void run(float2 (&acc)[kFirTile], float2 (&win)[kFirTile], const float2* __restrict__ ring,
-                                             const float2* __restrict__ Hc, long long F, long long R, long long head,
-                                             long long p0, long long P) {
-    constexpr int M = kFirTile - 1;
-    const long long p = p0 + Q;
-    if (p >= P) return;
-    if (p > 0) {                                         // p = 0: the window is the chunk itself
-      long long slot = head - p;                         // p <= P - 1 <= R - Tc: one wrap at the most
-      if (slot < 0) slot += R;
-      win[(kFirTile - Q) & M] = ring[slot * F];
-    }
-    const float2 h = Hc[p * F];
-#pragma unroll
-    for (int i = 0; i < kFirTile; ++i) acc[i] = cmla(acc[i], h, win[(i - Q) & M]);
-    StreamSteps<Q + 1>::run(acc, win, ring, Hc, F, R, head, p0, P);
-  }
-};
-template <>
-struct StreamSteps<kFirTile> {
-  static __device__ __forceinline__ void run(float2 (&)[kFirTile], float2 (&)[kFirTile], const float2* __restrict__,
-                                             const float2* __restrict__, long long, long long, long long, long long, long long) {}
-};
-
+// The causal steps at t0 = 0 over the ring: frame -p comes from it and replaces frame kFirTile - p in the window.
 // X: rows of Tc frames at x_row_stride; ring: (rows, R, F), read at [head - (P - 1), head) and written at [head, head + Tc)
 // modulo R; Y: (rows, Tc, F).  Accumulators past Tc run on zeros and are not stored.
 __global__ __launch_bounds__(kFirLanes) void spectral_fir_stream_kernel(const float2* __restrict__ X, long long x_row_stride,
@@ -197,7 +191,9 @@ __global__ __launch_bounds__(kFirLanes) void spectral_fir_stream_kernel(const fl
       acc[i] = make_float2(0.f, 0.f);
       win[i] = in[i] = (i < Tc) ? Xc[i * F] : make_float2(0.f, 0.f);
     }
-    for (long long p0 = 0; p0 < P; p0 += kFirTile) StreamSteps<0>::run(acc, win, ring_c, Hc, F, R, head, p0, P);
+    const RingFrames src = {ring_c, F, R, head};
+    for (long long p0 = 0; p0 < P; p0 += kFirTile)
+      FirSteps<RingFrames, false, 0>::run(acc, win, src, Hc, F, 0, p0, P, false);
     float2* Yc = Y + r * Tc * F + f;
 #pragma unroll
     for (int i = 0; i < kFirTile; ++i)

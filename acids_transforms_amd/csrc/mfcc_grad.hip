@@ -157,8 +157,8 @@ int launch_mfcc_backward(const MfccBwdParams& p, hipStream_t stream) {
       band_tab_floats(band_cols_floats(p.t) + (dct ? band_cols_floats(p.f) + (long long)p.C * p.N : 0));
   const long long tiles_per_clip = (p.T + kMfccTile - 1) / kMfccTile, tiles = p.B * tiles_per_clip;
   auto run = [&](auto kernel, long long tab_floats) {   // four waves on a tile at a time
-    return band_launch(kernel, 4, sizeof(float) * tab_floats + g_bytes + 4 * per_wave, tiles, stream, p, gs, g_floats,
-                       k_pad, n_pad, (int)tab_floats, tiles_per_clip, tiles);
+    return persistent_launch(kernel, 64 * 4, sizeof(float) * tab_floats + g_bytes + 4 * per_wave, tiles, stream, p, gs,
+                             g_floats, k_pad, n_pad, (int)tab_floats, tiles_per_clip, tiles);
   };
   if (sizeof(float) * tab + g_bytes + 4 * per_wave <= kBandLdsBudget) {
     if (p.K <= 9 * 64)   // n_fft <= 1024

@@ -44,6 +44,8 @@
 #include <stdint.h>
 
 #include "../../include/acids_hip.h"
+#include "persistent_launch.h"
+#include "stream_source.h"
 
 namespace at_hip {
 
@@ -160,10 +162,8 @@ __global__ __launch_bounds__(kPqThreads) void pqmf_analysis_kernel(const float* 
     }
     if (ST && st.state_out && t0 + TB >= T) {       // the row's last tile: the last H samples of [state | chunk]
       float* so = st.state_out + row * st.H;
-      for (int i = threadIdx.x; i < st.H; i += kPqThreads) {
-        const long long s = L - st.H + i;
-        so[i] = s >= 0 ? xr[s] : state ? sw[s - s0] : 0.f;
-      }
+      const StreamSource src = {state ? state + row * st.H : nullptr, xr, L, st.H};
+      for (int i = threadIdx.x; i < st.H; i += kPqThreads) so[i] = src.tail(i);
     }
     __syncthreads();
     // fold: item = (r, parity of t, group of four same-parity blocks)
@@ -276,8 +276,8 @@ __global__ __launch_bounds__(kPqThreads) void pqmf_synthesis_kernel(const float*
       float* so = st.state_out + row * M * st.H;
       for (int i = threadIdx.x; i < M * st.H; i += kPqThreads) {
         const int kb = i / st.H;
-        const long long tb = T - st.H + (i - kb * st.H);
-        so[i] = tb >= 0 ? yr[(long long)kb * T + tb] : state ? sr[kb * st.H + (tb - tlo)] : 0.f;
+        const StreamSource src = {state ? state + (row * M + kb) * st.H : nullptr, yr + (long long)kb * T, T, st.H};
+        so[i] = src.tail(i - kb * st.H);
       }
     }
     __syncthreads();
@@ -351,55 +351,44 @@ static int pq_check(const void* in, int64_t rows, int64_t L, const void* proto, 
   return AT_OK;
 }
 
-// persistent workgroups: as many as the chip holds at once, at most one per tile
-template <typename Kernel>
-static int pq_launch(Kernel kernel, size_t lds, const float* in, int64_t rows, int64_t L, const float* proto,
-                     const float* mod, float scale, float* out, const PqPlan& p, const PqStream& st, hipStream_t stream) {
+// Persistent workgroups, at most one per tile.  `pick` chooses the kernel: it is handed `run` and calls run(kernel).
+template <typename Pick>
+static int pq_tiles(size_t lds, const float* in, int64_t rows, int64_t L, const float* proto, const float* mod, float scale,
+                    float* out, const PqPlan& p, const PqStream& st, hipStream_t stream, Pick pick) {
   if (lds > kPqLdsBytes) return AT_EUNSUPPORTED;
-  const void* fn = (const void*)kernel;
-  if (lds > 64 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-    (void)hipGetLastError();
-    return AT_ELAUNCH;
-  }
-  int per_cu = 0, cus = 0, dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kPqThreads, lds) != hipSuccess) {
-    (void)hipGetLastError();
-    return AT_ELAUNCH;
-  }
   const long long T = L / p.M;
   const long long tiles = (T + p.TB - 1) / p.TB;
   if (rows > 0x7fffffffffffffffLL / tiles) return AT_EUNSUPPORTED;
   const long long units = (long long)rows * tiles;
-  long long blocks = (long long)(per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 1);
-  if (blocks > units) blocks = units;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(kPqThreads), lds, stream, in, (long long)L, T, tiles, units,
-                     proto, mod, scale, out, p, st);
-  return hipGetLastError() == hipSuccess ? AT_OK : AT_ELAUNCH;
+  return pick([&](auto kernel) {
+    return persistent_launch(kernel, kPqThreads, lds, units, stream, in, (long long)L, T, tiles, units, proto, mod, scale,
+                             out, p, st);
+  });
 }
 
 // the kernel of a band count: a specialisation for the usual counts, the general one otherwise -- same sums, same bits
-#define PQ_DISPATCH(kernel, lds)                                                                      \
-  switch (n_band) {                                                                                   \
-    case 4: return pq_launch(kernel<4, ST>, lds, in, rows, L, proto, mod, scale, out, p, st, s);           \
-    case 8: return pq_launch(kernel<8, ST>, lds, in, rows, L, proto, mod, scale, out, p, st, s);           \
-    case 16: return pq_launch(kernel<16, ST>, lds, in, rows, L, proto, mod, scale, out, p, st, s);         \
-    case 32: return pq_launch(kernel<32, ST>, lds, in, rows, L, proto, mod, scale, out, p, st, s);         \
-    case 64: return pq_launch(kernel<64, ST>, lds, in, rows, L, proto, mod, scale, out, p, st, s);         \
-    default: return pq_launch(kernel<0, ST>, lds, in, rows, L, proto, mod, scale, out, p, st, s);          \
+#define PQ_DISPATCH(kernel)              \
+  switch (n_band) {                      \
+    case 4: return run(kernel<4, ST>);   \
+    case 8: return run(kernel<8, ST>);   \
+    case 16: return run(kernel<16, ST>); \
+    case 32: return run(kernel<32, ST>); \
+    case 64: return run(kernel<64, ST>); \
+    default: return run(kernel<0, ST>);  \
   }
 
 template <bool ST>
 static int pq_analysis(const float* in, int64_t rows, int64_t L, const float* proto, const float* mod, float scale,
                        float* out, int n_band, const PqPlan& p, const PqStream& st, hipStream_t s) {
-  PQ_DISPATCH(pqmf_analysis_kernel, p.lds_analysis)
+  return pq_tiles(p.lds_analysis, in, rows, L, proto, mod, scale, out, p, st, s,
+                  [&](auto run) { PQ_DISPATCH(pqmf_analysis_kernel) });
 }
 
 template <bool ST>
 static int pq_synthesis(const float* in, int64_t rows, int64_t L, const float* proto, const float* mod, float scale,
                         float* out, int n_band, const PqPlan& p, const PqStream& st, hipStream_t s) {
-  PQ_DISPATCH(pqmf_synthesis_kernel, p.lds_synthesis)
+  return pq_tiles(p.lds_synthesis, in, rows, L, proto, mod, scale, out, p, st, s,
+                  [&](auto run) { PQ_DISPATCH(pqmf_synthesis_kernel) });
 }
 #undef PQ_DISPATCH
 

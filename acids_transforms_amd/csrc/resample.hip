@@ -9,56 +9,36 @@
 // builds in float64 (utils/audio_io.py), rounded to float32.  One thread per output sample; the filter bank and
 // the input window of a block of outputs sit in L1/L2 (h is at most a few hundred KB).
 //
-// Below it: the causal form of the same chain, reading its window from a carried state (utils.RealtimeResample), and the
-// adjoint of both, the transposed polyphase filter as a gather (autograd.ResampleFunction / ResampleStreamFunction).
+// The same kernel is the causal form of the chain, reading its window from a carried state (utils.RealtimeResample).  Below
+// it: the adjoint of both, the transposed polyphase filter as a gather (autograd.ResampleFunction / ResampleStreamFunction).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../../include/acids_hip.h"
+#include "persistent_launch.h"
+#include "stream_source.h"
 
 namespace at_hip {
 
-__global__ __launch_bounds__(256) void resample_sinc_kernel(const float* __restrict__ x, long long rows, long long L,
-                                                             int orig, int nw, int width, const float* __restrict__ h,
-                                                             long long out_len, float* __restrict__ out) {
-  const long long o = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+// The chain of both forms, over the source v = [state (H) | x (C) | zeros] of stream_source.h: the window of output block t
+// starts H places before the chunk's sample t orig,
+//     out[t new + j] = sum_k h[j][k] v[t orig + k],      k ascending, one fmaf each, from +0.f
+// Offline (ST false): no state, H = width, C = L and the caller's out_len -- v is xpad.  The state reads and the
+// workgroups that write one are compiled away.
+// The causal form (ST true; utils.RealtimeResample): with D = ceil(width / orig) blocks of delay and H = Ha = D orig + width
+// the sum is offline block t - D of the stream, with zeros before its start, and reads nothing behind the chunk (D orig >=
+// width).  The workgroups behind the output's write the next state, the last Ha samples of v, into a second buffer.
+template <bool ST>
+__global__ __launch_bounds__(256) void resample_sinc_kernel(const float* __restrict__ x, long long C,
+                                                             const float* __restrict__ state_in,
+                                                             float* __restrict__ state_out, int H, int orig, int nw,
+                                                             int width, const float* __restrict__ h, long long out_len,
+                                                             unsigned out_blocks, float* __restrict__ out) {
   const long long row = blockIdx.y;
-  if (o >= out_len) return;
-  const long long i = o / nw;
-  const int j = (int)(o - i * nw);
-  const int taps = 2 * width + orig;
-  const float* hj = h + (long long)j * taps;
-  const float* xr = x + row * L;
-  const long long first = i * orig - width;          // input index of tap 0
-  float acc = 0.f;
-  for (int k = 0; k < taps; ++k) {
-    const long long n = first + k;
-    const float v = (n >= 0 && n < L) ? xr[n] : 0.0f;
-    acc = fmaf(hj[k], v, acc);
-  }
-  out[row * out_len + o] = acc;
-}
-
-// ---- the causal form (utils.RealtimeResample) -------------------------------------------------------------------------
-// The forward chain with a generalised source.  With D = ceil(width / orig) blocks of delay and Ha = D orig + width, the
-// window of the chunk's output block t starts at v[t orig] of v = [state (Ha) | chunk (C)], so
-//     out[t new + j] = sum_k h[j][k] v[t orig + k]
-// is offline block t - D of the stream, with zeros before its start, and reads nothing behind the chunk (D orig >= width).
-// The workgroups behind the output's write the next state, the last Ha samples of v, into a second buffer.
-__global__ __launch_bounds__(256) void resample_sinc_stream_kernel(const float* __restrict__ x, long long C,
-                                                                    const float* __restrict__ state_in,
-                                                                    float* __restrict__ state_out, int Ha, int orig, int nw,
-                                                                    int width, const float* __restrict__ h, long long out_len,
-                                                                    unsigned out_blocks, float* __restrict__ out) {
-  const long long row = blockIdx.y;
-  const float* xr = x + row * C;
-  const float* sr = state_in ? state_in + row * Ha : nullptr;
-  if (blockIdx.x >= out_blocks) {
+  const StreamSource src = {ST && state_in ? state_in + row * H : nullptr, x + row * C, C, H};
+  if (ST && blockIdx.x >= out_blocks) {
     const int s = (int)(blockIdx.x - out_blocks) * 256 + (int)threadIdx.x;
-    if (s < Ha) {
-      const long long c = C - Ha + s;                  // place in the chunk; before it: place c + Ha of the state
-      state_out[row * Ha + s] = c >= 0 ? xr[c] : sr ? sr[c + Ha] : 0.0f;
-    }
+    if (s < H) state_out[row * H + s] = src.tail(s);
     return;
   }
   const long long o = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -67,14 +47,7 @@ __global__ __launch_bounds__(256) void resample_sinc_stream_kernel(const float* 
   const int j = (int)(o - i * nw);
   const int taps = 2 * width + orig;
   const float* hj = h + (long long)j * taps;
-  const long long first = i * orig - Ha;             // place in the chunk of tap 0
-  float acc = 0.f;
-  for (int k = 0; k < taps; ++k) {
-    const long long c = first + k;
-    const float v = c >= C ? 0.0f : c >= 0 ? xr[c] : sr ? sr[c + Ha] : 0.0f;
-    acc = fmaf(hj[k], v, acc);
-  }
-  out[row * out_len + o] = acc;
+  out[row * out_len + o] = src.dot(hj, taps, i * orig - H, 0.f);      // tap 0 reads place i orig - H of the chunk
 }
 
 // ---- the adjoint (autograd.ResampleFunction / ResampleStreamFunction) -------------------------------------------------
@@ -175,31 +148,6 @@ __global__ __launch_bounds__(kRbThreads) void resample_sinc_backward_kernel(cons
   }
 }
 
-template <bool BL, int NW>
-static int rb_launch(const float* g, int64_t rows, int64_t L, int64_t out_len, const float* h, float* gx, const RbPlan& p,
-                     hipStream_t stream) {
-  const void* fn = (const void*)resample_sinc_backward_kernel<BL, NW>;
-  if (p.lds > 64 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds) != hipSuccess) {
-    (void)hipGetLastError();
-    return AT_ELAUNCH;
-  }
-  int per_cu = 0, cus = 0, dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kRbThreads, p.lds) != hipSuccess) {
-    (void)hipGetLastError();
-    return AT_ELAUNCH;
-  }
-  const long long nblk = (L + p.orig - 1) / p.orig;
-  const long long tiles = (nblk + p.TB - 1) / p.TB;
-  const long long units = (long long)rows * tiles;          // rows <= 65535
-  long long blocks = (long long)(per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 1);
-  if (blocks > units) blocks = units;
-  hipLaunchKernelGGL((resample_sinc_backward_kernel<BL, NW>), dim3((unsigned)blocks), dim3(kRbThreads), p.lds, stream, g,
-                     (long long)L, (long long)out_len, tiles, units, h, gx, p);
-  return hipGetLastError() == hipSuccess ? AT_OK : AT_ELAUNCH;
-}
-
 }  // namespace at_hip
 
 using namespace at_hip;
@@ -227,13 +175,19 @@ int at_resample_sinc_backward(const float* g, int64_t rows, int64_t L, int orig,
   RbPlan p;
   const int rc = rb_plan(orig, new_, taps, lead, &p);
   if (rc != AT_OK) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  if (!p.bank_in_lds) return rb_launch<false, 0>(g, rows, L, out_len, filters, gx, p, s);
+  const long long nblk = (L + p.orig - 1) / p.orig;
+  const long long tiles = (nblk + p.TB - 1) / p.TB;
+  const long long units = (long long)rows * tiles;          // rows <= 65535
+  auto run = [&](auto kernel) {
+    return persistent_launch(kernel, kRbThreads, p.lds, units, (hipStream_t)stream, g, (long long)L, (long long)out_len,
+                             tiles, units, filters, gx, p);
+  };
+  if (!p.bank_in_lds) return run(resample_sinc_backward_kernel<false, 0>);
   switch (new_) {
-    case 1: return rb_launch<true, 1>(g, rows, L, out_len, filters, gx, p, s);
-    case 2: return rb_launch<true, 2>(g, rows, L, out_len, filters, gx, p, s);
-    case 3: return rb_launch<true, 3>(g, rows, L, out_len, filters, gx, p, s);
-    default: return rb_launch<true, 0>(g, rows, L, out_len, filters, gx, p, s);
+    case 1: return run(resample_sinc_backward_kernel<true, 1>);
+    case 2: return run(resample_sinc_backward_kernel<true, 2>);
+    case 3: return run(resample_sinc_backward_kernel<true, 3>);
+    default: return run(resample_sinc_backward_kernel<true, 0>);
   }
 }
 
@@ -249,7 +203,7 @@ int at_resample_sinc_stream(const float* x, int64_t rows, int64_t C, const float
   const long long out_len = C / orig * new_;
   const unsigned out_blocks = (unsigned)((out_len + 255) / 256);
   const unsigned state_blocks = state_out ? (unsigned)((Ha + 255) / 256) : 0u;
-  hipLaunchKernelGGL(resample_sinc_stream_kernel, dim3(out_blocks + state_blocks, (unsigned)rows), dim3(256), 0,
+  hipLaunchKernelGGL(resample_sinc_kernel<true>, dim3(out_blocks + state_blocks, (unsigned)rows), dim3(256), 0,
                      (hipStream_t)stream, x, (long long)C, state_in, state_out, Ha, orig, new_, width, filters, out_len,
                      out_blocks, out);
   return hipGetLastError() == hipSuccess ? AT_OK : AT_ELAUNCH;
@@ -261,9 +215,10 @@ int at_resample_sinc(const float* x, int64_t rows, int64_t L, int orig, int new_
   if (rows == 0 || out_len == 0) return AT_OK;
   if (!x || !filters || !out) return AT_EINVAL;
   if (rows > 65535) return AT_EUNSUPPORTED;
-  hipLaunchKernelGGL(resample_sinc_kernel, dim3((unsigned)((out_len + 255) / 256), (unsigned)rows), dim3(256), 0,
-                     (hipStream_t)stream, x, (long long)rows, (long long)L, orig, new_, width, filters,
-                     (long long)out_len, out);
+  const unsigned out_blocks = (unsigned)((out_len + 255) / 256);
+  hipLaunchKernelGGL(resample_sinc_kernel<false>, dim3(out_blocks, (unsigned)rows), dim3(256), 0, (hipStream_t)stream, x,
+                     (long long)L, (const float*)nullptr, (float*)nullptr, width, orig, new_, width, filters,
+                     (long long)out_len, out_blocks, out);
   return hipGetLastError() == hipSuccess ? AT_OK : AT_ELAUNCH;
 }
 

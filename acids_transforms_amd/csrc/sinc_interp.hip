@@ -27,6 +27,7 @@
 #include <stdint.h>
 
 #include "../../include/acids_hip.h"
+#include "persistent_launch.h"
 
 namespace at_hip {
 
@@ -128,30 +129,6 @@ __global__ __launch_bounds__(kSiThreads) void sinc_interp_kernel(const float* __
   }
 }
 
-template <bool TL>
-static int si_launch(const float* in, int64_t rows, int64_t in_len, const float* table, int64_t out_len, float* out,
-                     const SiPlan& p, hipStream_t stream) {
-  const void* fn = (const void*)sinc_interp_kernel<TL>;
-  if (p.lds > 64 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds) != hipSuccess) {
-    (void)hipGetLastError();
-    return AT_ELAUNCH;
-  }
-  int per_cu = 0, cus = 0, dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, kSiThreads, p.lds) != hipSuccess) {
-    (void)hipGetLastError();
-    return AT_ELAUNCH;
-  }
-  const long long tiles = (out_len + p.T - 1) / p.T;
-  const long long units = (long long)rows * tiles;
-  long long blocks = (long long)(per_cu > 0 ? per_cu : 1) * (cus > 0 ? cus : 1);
-  if (blocks > units) blocks = units;
-  hipLaunchKernelGGL((sinc_interp_kernel<TL>), dim3((unsigned)blocks), dim3(kSiThreads), p.lds, stream, in,
-                     (long long)in_len, table, (long long)out_len, tiles, units, out, p);
-  return hipGetLastError() == hipSuccess ? AT_OK : AT_ELAUNCH;
-}
-
 }  // namespace at_hip
 
 using namespace at_hip;
@@ -178,10 +155,14 @@ int at_sinc_interp(const float* in, int64_t rows, int64_t in_len, int a, int b, 
   SiPlan p;
   const int rc = si_plan(a, b, Qi, &p);
   if (rc != AT_OK) return rc;
-  if (rows > 0x7fffffffffffffffLL / ((out_len + p.T - 1) / p.T)) return AT_EUNSUPPORTED;
-  hipStream_t s = (hipStream_t)stream;
-  return p.table_in_lds ? si_launch<true>(in, rows, in_len, table, out_len, out, p, s)
-                        : si_launch<false>(in, rows, in_len, table, out_len, out, p, s);
+  const long long tiles = (out_len + p.T - 1) / p.T;
+  if (rows > 0x7fffffffffffffffLL / tiles) return AT_EUNSUPPORTED;
+  const long long units = (long long)rows * tiles;
+  auto run = [&](auto kernel) {
+    return persistent_launch(kernel, kSiThreads, p.lds, units, (hipStream_t)stream, in, (long long)in_len, table,
+                             (long long)out_len, tiles, units, out, p);
+  };
+  return p.table_in_lds ? run(sinc_interp_kernel<true>) : run(sinc_interp_kernel<false>);
 }
 
 }  // extern "C"

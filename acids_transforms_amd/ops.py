@@ -920,7 +920,8 @@ def pqmf_stream_sizes(n_band, taps):
     return D, D * M + P, D + P // M
 
 
-def _pqmf_state(state, shape, like):
+def _stream_state(state, shape, like):
+    """The carried float32 state of a streaming stage as its kernel reads it (None: zeros), on `like`'s device."""
     if state is None:
         return None
     require_device(like, state)
@@ -944,7 +945,7 @@ def pqmf_analysis_stream(x, state, proto, mod, scale=1.0, shift=None, want_state
     if C % M:
         raise ValueError("the chunk length %d is no multiple of n_band = %d" % (C, M))
     D, Ha, _ = pqmf_stream_sizes(M, N)
-    state = _pqmf_state(state, (rows, Ha), x)
+    state = _stream_state(state, (rows, Ha), x)
     y = torch.empty((rows, M, C // M), dtype=torch.float32, device=x.device)
     if rows == 0 or C == 0:
         return y, (state if want_state else None)
@@ -969,7 +970,7 @@ def pqmf_synthesis_stream(y, state, proto, mod, scale=1.0, shift=None, want_stat
     if bands != M:
         raise ValueError("the band axis holds %d bands, the bank has n_band = %d" % (bands, M))
     D, _, Hs = pqmf_stream_sizes(M, N)
-    state = _pqmf_state(state, (rows, M, Hs), y)
+    state = _stream_state(state, (rows, M, Hs), y)
     x = torch.empty((rows, M * c), dtype=torch.float32, device=y.device)
     if rows == 0 or c == 0:
         return x, (state if want_state else None)
@@ -1329,11 +1330,7 @@ def resample_sinc_stream(x, state, orig, new, width, filters, want_state=True):
     if C % orig:
         raise ValueError("the chunk length %d is no multiple of orig = %d" % (C, orig))
     _, Ha = resample_stream_sizes(orig, width)
-    if state is not None:
-        require_device(x, state)
-        state = _f32c(state)
-        assert tuple(state.shape) == (rows, Ha), "the carried state is %s, the stream needs %s" % (tuple(state.shape),
-                                                                                                   (rows, Ha))
+    state = _stream_state(state, (rows, Ha), x)
     y = torch.empty((rows, C // orig * new), dtype=torch.float32, device=x.device)
     if rows == 0 or C == 0:
         return y, (state if want_state else None)

@@ -34,6 +34,7 @@ from .. import ops
 from .._lib import device_scoped, require_device
 from ..autograd import FFTConvolveFunction, ImpulseResponseStreamFunction, wants_grad
 from .base import AudioTransform, InversionEnumType, NotInvertibleError
+from .carried import CarriedState
 
 __all__ = ["FFTConvolve", "Convolve", "ImpulseResponse", "RealtimeImpulseResponse", "fftconvolve"]
 
@@ -160,7 +161,7 @@ class ImpulseResponse(AudioTransform):
         assert y.shape == x.shape[:-1] + (n,) and time.shape == (2, 2)
 
 
-class RealtimeImpulseResponse(ImpulseResponse):
+class RealtimeImpulseResponse(CarriedState, ImpulseResponse):
     """ImpulseResponse over a stream.  `forward` takes the next (..., C) chunk, C a positive multiple of the block B
     (`block`: ops.fft_convolve_stream_plan; None is the offline rule, 128 and 256 by request), and returns (..., C): the
     outputs of any chunking concatenate to fftconvolve(x_all, ir, "full", block=B)[..., :L].  `latency` is 0.
@@ -191,6 +192,7 @@ class RealtimeImpulseResponse(ImpulseResponse):
         self._H = None                                           # ((device, ir._version, ir's address), H)
         self.register_buffer("input_buffer", torch.zeros(self.block))
         self.register_buffer("spectrum_ring", torch.zeros(self.ring_slots, self.block + 1, dtype=torch.complex64))
+        self._carries("input_buffer", "spectrum_ring")
 
     def _plan(self) -> None:
         self.block, self.partitions, self.ring_slots, self.max_frames = ops.fft_convolve_stream_plan(self.taps, self._block_arg)
@@ -205,22 +207,13 @@ class RealtimeImpulseResponse(ImpulseResponse):
     def set_extra_state(self, state) -> None:
         self.head = int(state["head"])
 
-    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
-        for k in ("input_buffer", "spectrum_ring"):              # any batch shape, as OverlapAdd's
-            if prefix + k in state_dict:
-                self._buffers[k] = torch.zeros_like(state_dict[prefix + k])
-        return super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
-
     def streaming(self, block: Optional[int] = None) -> "RealtimeImpulseResponse":
         return self
 
     def realtime(self):
         return self
 
-    def reset(self) -> None:
-        """Forget the stream: the state becomes zeros (of its current shape), head 0."""
-        self.input_buffer = torch.zeros_like(self.input_buffer)
-        self.spectrum_ring = torch.zeros_like(self.spectrum_ring)
+    def _reset_extra(self) -> None:
         self.head = 0
 
     def _filter_spectrum(self, ir: torch.Tensor) -> torch.Tensor:
@@ -245,25 +238,22 @@ class RealtimeImpulseResponse(ImpulseResponse):
         if rows == 0:                                            # nothing arrived: no launch, the state stays
             return torch.empty(x.shape, dtype=torch.float32, device=x.device)
         R, F = self.ring_slots, B + 1
-        tail, ring = self.input_buffer, self.spectrum_ring       # a new leading shape or device starts a new stream
-        if tuple(tail.shape) != lead + (B,) or tuple(ring.shape) != lead + (R, F) or tail.device != x.device \
-                or ring.device != x.device:
-            tail = torch.zeros(lead + (B,), dtype=torch.float32, device=x.device)
-            ring = torch.zeros(lead + (R, F), dtype=torch.complex64, device=x.device)
+        state = self._carried_rows(("input_buffer", "spectrum_ring"), lead, x)      # the two are one stream
+        if state is None:
+            state = [torch.zeros(rows, B, dtype=torch.float32, device=x.device),
+                     torch.zeros(rows, R, F, dtype=torch.complex64, device=x.device)]
             self.head = 0
-        if tail.dtype != torch.float32:                          # after module.double() / .half()
-            tail = tail.float()
-        ring = ring.contiguous().view(rows, R, F)                # a view: the kernel updates the module's ring in place
+        tail, ring = state                                       # the kernel updates the ring in place
         with torch.cuda.device(x.device):
             H = self._filter_spectrum(ir)
-            x2, tail2 = x.reshape(rows, C), tail.reshape(rows, B)
+            x2 = x.reshape(rows, C)
             if wants_grad(x) or wants_grad(ir):
-                y, new_tail = ImpulseResponseStreamFunction.apply(x2, ir, H, tail2, ring, self.head, B)
+                y, new_tail = ImpulseResponseStreamFunction.apply(x2, ir, H, tail, ring, self.head, B)
             else:
-                y, new_tail, _ = ops.fft_convolve_stream(x2, tail2, ring, self.head, H, B)
+                y, new_tail, _ = ops.fft_convolve_stream(x2, tail, ring, self.head, H, B)
         self.head = (self.head + C // B) % R
-        self.input_buffer = new_tail.detach().reshape(lead + (B,))
-        self.spectrum_ring = ring.view(lead + (R, F))
+        self._carry("input_buffer", new_tail, lead)
+        self._carry("spectrum_ring", ring, lead)
         return y.reshape(lead + (C,))
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:

@@ -35,6 +35,7 @@ import torch
 from .. import ops
 from ..autograd import SosFilterFunction, SosFilterStreamFunction, wants_grad
 from .base import AudioTransform, InversionEnumType, NotInvertibleError
+from .carried import CarriedState
 
 __all__ = ["SOSFilter", "RealtimeSOSFilter", "Preemphasis"]
 
@@ -143,7 +144,7 @@ class SOSFilter(AudioTransform):
             assert z.shape == x.shape and bool(torch.isfinite(z).all())
 
 
-class RealtimeSOSFilter(SOSFilter):
+class RealtimeSOSFilter(CarriedState, SOSFilter):
     """SOSFilter over a stream.  `forward` takes the next (..., C) chunk, any C >= 1, and returns (..., C); the sections'
     state after the chunk -- scipy's zf -- is carried in the float64 buffer `state` (lead..., n_sections, 2).  It is zeros
     on a new leading shape or device and after `reset()`, accepts any batch shape from a `state_dict`, and is taken back
@@ -160,25 +161,20 @@ class RealtimeSOSFilter(SOSFilter):
             raise ValueError("zero-phase filtering runs backwards over the whole signal: it has no streaming form")
         super().__init__(sos, False, sr)
         self.register_buffer("state", torch.zeros(self.n_sections, 2, dtype=torch.float64))
+        self._carries("state")
+
+    def _carried_tail(self, name: str) -> tuple:
+        return (self.n_sections, 2)                          # of the coefficients in use: a state_dict may bring others
 
     @property
     def latency(self) -> int:
         return 0
-
-    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
-        if prefix + "state" in state_dict:                   # any batch shape, as OverlapAdd's
-            self._buffers["state"] = torch.zeros_like(state_dict[prefix + "state"], dtype=torch.float64)
-        return super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
 
     def streaming(self) -> "RealtimeSOSFilter":
         return self
 
     def realtime(self):
         return self
-
-    def reset(self) -> None:
-        """Forget the stream: the state becomes zeros (of its current shape)."""
-        self.state = torch.zeros_like(self.state, dtype=torch.float64)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if x.ndim < 1:
@@ -189,14 +185,14 @@ class RealtimeSOSFilter(SOSFilter):
         if x.numel() == 0:                                   # nothing arrived: no launch, the state stays
             ops._no_fp64(x)
             return torch.empty(x.shape, dtype=torch.float32, device=x.device)
-        buf, zi = self.state, None                           # a new leading shape or device starts a new stream
-        if tuple(buf.shape) == lead + (self._co.n, 2) and buf.device == x.device:
-            zi = buf if buf.dtype == torch.float64 else buf.double()
+        (zi,) = self._carried_rows(("state",), lead, x) or (None,)
+        if zi is not None:
+            zi = zi.reshape(lead + (self._co.n, 2))          # ops.sos_filter takes x, and so the state, with its leading shape
         if wants_grad(x):
             y, zf = SosFilterStreamFunction.apply(x, zi, self._co)
         else:
             y, zf = ops.sos_filter(x, self._co, zi=zi, return_state=True)
-        self.state = zf.detach()
+        self._carry("state", zf, lead)
         return y
 
     def test_forward(self, x: torch.Tensor, time: Optional[torch.Tensor] = None):

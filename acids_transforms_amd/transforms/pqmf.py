@@ -37,7 +37,8 @@ blocks in each direction, with the filter state carried in two module buffers:
              the outputs concatenate to PQMF.invert(cat([zeros(..., M, D), y], -1))[..., :T M]
     state    `input_buffer` (lead..., Ha), the last Ha = D M + P input samples; `band_buffer` (lead..., M, Hs), the last
              Hs = D + floor(P / M) blocks of every band (input history, not an output tail: every output stays one
-             fmaf chain).  Zeros on a new leading batch shape or device and after `reset()`.
+             fmaf chain).  Zeros on a new leading batch shape or device and after `reset()`; float32 whatever a module
+             cast (`.double()`, `.half()`) made of the buffers -- the rule of transforms.carried.CarriedState.
 
 At the defaults (16 bands, 513 taps) D = 16, Ha = 512, Hs = 32: `analysis_delay` = `synthesis_delay` = 256 samples,
 `latency` = 512 = taps - 1 for the round trip.  The kernels are the offline ones with another staging (a tile's window
@@ -66,6 +67,7 @@ from .. import ops
 from .._lib import device_scoped, require_device
 from ..autograd import PqmfFunction, PqmfInvertFunction, PqmfStreamFunction, PqmfStreamInvertFunction, wants_grad
 from .base import AudioTransform
+from .carried import CarriedState
 
 __all__ = ["PQMF", "RealtimePQMF", "MIN_BANDS", "MAX_BANDS", "MAX_TAPS", "CUTOFF_GRID", "kaiser_prototype", "design_cutoff",
            "modulation_matrix"]
@@ -228,7 +230,7 @@ class PQMF(AudioTransform):
         return out.reshape(lead + (self.n_band * T,))
 
 
-class RealtimePQMF(PQMF):
+class RealtimePQMF(CarriedState, PQMF):
     """The causal PQMF with carried filter state (the module docstring): `forward` and `invert` take the next chunk of
     a stream and answer the offline bank delayed by `analysis_delay` / `synthesis_delay` samples."""
 
@@ -241,12 +243,7 @@ class RealtimePQMF(PQMF):
         self.delay_blocks, self._keep_in, self._keep_band = ops.pqmf_stream_sizes(self.n_band, self.taps)
         self.register_buffer("input_buffer", torch.zeros(self._keep_in))
         self.register_buffer("band_buffer", torch.zeros(self.n_band, self._keep_band))
-
-    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
-        for k in ("input_buffer", "band_buffer"):                 # any batch shape, as OverlapAdd's
-            if prefix + k in state_dict:
-                self._buffers[k] = torch.zeros_like(state_dict[prefix + k])
-        return super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+        self._carries("input_buffer", "band_buffer")
 
     @property
     def analysis_delay(self) -> int:
@@ -269,20 +266,8 @@ class RealtimePQMF(PQMF):
     def streaming(self) -> "RealtimePQMF":
         return self
 
-    def reset(self) -> None:
-        """Forget the stream: both states become zeros (of their current shape)."""
-        self.input_buffer = torch.zeros_like(self.input_buffer)
-        self.band_buffer = torch.zeros_like(self.band_buffer)
-
     def forward_with_time(self, x: torch.Tensor, time: torch.Tensor):
         return self.forward(x), time - self.analysis_delay / self.sr
-
-    def _state(self, buf: torch.Tensor, lead, tail, x: torch.Tensor):
-        """The carried state as the kernel reads it, (rows,) + tail, or None for zeros: a new leading batch shape or a
-        new device starts a new stream."""
-        if tuple(buf.shape) != tuple(lead) + tail or buf.device != x.device:
-            return None
-        return buf.reshape((math.prod(lead),) + tail)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if x.ndim < 1 or x.shape[-1] % self.n_band:
@@ -293,14 +278,14 @@ class RealtimePQMF(PQMF):
         lead, C = tuple(x.shape[:-1]), x.shape[-1]
         if x.numel() == 0:                                      # nothing arrived: no launch, the state stays
             return torch.empty(lead + (self.n_band, C // self.n_band), dtype=torch.float32, device=x.device)
-        state = self._state(self.input_buffer, lead, (self._keep_in,), x)
+        (state,) = self._carried_rows(("input_buffer",), lead, x) or (None,)      # forward and invert: separate streams
         proto, mod = self._tables(x)
         x2 = x.reshape(math.prod(lead), C)
         if wants_grad(x):
             y, new_state = PqmfStreamFunction.apply(x2, state, proto, mod)      # the state is a constant of the graph
         else:
             y, new_state = ops.pqmf_analysis_stream(x2, state, proto, mod, 1.0)
-        self.input_buffer = new_state.detach().reshape(lead + (self._keep_in,))
+        self._carry("input_buffer", new_state, lead)
         return y.reshape(lead + (self.n_band, C // self.n_band))
 
     def invert(self, x: torch.Tensor, inversion_mode: Union[str, None] = None, **kwargs) -> torch.Tensor:
@@ -312,13 +297,12 @@ class RealtimePQMF(PQMF):
         lead, c = tuple(x.shape[:-2]), x.shape[-1]
         if x.numel() == 0:
             return torch.empty(lead + (self.n_band * c,), dtype=torch.float32, device=x.device)
-        tail = (self.n_band, self._keep_band)
-        state = self._state(self.band_buffer, lead, tail, x)
+        (state,) = self._carried_rows(("band_buffer",), lead, x) or (None,)
         proto, mod = self._tables(x)
         y3 = x.reshape((math.prod(lead), self.n_band, c))
         if wants_grad(x):
             out, new_state = PqmfStreamInvertFunction.apply(y3, state, proto, mod)
         else:
             out, new_state = ops.pqmf_synthesis_stream(y3, state, proto, mod, float(self.n_band))
-        self.band_buffer = new_state.detach().reshape(lead + tail)
+        self._carry("band_buffer", new_state, lead)
         return out.reshape(lead + (self.n_band * c,))

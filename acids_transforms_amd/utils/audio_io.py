@@ -21,6 +21,7 @@ import torch
 from .. import ops
 from .._lib import device_scoped, require_device
 from ..autograd import ResampleDirectFunction, ResampleFunction, ResampleStreamFunction, wants_grad
+from ..transforms.carried import CarriedState
 
 __all__ = ["Resample", "RealtimeResample", "resample", "import_data", "load_wav"]
 
@@ -102,7 +103,7 @@ class Resample(torch.nn.Module):
         return rt
 
 
-class RealtimeResample(Resample):
+class RealtimeResample(CarriedState, Resample):
     """The converter made causal by a delay of D = ceil(width / orig) whole blocks, with the last Ha = D orig + width
     input samples carried in `input_buffer` (lead..., Ha).
 
@@ -112,7 +113,10 @@ class RealtimeResample(Resample):
     concatenate to Resample(cat([zeros(D orig), x], -1))[..., :L new / orig] -- for finite input to the bit: the kernel
     is the offline chain reading another source, and the offline call's zero padding behind the clip is never reached
     (D orig >= width).  The next state is written by the same launch into a second buffer that replaces the module's:
-    no torch.cat, one launch per call.  The state is zeros on a new leading batch shape or device and after `reset()`.
+    no torch.cat, one launch per call.  The state is zeros on a new leading batch shape or device and after `reset()`, and
+    float32 whatever a module cast (`.double()`, `.half()`) made of the buffer (transforms.carried.CarriedState).  The bank
+    is read as float32 too: exactly after `.double()`; after `.half()` it keeps the precision of the fp16 values the cast
+    left, as RealtimePQMF's tables do.
 
     `delay` is D orig input samples (`output_delay` = D new output samples), `ratio` = new / orig.
 
@@ -128,11 +132,7 @@ class RealtimeResample(Resample):
         super().__init__(orig_freq, new_freq, lowpass_filter_width, rolloff)
         self.delay_blocks, self._keep = (0, 0) if self.orig == self.new else ops.resample_stream_sizes(self.orig, self.width)
         self.register_buffer("input_buffer", torch.zeros(self._keep))
-
-    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
-        if prefix + "input_buffer" in state_dict:                 # any batch shape, as OverlapAdd's
-            self._buffers["input_buffer"] = torch.zeros_like(state_dict[prefix + "input_buffer"])
-        return super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+        self._carries("input_buffer")
 
     @property
     def delay(self) -> int:
@@ -151,10 +151,6 @@ class RealtimeResample(Resample):
     def streaming(self) -> "RealtimeResample":
         return self
 
-    def reset(self) -> None:
-        """Forget the stream: the state becomes zeros (of its current shape)."""
-        self.input_buffer = torch.zeros_like(self.input_buffer)
-
     def forward(self, waveform: torch.Tensor) -> torch.Tensor:
         if waveform.ndim < 1 or waveform.shape[-1] % self.orig:
             raise ValueError("RealtimeResample.forward takes a (..., C) chunk with C a multiple of orig = %d, got shape %s"
@@ -167,18 +163,14 @@ class RealtimeResample(Resample):
         out_c = C // self.orig * self.new
         if waveform.numel() == 0:                                 # nothing arrived: no launch, the state stays
             return torch.empty(lead + (out_c,), dtype=torch.float32, device=waveform.device)
-        rows = math.prod(lead)
-        buf = self.input_buffer
-        state = None                                              # a new leading shape or device starts a new stream
-        if tuple(buf.shape) == lead + (self._keep,) and buf.device == waveform.device:
-            state = buf.reshape(rows, self._keep)
-        bank = self.kernel.to(waveform.device)
-        x = waveform.reshape(rows, C)
+        (state,) = self._carried_rows(("input_buffer",), lead, waveform) or (None,)
+        bank = self.kernel.to(waveform.device, torch.float32)     # float32 again after module.double() / .half()
+        x = waveform.reshape(math.prod(lead), C)
         if wants_grad(waveform):
             y, new_state = ResampleStreamFunction.apply(x, state, bank, self.orig, self.new, self.width)
         else:
             y, new_state = ops.resample_sinc_stream(x, state, self.orig, self.new, self.width, bank)
-        self.input_buffer = new_state.detach().reshape(lead + (self._keep,))
+        self._carry("input_buffer", new_state, lead)
         return y if waveform.ndim == 2 else y.reshape(lead + (out_c,))
 
 

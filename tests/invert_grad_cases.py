@@ -1,5 +1,5 @@
 """The dispatch of the Magnitude.invert / Polar.invert backward (at_magnitude_invert_backward,
-csrc/invert_grad.hip: launch_magnitude_invert_backward, launch_maginv_form; csrc/band_cols.h: band_launch), restated for
+csrc/invert_grad.hip: launch_magnitude_invert_backward, launch_maginv_form; csrc/persistent_launch.h: persistent_launch), restated for
 the CPU, and the sweep of test_invert_grad_gpu.py that drives every path of it.
 
 test_invert_grad_cases_cpu.py checks that the sweep reaches every class named here, for both forms; the GPU file runs
@@ -43,7 +43,7 @@ def launch_plan(K, N, t_nnz, f_nnz=None, polar=False):
 
 
 def grid_blocks(rows, wpb, lds, cus=CUS):
-    """band_launch's grid: the workgroups the chip holds at once (bounded here by LDS and by the wave slots; the
+    """persistent_launch's grid: the workgroups the chip holds at once (bounded here by LDS and by the wave slots; the
     occupancy query may answer fewer when registers bind, which only adds trips), at most one per group of wpb rows."""
     per_cu = max(min(LDS_PER_CU // lds, THREADS_PER_CU // (64 * wpb)), 1)
     return min(per_cu * cus, -(-rows // wpb))

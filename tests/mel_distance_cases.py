@@ -2,7 +2,7 @@
 csrc/mel_distance.hip, float64 torch autograd of the stated expression on complex128 spectra (the module's float32
 bank cast to double), the float64 torch.stft chain, the plan rule of the two row kernels restated, and the case tables.
 The chunk rule, the STFT chain and the planted spectra are those of spectral_distance_cases.py; the grid and the row
-loop are those of invert_grad_cases.py (band_launch is one launcher)."""
+loop are those of invert_grad_cases.py (persistent_launch is one launcher)."""
 import numpy as np
 import torch
 

@@ -6,36 +6,22 @@ tests/band_plan_main.cpp is compiled with the host compiler of the ROCm toolchai
 anyway.  What goes into the plan -- the floats of the tables a launcher stages and the bytes of one wave's rows -- is
 formed here as each launcher forms it; everything compared is an integer.
 """
-import os
 import subprocess
 
 import pytest
 
 import grad_cases as G
+import host_program
 import invert_grad_cases as IG
 import mel_distance_cases as MD
 from acids_transforms_amd.utils.banded import bank_columns
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "acids_transforms_amd", "csrc")
 BUDGET = 160 * 1024
-
-
-def _host_compiler():
-    roots = [os.environ.get("ROCM_PATH"), os.environ.get("ROCM_HOME"), "/opt/rocm"]
-    for root in filter(None, roots):
-        for sub in ("llvm/bin/clang++", "lib/llvm/bin/clang++", "bin/amdclang++"):
-            if os.path.exists(os.path.join(root, sub)):
-                return os.path.join(root, sub)
-    pytest.fail("no host compiler of the ROCm toolchain found under %s" % [r for r in roots if r])
 
 
 @pytest.fixture(scope="module")
 def prog(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("band_plan") / "band_plan")
-    subprocess.run([_host_compiler(), "-std=c++17", "-O1", "-Wall", "-Werror", "-I", CSRC,
-                    os.path.join(ROOT, "tests", "band_plan_main.cpp"), "-o", exe], check=True)
-    return exe
+    return host_program.build("band_plan_main.cpp", str(tmp_path_factory.mktemp("band_plan") / "band_plan"))
 
 
 def _plans(prog, cases):
