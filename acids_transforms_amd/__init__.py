@@ -11,7 +11,7 @@ from .ops import allow_fp64_narrowing  # noqa: F401
 # .heapq; `misc` is transforms.misc there, imported last): same names here, plus the modules of the rows SURVEY 8f added
 from .utils import heapq  # noqa: F401,E402
 from .transforms import (base, raw, stft, dgt, norm, spectral_repr, mel, misc, oadd, phase_repr, channels,  # noqa: F401,E402
-                         sinebank, pqmf, stretch, filters, convolve)
+                         sinebank, pqmf, stretch, filters, convolve, loudness)
 from . import losses  # noqa: F401,E402  (not in the reference: the spectral distance a model is trained with)
 from .losses import MelSpectralDistance, SpectralDistance  # noqa: F401,E402
 

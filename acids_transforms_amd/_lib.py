@@ -21,6 +21,7 @@ c_i64 = ctypes.c_int64
 c_int = ctypes.c_int
 c_sz = ctypes.c_size_t
 c_flt = ctypes.c_float
+c_dbl = ctypes.c_double
 
 # name -> argtypes (restype is int unless listed in _RESTYPES)
 _SIGNATURES = {
@@ -59,6 +60,12 @@ _SIGNATURES = {
     "at_phase_vocoder_backward": [c_f, c_f, c_f, c_f, c_f, c_i64, c_i64, c_i64, c_i64, c_f, c_f],
     "at_sos_filter_plan": [c_i64, c_i64, c_int, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), ctypes.POINTER(c_int)],
     "at_sos_filter": [c_f, c_i64, c_i64, c_f, c_int, c_int, c_f, c_f, c_f, c_f],
+    "at_sos_hop_power_plan": [c_i64, c_i64, c_int, c_i64, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), ctypes.POINTER(c_int)],
+    "at_sos_hop_power": [c_f, c_i64, c_i64, c_f, c_int, c_i64, c_f, c_f],
+    "at_sos_filter_hop_scaled": [c_f, c_i64, c_i64, c_f, c_int, c_i64, c_f, c_f, c_f],
+    "at_loudness_gate": [c_f, c_i64, c_int, c_i64, c_i64, c_int, c_f, c_dbl, c_dbl, c_f, c_f, c_f, c_f],
+    "at_loudness_gate_backward": [c_f, c_f, c_f, c_i64, c_int, c_i64, c_i64, c_int, c_f, c_dbl, c_dbl, c_f, c_f],
+    "at_loudness_blocks_backward": [c_f, c_f, c_i64, c_int, c_i64, c_i64, c_int, c_f, c_f, c_f],
     "at_fft_convolve_plan": [c_i64, c_i64, c_int, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), ctypes.POINTER(c_i64),
                              ctypes.POINTER(c_int), ctypes.POINTER(c_i64)],
     "at_spectral_fir": [c_f, c_i64, c_f, c_i64, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_f, c_f],

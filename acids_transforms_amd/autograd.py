@@ -41,6 +41,11 @@ SosFilterFunction and SosFilterStreamFunction are transforms.SOSFilter's and Rea
 adjoint of a recursive filter with zero state is the same filter run backwards in time, so the backward is the forward
 kernel with its direction flag flipped; coefficients and carried state are constants of the graph, and neither saves a tensor.
 
+LoudnessFunction and LoudnessBlocksFunction are transforms.Loudness's (loudness.hip on the hop powers of sos_filter.hip):
+the gates are piecewise constant, hence constants of the graph, and the rest is a function of the hop powers, so the
+backward is a weight per hop, the K-weighted signal times it (recomputed, never stored) and the reverse filter.  They keep
+x, the (..., C, hops) powers and the three gating statistics per clip.
+
 FFTConvolveFunction is ops.fft_convolve's (fft_convolve.hip), the one Function here with two differentiable inputs that are
 both audio-like: it saves x and h and nothing else, and the backward (ops.fft_convolve_backward) rebuilds the spectra chunk
 by chunk and computes only the gradients that are asked for.
@@ -65,7 +70,7 @@ __all__ = ["wants_grad", "StftFunction", "IstftFunction", "IstftPolarFunction", 
            "SpectralDistanceFunction", "specdist_chunk_clips", "MelSpectralDistanceFunction", "meldist_sums",
            "meldist_loss", "PqmfFunction", "PqmfInvertFunction", "PqmfStreamFunction", "PqmfStreamInvertFunction",
            "ResampleFunction", "ResampleStreamFunction", "ResampleDirectFunction", "PhaseVocoderFunction",
-           "SosFilterFunction", "SosFilterStreamFunction", "FFTConvolveFunction", "ImpulseResponseStreamFunction"]
+           "SosFilterFunction", "SosFilterStreamFunction", "LoudnessFunction", "LoudnessBlocksFunction", "FFTConvolveFunction", "ImpulseResponseStreamFunction"]
 
 
 def wants_grad(x: torch.Tensor) -> bool:
@@ -645,6 +650,44 @@ class SosFilterStreamFunction(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, gy, _gstate):
         return ops.sos_filter(gy, ctx.sos, reverse=True).to(ctx.dtype), None, None
+
+
+class LoudnessFunction(torch.autograd.Function):
+    """ops.loudness(x, sr, channel_weights): x (..., C, L) -> (...,) LUFS.  The forward is the plain route, bit for bit.
+    Saves x, the hop powers and the gating statistics; the backward is ops.loudness_backward (three launches).  A clip that
+    reads -inf has an exactly zero gradient."""
+
+    @staticmethod
+    def forward(ctx, x, sr, channel_weights):
+        ctx.sr, ctx.weights = sr, channel_weights
+        lufs, power, stats = ops.loudness(x, sr, channel_weights, return_state=True)
+        ctx.save_for_backward(x, power, stats)
+        return lufs
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        x, power, stats = ctx.saved_tensors
+        return ops.loudness_backward(x, power, stats, g, ctx.sr, ctx.weights).reshape(x.shape).to(x.dtype), None, None
+
+
+class LoudnessBlocksFunction(torch.autograd.Function):
+    """ops.loudness_blocks(x, sr, hops_per_block, channel_weights): x (..., C, L) -> (..., nb) LUFS, ungated.  Saves x and the
+    hop powers; the backward is ops.loudness_blocks_backward.  Silent blocks (-inf) pass nothing back."""
+
+    @staticmethod
+    def forward(ctx, x, sr, hops_per_block, channel_weights):
+        ctx.sr, ctx.hb, ctx.weights = sr, hops_per_block, channel_weights
+        blocks, power = ops.loudness_blocks(x, sr, hops_per_block, channel_weights, return_state=True)
+        ctx.save_for_backward(x, power)
+        return blocks
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        x, power = ctx.saved_tensors
+        gx = ops.loudness_blocks_backward(x, power, g, ctx.sr, ctx.hb, ctx.weights)
+        return gx.reshape(x.shape).to(x.dtype), None, None, None
 
 
 class FFTConvolveFunction(torch.autograd.Function):

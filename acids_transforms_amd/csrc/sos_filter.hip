@@ -30,6 +30,24 @@
 // anchored at the row's last sample: bit for bit flip -> forward -> flip.  It is the adjoint of the forward filter with
 // zero state, so this one kernel is the forward, the backward and both halves of zero-phase filtering.
 //
+// The same walk has two more endings (MODE below), both forwards in time and from zero state, for a row cut into hops of
+// `hop` >= 16 samples, nh = L / hop of them whole (the samples past nh hop belong to no hop):
+//   hop power   nothing of y is written: the last section's DOUBLE output is squared before any rounding and summed into
+//               power[r][h], float64.  hop >= S, so a lane's samples touch at most two hops: a head sum and a tail sum, each a
+//               chain in sample order.  The lane below's tail joins the head (tail + head), a segmented Hillis-Steele scan
+//               keyed by the hop index adds the heads of a wave that share a hop, a hop that begins and ends inside one wave
+//               is stored by its last lane, and lane 0 of the workgroup chains what is left -- per wave: the piece of the hop
+//               that came in, the piece of the hop that goes out, the last lane's tail -- onto the open hop it carries from
+//               tile to tile in registers; it does so behind the NEXT tile's first barrier (the ending has none of its own),
+//               and behind one more at the row's end.  The tiling is anchored at sample 0, so which lanes, waves and tiles a hop meets
+//               is a function of (hop, h): power[r][h] is a function of (sos, L, hop, h) and row r's samples alone.  No
+//               atomics; sums are selected, never masked by a multiply, so a NaN at sample n leaves the hops before n / hop
+//               as they were; zeros give +0.
+//   hop scaled  u[r][n] = (float)(w[r][n / hop] y[n]) with w (rows, nh) float64, +0 for n >= nh hop: the backward of a
+//               function of the hop powers, before the reverse filter.
+// The hop index of a lane's first sample comes from one 32-bit division per tile (the tile's own offset into its first hop
+// is carried along by additions); there is no division per sample.
+//
 // No workgroup ever waits for another one.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -49,6 +67,16 @@ constexpr int kSosMaxSections = 16;
 constexpr int kSosMaxGrid = 2048;                        // persistent workgroups: rows past the grid are walked in turn
 // a section's table of 2 x 2 matrices in LDS: (A^S)^0 .. (A^S)^64
 constexpr int kSosEntries = 65;
+// how a tile leaves: y as float; its squares summed per hop in double; y times a per-hop weight as float
+constexpr int kSosFilter = 0, kSosHopPower = 1, kSosHopScaled = 2;
+constexpr int kSosMinHop = kSosPerLane;                  // a lane's samples touch at most two hops
+
+struct SosHop {
+  int hop;                                               // samples per hop
+  long long nh;                                          // whole hops in a row: L / hop
+  const double* w;                                       // hop scaled: (rows, nh)
+  double* power;                                         // hop power: (rows, nh)
+};
 
 struct SosCoef {
   double c[kSosMaxSections][5];                          // b0 b1 b2 a1 a2
@@ -96,15 +124,20 @@ __device__ __forceinline__ int sos_slot(int q, int tid) {
   return (tid + tid / kSosPerLane) + q * (kSosLanes + kSosLanes / kSosPerLane);
 }
 
-template <bool REV>
+template <bool REV, int MODE>
 __global__ __launch_bounds__(kSosLanes) void sos_filter_kernel(const float* __restrict__ x, float* __restrict__ y,
                                                                const double* __restrict__ zi, double* __restrict__ zf,
-                                                               long long rows, long long L, SosCoef co, int n) {
+                                                               long long rows, long long L, SosCoef co, int n, SosHop hp) {
+  static_assert(MODE == kSosFilter || !REV, "the hop endings run forwards in time");
   extern __shared__ double sos_tab[];                    // n x kSosEntries matrices
   __shared__ float stage[kSosLanes * kSosStride];
   __shared__ double wtot[kSosMaxSections][kSosWaves][2];
   __shared__ double carry[2][kSosMaxSections][2];        // the tile's incoming state, and the next tile's
   __shared__ double aside[kSosPerLane];                  // one lane's: see `owner`
+  // hop power: what each wave hands to lane 0 of the workgroup -- the sums of the hops of its first and of its last lane,
+  // its last lane's tail, and those two hop indices (counted from the tile's first hop) with the tail's flag
+  __shared__ double hop_sum[MODE == kSosHopPower ? kSosWaves : 1][3];
+  __shared__ unsigned hop_idx[MODE == kSosHopPower ? kSosWaves : 1][3];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 
   // (A^S)^l for l = 0 .. 64 and every section: A^S by four squarings, then lane l raises it to its own power, bit by bit
@@ -149,16 +182,89 @@ __global__ __launch_bounds__(kSosLanes) void sos_filter_kernel(const float* __re
     };
     request(0);
     int par = 0;
+    // the hop endings: the tile's first sample lies in hop hop_base, hop_off samples after that hop's first one; lane 0
+    // of the workgroup carries the hop that is still open, open_hop, and what it has of its sum
+    long long hop_base = 0, open_hop = 0, handed_hop = 0;
+    unsigned hop_off = 0;
+    double open_sum = 0.0;
+    // hop power, lane 0 of the workgroup: what the waves handed over for the tile whose first hop is handed_hop goes onto
+    // the open hop, wave by wave -- the piece of the hop that came into the wave, the hop that leaves it, its last lane's
+    // tail -- and a hop is stored when the next one opens (and the open one at the row's end).  All twelve cells are read
+    // first; the tile after has passed one barrier by then and rewrites them only behind another.
+    auto chain = [&](bool row_ends) {
+      double sum[kSosWaves][3];
+      unsigned idx[kSosWaves][3];
+#pragma unroll
+      for (int w = 0; w < kSosWaves; ++w)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+          sum[w][j] = hop_sum[w][j];
+          idx[w][j] = hop_idx[w][j];
+        }
+      double* pr = hp.power + r * hp.nh;
+      auto close = [&]() {
+        if (open_hop < hp.nh) pr[open_hop] = open_sum;
+      };
+#pragma unroll
+      for (int w = 0; w < kSosWaves; ++w) {
+        const long long h = handed_hop + idx[w][0];
+        if (h == open_hop) {
+          open_sum = open_sum + sum[w][0];
+        } else {                                         // the wave begins where a hop begins
+          close();
+          open_sum = sum[w][0];
+          open_hop = h;
+        }
+        if (idx[w][1] != idx[w][0]) {
+          close();
+          open_sum = sum[w][1];
+          open_hop = handed_hop + idx[w][1];
+        }
+        if (idx[w][2]) {
+          close();
+          open_sum = sum[w][2];
+          ++open_hop;
+        }
+      }
+      if (row_ends) close();
+    };
     auto tile = [&](auto tail, long long t0) {
       constexpr bool TAIL = decltype(tail)::value;       // the row's last tile: partial stores, and the final state
       const int rem = TAIL ? (int)(L - t0) : kSosTile;   // 1 .. kSosTile
 #pragma unroll
       for (int q = 0; q < kSosPerLane; ++q) stage[sos_slot(q, tid)] = pf[q];
       __syncthreads();                                   // (also: the tables, and carry[0] at a row's first tile)
+      if constexpr (MODE == kSosHopPower) {
+        if (t0 > 0 && tid == 0) chain(false);            // the tile before's hand-over, behind this tile's first barrier
+      }
       double v[kSosPerLane];
 #pragma unroll
       for (int i = 0; i < kSosPerLane; ++i) v[i] = (double)stage[tid * kSosStride + i];
       if (!TAIL) request(t0 + kSosTile);
+      // where the lane's samples fall: its first one in hop hop_base + hr, the first `cut` of them (1 .. S) in that hop and
+      // the rest in the next, and only the first `live` (0 .. S) inside a whole hop.  hop < 2^31, so `at` < 2^31 + tile.
+      unsigned hr = 0;
+      int cut = kSosPerLane, live = kSosPerLane;
+      double w0 = 0.0, w1 = 0.0;
+      const long long tile_hop = hop_base;
+      if constexpr (MODE != kSosFilter) {
+        const unsigned at = hop_off + (unsigned)(tid * kSosPerLane);
+        hr = at / (unsigned)hp.hop;
+        const long long ends = (long long)(hr + 1) * hp.hop - at, left = hp.nh * hp.hop - (t0 + tid * kSosPerLane);
+        cut = ends < kSosPerLane ? (int)ends : kSosPerLane;
+        live = left < 0 ? 0 : left < kSosPerLane ? (int)left : kSosPerLane;
+        if constexpr (MODE == kSosHopScaled) {
+          const long long h = tile_hop + hr;
+          if (h < hp.nh) w0 = hp.w[r * hp.nh + h];
+          if (h + 1 < hp.nh) w1 = hp.w[r * hp.nh + h + 1];
+        }
+        hop_base += kSosTile / hp.hop;                   // the next tile's first sample, by additions
+        hop_off += (unsigned)(kSosTile % hp.hop);
+        if (hop_off >= (unsigned)hp.hop) {
+          hop_off -= (unsigned)hp.hop;
+          ++hop_base;
+        }
+      }
       // the lane of the row's last sample hands out the final state: it keeps each section's input to its cnt samples
       // aside and, once it knows its s_in, runs the recurrence itself over them
       const bool owner = TAIL && zf && tid == (rem - 1) / kSosPerLane;
@@ -236,6 +342,54 @@ __global__ __launch_bounds__(kSosLanes) void sos_filter_kernel(const float* __re
           s0 = t;
         }
       }
+      if constexpr (MODE == kSosHopPower) {
+        double head = 0.0, rest = 0.0;                   // the squares in the lane's first hop, and in the next
+        if (__all(cut == kSosPerLane && live == kSosPerLane)) {          // the same sums without the selects
+#pragma unroll
+          for (int i = 0; i < kSosPerLane; ++i) head = head + v[i] * v[i];
+        } else {
+#pragma unroll
+          for (int i = 0; i < kSosPerLane; ++i) {
+            const double sq = v[i] * v[i];
+            head = head + (i < cut && i < live ? sq : 0.0);
+            rest = rest + (i >= cut && i < live ? sq : 0.0);
+          }
+        }
+        const bool has_rest = cut < kSosPerLane;
+        // (shuffles first, conditions after: a shuffle under `lane == 0 ||` would leave lane 0 out, and lane 1 reads it)
+        const double below = __shfl_up(rest, 1);
+        const int below_has = __shfl_up((int)has_rest, 1);
+        const unsigned hr_below = __shfl_up(hr, 1);
+        const bool opens = lane == 0 || hr_below != hr;                  // the first lane of its hop in this wave
+        const unsigned long long heads = __ballot(opens);
+        // hop indices ascend along the wave, so the lanes of a hop are a run: from `first` up to the lane below the next head
+        const int first = 63 - __clzll((long long)(heads & (~0ull >> (63 - lane))));
+        double c = lane > 0 && below_has ? below + head : head;
+#pragma unroll
+        for (int d = 1; d < 64; d *= 2) {
+          const double u = __shfl_up(c, d);
+          if (lane - d >= first) c = u + c;
+        }
+        const unsigned hr_first = __shfl(hr, 0);         // (a shuffle: every lane takes part)
+        if (lane == 63 || ((heads >> (lane + 1)) & 1)) {   // the last lane of its hop in this wave
+          if (first == 0) hop_sum[wave][0] = c;
+          else if (lane == 63) hop_sum[wave][1] = c;
+          else if (tile_hop + hr < hp.nh) hp.power[r * hp.nh + tile_hop + hr] = c;        // begun and ended inside this wave
+        }
+        if (lane == 63) {
+          hop_sum[wave][2] = rest;
+          hop_idx[wave][0] = hr_first;
+          hop_idx[wave][1] = hr;
+          hop_idx[wave][2] = has_rest;
+        }
+        handed_hop = tile_hop;                           // lane 0 chains these behind the next barrier
+        par ^= 1;
+        return;
+      }
+      if constexpr (MODE == kSosHopScaled) {
+#pragma unroll
+        for (int i = 0; i < kSosPerLane; ++i) v[i] = i < live ? (i < cut ? w0 : w1) * v[i] : 0.0;
+      }
 #pragma unroll
       for (int i = 0; i < kSosPerLane; ++i) stage[tid * kSosStride + i] = (float)v[i] + 0.0f;     // -0 -> +0
       __syncthreads();
@@ -251,6 +405,10 @@ __global__ __launch_bounds__(kSosLanes) void sos_filter_kernel(const float* __re
     long long t0 = 0;
     for (; t0 + kSosTile < L; t0 += kSosTile) tile(std::false_type(), t0);
     tile(std::true_type(), t0);
+    if constexpr (MODE == kSosHopPower) {
+      __syncthreads();
+      if (tid == 0) chain(true);
+    }
   }
 }
 
@@ -259,6 +417,53 @@ static int sos_check_shape(int64_t rows, int64_t L, int n_sections) {
   if (n_sections > kSosMaxSections) return AT_EUNSUPPORTED;
   if (rows > 0 && L > INT64_MAX / 8 / rows) return AT_EUNSUPPORTED;        // 64-bit byte offsets
   return AT_OK;
+}
+
+// the sections as the kernels take them; false for a non-finite coefficient or a0 != 1
+static bool sos_pack(const double* sos, int n_sections, SosCoef& co) {
+  for (int k = 0; k < kSosMaxSections; ++k)
+    for (int j = 0; j < 5; ++j) co.c[k][j] = 0.0;
+  for (int k = 0; k < n_sections; ++k) {
+    const double* s = sos + k * 6;
+    for (int j = 0; j < 6; ++j)
+      if (!isfinite(s[j])) return false;
+    if (s[3] != 1.0) return false;
+    co.c[k][0] = s[0];
+    co.c[k][1] = s[1];
+    co.c[k][2] = s[2];
+    co.c[k][3] = s[4];
+    co.c[k][4] = s[5];
+  }
+  return true;
+}
+
+// what the two hop endings share: the checks, then the forward walk from zero state with the ending MODE
+template <int MODE>
+static int sos_hop_launch(const float* x, int64_t rows, int64_t L, const double* sos, int n_sections, int64_t hop,
+                          const double* w, double* power, float* u, void* stream) {
+  const int rc = sos_check_shape(rows, L, n_sections);
+  if (rc != AT_OK) return rc;
+  if (!sos || hop < 1) return AT_EINVAL;
+  if (hop < kSosMinHop) return AT_EUNSUPPORTED;
+  SosCoef co;
+  if (!sos_pack(sos, n_sections, co)) return AT_EINVAL;
+  const int64_t nh = L / hop;
+  if (rows == 0 || (MODE == kSosHopPower ? nh : L) == 0) return AT_OK;
+  if (!x || (MODE == kSosHopPower ? !power : !u || (nh > 0 && !w))) return AT_EINVAL;
+  if ((((uintptr_t)x | (uintptr_t)u) & 3) || (((uintptr_t)w | (uintptr_t)power) & 7)) return AT_EINVAL;
+  if (nh == 0)                                           // hop scaled, no whole hop: every sample is past the last one
+    return hipMemsetAsync(u, 0, (size_t)rows * L * sizeof(float), (hipStream_t)stream) == hipSuccess ? AT_OK : AT_ELAUNCH;
+  if (hop > INT32_MAX) return AT_EUNSUPPORTED;           // (L >= 2^31 then)
+  SosHop hp;
+  hp.hop = (int)hop;
+  hp.nh = nh;
+  hp.w = w;
+  hp.power = power;
+  const dim3 grid((unsigned)(rows < kSosMaxGrid ? rows : kSosMaxGrid)), block(kSosLanes);
+  const size_t lds = (size_t)n_sections * kSosEntries * 4 * sizeof(double);
+  hipLaunchKernelGGL((sos_filter_kernel<false, MODE>), grid, block, lds, (hipStream_t)stream, x, u, (const double*)nullptr,
+                     (double*)nullptr, (long long)rows, (long long)L, co, n_sections, hp);
+  return hipGetLastError() == hipSuccess ? AT_OK : AT_ELAUNCH;
 }
 
 }  // namespace at_hip
@@ -283,19 +488,7 @@ int at_sos_filter(const float* x, int64_t rows, int64_t L, const double* sos, in
   if (rc != AT_OK) return rc;
   if (!sos || (reverse != 0 && reverse != 1) || (reverse && (zi || zf))) return AT_EINVAL;
   SosCoef co;
-  for (int k = 0; k < kSosMaxSections; ++k)
-    for (int j = 0; j < 5; ++j) co.c[k][j] = 0.0;
-  for (int k = 0; k < n_sections; ++k) {
-    const double* s = sos + k * 6;
-    for (int j = 0; j < 6; ++j)
-      if (!isfinite(s[j])) return AT_EINVAL;
-    if (s[3] != 1.0) return AT_EINVAL;
-    co.c[k][0] = s[0];
-    co.c[k][1] = s[1];
-    co.c[k][2] = s[2];
-    co.c[k][3] = s[4];
-    co.c[k][4] = s[5];
-  }
+  if (!sos_pack(sos, n_sections, co)) return AT_EINVAL;
   if (((uintptr_t)zi | (uintptr_t)zf) & 7) return AT_EINVAL;
   if (zf && zf == zi) return AT_EINVAL;
   hipStream_t st = (hipStream_t)stream;
@@ -310,9 +503,33 @@ int at_sos_filter(const float* x, int64_t rows, int64_t L, const double* sos, in
   if (((uintptr_t)x | (uintptr_t)y) & 3) return AT_EINVAL;
   const dim3 grid((unsigned)(rows < kSosMaxGrid ? rows : kSosMaxGrid)), block(kSosLanes);
   const size_t lds = (size_t)n_sections * kSosEntries * 4 * sizeof(double);
-  if (reverse) hipLaunchKernelGGL(sos_filter_kernel<true>, grid, block, lds, st, x, y, zi, zf, (long long)rows, (long long)L, co, n_sections);
-  else hipLaunchKernelGGL(sos_filter_kernel<false>, grid, block, lds, st, x, y, zi, zf, (long long)rows, (long long)L, co, n_sections);
+  const SosHop none = {0, 0, nullptr, nullptr};
+  if (reverse) hipLaunchKernelGGL((sos_filter_kernel<true, kSosFilter>), grid, block, lds, st, x, y, zi, zf, (long long)rows, (long long)L, co, n_sections, none);
+  else hipLaunchKernelGGL((sos_filter_kernel<false, kSosFilter>), grid, block, lds, st, x, y, zi, zf, (long long)rows, (long long)L, co, n_sections, none);
   return hipGetLastError() == hipSuccess ? AT_OK : AT_ELAUNCH;
+}
+
+int at_sos_hop_power_plan(int64_t rows, int64_t L, int n_sections, int64_t hop, int64_t* tile, int64_t* per_lane,
+                          int* dispatch) {
+  if (!tile || !per_lane || !dispatch) return AT_EINVAL;
+  const int rc = sos_check_shape(rows, L, n_sections);
+  if (rc != AT_OK) return rc;
+  if (hop < 1) return AT_EINVAL;
+  if (hop < kSosMinHop || (hop > INT32_MAX && L / hop > 0)) return AT_EUNSUPPORTED;
+  *tile = kSosTile;
+  *per_lane = kSosPerLane;
+  *dispatch = 0;                                         // one dispatch, the filter's: a workgroup per row
+  return AT_OK;
+}
+
+int at_sos_hop_power(const float* x, int64_t rows, int64_t L, const double* sos, int n_sections, int64_t hop, double* power,
+                     void* stream) {
+  return sos_hop_launch<kSosHopPower>(x, rows, L, sos, n_sections, hop, nullptr, power, nullptr, stream);
+}
+
+int at_sos_filter_hop_scaled(const float* x, int64_t rows, int64_t L, const double* sos, int n_sections, int64_t hop,
+                             const double* w, float* u, void* stream) {
+  return sos_hop_launch<kSosHopScaled>(x, rows, L, sos, n_sections, hop, w, nullptr, u, stream);
 }
 
 }  // extern "C"

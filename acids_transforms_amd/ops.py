@@ -1618,6 +1618,210 @@ def sos_filter(x, sos, zi=None, reverse=False, return_state=False):
     return (y, zf) if return_state else y
 
 
+SOS_MIN_HOP = 16
+
+
+def sos_hop_power_plan(rows, L, n_sections, hop):
+    """(tile, per_lane, dispatch) of at_sos_hop_power at a shape: sos_filter_plan's answer -- it is the same walk -- after
+    the checks on hop (per_lane is also the smallest hop).  Reads no device state."""
+    tile, per_lane, dispatch = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int(0)
+    check(lib().at_sos_hop_power_plan(int(rows), int(L), int(n_sections), int(hop), ctypes.byref(tile), ctypes.byref(per_lane),
+                                      ctypes.byref(dispatch)), "at_sos_hop_power_plan")
+    return tile.value, per_lane.value, dispatch.value
+
+
+def _hop_rows(x, hop, what):
+    if x.ndim < 1:
+        raise ValueError("%s takes (..., L), got a scalar" % what)
+    hop = int(hop)
+    if hop < 1:
+        raise ValueError("hop must be >= 1, got %d" % hop)
+    return hop
+
+
+def sos_hop_power(x, sos, hop):
+    """The energy envelope of an SOS-filtered signal: x (..., L) float32 -> (..., L // hop) FLOAT64, entry h the sum over
+    samples [h hop, (h + 1) hop) of y^2 with y = sos_filter(x, sos) taken in double BEFORE it is rounded to float; y itself
+    is never written (include/acids_hip.h, at_sos_hop_power).  The samples past (L // hop) hop belong to no hop.  hop >=
+    SOS_MIN_HOP (smaller: the library's AT_EUNSUPPORTED).  The section [1, 0, 0, 1, 0, 0] gives the envelope of x itself
+    (divide by hop and take the root for an RMS envelope).  A row's bits do not depend on the batch."""
+    co = sos_coefficients(sos)
+    hop = _hop_rows(x, hop, "sos_hop_power")
+    require_device(x)
+    x = _f32c(x)
+    lead, L = tuple(x.shape[:-1]), x.shape[-1]
+    power = torch.empty(lead + (L // hop,), dtype=torch.float64, device=x.device)
+    check(lib().at_sos_hop_power(ptr(x), math.prod(lead), L, co.ptr, co.n, hop, ptr(power), stream_ptr()), "at_sos_hop_power")
+    return power
+
+
+def sos_filter_hop_scaled(x, sos, hop, w):
+    """x (..., L) float32, w (..., L // hop) FLOAT64 -> u (..., L) float32, u[n] = (float)(w[n // hop] y[n]) with y as in
+    sos_hop_power and +0 past the last whole hop: the gradient of a function of the hop powers with respect to y (its
+    gradient with respect to x is sos_filter(u, sos, reverse=True))."""
+    co = sos_coefficients(sos)
+    hop = _hop_rows(x, hop, "sos_filter_hop_scaled")
+    require_device(x, w)
+    x = _f32c(x)
+    lead, L = tuple(x.shape[:-1]), x.shape[-1]
+    if w.dtype != torch.float64:
+        raise AcidsHipError("w is %s: the hop weights are float64" % str(w.dtype).replace("torch.", ""))
+    if tuple(w.shape) != lead + (L // hop,):
+        raise ValueError("w is %s, x %s with hop %d needs %s" % (tuple(w.shape), tuple(x.shape), hop, lead + (L // hop,)))
+    w = w if w.is_contiguous() else w.contiguous()
+    u = torch.empty_like(x)
+    check(lib().at_sos_filter_hop_scaled(ptr(x), math.prod(lead), L, co.ptr, co.n, hop, ptr(w), ptr(u), stream_ptr()),
+          "at_sos_filter_hop_scaled")
+    return u
+
+
+# ----------------------------------------------------------------------------------------------
+# gated loudness, ITU-R BS.1770 / EBU R128 (loudness.hip on top of at_sos_hop_power)
+# ----------------------------------------------------------------------------------------------
+LOUDNESS_CHANNEL_WEIGHTS = (1.0, 1.0, 1.0, 1.41, 1.41)               # L R C Ls Rs
+LOUDNESS_ABS_THRESHOLD = 10.0 ** ((-70.0 + 0.691) / 10.0)            # -70 LUFS as a block power
+LOUDNESS_REL_RATIO = 0.1                                             # -10 LU
+LOUDNESS_BLOCK_HOPS = 4                                              # 400 ms blocks of 100 ms hops: 75 % overlap
+LOUDNESS_SHORT_TERM_HOPS = 30                                        # 3 s
+
+
+class _Loud:
+    """What loudness_plan has checked for one call: the K-weighting sections, the hop, the block, the channel weights on
+    the host, and the shape."""
+
+    def __init__(self, co, hop, hb, weights, lead, C, L, mono):
+        self.co, self.hop, self.hb, self.weights = co, hop, hb, weights
+        self.wptr = ctypes.c_void_p(weights.ctypes.data)
+        self.lead, self.C, self.L, self.mono = lead, C, L, mono
+        self.clips, self.nh = math.prod(lead), L // hop
+        self.nb = self.nh - hb + 1
+
+
+_K_WEIGHTING = {}
+
+
+def _k_weighting(sr):
+    from .utils.filter_design import k_weighting
+    key = float(sr)
+    if key not in _K_WEIGHTING:
+        _K_WEIGHTING[key] = sos_coefficients(k_weighting(key))       # ValueError below 3364 Hz
+    return _K_WEIGHTING[key]
+
+
+def loudness_plan(shape, sr, hops_per_block=LOUDNESS_BLOCK_HOPS, channel_weights=None):
+    """The checks of loudness and loudness_blocks on a shape (..., C, L) -- (L,) is one mono clip -- without a device.
+    ValueError: sr at which filter_design.k_weighting raises; hops_per_block < 1; C > 5 without explicit channel_weights
+    (BS.1770 names five weights; it is also what catches a (batch, L) tensor read as `batch` channels); weights that are
+    not C finite numbers; L < hops_per_block round(sr / 10), no block."""
+    import numpy as np
+    co = _k_weighting(sr)
+    hop, hb = int(round(float(sr) / 10.0)), int(hops_per_block)
+    if hb < 1:
+        raise ValueError("hops_per_block must be >= 1, got %d" % hb)
+    shape = tuple(shape)
+    if len(shape) < 1:
+        raise ValueError("loudness takes (..., C, L), got a scalar")
+    mono = len(shape) == 1
+    lead, C, L = (shape[:-2], shape[-2], shape[-1]) if not mono else ((), 1, shape[-1])
+    if channel_weights is None:
+        if C > len(LOUDNESS_CHANNEL_WEIGHTS):
+            raise ValueError("%d channels and no channel_weights: BS.1770 names weights for up to %d channels (input is "
+                             "(..., C, L): a (batch, L) tensor needs a channel axis, x[:, None])"
+                             % (C, len(LOUDNESS_CHANNEL_WEIGHTS)))
+        weights = np.array(LOUDNESS_CHANNEL_WEIGHTS[:C], dtype=np.float64)
+    else:
+        weights = np.array(channel_weights, dtype=np.float64, ndmin=1)
+        if weights.ndim != 1 or weights.shape[0] != C:
+            raise ValueError("channel_weights has shape %s, the input has %d channels" % (tuple(weights.shape), C))
+        if not np.isfinite(weights).all():
+            raise ValueError("channel_weights has non-finite entries")
+    if C < 1:
+        raise ValueError("loudness needs at least one channel, got shape %s" % (shape,))
+    if L < hb * hop:
+        raise ValueError("%d samples hold no block of %d hops of %d samples (sr %g)" % (L, hb, hop, sr))
+    return _Loud(co, hop, hb, np.ascontiguousarray(weights), tuple(lead), C, L, mono)
+
+
+def _loudness_power(x, plan):
+    _no_fp64(x)
+    require_device(x)
+    x = _f32c(x)
+    power = torch.empty(plan.lead + (plan.C, plan.nh), dtype=torch.float64, device=x.device)
+    check(lib().at_sos_hop_power(ptr(x), plan.clips * plan.C, plan.L, plan.co.ptr, plan.co.n, plan.hop, ptr(power),
+                                 stream_ptr()), "at_sos_hop_power")
+    return x, power
+
+
+def loudness(x, sr, channel_weights=None, return_state=False):
+    """Integrated loudness of ITU-R BS.1770-4 / EBU R128 in LUFS: x (..., C, L) float32 -> (...,) float32; (L,) is one mono
+    clip.  K-weighting (utils.filter_design.k_weighting(sr), the standard's table at 48 kHz) and the mean squares of the
+    100 ms hops in one launch (at_sos_hop_power: the filtered signal is never written), then 400 ms blocks with 75 %
+    overlap, the -70 LUFS absolute and the -10 LU relative gate in a second (at_loudness_gate).  -inf when no block passes
+    the absolute gate; NaN when the clip holds one.  channel_weights: C numbers, None for (1, 1, 1, 1.41, 1.41)[:C].
+    return_state=True: (lufs, power (..., C, L // hop) float64, stats (..., 3) float64 = Pabs, P, N2), what the backward
+    reads.  ValueError: see loudness_plan."""
+    plan = loudness_plan(x.shape, sr, LOUDNESS_BLOCK_HOPS, channel_weights)
+    x, power = _loudness_power(x, plan)
+    lufs = torch.empty(plan.lead, dtype=torch.float32, device=x.device)
+    stats = torch.empty(plan.lead + (3,), dtype=torch.float64, device=x.device)
+    check(lib().at_loudness_gate(ptr(power), plan.clips, plan.C, plan.nh, plan.hop, plan.hb, plan.wptr,
+                                 LOUDNESS_ABS_THRESHOLD, LOUDNESS_REL_RATIO, ptr(lufs), ptr(stats), None, stream_ptr()),
+          "at_loudness_gate")
+    return (lufs, power, stats) if return_state else lufs
+
+
+def loudness_blocks(x, sr, hops_per_block=LOUDNESS_BLOCK_HOPS, channel_weights=None, return_state=False):
+    """Ungated block loudness in LUFS: x (..., C, L) float32 -> (..., nb) float32 with nb = L // hop - hops_per_block + 1,
+    one value per 100 ms step.  hops_per_block = 4 is momentary loudness (400 ms), 30 short-term (3 s).  -inf for a silent
+    block.  return_state=True: (blocks, power).  ValueError: see loudness_plan."""
+    plan = loudness_plan(x.shape, sr, hops_per_block, channel_weights)
+    x, power = _loudness_power(x, plan)
+    blocks = torch.empty(plan.lead + (plan.nb,), dtype=torch.float32, device=x.device)
+    check(lib().at_loudness_gate(ptr(power), plan.clips, plan.C, plan.nh, plan.hop, plan.hb, plan.wptr, 0.0, 0.0, None, None,
+                                 ptr(blocks), stream_ptr()), "at_loudness_gate")
+    return (blocks, power) if return_state else blocks
+
+
+def _loudness_finish(x, plan, w):
+    """w (..., C, nh) -> gx: the weighted K-weighted signal, then the reverse K-weighting filter (its adjoint)."""
+    u = torch.empty_like(x)
+    check(lib().at_sos_filter_hop_scaled(ptr(x), plan.clips * plan.C, plan.L, plan.co.ptr, plan.co.n, plan.hop, ptr(w), ptr(u),
+                                         stream_ptr()), "at_sos_filter_hop_scaled")
+    return sos_filter(u, plan.co, reverse=True)
+
+
+def loudness_backward(x, power, stats, g, sr, channel_weights=None):
+    """The gradient of loudness with respect to x: g (...,) = dL/dlufs -> (..., C, L) float32, from what return_state
+    handed out.  Three launches: the hop weights (the gates recomputed from power and stats, constants of the graph),
+    the K-weighted signal times them, the reverse filter.  A clip that read -inf gets exactly zero."""
+    plan = loudness_plan(x.shape, sr, LOUDNESS_BLOCK_HOPS, channel_weights)
+    require_device(x, power, stats, g)
+    x, g = _f32c(x), _f32c(g)
+    if tuple(g.shape) != plan.lead or tuple(power.shape) != plan.lead + (plan.C, plan.nh) or \
+            tuple(stats.shape) != plan.lead + (3,) or power.dtype != torch.float64 or stats.dtype != torch.float64:
+        raise ValueError("loudness_backward: g, power and stats are not those of loudness(x, return_state=True)")
+    w = torch.empty_like(power)
+    check(lib().at_loudness_gate_backward(ptr(power.contiguous()), ptr(stats.contiguous()), ptr(g), plan.clips, plan.C,
+                                          plan.nh, plan.hop, plan.hb, plan.wptr, LOUDNESS_ABS_THRESHOLD, LOUDNESS_REL_RATIO,
+                                          ptr(w), stream_ptr()), "at_loudness_gate_backward")
+    return _loudness_finish(x, plan, w)
+
+
+def loudness_blocks_backward(x, power, g, sr, hops_per_block=LOUDNESS_BLOCK_HOPS, channel_weights=None):
+    """The gradient of loudness_blocks with respect to x: g (..., nb) -> (..., C, L) float32.  Silent blocks (-inf)
+    contribute nothing."""
+    plan = loudness_plan(x.shape, sr, hops_per_block, channel_weights)
+    require_device(x, power, g)
+    x, g = _f32c(x), _f32c(g)
+    if tuple(g.shape) != plan.lead + (plan.nb,) or tuple(power.shape) != plan.lead + (plan.C, plan.nh) or \
+            power.dtype != torch.float64:
+        raise ValueError("loudness_blocks_backward: g and power are not those of loudness_blocks(x, return_state=True)")
+    w = torch.empty_like(power)
+    check(lib().at_loudness_blocks_backward(ptr(power.contiguous()), ptr(g), plan.clips, plan.C, plan.nh, plan.hop, plan.hb,
+                                            plan.wptr, ptr(w), stream_ptr()), "at_loudness_blocks_backward")
+    return _loudness_finish(x, plan, w)
+
+
 # ----------------------------------------------------------------------------------------------
 # long-filter convolution (fft_convolve.hip): uniformly partitioned overlap-save
 # ----------------------------------------------------------------------------------------------

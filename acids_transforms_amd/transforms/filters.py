@@ -25,7 +25,7 @@ look-ahead: `latency` is 0.  The outputs of any chunking concatenate to the one-
 the bit: the kernel's tile grid starts at each chunk's first sample, so the lanes' partial sums meet in another order.
 
 Not built: gradients with respect to the coefficients, per-row or time-varying coefficients, bit-equal chunking, second-order
-gradients, a gated loudness measure on top of filter_design.k_weighting.
+gradients.  (The gated loudness measure on top of filter_design.k_weighting is transforms/loudness.py.)
 """
 import warnings
 from typing import Optional

@@ -15,7 +15,7 @@ R. Bristow-Johnson's Audio EQ Cookbook, restated: with w0 = 2 pi f / sr and alph
 
 `k_weighting(sr)` is the two-section pre-filter of ITU-R BS.1770 (a high shelf, then a high-pass), from the analogue
 prototypes behind the standard's 48 kHz table by the bilinear transform with K = tan(pi fc / sr); at 48 kHz it reproduces
-the printed coefficients.  A gated loudness measure on top of it is not built.
+the printed coefficients.  transforms.Loudness is the gated loudness measure on top of it.
 
 ValueError: f outside (0, sr / 2), Q <= 0, a non-finite argument.
 """

@@ -844,6 +844,58 @@ int at_sos_filter_plan(int64_t rows, int64_t L, int n_sections, int64_t *tile, i
 int at_sos_filter(const float *x, int64_t rows, int64_t L, const double *sos_host, int n_sections, int reverse,
                   const double *zi, double *zf, float *y, void *stream);
 
+/* The same walk with two other endings (sos_filter.hip), forwards in time from zero state, for rows cut into hops of `hop`
+ * samples: nh = L / hop whole hops, the samples past nh hop belong to none.
+ * at_sos_hop_power: power (rows, nh) float64, power[r][h] = the sum over hop h of y[n]^2, with y the last section's DOUBLE
+ * output, squared before any rounding; nothing of y is written.  The energy envelope of any SOS-filtered signal (one
+ * section 1 0 0 1 0 0: of the signal itself).  hop >= 16 = *per_lane, so that a lane's samples touch at most two hops; a
+ * hop that straddles lanes, waves or tiles is combined in one fixed order (a chain per lane, a segmented scan per wave, a
+ * chain over the waves that lane 0 carries from tile to tile): power[r][h] is a function of (sos, L, hop, h) and row r's
+ * samples alone -- no atomics, no workgroup waits for another, the batch and the grid do not enter.  Zeros give +0; a NaN at
+ * sample n leaves the hops before n / hop bit-identical and other rows untouched.  The plan routine answers as
+ * at_sos_filter_plan does, without a device.
+ * at_sos_filter_hop_scaled: u (rows, L) float32, u[r][n] = (float)(w[r][n / hop] y[n]) for n < nh hop and +0 after, w (rows,
+ * nh) float64: the gradient of a function of the hop powers with respect to y, ready for at_sos_filter(reverse = 1).
+ * AT_EINVAL: as at_sos_filter, and hop < 1, a null power, w (with nh > 0) or u, misalignment (4 bytes audio, 8 power and
+ * w).  AT_EUNSUPPORTED: more than 16 sections, hop < 16, hop >= 2^31 with nh > 0.  AT_OK without a kernel for rows == 0 and
+ * for nh == 0 (at_sos_filter_hop_scaled then clears u). */
+int at_sos_hop_power_plan(int64_t rows, int64_t L, int n_sections, int64_t hop, int64_t *tile, int64_t *per_lane,
+                          int *dispatch);
+int at_sos_hop_power(const float *x, int64_t rows, int64_t L, const double *sos_host, int n_sections, int64_t hop,
+                     double *power, void *stream);
+int at_sos_filter_hop_scaled(const float *x, int64_t rows, int64_t L, const double *sos_host, int n_sections, int64_t hop,
+                             const double *w, float *u, void *stream);
+
+/* ---- gated loudness (loudness.hip; ops.loudness, ops.loudness_blocks, transforms.Loudness) ------------------------- */
+/* ITU-R BS.1770 / EBU R128 gating of hop powers (restated; no reference counterpart).  power (clips, C, nh) float64 is
+ * at_sos_hop_power of the K-weighted channels, a hop has `hop` samples (100 ms), a block hb hops (4: momentary and the
+ * integrated measure; 30: short-term), nb = nh - hb + 1, weights_host C doubles ON THE HOST (by value to the kernel):
+ *   p_j = (sum over c ascending of G_c (power[c][j] + ... + power[c][j + hb - 1], ascending)) / (hb hop),
+ *   block_lufs[j] = (float)(-0.691 + 10 log10 p_j)   (clips, nb), ungated, -inf where p_j == 0; NULL: not wanted,
+ *   J1 = {j: p_j > abs_threshold}, Pabs = mean over J1, J2 = {j in J1: p_j > rel_ratio Pabs}, P = mean over J2, N2 = |J2|,
+ *   lufs = (float)(-0.691 + 10 log10 P)   (clips), -inf when J1 is empty;  stats (clips, 3) float64 = Pabs, P, N2.
+ * lufs == NULL skips the gates and writes block_lufs alone.  The gates compare powers in double with the thresholds given
+ * (no logarithm decides one), as !(p <= threshold): a NaN block passes, so a clip with a NaN reads NaN.  One workgroup per
+ * clip, persistent past the grid; a mean is 256 lane-strided chains in block order joined by a fixed halving tree, a function
+ * of nb alone: a clip's bits do not depend on the batch.
+ * at_loudness_gate_backward: g (clips) float32 = dL/dlufs -> w (clips, C, nh) float64 with dL/dy_c[n] = w[c][n / hop] y_c[n]:
+ *   w[c][h] = g (10 / ln 10) / (P N2) G_c (2 / (hb hop)) m[h],   m[h] = the blocks of J2 that cover hop h,
+ * the masks recomputed from power and stats; +0 is SELECTED where N2 == 0 or m[h] == 0 (a silent clip's gradient is exactly
+ * zero whatever g is).  at_loudness_blocks_backward: g_blocks (clips, nb) float32 = dL/dblock_lufs ->
+ *   w[c][h] = G_c (2 / (hb hop)) (sum over the blocks j that cover h, ascending, of g_j (10 / ln 10) / p_j),
+ * blocks with p_j == 0 contributing nothing.  The gates are piecewise constant: constants of the graph.  First order only.
+ * AT_EINVAL: negative sizes, C < 1, hop < 1, hb < 1, null weights_host, a non-finite weight, a negative or non-finite
+ * threshold, null pointers for what is to be read or written (lufs and block_lufs both NULL; lufs without stats),
+ * misalignment.  AT_EUNSUPPORTED: C > 32, hb > 4096.  AT_OK without a kernel when clips == 0 (backwards: or nh == 0); with
+ * nh < hb there is no block: lufs is -inf, stats zeros, w zeros. */
+int at_loudness_gate(const double *power, int64_t clips, int C, int64_t nh, int64_t hop, int hb, const double *weights_host,
+                     double abs_threshold, double rel_ratio, float *lufs, double *stats, float *block_lufs, void *stream);
+int at_loudness_gate_backward(const double *power, const double *stats, const float *g, int64_t clips, int C, int64_t nh,
+                              int64_t hop, int hb, const double *weights_host, double abs_threshold, double rel_ratio,
+                              double *w, void *stream);
+int at_loudness_blocks_backward(const double *power, const float *g_blocks, int64_t clips, int C, int64_t nh, int64_t hop,
+                                int hb, const double *weights_host, double *w, void *stream);
+
 /* ---- long-filter convolution (fft_convolve.hip; ops.fft_convolve, autograd.FFTConvolveFunction) -------------------- */
 /* Uniformly partitioned overlap-save convolution of a row of L samples with K taps (torchaudio.functional.fftconvolve,
  * restated; no reference counterpart): block B, n_fft N = 2 B, F = B + 1, M = L + K - 1, T = ceil(M / B) frames,
