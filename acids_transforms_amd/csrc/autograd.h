@@ -5,6 +5,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "../../include/acids_hip.h"     // the launchers return AT_OK or an AT_E* code
 #include "band_cols.h"
 
 namespace at_hip {

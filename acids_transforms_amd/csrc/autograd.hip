@@ -131,7 +131,7 @@ __global__ void adj_ola_fold_kernel(AdjOlaParams p, int vec4) {
 int launch_adj_window(const float* w, int n_fft, float scale, float* out, hipStream_t stream) {
   const int blocks = (n_fft + 255) / 256;
   hipLaunchKernelGGL(adj_window_kernel, dim3(blocks), dim3(256), 0, stream, w, n_fft, scale, out);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return hipGetLastError() == hipSuccess ? AT_OK : AT_ELAUNCH;
 }
 
 int launch_adj_ola_fold(const float* frames, const float2* G, const float* window, float* dx, long long B, long long T,
@@ -142,7 +142,7 @@ int launch_adj_ola_fold(const float* frames, const float2* G, const float* windo
   const long long bx = (L + 1023) / 1024;
   hipLaunchKernelGGL(adj_ola_fold_kernel, dim3((unsigned)bx, (unsigned)(B < 65535 ? B : 65535)), dim3(256), 0, stream, p,
                      vec4);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return hipGetLastError() == hipSuccess ? AT_OK : AT_ELAUNCH;
 }
 
 // ---- ISTFT adjoint ----------------------------------------------------------------------------------------------------
@@ -204,7 +204,7 @@ int launch_istft_adj_prep(const float* gy, const float* window, float* u, long l
   if (B <= 0 || P <= 0) return 0;
   hipLaunchKernelGGL(istft_adj_prep_kernel, dim3((unsigned)((P + 255) / 256), (unsigned)(B < kPrepClipRows ? B : kPrepClipRows)), dim3(256),
                      0, stream, gy, window, u, B, T, Ly, P, n_fft, hop);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return hipGetLastError() == hipSuccess ? AT_OK : AT_ELAUNCH;
 }
 
 int launch_istft_adj_finish(const float2* gX, const float* phase, void* out, long long rows, int n_fft, hipStream_t stream) {
@@ -216,7 +216,7 @@ int launch_istft_adj_finish(const float2* gX, const float* phase, void* out, lon
   } else {
     hipLaunchKernelGGL(istft_adj_halve_kernel, dim3(flat_grid(rows)), dim3(256), 0, stream, (float2*)out, rows, F, nyq);
   }
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return hipGetLastError() == hipSuccess ? AT_OK : AT_ELAUNCH;
 }
 
 // ---- Magnitude backward -----------------------------------------------------------------------------------------------
@@ -347,12 +347,12 @@ int launch_magnitude_backward(const MagBwdParams& p, hipStream_t stream) {
   if (p.rows == 0) return 0;
   if (!p.f.w) {
     hipLaunchKernelGGL(mag_bwd_pointwise_kernel, dim3(flat_grid(p.rows * p.K)), dim3(256), 0, stream, p);
-    return hipGetLastError() == hipSuccess ? 0 : -5;
+    return hipGetLastError() == hipSuccess ? AT_OK : AT_ELAUNCH;
   }
   const int k_pad = pad64(p.K), n_pad = pad64(p.N);
   const size_t per_wave = sizeof(float) * (size_t)(k_pad + n_pad);
   const BandPlan pl = band_plan(band_tab_floats(band_cols_floats(p.t) + band_cols_floats(p.f)), per_wave);
-  if (!pl.ok) return -2;
+  if (!pl.ok) return AT_EUNSUPPORTED;
   auto run = [&](auto kernel) { return band_launch_rows(kernel, pl, p.rows, stream, p, k_pad, n_pad, (int)pl.tab_floats); };
   if (!pl.tab_lds) return run(mag_bwd_banded_kernel<false, 0>);
   return p.K <= kBandKit * 64 ? run(mag_bwd_banded_kernel<true, kBandKit>) : run(mag_bwd_banded_kernel<true, 0>);

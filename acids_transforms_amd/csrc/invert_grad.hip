@@ -139,7 +139,7 @@ static int launch_maginv_form(const MagInvBwdParams& p, hipStream_t stream) {
   const size_t per_wave = sizeof(float) * (size_t)(POLAR ? n_pad + 2 * k_pad : n_pad);
   // tables: the transposed bank's and, polar, the bank's
   const BandPlan pl = band_plan(band_tab_floats(band_cols_floats(p.t) + (POLAR ? band_cols_floats(p.f) : 0)), per_wave);
-  if (!pl.ok) return -2;
+  if (!pl.ok) return AT_EUNSUPPORTED;
   auto run = [&](auto kernel) { return band_launch_rows(kernel, pl, p.rows, stream, p, k_pad, n_pad, (int)pl.tab_floats); };
   return pl.tab_lds ? run(maginv_bwd_banded_kernel<true, POLAR>) : run(maginv_bwd_banded_kernel<false, POLAR>);
 }
@@ -150,7 +150,7 @@ int launch_magnitude_invert_backward(const MagInvBwdParams& p, hipStream_t strea
     const long long total = p.rows * (p.K - p.pad_last);
     if (total < 1) return 0;
     hipLaunchKernelGGL(maginv_bwd_pointwise_kernel, dim3(flat_grid(total)), dim3(256), 0, stream, p);
-    return hipGetLastError() == hipSuccess ? 0 : -5;
+    return hipGetLastError() == hipSuccess ? AT_OK : AT_ELAUNCH;
   }
   return p.polar ? launch_maginv_form<true>(p, stream) : launch_maginv_form<false>(p, stream);
 }

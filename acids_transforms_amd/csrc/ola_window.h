@@ -139,7 +139,7 @@ inline int launch_istft_ola(void (*const (&kernels)[2][3])(POla), int n_fft, int
   if (B == 0 || T <= 1) return 0;
   const int slot = n_fft / 8;
   const int hs_log2 = hop == slot ? 0 : hop == 2 * slot ? 1 : hop == 4 * slot ? 2 : -1;
-  if (hs_log2 < 0) return -2;
+  if (hs_log2 < 0) return AT_EUNSUPPORTED;
   POla p = {X, mag, phase, window, env, tw, tw_n, y, B, T, 0, 0};
   const long long blocks = T - 1;                        // output hops per clip
   p.blocks_per_run = plan_ola_runs(B, blocks, 2048, 8);
@@ -147,7 +147,7 @@ inline int launch_istft_ola(void (*const (&kernels)[2][3])(POla), int n_fft, int
   const long long waves = B * p.runs_per_clip;
   const unsigned grid = (unsigned)((waves + waves_per_block - 1) / waves_per_block);
   hipLaunchKernelGGL(kernels[X == nullptr][hs_log2], dim3(grid), dim3(64 * waves_per_block), 0, stream, p);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return hipGetLastError() == hipSuccess ? AT_OK : AT_ELAUNCH;
 }
 
 }  // namespace at_hip

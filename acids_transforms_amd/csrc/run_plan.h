@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "../../include/acids_hip.h"
 #include "variants.h"
 
 namespace at_hip {
@@ -80,6 +81,53 @@ inline long long units_per_block(long long n, int waves) {
   long long upb = (n + max_blocks - 1) / max_blocks;
   upb = ((upb + waves - 1) / waves) * waves;
   return upb < waves ? waves : upb;
+}
+
+// What the frame-per-wave kernels of n_fft 2048 and 4096 take, forward and irfft*_frames (n_fft 512 counts pairs: P5).
+struct PFrames {
+  const float* x;        // forward: audio, clip b at x + b*clip_stride
+  const float* window;   // n_fft samples (analysis or synthesis)
+  const float2* tw;      // fft512 twiddle table (capi.hip)
+  const float2* tw_n;    // the size's own table (W2048^k; the n_fft-4096 block of the side table)
+  float2* X;             // (frames, n_fft / 2 + 1) complex64: forward output / inverse input
+  const float* mag;      // inverse, polar input
+  const float* phase;
+  float* phase_out;      // forward: optional angle output (frames, n_fft / 2 + 1)
+  float* y;              // inverse: (frames, n_fft) windowed time frames
+  long long L, clip_stride, T, total_frames, frames_per_block;
+  int hop, center;
+};
+
+// kernels[second] over p.total_frames frames, units_per_block of them per workgroup of `waves_per_block` waves
+inline int launch_frames(void (*const (&kernels)[2])(PFrames), bool second, int waves_per_block, PFrames p,
+                         hipStream_t stream) {
+  p.frames_per_block = units_per_block(p.total_frames, waves_per_block);
+  const long long blocks = (p.total_frames + p.frames_per_block - 1) / p.frames_per_block;
+  hipLaunchKernelGGL(kernels[second], dim3((unsigned)blocks), dim3(64 * waves_per_block), 0, stream, p);
+  return hipGetLastError() == hipSuccess ? AT_OK : AT_ELAUNCH;
+}
+
+// What the sliding-window forwards of n_fft 512, 2048 and 4096 take (row_stream.h): a wave walks one run of a clip.
+struct PRunFwd {
+  const float* x;
+  const float* window;
+  const float2* tw;      // fft512 twiddle table
+  const float2* tw_n;    // the size's own table
+  float2* X;
+  long long B, L, clip_stride, T, runs_per_clip, units_per_run;     // units: frames; frame pairs at n_fft 512
+};
+
+// The plan those three share: runs of at least 8 of the clip's `units`, one unit of overhead per run start, or the
+// forced length (tests); one wave per run.
+inline int launch_run_fwd(void (*kernel)(PRunFwd), int waves_per_block, long long units, PRunFwd p, hipStream_t stream) {
+  const long long slots = resident_waves(kernel, 64 * waves_per_block, 0);
+  p.units_per_run = plan_units_per_run(p.B, units, slots, 8, 1);
+  if (const long long v = forced_units_per_run(units)) p.units_per_run = v;
+  p.runs_per_clip = (units + p.units_per_run - 1) / p.units_per_run;
+  const long long waves = p.B * p.runs_per_clip;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((waves + waves_per_block - 1) / waves_per_block)), dim3(64 * waves_per_block), 0,
+                     stream, p);
+  return hipGetLastError() == hipSuccess ? AT_OK : AT_ELAUNCH;
 }
 
 // Run length of the fused overlap-add kernels, one wave per run of a clip's `units` (output hops; frame pairs at n_fft

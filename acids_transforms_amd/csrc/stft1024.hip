@@ -24,6 +24,7 @@
 #include "band_bank.h"
 #include "fft512.h"
 #include "fwd1024_forms.h"
+#include "row_stream.h"
 #include "run_plan.h"
 #include "stft_launch.h"
 #include "variants.h"
@@ -217,8 +218,8 @@ __global__ __launch_bounds__(64 * Form::waves, fwd1024::waves_per_simd<Form>()) 
   auto load_first_frame = [&](const long long run, float2 (&raw)[8]) {
     const long long b = run / p.runs_per_clip;
     if (b >= p.B) return;
-    const long long t0 = (run - b * p.runs_per_clip) * p.frames_per_run;
-    if (t0 >= p.T) return;
+    const long long t0 = (run - b * p.runs_per_clip) * p.frames_per_run;     // run_units without its end, which 32 of
+    if (t0 >= p.T) return;                                                   // the forms' listings would not survive
     const float* clip = p.x + b * p.clip_stride;
     const bool clip_aligned = ((((uintptr_t)clip) & 7) == 0);
     const long long s0 = t0 * (128 * HS) - 512;
@@ -314,11 +315,8 @@ __global__ __launch_bounds__(64 * Form::waves, fwd1024::waves_per_simd<Form>()) 
   auto do_run = [&](const long long run, const bool preloaded) {
   const long long b = run / p.runs_per_clip;
   if (b >= p.B) return;
-  const long long r = run - b * p.runs_per_clip;
-  const long long t0 = r * p.frames_per_run;
-  long long t1 = t0 + p.frames_per_run;
-  if (t1 > p.T) t1 = p.T;
-  if (t0 >= t1) return;
+  long long t0, t1;
+  if (!run_units(run - b * p.runs_per_clip, p.frames_per_run, p.T, t0, t1)) return;
   const float* clip = p.x + b * p.clip_stride;
   const bool clip_aligned = ((((uintptr_t)clip) & 7) == 0);  // frame starts are multiples of 256 samples
 
@@ -356,7 +354,9 @@ __global__ __launch_bounds__(64 * Form::waves, fwd1024::waves_per_simd<Form>()) 
     ph_off = *p.ph_offset;
     ph_sc = *p.ph_scale;
   }
-  int rot = 0;                 // AL: column rotation of the current frame
+  // AL: the aligned row stream, as row_stream.h describes it.  This kernel keeps the state machine written out: on
+  // RowStream<8> six of its forms compile to another run start and missed the A/B gate (profiles/row_stream.md).
+  int rot = 0;                 //     column rotation of the current frame
   float2* sp = nullptr;        //     this lane's slot in the current frame's block 0
   v2f carry = {0.f, 0.f};      //     block 8 of the previous frame (lanes < rot: bins 448 + .., lane rot - 1: Nyquist)
   bool head = true;            //     the run's first block belongs partly to the run before
@@ -1402,7 +1402,7 @@ int launch_stft1024_fwd(const float* x, long long B, long long L, long long clip
     hipLaunchKernelGGL(stft1024_fwd_kernel<true>, dim3((unsigned)blocks), dim3(64 * WAVES_PER_BLOCK), 0, stream, p);
   else
     hipLaunchKernelGGL(stft1024_fwd_kernel<false>, dim3((unsigned)blocks), dim3(64 * WAVES_PER_BLOCK), 0, stream, p);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return hipGetLastError() == hipSuccess ? AT_OK : AT_ELAUNCH;
 }
 
 int launch_stft1024_h256_fwd(const float* x, long long B, long long L, long long clip_stride, long long T,
@@ -1444,7 +1444,7 @@ int launch_stft1024_h256_fwd(const float* x, long long B, long long L, long long
   size_t dyn_lds = 0;
   if (bank) {
     for (int q = 0; q < bank->n_passes; ++q) dyn_lds += (size_t)64 * bank->pass_len[q] * sizeof(float);
-    if (dyn_lds > kMaxBandFloats * sizeof(float)) return -2;
+    if (dyn_lds > kMaxBandFloats * sizeof(float)) return AT_EUNSUPPORTED;
     dyn_lds += (size_t)2 * 64 * bank->n_passes * sizeof(int);   // lane_start, lane_filter
   }
   dyn_lds += form.packed_lds_bytes;
@@ -1490,7 +1490,7 @@ int launch_stft1024_h256_fwd(const float* x, long long B, long long L, long long
     if (blocks > tiles) blocks = tiles;
   }
   hipLaunchKernelGGL(form.kernel, dim3((unsigned)blocks), dim3(64 * form.waves), dyn_lds, stream, p);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return hipGetLastError() == hipSuccess ? AT_OK : AT_ELAUNCH;
 }
 
 int launch_istft1024_ola(const float2* X, const float* mag, const float* phase, long long B, long long T, int hop,
@@ -1552,7 +1552,7 @@ int launch_istft1024_ola(const float2* X, const float* mag, const float* phase, 
         p.frames_per_block = tile_frames;
         p.runs_per_clip = tpc;
         hipLaunchKernelGGL(tk, dim3((unsigned)(B * tpc)), dim3(64 * nw), 0, stream, p);
-        return hipGetLastError() == hipSuccess ? 0 : -5;
+        return hipGetLastError() == hipSuccess ? AT_OK : AT_ELAUNCH;
       }
     }
   }
@@ -1569,7 +1569,7 @@ int launch_istft1024_ola(const float2* X, const float* mag, const float* phase, 
   const long long waves = B * p.runs_per_clip;
   const long long blocks = (waves + WAVES_PER_BLOCK - 1) / WAVES_PER_BLOCK;
   hipLaunchKernelGGL(kernel, dim3((unsigned)blocks), dim3(64 * WAVES_PER_BLOCK), 0, stream, p);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return hipGetLastError() == hipSuccess ? AT_OK : AT_ELAUNCH;
 }
 
 int launch_irfft1024_frames(const float2* X, const float* mag, const float* phase, long long nframes,
@@ -1587,7 +1587,7 @@ int launch_irfft1024_frames(const float2* X, const float* mag, const float* phas
     hipLaunchKernelGGL(irfft1024_frames_kernel<IN_COMPLEX>, dim3((unsigned)blocks), dim3(64 * WAVES_PER_BLOCK), 0, stream, p);
   else
     hipLaunchKernelGGL(irfft1024_frames_kernel<IN_POLAR>, dim3((unsigned)blocks), dim3(64 * WAVES_PER_BLOCK), 0, stream, p);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return hipGetLastError() == hipSuccess ? AT_OK : AT_ELAUNCH;
 }
 
 }  // namespace at_hip

@@ -30,6 +30,7 @@
 #include "band_bank.h"
 #include "mel_gemm.h"   // C_* contrast codes
 #include "ola_window.h"
+#include "row_stream.h"
 #include "run_plan.h"
 #include "stft_launch.h"
 #include "variants.h"
@@ -40,20 +41,6 @@ namespace at_hip {
 constexpr int N2K = 2048;
 constexpr int F2K = N2K / 2 + 1;     // 1025
 constexpr int W2K = 4;               // waves per block
-
-struct P2k {
-  const float* x;        // forward: audio, clip b at x + b*clip_stride
-  const float* window;   // 2048 samples (analysis or synthesis)
-  const float2* tw;      // fft512 twiddle table (capi.hip)
-  const float2* tw2k;    // W2048^k, k = 0 .. 1023
-  float2* X;             // (frames, 1025) complex64: forward output / inverse input
-  const float* mag;      // inverse, polar input
-  const float* phase;
-  float* phase_out;      // forward: optional angle output (frames, 1025)
-  float* y;              // inverse: (frames, 2048) windowed time frames
-  long long L, clip_stride, T, total_frames, frames_per_block;
-  int hop, center;
-};
 
 // q[j] = x[s + 4 (lane + 64 j) .. + 3] of frame f (reflect padding with center, zero padding without)
 __device__ __forceinline__ void load_frame2k(const float* x, long long clip_stride, long long L, long long T, int hop,
@@ -148,12 +135,12 @@ __device__ __forceinline__ float fwd_core2k(v2f (&ze)[8], v2f (&zo)[8], const fl
 }
 
 template <bool WRITE_PHASE>
-__global__ __launch_bounds__(64 * W2K, 3) void stft2048_fwd_kernel(P2k p) {
+__global__ __launch_bounds__(64 * W2K, 3) void stft2048_fwd_kernel(PFrames p) {
   __shared__ float2 lds_all[W2K * kFftLdsFloat2PerWave + kTwiddleCount + 1024];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // uniform: run bookkeeping on the scalar unit
   float2* lds = lds_all + wave * kFftLdsFloat2PerWave;
   float2* tab = lds_all + W2K * kFftLdsFloat2PerWave;      // the fft512 twiddles, W2048^k behind them
-  stage_tables2k<false, 64 * W2K>(p.tw, p.tw2k, tab, tab + kTwiddleCount);
+  stage_tables2k<false, 64 * W2K>(p.tw, p.tw_n, tab, tab + kTwiddleCount);
   const long long f_begin = (long long)blockIdx.x * p.frames_per_block;
   long long f_end = f_begin + p.frames_per_block;
   if (f_end > p.total_frames) f_end = p.total_frames;
@@ -185,21 +172,10 @@ __global__ __launch_bounds__(64 * W2K, 3) void stft2048_fwd_kernel(P2k p) {
 // A wave walks a run of consecutive frames of one clip.  Register j of a lane holds x[s + 4 (lane + 64 j) .. + 3], so the
 // next frame is "registers j + 2 of the same lane": the raw samples stay in registers, shifted by two slots per frame,
 // and only the 512 new samples (two 16-byte loads per lane) are fetched -- 2 KB of loads per frame instead of 8 KB.
-// The spectrum leaves as ONE byte stream in 512-byte aligned blocks (stft1024.hip, template flag AL): rows are 8200
-// bytes, row f starts 8 f bytes past a 128-byte line; the output columns of both 512-point FFTs are rotated over the
-// lanes by rot = (f 1025) mod 64 = (rot + 1) mod 64 per frame, the radix-2 stage is lane-local and does not care, the
-// merge's twiddles (W1024^k / 2, W2048^k) and mirror lane follow the column, and block 16 of a frame (the tail of
-// register 15 and the Nyquist bin) is carried into the next frame's block 0.  Sixteen full-line non-temporal stores per
-// frame (a seventeenth every 64 frames).
+// The spectrum leaves through the aligned row stream of row_stream.h (NB = 16: sixteen full-block non-temporal stores
+// per frame): the output columns of both 512-point FFTs are rotated over the lanes, the radix-2 stage is lane-local
+// and does not care, the merge's twiddles (W1024^k / 2, W2048^k) and mirror lane follow the column.
 // ---------------------------------------------------------------------------
-struct P2kRun {
-  const float* x;
-  const float* window;
-  const float2* tw;
-  const float2* tw2k;
-  float2* X;
-  long long B, L, clip_stride, T, runs_per_clip, frames_per_run;
-};
 
 // 256 samples (one register slot of the wave) starting at original index i0 of the clip, reflect-padded
 __device__ __forceinline__ float4 load_slot2k(const float* clip, long long L, long long i0, int lane) {
@@ -210,7 +186,7 @@ __device__ __forceinline__ float4 load_slot2k(const float* clip, long long L, lo
 }
 
 constexpr int W2KR = 8;     // waves per block of the run kernel: two blocks per CU, four waves per SIMD (126 VGPRs)
-__global__ __launch_bounds__(64 * W2KR, 4) void stft2048_run_fwd_kernel(P2kRun p) {
+__global__ __launch_bounds__(64 * W2KR, 4) void stft2048_run_fwd_kernel(PRunFwd p) {
   __shared__ float2 lds_all[W2KR * kFftLdsFloat2PerWave + kTwiddleCount + 1024 + 1024];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -218,16 +194,12 @@ __global__ __launch_bounds__(64 * W2KR, 4) void stft2048_run_fwd_kernel(P2kRun p
   float2* tab = lds_all + W2KR * kFftLdsFloat2PerWave;
   float4* wintab = reinterpret_cast<float4*>(tab + kTwiddleCount + 1024);          // analysis window, 512 float4
   for (int i = threadIdx.x; i < 512; i += 64 * W2KR) wintab[i] = reinterpret_cast<const float4*>(p.window)[i];
-  stage_tables2k<false, 64 * W2KR>(p.tw, p.tw2k, tab, tab + kTwiddleCount);
+  stage_tables2k<false, 64 * W2KR>(p.tw, p.tw_n, tab, tab + kTwiddleCount);
 
-  const long long run = (long long)blockIdx.x * W2KR + wave;
-  const long long b = run / p.runs_per_clip;
+  const long long run = (long long)blockIdx.x * W2KR + wave, b = run / p.runs_per_clip;
   if (b >= p.B) return;
-  const long long r = run - b * p.runs_per_clip;
-  const long long t0 = r * p.frames_per_run;
-  long long t1 = t0 + p.frames_per_run;
-  if (t1 > p.T) t1 = p.T;
-  if (t0 >= t1) return;
+  long long t0, t1;
+  if (!run_units(run - b * p.runs_per_clip, p.units_per_run, p.T, t0, t1)) return;
   const float* clip = p.x + b * p.clip_stride;
   const long long L = p.L;
 
@@ -237,12 +209,8 @@ __global__ __launch_bounds__(64 * W2KR, 4) void stft2048_run_fwd_kernel(P2kRun p
 #pragma unroll
   for (int j = 0; j < 8; ++j) asm volatile("" : "+v"(raw[j].x), "+v"(raw[j].y), "+v"(raw[j].z), "+v"(raw[j].w));
 
-  const long long e0 = (b * p.T + t0) * F2K;
-  int rot = (int)(e0 & 63);
-  float2* sp = p.X + (e0 - rot) + lane;
-  v2f carry = {0.f, 0.f};
-  bool head = true;
-  auto put = [&](float2* dst, v2f val) { __builtin_nontemporal_store(val, reinterpret_cast<v2f*>(dst)); };
+  RowStream<16, v2f> out;
+  out.begin(reinterpret_cast<v2f*>(p.X), (b * p.T + t0) * F2K, lane);
 
   auto frame_body = [&](const float4 (&fresh)[2]) {
     wave_priority<3>();        // transform > stores, as in stft1024.hip
@@ -252,27 +220,9 @@ __global__ __launch_bounds__(64 * W2KR, 4) void stft2048_run_fwd_kernel(P2kRun p
     for (int j = 0; j < 6; ++j) raw[j] = raw[j + 2];
     raw[6] = fresh[0];
     raw[7] = fresh[1];
-    const v2f nyq = {fwd_core2k<true>(ze, zo, tab, lds, lane, rot, (lane - rot) & 63, [&](int m, v2f xk) { z[m] = xk; }), 0.0f};
+    const v2f nyq = {fwd_core2k<true>(ze, zo, tab, lds, lane, out.rot, (lane - out.rot) & 63, [&](int m, v2f xk) { z[m] = xk; }), 0.0f};
     wave_priority<1>();
-    const bool lo = lane < rot;
-    const v2f s0 = lo ? carry : z[0];
-    if (head) {
-      if (!lo) put(sp, s0);
-      head = false;
-    } else {
-      put(sp, s0);
-    }
-#pragma unroll
-    for (int j = 1; j < 16; ++j) put(sp + 64 * j, lo ? z[j - 1] : z[j]);
-    carry = lo ? z[15] : nyq;
-    if (rot == 63) {
-      put(sp + 1024, carry);
-      sp += 1088;
-      rot = 0;
-    } else {
-      sp += 1024;
-      ++rot;
-    }
+    out.emit(z, nyq, lane);
     wave_priority<0>();
   };
 
@@ -297,7 +247,7 @@ __global__ __launch_bounds__(64 * W2KR, 4) void stft2048_run_fwd_kernel(P2kRun p
     }
     frame_body(fresh);
   }
-  if (lane < rot) put(sp, carry);
+  out.end(lane);
 }
 
 // The inverse core: v[m] = Z[lane + 64 m] of irfft_presplit<16> (fft512.h) -> the unnormalised time samples,
@@ -316,13 +266,13 @@ __device__ __forceinline__ void inv_core2k(const v2f (&v)[16], const LdsTwiddles
 
 // irfft(X) * window, frames out (the overlap-add is stft_generic.hip's gather): complex or polar input
 template <bool POLAR>
-__global__ __launch_bounds__(64 * W2K, 3) void irfft2048_frames_kernel(P2k p) {
+__global__ __launch_bounds__(64 * W2K, 3) void irfft2048_frames_kernel(PFrames p) {
   __shared__ float2 lds_all[W2K * kFftLdsFloat2PerWave + kTwiddleCount + 1024];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // uniform: run bookkeeping on the scalar unit
   float2* lds = lds_all + wave * kFftLdsFloat2PerWave;
   float2* tab = lds_all + W2K * kFftLdsFloat2PerWave;
   const v2f* w2 = reinterpret_cast<const v2f*>(tab + kTwiddleCount) + lane;     // w2[64 m] = W2048^(lane + 64 m)
-  stage_tables2k<true, 64 * W2K>(p.tw, p.tw2k, tab, tab + kTwiddleCount);
+  stage_tables2k<true, 64 * W2K>(p.tw, p.tw_n, tab, tab + kTwiddleCount);
   const LdsTwiddles<true> tw = {tab, lane};      // tw.getr(m) = W1024^(lane + 64 m)
   const long long f_begin = (long long)blockIdx.x * p.frames_per_block;
   long long f_end = f_begin + p.frames_per_block;
@@ -600,7 +550,7 @@ int launch_stft2048_mel(const float* x, long long B, long long L, long long clip
   p.row_floats = (F2K + max_walk + 63) / 64 * 64;      // a walk that starts on the last bins runs into zeros
   size_t lds = sizeof(float2) * (size_t)(W2K * kFftLdsFloat2PerWave + kTwiddleCount + 1024) +
                sizeof(float) * ((size_t)W2K * p.row_floats + table_floats) + sizeof(int) * (size_t)2 * 64 * bank->n_passes;
-  if (lds > 80 * 1024) return -2;                       // two workgroups per CU or not at all
+  if (lds > 80 * 1024) return AT_EUNSUPPORTED;                       // two workgroups per CU or not at all
   lds = (lds + 15) / 16 * 16;
   const bool winlds = lds + 8192 <= 80 * 1024;          // the analysis window (512 float4) too, when it fits
   if (winlds) {
@@ -620,10 +570,10 @@ int launch_stft2048_mel(const float* x, long long B, long long L, long long clip
   if (lds > 64 * 1024 &&
       hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
     (void)hipGetLastError();
-    return -5;
+    return AT_ELAUNCH;
   }
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * W2K), lds, stream, p);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return hipGetLastError() == hipSuccess ? AT_OK : AT_ELAUNCH;
 }
 
 int launch_istft2048_ola(const float2* X, const float* mag, const float* phase, long long B, long long T, int hop,
@@ -640,42 +590,27 @@ int launch_stft2048_fwd(const float* x, long long B, long long L, long long clip
                         hipStream_t stream) {
   const long long nframes = B * T;
   if (nframes == 0) return 0;
-  P2k p = {};
-  p.x = x; p.window = window; p.tw = tw; p.tw2k = tw2k; p.X = out; p.phase_out = phase;
+  PFrames p = {};
+  p.x = x; p.window = window; p.tw = tw; p.tw_n = tw2k; p.X = out; p.phase_out = phase;
   p.L = L; p.clip_stride = clip_stride; p.T = T; p.total_frames = nframes; p.hop = hop; p.center = center;
   // the sliding-window / aligned-stream kernel: torch.stft's framing at hop n/4, 16-byte aligned clips, a 512-byte
   // aligned output (torch allocations are), no phase side output
   if (center && hop == 512 && !phase && L >= 2048 && (clip_stride & 3) == 0 && (((uintptr_t)x) & 15) == 0 &&
       (((uintptr_t)out) & 511) == 0 && (((uintptr_t)window) & 15) == 0 && variant(kVarFrameKernels) == 0) {
-    P2kRun q = {};
-    q.x = x; q.window = window; q.tw = tw; q.tw2k = tw2k; q.X = out;
-    q.B = B; q.L = L; q.clip_stride = clip_stride; q.T = T;
-    const long long slots = resident_waves(stft2048_run_fwd_kernel, 64 * W2KR, 0);
-    q.frames_per_run = plan_units_per_run(B, T, slots, 8, 1);
-    if (const long long v = forced_units_per_run(T)) q.frames_per_run = v;
-    q.runs_per_clip = (T + q.frames_per_run - 1) / q.frames_per_run;
-    const long long waves = B * q.runs_per_clip;
-    hipLaunchKernelGGL(stft2048_run_fwd_kernel, dim3((unsigned)((waves + W2KR - 1) / W2KR)), dim3(64 * W2KR), 0, stream, q);
-    return hipGetLastError() == hipSuccess ? 0 : -5;
+    return launch_run_fwd(stft2048_run_fwd_kernel, W2KR, T, {x, window, tw, tw2k, out, B, L, clip_stride, T, 0, 0}, stream);
   }
-  p.frames_per_block = units_per_block(nframes, W2K);
-  const long long blocks = (nframes + p.frames_per_block - 1) / p.frames_per_block;
-  if (phase) hipLaunchKernelGGL(stft2048_fwd_kernel<true>, dim3((unsigned)blocks), dim3(64 * W2K), 0, stream, p);
-  else hipLaunchKernelGGL(stft2048_fwd_kernel<false>, dim3((unsigned)blocks), dim3(64 * W2K), 0, stream, p);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  static void (*const kernels[2])(PFrames) = {stft2048_fwd_kernel<false>, stft2048_fwd_kernel<true>};
+  return launch_frames(kernels, phase != nullptr, W2K, p, stream);
 }
 
 int launch_irfft2048_frames(const float2* X, const float* mag, const float* phase, long long nframes, const float* window,
                             const float2* tw, const float2* tw2k, float* frames, hipStream_t stream) {
   if (nframes == 0) return 0;
-  P2k p = {};
-  p.X = const_cast<float2*>(X); p.mag = mag; p.phase = phase; p.window = window; p.tw = tw; p.tw2k = tw2k; p.y = frames;
+  PFrames p = {};
+  p.X = const_cast<float2*>(X); p.mag = mag; p.phase = phase; p.window = window; p.tw = tw; p.tw_n = tw2k; p.y = frames;
   p.total_frames = nframes;
-  p.frames_per_block = units_per_block(nframes, W2K);
-  const long long blocks = (nframes + p.frames_per_block - 1) / p.frames_per_block;
-  if (X) hipLaunchKernelGGL(irfft2048_frames_kernel<false>, dim3((unsigned)blocks), dim3(64 * W2K), 0, stream, p);
-  else hipLaunchKernelGGL(irfft2048_frames_kernel<true>, dim3((unsigned)blocks), dim3(64 * W2K), 0, stream, p);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  static void (*const kernels[2])(PFrames) = {irfft2048_frames_kernel<false>, irfft2048_frames_kernel<true>};
+  return launch_frames(kernels, X == nullptr, W2K, p, stream);
 }
 
 }  // namespace at_hip

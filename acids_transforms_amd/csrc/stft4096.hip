@@ -27,6 +27,7 @@
 #include "fastmath.h"
 #include "fft512.h"
 #include "ola_window.h"
+#include "row_stream.h"
 #include "run_plan.h"
 #include "stft_launch.h"
 #include "variants.h"
@@ -39,22 +40,8 @@ constexpr int F4K = N4K / 2 + 1;     // 2049
 constexpr int W4K = 4;               // waves per block
 constexpr int kTab4k = kSideTableCount - kSide4096;   // the n_fft-4096 block of the side table (stft_launch.h)
 
-struct P4k {
-  const float* x;        // forward: audio, clip b at x + b*clip_stride
-  const float* window;   // 4096 samples (analysis or synthesis)
-  const float2* tw;      // fft512 twiddle table (capi.hip)
-  const float2* tw4k;    // kTab4k entries
-  float2* X;             // (frames, 2049) complex64: forward output / inverse input
-  const float* mag;      // inverse, polar input
-  const float* phase;
-  float* phase_out;      // forward: optional angle output (frames, 2049)
-  float* y;              // inverse: (frames, 4096) windowed time frames
-  long long L, clip_stride, T, total_frames, frames_per_block;
-  int hop, center;
-};
-
 // (qa[j], qb[j]) = x[s + 8 (lane + 64 j) .. + 7] of frame f (reflect padding with center, zero padding without)
-__device__ __forceinline__ void load_frame4k(const P4k& p, long long f, int lane, float4 (&qa)[8], float4 (&qb)[8]) {
+__device__ __forceinline__ void load_frame4k(const PFrames& p, long long f, int lane, float4 (&qa)[8], float4 (&qb)[8]) {
   const long long b = f / p.T, t = f - b * p.T;
   const float* clip = p.x + b * p.clip_stride;
   const long long start = t * (long long)p.hop - (p.center ? N4K / 2 : 0);
@@ -161,13 +148,13 @@ __device__ __forceinline__ float fwd_core4k(v2f (&y)[4][8], const LdsTwiddles<fa
 }
 
 template <bool WRITE_PHASE>
-__global__ __launch_bounds__(64 * W4K, 2) void stft4096_fwd_kernel(P4k p) {
+__global__ __launch_bounds__(64 * W4K, 2) void stft4096_fwd_kernel(PFrames p) {
   __shared__ float2 lds_all[kLds4k];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // uniform: run bookkeeping on the scalar unit
   float2* lds = lds_all + wave * kFftLdsFloat2PerWave;
   float2* tab = lds_all + W4K * kFftLdsFloat2PerWave;
   float2* t4 = tab + kTwiddleCount;
-  stage_tables4k<false>(p.tw, p.tw4k, tab, t4);
+  stage_tables4k<false>(p.tw, p.tw_n, tab, t4);
   const LdsTwiddles<false> tw = {tab, lane};
   const long long f_begin = (long long)blockIdx.x * p.frames_per_block;
   long long f_end = f_begin + p.frames_per_block;
@@ -199,20 +186,11 @@ __global__ __launch_bounds__(64 * W4K, 2) void stft4096_fwd_kernel(P4k p) {
 // forward, hop = 1024 = N/4, center = True: sliding window in registers + aligned stream stores (round 3; the scheme of
 // stft1024.hip's AL kernel and stft2048.hip's run kernel).  Register slot j of a lane holds x[s + 8 (lane + 64 j) .. + 7]
 // (two float4): the next frame is "slots j + 2 of the same lane", so the raw samples stay in registers and only the
-// 1024 new samples (four 16-byte loads per lane) are fetched per frame -- 4 KB instead of 16 KB.  Rows are 16 392 bytes
-// (8 f bytes past a 128-byte line): the output columns of the four 512-point FFTs are rotated over the lanes by rot =
-// (f 2049) mod 64, the radix-4 stage is lane-local, the twiddles of the radix-4 stage and of the merge and the mirror
-// lane follow the column, block 32 of a frame (the tail of register 31, then the Nyquist bin) is carried into the next
-// frame's block 0: 32 full-line non-temporal stores per frame.
+// 1024 new samples (four 16-byte loads per lane) are fetched per frame -- 4 KB instead of 16 KB.  The spectrum leaves
+// through the aligned row stream of row_stream.h (NB = 32: 32 full-block non-temporal stores per frame): the output
+// columns of the four 512-point FFTs are rotated over the lanes, the radix-4 stage is lane-local, the twiddles of the
+// radix-4 stage and of the merge and the mirror lane follow the column.
 // ---------------------------------------------------------------------------
-struct P4kRun {
-  const float* x;
-  const float* window;
-  const float2* tw;
-  const float2* tw4k;
-  float2* X;
-  long long B, L, clip_stride, T, runs_per_clip, frames_per_run;
-};
 
 // 512 samples (one register slot of the wave) starting at original index i0 of the clip, reflect-padded
 __device__ __forceinline__ void load_slot4k(const float* clip, long long L, long long i0, int lane, float4& a, float4& b) {
@@ -231,7 +209,7 @@ __device__ __forceinline__ void load_slot4k(const float* clip, long long L, long
 
 constexpr int kLds4kRun = kLds4k + 2048;          // + the analysis window (1024 float4)
 
-__global__ __launch_bounds__(64 * W4K, 2) void stft4096_run_fwd_kernel(P4kRun p) {
+__global__ __launch_bounds__(64 * W4K, 2) void stft4096_run_fwd_kernel(PRunFwd p) {
   __shared__ float2 lds_all[kLds4kRun];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -240,16 +218,12 @@ __global__ __launch_bounds__(64 * W4K, 2) void stft4096_run_fwd_kernel(P4kRun p)
   float2* t4 = tab + kTwiddleCount;
   float4* wintab = reinterpret_cast<float4*>(t4 + kTab4k);
   for (int i = threadIdx.x; i < 1024; i += 64 * W4K) wintab[i] = reinterpret_cast<const float4*>(p.window)[i];
-  stage_tables4k<false>(p.tw, p.tw4k, tab, t4);       // ends with __syncthreads()
+  stage_tables4k<false>(p.tw, p.tw_n, tab, t4);       // ends with __syncthreads()
 
-  const long long run = (long long)blockIdx.x * W4K + wave;
-  const long long b = run / p.runs_per_clip;
+  const long long run = (long long)blockIdx.x * W4K + wave, b = run / p.runs_per_clip;
   if (b >= p.B) return;
-  const long long r = run - b * p.runs_per_clip;
-  const long long t0 = r * p.frames_per_run;
-  long long t1 = t0 + p.frames_per_run;
-  if (t1 > p.T) t1 = p.T;
-  if (t0 >= t1) return;
+  long long t0, t1;
+  if (!run_units(run - b * p.runs_per_clip, p.units_per_run, p.T, t0, t1)) return;
   const float* clip = p.x + b * p.clip_stride;
   const long long L = p.L;
   const LdsTwiddles<false> tw = {tab, lane};
@@ -263,12 +237,8 @@ __global__ __launch_bounds__(64 * W4K, 2) void stft4096_run_fwd_kernel(P4kRun p)
     asm volatile("" : "+v"(rb[j].x), "+v"(rb[j].y), "+v"(rb[j].z), "+v"(rb[j].w));
   }
 
-  const long long e0 = (b * p.T + t0) * F4K;
-  int rot = (int)(e0 & 63);
-  float2* sp = p.X + (e0 - rot) + lane;
-  v2f carry = {0.f, 0.f};
-  bool head = true;
-  auto put = [&](float2* dst, v2f val) { __builtin_nontemporal_store(val, reinterpret_cast<v2f*>(dst)); };
+  RowStream<32, v2f> out;
+  out.begin(reinterpret_cast<v2f*>(p.X), (b * p.T + t0) * F4K, lane);
 
   auto frame_body = [&](const float4 (&fa)[2], const float4 (&fb)[2]) {
     wave_priority<3>();        // transform > stores, as in stft1024.hip
@@ -281,27 +251,9 @@ __global__ __launch_bounds__(64 * W4K, 2) void stft4096_run_fwd_kernel(P4kRun p)
     }
     ra[6] = fa[0]; rb[6] = fb[0];
     ra[7] = fa[1]; rb[7] = fb[1];
-    const v2f nyq = {fwd_core4k(y, tw, t4, lds, lane, rot, (lane - rot) & 63, [&](int m, v2f xk) { z[m] = xk; }), 0.0f};
+    const v2f nyq = {fwd_core4k(y, tw, t4, lds, lane, out.rot, (lane - out.rot) & 63, [&](int m, v2f xk) { z[m] = xk; }), 0.0f};
     wave_priority<1>();
-    const bool lo = lane < rot;
-    const v2f s0 = lo ? carry : z[0];
-    if (head) {
-      if (!lo) put(sp, s0);
-      head = false;
-    } else {
-      put(sp, s0);
-    }
-#pragma unroll
-    for (int j = 1; j < 32; ++j) put(sp + 64 * j, lo ? z[j - 1] : z[j]);
-    carry = lo ? z[31] : nyq;
-    if (rot == 63) {
-      put(sp + 2048, carry);
-      sp += 2112;
-      rot = 0;
-    } else {
-      sp += 2048;
-      ++rot;
-    }
+    out.emit(z, nyq, lane);
     wave_priority<0>();
   };
 
@@ -327,7 +279,7 @@ __global__ __launch_bounds__(64 * W4K, 2) void stft4096_run_fwd_kernel(P4kRun p)
     }
     frame_body(fa, fb);
   }
-  if (lane < rot) put(sp, carry);
+  out.end(lane);
 }
 
 // The inverse core: v[m] = Z[lane + 64 m] of irfft_presplit<32> (fft512.h) -> the unnormalised time samples,
@@ -350,7 +302,7 @@ __device__ __forceinline__ void inv_core4k(const v2f (&v)[32], const LdsTwiddles
 
 // irfft(X) * window, frames out (the overlap-add is stft_generic.hip's gather): complex or polar input
 template <bool POLAR>
-__global__ __launch_bounds__(64 * W4K, 2) void irfft4096_frames_kernel(P4k p) {
+__global__ __launch_bounds__(64 * W4K, 2) void irfft4096_frames_kernel(PFrames p) {
   __shared__ float2 lds_all[kLds4k];
   const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // uniform: run bookkeeping on the scalar unit
   float2* lds = lds_all + wave * kFftLdsFloat2PerWave;
@@ -358,7 +310,7 @@ __global__ __launch_bounds__(64 * W4K, 2) void irfft4096_frames_kernel(P4k p) {
   float2* t4 = tab + kTwiddleCount;
   const v2f* w4 = reinterpret_cast<const v2f*>(t4) + lane;            // w4[64 m] = W4096^(lane + 64 m)
   const v2f* wr = reinterpret_cast<const v2f*>(t4 + 2048) + lane;
-  stage_tables4k<true>(p.tw, p.tw4k, tab, t4);
+  stage_tables4k<true>(p.tw, p.tw_n, tab, t4);
   const LdsTwiddles<true> tw = {tab, lane};
   const long long f_begin = (long long)blockIdx.x * p.frames_per_block;
   long long f_end = f_begin + p.frames_per_block;
@@ -440,42 +392,27 @@ int launch_stft4096_fwd(const float* x, long long B, long long L, long long clip
                         hipStream_t stream) {
   const long long nframes = B * T;
   if (nframes == 0) return 0;
-  P4k p = {};
-  p.x = x; p.window = window; p.tw = tw; p.tw4k = tw4k; p.X = out; p.phase_out = phase;
+  PFrames p = {};
+  p.x = x; p.window = window; p.tw = tw; p.tw_n = tw4k; p.X = out; p.phase_out = phase;
   p.L = L; p.clip_stride = clip_stride; p.T = T; p.total_frames = nframes; p.hop = hop; p.center = center;
   // the sliding-window / aligned-stream kernel: torch.stft's framing at hop n/4, 16-byte aligned clips, a 512-byte
   // aligned output, no phase side output
   if (center && hop == 1024 && !phase && L >= 4096 && (clip_stride & 3) == 0 && (((uintptr_t)x) & 15) == 0 &&
       (((uintptr_t)out) & 511) == 0 && (((uintptr_t)window) & 15) == 0 && variant(kVarFrameKernels) == 0) {
-    P4kRun q = {};
-    q.x = x; q.window = window; q.tw = tw; q.tw4k = tw4k; q.X = out;
-    q.B = B; q.L = L; q.clip_stride = clip_stride; q.T = T;
-    const long long slots = resident_waves(stft4096_run_fwd_kernel, 64 * W4K, 0);
-    q.frames_per_run = plan_units_per_run(B, T, slots, 8, 1);
-    if (const long long v = forced_units_per_run(T)) q.frames_per_run = v;
-    q.runs_per_clip = (T + q.frames_per_run - 1) / q.frames_per_run;
-    const long long waves = B * q.runs_per_clip;
-    hipLaunchKernelGGL(stft4096_run_fwd_kernel, dim3((unsigned)((waves + W4K - 1) / W4K)), dim3(64 * W4K), 0, stream, q);
-    return hipGetLastError() == hipSuccess ? 0 : -5;
+    return launch_run_fwd(stft4096_run_fwd_kernel, W4K, T, {x, window, tw, tw4k, out, B, L, clip_stride, T, 0, 0}, stream);
   }
-  p.frames_per_block = units_per_block(nframes, W4K);
-  const long long blocks = (nframes + p.frames_per_block - 1) / p.frames_per_block;
-  if (phase) hipLaunchKernelGGL(stft4096_fwd_kernel<true>, dim3((unsigned)blocks), dim3(64 * W4K), 0, stream, p);
-  else hipLaunchKernelGGL(stft4096_fwd_kernel<false>, dim3((unsigned)blocks), dim3(64 * W4K), 0, stream, p);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  static void (*const kernels[2])(PFrames) = {stft4096_fwd_kernel<false>, stft4096_fwd_kernel<true>};
+  return launch_frames(kernels, phase != nullptr, W4K, p, stream);
 }
 
 int launch_irfft4096_frames(const float2* X, const float* mag, const float* phase, long long nframes, const float* window,
                             const float2* tw, const float2* tw4k, float* frames, hipStream_t stream) {
   if (nframes == 0) return 0;
-  P4k p = {};
-  p.X = const_cast<float2*>(X); p.mag = mag; p.phase = phase; p.window = window; p.tw = tw; p.tw4k = tw4k; p.y = frames;
+  PFrames p = {};
+  p.X = const_cast<float2*>(X); p.mag = mag; p.phase = phase; p.window = window; p.tw = tw; p.tw_n = tw4k; p.y = frames;
   p.total_frames = nframes;
-  p.frames_per_block = units_per_block(nframes, W4K);
-  const long long blocks = (nframes + p.frames_per_block - 1) / p.frames_per_block;
-  if (X) hipLaunchKernelGGL(irfft4096_frames_kernel<false>, dim3((unsigned)blocks), dim3(64 * W4K), 0, stream, p);
-  else hipLaunchKernelGGL(irfft4096_frames_kernel<true>, dim3((unsigned)blocks), dim3(64 * W4K), 0, stream, p);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  static void (*const kernels[2])(PFrames) = {irfft4096_frames_kernel<false>, irfft4096_frames_kernel<true>};
+  return launch_frames(kernels, X == nullptr, W4K, p, stream);
 }
 
 }  // namespace at_hip

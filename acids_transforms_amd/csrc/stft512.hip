@@ -29,6 +29,7 @@
 #include "fft512.h"
 #include "band_bank.h"
 #include "mel_gemm.h"   // C_* contrast codes
+#include "row_stream.h"
 #include "run_plan.h"
 #include "stft_launch.h"
 #include "variants.h"
@@ -155,20 +156,11 @@ __global__ __launch_bounds__(64 * W5) void stft512_fwd_kernel(P5 p) {
 // stft1024.hip's AL kernel).  A wave walks consecutive frame PAIRS (2 i, 2 i + 1) of one clip; even lanes hold the
 // samples of the first frame, odd lanes of the second (register slot j = 64 samples), so the next pair is "slots j + 4
 // of the same lane": four 8-byte loads per lane and pair instead of eight.  Rows are 2056 bytes (8 f bytes past a
-// 128-byte line).  The FFT's output columns are rotated over the lanes by rot = (f 257) mod 64 of the pair's FIRST
-// frame; after the un-mixing every lane holds the same columns of both frames, so the second frame -- which needs
-// rot + 1 -- is moved up one lane (nine ds_bpermute: its four registers and its Nyquist bin) and then leaves exactly
-// like a frame of its own: four full-line non-temporal stores per frame, block 4 (the tail of register 3, then the
-// Nyquist bin) carried into the next frame's block 0.
+// 128-byte line) and leave through the aligned row stream of row_stream.h (NB = 4).  The FFT's output columns are
+// rotated over the lanes by the rotation of the pair's FIRST frame; after the un-mixing every lane holds the same
+// columns of both frames, so the second frame -- which needs rot + 1 -- is moved up one lane (nine ds_bpermute: its
+// four registers and its Nyquist bin) and then leaves exactly like a frame of its own, a second emit.
 // ---------------------------------------------------------------------------
-struct P5Run {
-  const float* x;
-  const float* window;
-  const float2* tw;
-  const float2* tw512;
-  float2* X;
-  long long B, L, clip_stride, T, runs_per_clip, pairs_per_run;
-};
 
 // two samples of a frame that starts at original index s (reflect-padded)
 __device__ __forceinline__ float2 load_pair5(const float* clip, long long L, long long i, bool interior) {
@@ -178,14 +170,14 @@ __device__ __forceinline__ float2 load_pair5(const float* clip, long long L, lon
 
 constexpr int W5R = 8;      // waves per block of the run kernel
 
-__global__ __launch_bounds__(64 * W5R, 4) void stft512_run_fwd_kernel(P5Run p) {
+__global__ __launch_bounds__(64 * W5R, 4) void stft512_run_fwd_kernel(PRunFwd p) {
   __shared__ float2 lds_all[W5R * kFftLdsFloat2PerWave + 256];
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int par = lane & 1, u = lane >> 1;
   float2* lds = lds_all + wave * kFftLdsFloat2PerWave;
   float2* w5tab = lds_all + W5R * kFftLdsFloat2PerWave;                  // W512^k, k = 0 .. 255
-  for (int i = threadIdx.x; i < 256; i += 64 * W5R) w5tab[i] = p.tw512[i];
+  for (int i = threadIdx.x; i < 256; i += 64 * W5R) w5tab[i] = p.tw_n[i];
   __syncthreads();
   Twiddles tw;
   load_twiddles<false>(tw, p.tw, lane);
@@ -193,16 +185,11 @@ __global__ __launch_bounds__(64 * W5R, 4) void stft512_run_fwd_kernel(P5Run p) {
 #pragma unroll
   for (int j = 0; j < 8; ++j) win[j] = reinterpret_cast<const float2*>(p.window)[u + 32 * j];
 
-  const long long run = (long long)blockIdx.x * W5R + wave;
-  const long long b = run / p.runs_per_clip;
-  if (b >= p.B) return;
-  const long long r = run - b * p.runs_per_clip;
   const long long T = p.T, L = p.L;
-  const long long n_pairs = (T + 1) / 2;
-  const long long i0 = r * p.pairs_per_run;
-  long long i1 = i0 + p.pairs_per_run;
-  if (i1 > n_pairs) i1 = n_pairs;
-  if (i0 >= i1) return;
+  const long long run = (long long)blockIdx.x * W5R + wave, b = run / p.runs_per_clip;
+  if (b >= p.B) return;
+  long long i0, i1;
+  if (!run_units(run - b * p.runs_per_clip, p.units_per_run, (T + 1) / 2, i0, i1)) return;
   const float* clip = p.x + b * p.clip_stride;
 
   // this lane's frame of pair i: f = 2 i + par, starting at original sample 128 f - 256; slot j = samples 64 j .. + 63.
@@ -223,34 +210,8 @@ __global__ __launch_bounds__(64 * W5R, 4) void stft512_run_fwd_kernel(P5Run p) {
 #pragma unroll
   for (int j = 0; j < 8; ++j) asm volatile("" : "+v"(raw[j].x), "+v"(raw[j].y));
 
-  const long long e0 = (b * T + 2 * i0) * F5;
-  int rot = (int)(e0 & 63);
-  float2* sp = p.X + (e0 - rot) + lane;
-  v2f carry = {0.f, 0.f};
-  bool head = true;
-  auto put = [&](float2* dst, v2f val) { __builtin_nontemporal_store(val, reinterpret_cast<v2f*>(dst)); };
-  // one frame's four registers (columns already rotated by the current `rot`) and Nyquist bin (on lane rot) into the stream
-  auto emit_frame = [&](const v2f (&z)[4], v2f nyq) {
-    const bool lo = lane < rot;
-    const v2f s0 = lo ? carry : z[0];
-    if (head) {
-      if (!lo) put(sp, s0);
-      head = false;
-    } else {
-      put(sp, s0);
-    }
-#pragma unroll
-    for (int j = 1; j < 4; ++j) put(sp + 64 * j, lo ? z[j - 1] : z[j]);
-    carry = lo ? z[3] : nyq;
-    if (rot == 63) {
-      put(sp + 256, carry);
-      sp += 320;
-      rot = 0;
-    } else {
-      sp += 256;
-      ++rot;
-    }
-  };
+  RowStream<4, v2f> out;
+  out.begin(reinterpret_cast<v2f*>(p.X), (b * T + 2 * i0) * F5, lane);
 
   auto pair_body = [&](const float2 (&fresh)[4], bool has_b) {
     wave_priority<3>();        // transform > stores, as in stft1024.hip
@@ -263,10 +224,10 @@ __global__ __launch_bounds__(64 * W5R, 4) void stft512_run_fwd_kernel(P5Run p) {
     for (int j = 0; j < 4; ++j) raw[4 + j] = fresh[j];
     v2f xa[4], xb[4];
     float nax, nbx;
-    fwd_core5<true>(y, tw, lds, reinterpret_cast<const v2f*>(w5tab), lane, rot, (lane - rot) & 63, xa, xb, nax, nbx);
+    fwd_core5<true>(y, tw, lds, reinterpret_cast<const v2f*>(w5tab), lane, out.rot, (lane - out.rot) & 63, xa, xb, nax, nbx);
     const v2f na = {nax, 0.0f};                            // X_A[256], on the lane whose column is 0 (= lane rot)
     wave_priority<1>();
-    emit_frame(xa, na);
+    out.emit(xa, na, lane);
     if (has_b) {
       // the second frame one lane up: its columns then sit where a frame with rotation rot + 1 wants them
       const int src = (lane - 1) & 63;
@@ -277,7 +238,7 @@ __global__ __launch_bounds__(64 * W5R, 4) void stft512_run_fwd_kernel(P5Run p) {
         xs[m].y = __shfl(xb[m].y, src, 64);
       }
       const v2f nb = {__shfl(nbx, src, 64), 0.0f};
-      emit_frame(xs, nb);
+      out.emit(xs, nb, lane);
     }
     wave_priority<0>();
   };
@@ -317,7 +278,7 @@ __global__ __launch_bounds__(64 * W5R, 4) void stft512_run_fwd_kernel(P5Run p) {
     }
     pair_body(fresh, 2 * i + 1 < T);
   }
-  if (lane < rot) put(sp, carry);
+  out.end(lane);
 }
 
 // one frame's one-sided spectrum -> A[k] * 2 (k = lane + 64 m, m = 0..3): E + i O of the inverse split
@@ -534,9 +495,9 @@ int launch_istft512_ola(const float2* X, const float* mag, const float* phase, l
   if (hop == 64) { if (polar) OLA5(true, 1); else OLA5(false, 1); }
   else if (hop == 128) { if (polar) OLA5(true, 2); else OLA5(false, 2); }
   else if (hop == 256) { if (polar) OLA5(true, 4); else OLA5(false, 4); }
-  else return -2;
+  else return AT_EUNSUPPORTED;
 #undef OLA5
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return hipGetLastError() == hipSuccess ? AT_OK : AT_ELAUNCH;
 }
 
 // ---------------------------------------------------------------------------
@@ -793,7 +754,7 @@ int launch_stft512_mel(const float* x, long long B, long long L, long long clip_
   p.table_floats = table_floats;
   p.row_floats = (F5 + max_walk + 63) / 64 * 64;
   const size_t lds = sizeof(float) * ((size_t)2 * W5 * p.row_floats + table_floats) + sizeof(int) * (size_t)2 * 64 * bank->n_passes;
-  if (lds > 48 * 1024) return -2;
+  if (lds > 48 * 1024) return AT_EUNSUPPORTED;
   const long long npairs = B * p.pairs_per_clip;
   long long ppw = (npairs + 256LL * 8 * W5 - 1) / (256LL * 8 * W5);
   if (ppw < 4) ppw = 4;
@@ -805,7 +766,7 @@ int launch_stft512_mel(const float* x, long long B, long long L, long long clip_
   if (channel_major && bank->n_passes == 1) kernel = stft512_mel_kernel<1>;
   else if (channel_major && bank->n_passes == 2) kernel = stft512_mel_kernel<2>;
   hipLaunchKernelGGL(kernel, dim3(grid), dim3(64 * W5), lds, stream, p);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return hipGetLastError() == hipSuccess ? AT_OK : AT_ELAUNCH;
 }
 
 int launch_stft512_fwd(const float* x, long long B, long long L, long long clip_stride, long long T, int hop, int center,
@@ -820,24 +781,15 @@ int launch_stft512_fwd(const float* x, long long B, long long L, long long clip_
   // output, no phase side output
   if (center && hop == 128 && !phase && L >= 512 && (clip_stride & 1) == 0 && (((uintptr_t)x) & 7) == 0 &&
       (((uintptr_t)out) & 511) == 0 && (((uintptr_t)window) & 7) == 0 && variant(kVarFrameKernels) == 0) {
-    P5Run q = {};
-    q.x = x; q.window = window; q.tw = tw; q.tw512 = tw512; q.X = out;
-    q.B = B; q.L = L; q.clip_stride = clip_stride; q.T = T;
-    const long long slots = resident_waves(stft512_run_fwd_kernel, 64 * W5R, 0);
-    const long long pairs = (T + 1) / 2;
-    q.pairs_per_run = plan_units_per_run(B, pairs, slots, 8, 1);
-    if (const long long v = forced_units_per_run(pairs)) q.pairs_per_run = v;
-    q.runs_per_clip = (pairs + q.pairs_per_run - 1) / q.pairs_per_run;
-    const long long waves = B * q.runs_per_clip;
-    hipLaunchKernelGGL(stft512_run_fwd_kernel, dim3((unsigned)((waves + W5R - 1) / W5R)), dim3(64 * W5R), 0, stream, q);
-    return hipGetLastError() == hipSuccess ? 0 : -5;
+    return launch_run_fwd(stft512_run_fwd_kernel, W5R, (T + 1) / 2, {x, window, tw, tw512, out, B, L, clip_stride, T, 0, 0},
+                          stream);
   }
   const long long npairs = B * p.pairs_per_clip;
   p.pairs_per_block = units_per_block(npairs, W5);
   const long long blocks = (npairs + p.pairs_per_block - 1) / p.pairs_per_block;
   if (phase) hipLaunchKernelGGL(stft512_fwd_kernel<true>, dim3((unsigned)blocks), dim3(64 * W5), 0, stream, p);
   else hipLaunchKernelGGL(stft512_fwd_kernel<false>, dim3((unsigned)blocks), dim3(64 * W5), 0, stream, p);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return hipGetLastError() == hipSuccess ? AT_OK : AT_ELAUNCH;
 }
 
 int launch_irfft512_frames(const float2* X, const float* mag, const float* phase, long long nframes,
@@ -846,14 +798,14 @@ int launch_irfft512_frames(const float2* X, const float* mag, const float* phase
   if (nframes == 0) return 0;
   P5 p = {};
   p.X = const_cast<float2*>(X); p.mag = mag; p.phase = phase; p.window = window; p.tw = tw; p.tw512 = tw512; p.y = frames;
-  if (frames_per_clip <= 0 || nframes % frames_per_clip) return -2;
+  if (frames_per_clip <= 0 || nframes % frames_per_clip) return AT_EUNSUPPORTED;
   p.T = frames_per_clip; p.n_clips = nframes / frames_per_clip; p.pairs_per_clip = (frames_per_clip + 1) / 2;
   const long long npairs = p.n_clips * p.pairs_per_clip;
   p.pairs_per_block = units_per_block(npairs, W5);
   const long long blocks = (npairs + p.pairs_per_block - 1) / p.pairs_per_block;
   if (X) hipLaunchKernelGGL(irfft512_frames_kernel<false>, dim3((unsigned)blocks), dim3(64 * W5), 0, stream, p);
   else hipLaunchKernelGGL(irfft512_frames_kernel<true>, dim3((unsigned)blocks), dim3(64 * W5), 0, stream, p);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return hipGetLastError() == hipSuccess ? AT_OK : AT_ELAUNCH;
 }
 
 }  // namespace at_hip

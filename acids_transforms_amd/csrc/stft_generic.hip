@@ -297,7 +297,7 @@ static int set_lds(const void* fn, size_t bytes) {
   if (bytes > 64 * 1024) {
     if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
       (void)hipGetLastError();   // do not leave the error latched for the next launch's check
-      return -5;
+      return AT_ELAUNCH;
     }
   }
   return 0;
@@ -316,10 +316,10 @@ int launch_rfft_generic(const float* x, long long B, long long L, long long clip
   GenFwdParams p = {x, window, out, phase, B, L, clip_stride, T, n_fft, hop, center, use_tw};
   // 2 M (+ 3 M / 4 + 1 FFT twiddles + M + 1 split twiddles)
   size_t lds = sizeof(float2) * (size_t)(n_fft + (use_tw ? 3 * n_fft / 8 + 1 + n_fft / 2 + 1 : 0));
-  if (set_lds((const void*)rfft_generic_kernel, lds)) return -5;
+  if (set_lds((const void*)rfft_generic_kernel, lds)) return AT_ELAUNCH;
   int threads = n_fft / 4 < 64 ? 64 : (n_fft / 4 > 256 ? 256 : n_fft / 4);
   hipLaunchKernelGGL(rfft_generic_kernel, dim3(frame_walkers(B * T)), dim3(threads), lds, stream, p);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return hipGetLastError() == hipSuccess ? AT_OK : AT_ELAUNCH;
 }
 
 int launch_irfft_generic(const float2* X, const float* mag, const float* phase, long long nframes, int n_fft,
@@ -328,10 +328,10 @@ int launch_irfft_generic(const float2* X, const float* mag, const float* phase, 
   const int use_tw = n_fft <= 8192;      // 16384: the tables do not fit next to the two frame buffers
   GenInvParams p = {X, mag, phase, window, frames, nframes, n_fft, use_tw};
   size_t lds = sizeof(float2) * (size_t)(n_fft + 2 + (use_tw ? 3 * n_fft / 8 + 1 + n_fft / 2 + 1 : 0));   // a, b (+ twiddles)
-  if (set_lds((const void*)irfft_generic_kernel, lds)) return -5;
+  if (set_lds((const void*)irfft_generic_kernel, lds)) return AT_ELAUNCH;
   int threads = n_fft / 4 < 64 ? 64 : (n_fft / 4 > 256 ? 256 : n_fft / 4);
   hipLaunchKernelGGL(irfft_generic_kernel, dim3(frame_walkers(nframes)), dim3(threads), lds, stream, p);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return hipGetLastError() == hipSuccess ? AT_OK : AT_ELAUNCH;
 }
 
 int launch_ola_gather(const float* frames, long long B, long long T, int n_fft, int hop, const float* window,
@@ -345,7 +345,7 @@ int launch_ola_gather(const float* frames, long long B, long long T, int n_fft, 
   blocks = forced_walkers(blocks, blocks > 65536 ? 65536 : blocks);       // AT_VARIANT_FRAME_WALKERS (tests)
   if (vec4) hipLaunchKernelGGL(ola_gather4_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, p);
   else hipLaunchKernelGGL(ola_gather_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, p);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return hipGetLastError() == hipSuccess ? AT_OK : AT_ELAUNCH;
 }
 
 }  // namespace at_hip

@@ -293,7 +293,7 @@ static bool mix_plan(int M, MixPlan* plan) {
 static int mix_set_lds(const void* fn, size_t bytes) {
   if (bytes > 64 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
     (void)hipGetLastError();
-    return -5;
+    return AT_ELAUNCH;
   }
   return 0;
 }
@@ -313,11 +313,11 @@ int launch_rfft_mixed(const float* x, long long B, long long L, long long clip_s
   if (B * T == 0) return 0;
   const int M = (n_fft & 1) ? n_fft : n_fft / 2;
   MixFwdParams p = {x, window, out, phase, B, L, clip_stride, T, n_fft, hop, center, M <= 4096, {}};
-  if (!mix_plan(M, &p.plan)) return -2;
+  if (!mix_plan(M, &p.plan)) return AT_EUNSUPPORTED;
   const size_t lds = sizeof(float2) * (size_t)(2 * M + (p.use_tw ? 2 * M + 1 : 0));     // a, b (+ FFT and split twiddles)
-  if (mix_set_lds((const void*)rfft_mixed_kernel, lds)) return -5;
+  if (mix_set_lds((const void*)rfft_mixed_kernel, lds)) return AT_ELAUNCH;
   hipLaunchKernelGGL(rfft_mixed_kernel, dim3(mix_walkers(B * T)), dim3(mix_threads(M)), lds, stream, p);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return hipGetLastError() == hipSuccess ? AT_OK : AT_ELAUNCH;
 }
 
 int launch_irfft_mixed(const float2* X, const float* mag, const float* phase, long long nframes, int n_fft,
@@ -325,11 +325,11 @@ int launch_irfft_mixed(const float2* X, const float* mag, const float* phase, lo
   if (nframes == 0) return 0;
   const int M = (n_fft & 1) ? n_fft : n_fft / 2;
   MixInvParams p = {X, mag, phase, window, frames, nframes, n_fft, M <= 4096, {}};
-  if (!mix_plan(M, &p.plan)) return -2;
+  if (!mix_plan(M, &p.plan)) return AT_EUNSUPPORTED;
   const size_t lds = sizeof(float2) * (size_t)(2 * M + 2 + (p.use_tw ? 2 * M + 1 : 0));
-  if (mix_set_lds((const void*)irfft_mixed_kernel, lds)) return -5;
+  if (mix_set_lds((const void*)irfft_mixed_kernel, lds)) return AT_ELAUNCH;
   hipLaunchKernelGGL(irfft_mixed_kernel, dim3(mix_walkers(nframes)), dim3(mix_threads(M)), lds, stream, p);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return hipGetLastError() == hipSuccess ? AT_OK : AT_ELAUNCH;
 }
 
 }  // namespace at_hip

@@ -251,9 +251,9 @@ int launch_stft_small_fwd(int n_fft, const float* x, long long B, long long L, l
     if (phase) hipLaunchKernelGGL((stft_small_fwd_kernel<8, true>), dim3(blocks), dim3(64 * WS), 0, stream, p);
     else hipLaunchKernelGGL((stft_small_fwd_kernel<8, false>), dim3(blocks), dim3(64 * WS), 0, stream, p);
   } else {
-    return -2;
+    return AT_EUNSUPPORTED;
   }
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return hipGetLastError() == hipSuccess ? AT_OK : AT_ELAUNCH;
 }
 
 int launch_irfft_small_frames(int n_fft, const float2* X, const float* mag, const float* phase, long long nframes,
@@ -262,7 +262,7 @@ int launch_irfft_small_frames(int n_fft, const float2* X, const float* mag, cons
   const int K = 1024 / n_fft;
   PSm p = {};
   p.X = const_cast<float2*>(X); p.mag = mag; p.phase = phase; p.window = window; p.tw = tw; p.twk = twk; p.y = frames;
-  if (frames_per_clip <= 0 || nframes % frames_per_clip) return -2;
+  if (frames_per_clip <= 0 || nframes % frames_per_clip) return AT_EUNSUPPORTED;
   p.T = frames_per_clip; p.n_clips = nframes / frames_per_clip;
   p.groups_per_clip = (frames_per_clip + K - 1) / K;
   const long long ngroups = p.n_clips * p.groups_per_clip;
@@ -276,9 +276,9 @@ int launch_irfft_small_frames(int n_fft, const float2* X, const float* mag, cons
     if (polar) hipLaunchKernelGGL((irfft_small_frames_kernel<8, true>), dim3(blocks), dim3(64 * WS), 0, stream, p);
     else hipLaunchKernelGGL((irfft_small_frames_kernel<8, false>), dim3(blocks), dim3(64 * WS), 0, stream, p);
   } else {
-    return -2;
+    return AT_EUNSUPPORTED;
   }
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return hipGetLastError() == hipSuccess ? AT_OK : AT_ELAUNCH;
 }
 
 }  // namespace at_hip

@@ -64,7 +64,7 @@ int launch_rfft_adj_edge(float* frames, const float2* G, const float* window, lo
   else
     hipLaunchKernelGGL(rfft_adj_edge_kernel<1>, dim3(flat_grid(rows * n_fft)), dim3(256), 0, stream, frames, G, window,
                        rows, n_fft);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return hipGetLastError() == hipSuccess ? AT_OK : AT_ELAUNCH;
 }
 
 // ---- adjoint of OverlapAdd.forward --------------------------------------------------------------------------------------
@@ -124,7 +124,7 @@ int launch_oadd_forward_adj(const float* gframes, long long S, long long n, int 
     hipLaunchKernelGGL(oadd_forward_adj_kernel<4>, dim3((unsigned)((C / 4 + 255) / 256), gy), dim3(256), 0, stream, p);
   else
     hipLaunchKernelGGL(oadd_forward_adj_kernel<1>, dim3((unsigned)((C + 255) / 256), gy), dim3(256), 0, stream, p);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return hipGetLastError() == hipSuccess ? AT_OK : AT_ELAUNCH;
 }
 
 // ---- adjoint of OverlapAdd.invert ---------------------------------------------------------------------------------------
@@ -168,7 +168,7 @@ int launch_oadd_invert_adj(const float* gy, long long S, long long n, int n_fft,
   else
     hipLaunchKernelGGL(oadd_invert_adj_kernel<1>, dim3((unsigned)((per_stream + 255) / 256), grid_y), dim3(256), 0, stream,
                        gy, gain, gframes, S, n, n_fft, hop, out_len);
-  return hipGetLastError() == hipSuccess ? 0 : -5;
+  return hipGetLastError() == hipSuccess ? AT_OK : AT_ELAUNCH;
 }
 
 }  // namespace at_hip

@@ -147,6 +147,38 @@ def fwd_case_classes(n_fft, hop, v, T, L):
     return run_classes(T, v, tail_unit=tail_start(n_fft, hop, L))
 
 
+# ---- the aligned row stream of the sliding forwards (csrc/row_stream.h) -----------------------------------------------------
+# The spectrum's rows leave as one stream of 64-element blocks, rotated by the global frame index g = b T + t mod 64; the
+# frame with g = 63 (mod 64) ends on a block boundary and stores one block more -- the wrap.  Where it falls in a run
+# (first frame: on the masked head block; last: an empty carry at the end) depends on the clip's place in the batch, so
+# the classes are taken over the BATCH clips the GPU sweeps run.  At n_fft 512 a run is frame pairs and the wrap falls on
+# a pair's first or second frame (the one moved up a lane).
+BATCH = 3
+STREAM_CLASSES = {"wrap_first_in_run", "wrap_inside_run", "wrap_last_in_run"}
+STREAM_CLASSES_512 = STREAM_CLASSES | {"wrap_on_pair_first", "wrap_on_pair_second"}
+
+
+def stream_classes(n_fft, v, T, B=BATCH):
+    """Where the wrap frames of B clips of T frames fall in the runs of the forced length v."""
+    per = 2 if n_fft == 512 else 1                      # frames per unit
+    c = set()
+    for b in range(B):
+        for a, e in runs((T + per - 1) // per, v):
+            t0, t1 = per * a, min(per * e, T)
+            for t in range(t0, t1):
+                if (b * T + t) % 64 != 63:
+                    continue
+                if t == t0:
+                    c.add("wrap_first_in_run")
+                if t == t1 - 1:
+                    c.add("wrap_last_in_run")
+                if t0 < t < t1 - 1:
+                    c.add("wrap_inside_run")
+                if n_fft == 512:
+                    c.add("wrap_on_pair_second" if t % 2 else "wrap_on_pair_first")
+    return c
+
+
 # ---- fused inverses at n_fft 512 / 2048 / 4096 (istft512_ola_kernel, istft2048_ola_kernel, istft4096_ola_kernel) ---------
 # R = n_fft / hop frames overlap a hop; output hop q is block c = q + lead, summed from frames c - R + 1 .. c; the first
 # lead = R / 2 blocks are torch.istft's trimmed front.  Units: output hops at 2048 / 4096, frame pairs at 512 (pair i holds

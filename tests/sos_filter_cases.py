@@ -142,7 +142,9 @@ def case(name, L):
     stacked = np.concatenate([x64, x64[:, ::-1], x64])
     y, zf = sosfilt(sos, stacked, np.concatenate([np.zeros_like(zi), np.zeros_like(zi), zi]))
     fwd = y[:ROWS]
-    out = dict(sos=sos, x=x, zi=zi, fwd=fwd, rev=y[ROWS:2 * ROWS, ::-1].copy(), yzi=y[2 * ROWS:], zf=zf[2 * ROWS:],
+    # sos: a copy, so that freezing the case leaves FILTERS writable (scipy.signal.sosfilt refuses a read-only table, and
+    # test_sos_filter_cpu.py hands it FILTERS' own arrays after the GPU tests have been through here)
+    out = dict(sos=sos.copy(), x=x, zi=zi, fwd=fwd, rev=y[ROWS:2 * ROWS, ::-1].copy(), yzi=y[2 * ROWS:], zf=zf[2 * ROWS:],
                zp=sosfilt_reverse(sos, fwd))
     for v in out.values():
         v.setflags(write=False)

@@ -54,6 +54,24 @@ def test_run_sweeps_reach_every_run_geometry():
     assert P.RUN_CLASSES - {"run_in_padded_tail"} <= hit, sorted(P.RUN_CLASSES - {"run_in_padded_tail"} - hit)
 
 
+def test_forward_sweeps_reach_every_place_of_the_stream_wrap():
+    """With the BATCH clips of the GPU sweeps, every forward sweep puts a wrap frame (global index 63 mod 64) first in a
+    run, inside one and last in one; at n_fft 512 on either frame of a pair."""
+    assert P.stream_classes(1024, 8, 64, B=1) == {"wrap_last_in_run"}                 # frame 63 closes the run [56, 64)
+    assert P.stream_classes(1024, 13, 66, B=1) == {"wrap_inside_run"}                 # the run [52, 65)
+    assert P.stream_classes(1024, 9, 64, B=1) == {"wrap_first_in_run", "wrap_last_in_run"}     # the run [63, 64)
+    assert P.stream_classes(512, 8, 64, B=1) == {"wrap_last_in_run", "wrap_on_pair_second"}
+    assert P.stream_classes(512, 8, 21, B=4) == {"wrap_first_in_run", "wrap_on_pair_first"}     # clip 3, frame 0
+    for (n_fft, hop), sweep in P.FWD_SWEEPS.items():
+        hit = set()
+        for v, T, L in sweep:
+            hit |= P.stream_classes(n_fft, v, T)
+        want = P.STREAM_CLASSES_512 if n_fft == 512 else P.STREAM_CLASSES
+        assert want <= hit, (n_fft, hop, sorted(want - hit))
+    # FUSED_SWEEP stops at 3 x 20 frames, before the first wrap: the fused forms' wrap is not this sweep's subject
+    assert not any(P.stream_classes(1024, v, T) for v, T, L in P.FUSED_SWEEP)
+
+
 # ---- fused inverses at n_fft 512 / 2048 / 4096 --------------------------------------------------------------------------
 def test_inverse_units_and_default_plan():
     # n_fft 512: pairs that hold a valid block; lead = 256 / hop blocks are trimmed at the front

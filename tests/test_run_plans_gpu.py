@@ -22,7 +22,7 @@ from oracle import oracle as O
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-5
-B = 3
+B = P.BATCH      # 3 clips: where the stream's wrap frames fall in the runs depends on it (plan_cases.stream_classes)
 
 
 def cpu(t):

@@ -12,7 +12,9 @@ library exports are bound, so an older build of the same ABI version loads too.
 
 --equal times nothing: it runs every entry the n_fft 512 / 2048 / 4096 kernels serve (equal_entries) under the in-tree
 library and under each of --libs on the same seeded inputs, 3 short clips and the 1024 x 176400 batch, and exits
-non-zero unless every output is bit-identical (torch.equal) -- the check of a refactor of those kernels."""
+non-zero unless every output is bit-identical (torch.equal) -- the check of a refactor of those kernels.  At n_fft 1024
+the entries are the two forwards that write the spectrum as an aligned stream (csrc/row_stream.h): the plain forward
+and the fused 128-mel forward with the spectrum stored."""
 import argparse
 import ctypes
 import os
@@ -71,6 +73,10 @@ def equal_entries(n, xs):
     from oracle import oracle as O
     B, Lx = xs.shape
     w = torch.hann_window(n, device=dev)
+    if n == 1024:
+        band = BandedBank(A.Magnitude(n_mels=128).mel_bank.reshape(513, -1))
+        return [("forward run", lambda: ops.stft_forward(xs, w, n, n // 4)),
+                ("fused mel 128 + spectrum", lambda: ops.stft_mel_forward(xs, w, band, "log1p", power=1, want_spectrum=True))]
     odd = xs[:, :Lx - 1].contiguous()
     out = [("forward run", lambda: ops.stft_forward(xs, w, n, n // 4))]
     for hop in (n // 4, 100):
@@ -102,6 +108,8 @@ def equal_entries(n, xs):
 def same(a, b):
     if isinstance(a, tuple):
         return all(same(u, v) for u, v in zip(a, b))
+    if a is None or b is None:
+        return a is b
     return torch.equal(a, b) or torch.equal(a.view(torch.int32 if a.dtype == torch.float32 else torch.int64),
                                             b.view(torch.int32 if b.dtype == torch.float32 else torch.int64))
 
