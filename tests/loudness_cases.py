@@ -37,6 +37,7 @@ TOL = 1e-5                         # the project's standing normwise bound, max|
 TOL_LU = 1e-4                      # 1e-5 on y: 10 log10(1 + 2e-5) = 8.7e-5
 LEADS = ((), (3,), (2, 3), (70,))
 HOPS = (16, 17, 255, 800, 4096, 4097, 4410)
+PARITY_LENGTHS = (TILE - 1, TILE, TILE + 1, 2 * TILE + 5)             # the rows every hop of HOPS runs at: around the tile cuts
 
 
 def hop_of(sr):

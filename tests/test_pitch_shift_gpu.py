@@ -21,13 +21,19 @@ def _fit(y, n):
     return torch.nn.functional.pad(y, (0, n - y.shape[-1]))
 
 
-def _chain(x, n_steps, n_fft=512):
-    """torchaudio.functional.pitch_shift written out with the package's public pieces."""
-    rate, orig_freq = C.pitch_rates(SR, n_steps)
-    L = x.shape[-1]
+def _stretched(x, n_steps, n_fft=512):
+    """The chain up to the converter: STFT -> TimeStretch -> STFT.invert, cropped or padded to round(L / rate) samples."""
+    rate, _ = C.pitch_rates(SR, n_steps)
     stft = A.STFT(SR, n_fft, n_fft // 4).to(x.device)
     y = stft.invert(A.TimeStretch(rate)(stft(x)))
-    y = _fit(y, int(round(L / rate)))
+    return _fit(y, int(round(x.shape[-1] / rate)))
+
+
+def _chain(x, n_steps, n_fft=512):
+    """torchaudio.functional.pitch_shift written out with the package's public pieces."""
+    _, orig_freq = C.pitch_rates(SR, n_steps)
+    L = x.shape[-1]
+    y = _stretched(x, n_steps, n_fft)
     if x.requires_grad:
         y = A.Resample(orig_freq, SR, direct=True).to(x.device)(y)
     else:
