@@ -63,7 +63,10 @@ _SIGNATURES = {
     "at_sos_hop_power_plan": [c_i64, c_i64, c_int, c_i64, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), ctypes.POINTER(c_int)],
     "at_sos_hop_power": [c_f, c_i64, c_i64, c_f, c_int, c_i64, c_f, c_f],
     "at_sos_filter_hop_scaled": [c_f, c_i64, c_i64, c_f, c_int, c_i64, c_f, c_f, c_f],
+    "at_sos_hop_power_stream": [c_f, c_i64, c_i64, c_f, c_int, c_i64, c_i64, c_f, c_f, c_f, c_f, c_f, c_i64, c_i64, c_f],
     "at_loudness_gate": [c_f, c_i64, c_int, c_i64, c_i64, c_int, c_f, c_dbl, c_dbl, c_f, c_f, c_f, c_f],
+    "at_loudness_gate_ld": [c_f, c_i64, c_int, c_i64, c_i64, c_i64, c_int, c_f, c_dbl, c_dbl, c_f, c_f, c_f, c_f],
+    "at_loudness_range": [c_f, c_i64, c_int, c_i64, c_i64, c_i64, c_int, c_f, c_dbl, c_dbl, c_f, c_f, c_f, c_f],
     "at_loudness_gate_backward": [c_f, c_f, c_f, c_i64, c_int, c_i64, c_i64, c_int, c_f, c_dbl, c_dbl, c_f, c_f],
     "at_loudness_blocks_backward": [c_f, c_f, c_i64, c_int, c_i64, c_i64, c_int, c_f, c_f, c_f],
     "at_fft_convolve_plan": [c_i64, c_i64, c_int, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), ctypes.POINTER(c_i64),

@@ -37,11 +37,12 @@ struct LoudWeights {
   double g[kLoudMaxChannels];
 };
 
-__device__ __forceinline__ double loud_block_power(const double* __restrict__ pc, int C, long long nh, int hb, long long j,
+// (ld: the hops between one channel's row and the next -- nh for a packed tensor, more for a window of a longer history)
+__device__ __forceinline__ double loud_block_power(const double* __restrict__ pc, int C, long long ld, int hb, long long j,
                                                    const LoudWeights& G, double norm) {
   double acc = 0.0;
   for (int c = 0; c < C; ++c) {
-    const double* s = pc + c * nh + j;
+    const double* s = pc + c * ld + j;
     double sum = 0.0;
     for (int k = 0; k < hb; ++k) sum = sum + s[k];
     acc = acc + G.g[c] * sum;
@@ -71,7 +72,7 @@ __device__ __forceinline__ void loud_join(double* rs, double* rn, int tid, doubl
 }
 
 __global__ __launch_bounds__(kLoudLanes) void loudness_gate_kernel(const double* __restrict__ power, long long clips, int C,
-                                                                   long long nh, int hb, LoudWeights G, double norm,
+                                                                   long long nh, long long ld, int hb, LoudWeights G, double norm,
                                                                    double abs_threshold, double rel_ratio,
                                                                    float* __restrict__ lufs, double* __restrict__ stats,
                                                                    float* __restrict__ block_lufs) {
@@ -79,10 +80,10 @@ __global__ __launch_bounds__(kLoudLanes) void loudness_gate_kernel(const double*
   const int tid = threadIdx.x;
   const long long nb = nh - hb + 1;
   for (long long clip = blockIdx.x; clip < clips; clip += gridDim.x) {
-    const double* pc = power + clip * C * nh;
+    const double* pc = power + clip * C * ld;
     double s1 = 0.0, n1 = 0.0;
     for (long long j = tid; j < nb; j += kLoudLanes) {
-      const double p = loud_block_power(pc, C, nh, hb, j, G, norm);
+      const double p = loud_block_power(pc, C, ld, hb, j, G, norm);
       if (block_lufs) block_lufs[clip * nb + j] = (float)(kLoudOffset + 10.0 * log10(p));
       if (loud_above(p, abs_threshold)) {
         s1 = s1 + p;
@@ -96,7 +97,7 @@ __global__ __launch_bounds__(kLoudLanes) void loudness_gate_kernel(const double*
     double s2 = 0.0, n2 = 0.0;
     if (n1 > 0.0) {
       for (long long j = tid; j < nb; j += kLoudLanes) {
-        const double p = loud_block_power(pc, C, nh, hb, j, G, norm);
+        const double p = loud_block_power(pc, C, ld, hb, j, G, norm);
         if (loud_above(p, abs_threshold) && loud_above(p, rel_threshold)) {
           s2 = s2 + p;
           n2 = n2 + 1.0;
@@ -111,6 +112,114 @@ __global__ __launch_bounds__(kLoudLanes) void loudness_gate_kernel(const double*
       stats[clip * 3 + 1] = p_rel;
       stats[clip * 3 + 2] = n2;
     }
+  }
+}
+
+// Loudness range (EBU Tech 3342) of the block powers (hb = 30 by the host): with J2 as above (rel_ratio 0.01 by the host),
+// n = |J2| and q the ascending order of {p_j : j in J2},
+//     lra = 10 log10(q[rnd(0.95 (n - 1))] / q[rnd(0.10 (n - 1))]),   rnd(v) = floor(v + 0.5);   0 when n == 0.
+// The two order statistics come from a radix select on the order-preserving unsigned image of the double's bits: eight
+// passes of eight bits from the top, each a 256-bin histogram in LDS of the keys that share the prefix found so far, one
+// histogram per statistic.  The counts are integers, so the LDS atomics cannot change the result: it is a function of the
+// clip's hop powers alone.  The block powers are formed once, into `work`, by the lanes that read them back.
+__device__ __forceinline__ unsigned long long loud_key(double p) {
+  const unsigned long long u = (unsigned long long)__double_as_longlong(p);
+  return (u >> 63) ? ~u : u | 0x8000000000000000ull;
+}
+__device__ __forceinline__ double loud_unkey(unsigned long long k) {
+  return __longlong_as_double((long long)((k >> 63) ? k & 0x7fffffffffffffffull : ~k));
+}
+
+__global__ __launch_bounds__(kLoudLanes) void loudness_range_kernel(const double* __restrict__ power, long long clips, int C,
+                                                                    long long nh, long long ld, int hb, LoudWeights G,
+                                                                    double norm, double abs_threshold, double rel_ratio,
+                                                                    float* __restrict__ lra, double* __restrict__ stats,
+                                                                    double* __restrict__ work) {
+  __shared__ double rs[kLoudLanes], rn[kLoudLanes];
+  __shared__ unsigned hist[2][256];
+  __shared__ unsigned long long prefix[2], rank[2];
+  const int tid = threadIdx.x;
+  const long long nb = nh - hb + 1;
+  for (long long clip = blockIdx.x; clip < clips; clip += gridDim.x) {
+    const double* pc = power + clip * C * ld;
+    double* ws = work + clip * nb;                       // lane t writes and reads blocks t, t + 256, ...: no barrier
+    double s1 = 0.0, n1 = 0.0;
+    for (long long j = tid; j < nb; j += kLoudLanes) {
+      const double p = loud_block_power(pc, C, ld, hb, j, G, norm);
+      ws[j] = p;
+      if (loud_above(p, abs_threshold)) {
+        s1 = s1 + p;
+        n1 = n1 + 1.0;
+      }
+    }
+    loud_join(rs, rn, tid, s1, n1);
+    const double p_abs = n1 > 0.0 ? s1 / n1 : 0.0;
+    const double rel_threshold = rel_ratio * p_abs;
+    double nans = 0.0, n2 = 0.0;
+    if (n1 > 0.0) {
+      for (long long j = tid; j < nb; j += kLoudLanes) {
+        const double p = ws[j];
+        if (loud_above(p, abs_threshold) && loud_above(p, rel_threshold)) {
+          n2 = n2 + 1.0;
+          if (p != p) nans = nans + 1.0;
+        }
+      }
+    }
+    loud_join(rs, rn, tid, nans, n2);
+    if (!(n2 > 0.0) || nans > 0.0) {                     // (uniform: every lane holds the joined values)
+      if (tid == 0) {
+        const double v = nans > 0.0 ? (double)NAN : 0.0;
+        lra[clip] = (float)v;
+        stats[clip * 4] = v;
+        stats[clip * 4 + 1] = v;
+        stats[clip * 4 + 2] = n2;
+        stats[clip * 4 + 3] = p_abs;
+      }
+      continue;
+    }
+    if (tid < 2) {
+      prefix[tid] = 0;
+      rank[tid] = (unsigned long long)floor((tid ? 0.95 : 0.10) * (n2 - 1.0) + 0.5);
+    }
+    for (int byte = 7; byte >= 0; --byte) {
+      hist[0][tid] = 0;
+      hist[1][tid] = 0;
+      __syncthreads();                                   // (also: prefix and rank)
+      const unsigned long long pre0 = prefix[0], pre1 = prefix[1];
+      for (long long j = tid; j < nb; j += kLoudLanes) {
+        const double p = ws[j];
+        if (loud_above(p, abs_threshold) && loud_above(p, rel_threshold)) {
+          const unsigned long long key = loud_key(p);
+          const unsigned long long above = byte == 7 ? 0ull : key >> (8 * byte + 8);
+          const unsigned bin = (unsigned)(key >> (8 * byte)) & 255u;
+          if (above == pre0) atomicAdd(&hist[0][bin], 1u);
+          if (above == pre1) atomicAdd(&hist[1][bin], 1u);
+        }
+      }
+      __syncthreads();
+      if (tid == 0 || tid == 64) {                       // one lane per statistic walks its bins
+        const int s = tid >> 6;
+        unsigned long long k = rank[s], before = 0;
+        int bin = 0;
+        for (; bin < 255; ++bin) {
+          const unsigned long long c = hist[s][bin];
+          if (k < before + c) break;
+          before += c;
+        }
+        rank[s] = k - before;
+        prefix[s] = (prefix[s] << 8) | (unsigned long long)bin;
+      }
+      __syncthreads();
+    }
+    if (tid == 0) {
+      const double lo = loud_unkey(prefix[0]), hi = loud_unkey(prefix[1]);
+      lra[clip] = (float)(10.0 * log10(hi / lo));
+      stats[clip * 4] = lo;
+      stats[clip * 4 + 1] = hi;
+      stats[clip * 4 + 2] = n2;
+      stats[clip * 4 + 3] = p_abs;
+    }
+    __syncthreads();                                     // prefix is rewritten for the next clip
   }
 }
 
@@ -180,6 +289,15 @@ static int loud_check(int64_t clips, int C, int64_t nh, int64_t hop, int hb, con
   return AT_OK;
 }
 
+// a window of nh hops of rows that lie ld hops apart
+static int loud_check_ld(int64_t clips, int C, int64_t nh, int64_t ld, int64_t hop, int hb, const double* weights, LoudWeights& G) {
+  if (ld < nh) return AT_EINVAL;
+  const int rc = loud_check(clips, C, nh, hop, hb, weights, G);
+  if (rc != AT_OK) return rc;
+  if (clips > 0 && ld > INT64_MAX / 8 / C / clips) return AT_EUNSUPPORTED;          // 64-bit byte offsets
+  return AT_OK;
+}
+
 static dim3 loud_grid(int64_t clips) {
   return dim3((unsigned)(clips < kLoudMaxGrid ? clips : kLoudMaxGrid));
 }
@@ -190,10 +308,11 @@ using namespace at_hip;
 
 extern "C" {
 
-int at_loudness_gate(const double* power, int64_t clips, int C, int64_t nh, int64_t hop, int hb, const double* weights_host,
-                     double abs_threshold, double rel_ratio, float* lufs, double* stats, float* block_lufs, void* stream) {
+int at_loudness_gate_ld(const double* power, int64_t clips, int C, int64_t nh, int64_t ld, int64_t hop, int hb,
+                        const double* weights_host, double abs_threshold, double rel_ratio, float* lufs, double* stats,
+                        float* block_lufs, void* stream) {
   LoudWeights G;
-  const int rc = loud_check(clips, C, nh, hop, hb, weights_host, G);
+  const int rc = loud_check_ld(clips, C, nh, ld, hop, hb, weights_host, G);
   if (rc != AT_OK) return rc;
   if (lufs && (!isfinite(abs_threshold) || !isfinite(rel_ratio) || abs_threshold < 0.0 || rel_ratio < 0.0)) return AT_EINVAL;
   if ((!lufs && !block_lufs) || (lufs && !stats)) return AT_EINVAL;
@@ -202,7 +321,32 @@ int at_loudness_gate(const double* power, int64_t clips, int C, int64_t nh, int6
   if (!power && nh >= hb) return AT_EINVAL;
   if ((((uintptr_t)power | (uintptr_t)stats) & 7) || (((uintptr_t)lufs | (uintptr_t)block_lufs) & 3)) return AT_EINVAL;
   hipLaunchKernelGGL(loudness_gate_kernel, loud_grid(clips), dim3(kLoudLanes), 0, (hipStream_t)stream, power, (long long)clips,
-                     C, (long long)nh, hb, G, (double)hb * (double)hop, abs_threshold, rel_ratio, lufs, stats, block_lufs);
+                     C, (long long)nh, (long long)ld, hb, G, (double)hb * (double)hop, abs_threshold, rel_ratio, lufs, stats,
+                     block_lufs);
+  return hipGetLastError() == hipSuccess ? AT_OK : AT_ELAUNCH;
+}
+
+int at_loudness_gate(const double* power, int64_t clips, int C, int64_t nh, int64_t hop, int hb, const double* weights_host,
+                     double abs_threshold, double rel_ratio, float* lufs, double* stats, float* block_lufs, void* stream) {
+  return at_loudness_gate_ld(power, clips, C, nh, nh, hop, hb, weights_host, abs_threshold, rel_ratio, lufs, stats, block_lufs,
+                             stream);
+}
+
+int at_loudness_range(const double* power, int64_t clips, int C, int64_t nh, int64_t ld, int64_t hop, int hb,
+                      const double* weights_host, double abs_threshold, double rel_ratio, float* lra, double* stats,
+                      double* workspace, void* stream) {
+  LoudWeights G;
+  const int rc = loud_check_ld(clips, C, nh, ld, hop, hb, weights_host, G);
+  if (rc != AT_OK) return rc;
+  if (!isfinite(abs_threshold) || !isfinite(rel_ratio) || abs_threshold < 0.0 || rel_ratio < 0.0) return AT_EINVAL;
+  if (!lra || !stats) return AT_EINVAL;
+  if (clips == 0) return AT_OK;
+  if (nh >= hb && (!power || !workspace)) return AT_EINVAL;
+  if (nh - hb + 1 > INT32_MAX) return AT_EUNSUPPORTED;   // the histograms count in 32 bits
+  if ((((uintptr_t)power | (uintptr_t)stats | (uintptr_t)workspace) & 7) || ((uintptr_t)lra & 3)) return AT_EINVAL;
+  hipLaunchKernelGGL(loudness_range_kernel, loud_grid(clips), dim3(kLoudLanes), 0, (hipStream_t)stream, power, (long long)clips,
+                     C, (long long)nh, (long long)ld, hb, G, (double)hb * (double)hop, abs_threshold, rel_ratio, lra, stats,
+                     workspace);
   return hipGetLastError() == hipSuccess ? AT_OK : AT_ELAUNCH;
 }
 

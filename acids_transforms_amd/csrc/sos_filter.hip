@@ -30,8 +30,8 @@
 // anchored at the row's last sample: bit for bit flip -> forward -> flip.  It is the adjoint of the forward filter with
 // zero state, so this one kernel is the forward, the backward and both halves of zero-phase filtering.
 //
-// The same walk has two more endings (MODE below), both forwards in time and from zero state, for a row cut into hops of
-// `hop` >= 16 samples, nh = L / hop of them whole (the samples past nh hop belong to no hop):
+// The same walk has three more endings (MODE below), forwards in time and (the first two) from zero state, for a row cut
+// into hops of `hop` >= 16 samples, nh = L / hop of them whole (the samples past nh hop belong to no hop):
 //   hop power   nothing of y is written: the last section's DOUBLE output is squared before any rounding and summed into
 //               power[r][h], float64.  hop >= S, so a lane's samples touch at most two hops: a head sum and a tail sum, each a
 //               chain in sample order.  The lane below's tail joins the head (tail + head), a segmented Hillis-Steele scan
@@ -45,6 +45,14 @@
 //               as they were; zeros give +0.
 //   hop scaled  u[r][n] = (float)(w[r][n / hop] y[n]) with w (rows, nh) float64, +0 for n >= nh hop: the backward of a
 //               function of the hop powers, before the reverse filter.
+//   hop stream  hop power over a STREAM: the row is the next chunk, it begins `filled` samples inside a hop that already holds
+//               open_in[r], and the filter starts from zi.  The hops that complete, done = (filled + L) / hop of them, go to
+//               power[r ld + first + k]; the trailing partial hop is hop index `done` -- every sample of the chunk is live --
+//               and its sum goes to open_out[r] (+0 when the chunk ends where a hop ends); zf comes from the owner lane.
+//               zf may be zi and open_out may be open_in: a row's state is read at the row's start by the one workgroup
+//               that writes it at the row's end.  The tiling is anchored at the CHUNK's first sample, so a chunked stream's
+//               hop powers agree with the one call within rounding, not to the bit; power, open_out and zf of row r are
+//               functions of (sos, hop, filled, L), the row's samples and the row's incoming state alone.
 // The hop index of a lane's first sample comes from one 32-bit division per tile (the tile's own offset into its first hop
 // is carried along by additions); there is no division per sample.
 //
@@ -69,6 +77,8 @@ constexpr int kSosMaxGrid = 2048;                        // persistent workgroup
 constexpr int kSosEntries = 65;
 // how a tile leaves: y as float; its squares summed per hop in double; y times a per-hop weight as float
 constexpr int kSosFilter = 0, kSosHopPower = 1, kSosHopScaled = 2;
+// hop power over a stream: the row is a chunk that begins `filled` samples inside a hop, from a filter state
+constexpr int kSosHopStream = 3;
 constexpr int kSosMinHop = kSosPerLane;                  // a lane's samples touch at most two hops
 
 struct SosHop {
@@ -77,6 +87,20 @@ struct SosHop {
   const double* w;                                       // hop scaled: (rows, nh)
   double* power;                                         // hop power: (rows, nh)
 };
+
+// hop power over a stream.  nh counts the hops that complete inside the chunk, (filled + L) / hop: hop k of the chunk is
+// power[r ld + first + k], and the trailing partial hop is hop index nh, which goes to open_out.  The states are not the
+// kernel's __restrict__ arguments: zf may be zi and open_out may be open_in.
+struct SosStream : SosHop {
+  unsigned filled;                                       // samples the open hop already holds: 0 .. hop - 1
+  long long ld, first;
+  const double* zi;                                      // (rows, n, 2), or null for zeros
+  double* zf;
+  const double* open_in;                                 // (rows,), or null for zeros
+  double* open_out;
+};
+template <int MODE>
+using SosEnding = std::conditional_t<MODE == kSosHopStream, SosStream, SosHop>;
 
 struct SosCoef {
   double c[kSosMaxSections][5];                          // b0 b1 b2 a1 a2
@@ -127,8 +151,11 @@ __device__ __forceinline__ int sos_slot(int q, int tid) {
 template <bool REV, int MODE>
 __global__ __launch_bounds__(kSosLanes) void sos_filter_kernel(const float* __restrict__ x, float* __restrict__ y,
                                                                const double* __restrict__ zi, double* __restrict__ zf,
-                                                               long long rows, long long L, SosCoef co, int n, SosHop hp) {
+                                                               long long rows, long long L, SosCoef co, int n,
+                                                               SosEnding<MODE> hp) {
   static_assert(MODE == kSosFilter || !REV, "the hop endings run forwards in time");
+  constexpr bool STREAM = MODE == kSosHopStream;
+  constexpr bool SUMS = MODE == kSosHopPower || STREAM;  // the two endings that sum squares per hop
   extern __shared__ double sos_tab[];                    // n x kSosEntries matrices
   __shared__ float stage[kSosLanes * kSosStride];
   __shared__ double wtot[kSosMaxSections][kSosWaves][2];
@@ -136,8 +163,8 @@ __global__ __launch_bounds__(kSosLanes) void sos_filter_kernel(const float* __re
   __shared__ double aside[kSosPerLane];                  // one lane's: see `owner`
   // hop power: what each wave hands to lane 0 of the workgroup -- the sums of the hops of its first and of its last lane,
   // its last lane's tail, and those two hop indices (counted from the tile's first hop) with the tail's flag
-  __shared__ double hop_sum[MODE == kSosHopPower ? kSosWaves : 1][3];
-  __shared__ unsigned hop_idx[MODE == kSosHopPower ? kSosWaves : 1][3];
+  __shared__ double hop_sum[SUMS ? kSosWaves : 1][3];
+  __shared__ unsigned hop_idx[SUMS ? kSosWaves : 1][3];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 
   // (A^S)^l for l = 0 .. 64 and every section: A^S by four squarings, then lane l raises it to its own power, bit by bit
@@ -163,7 +190,12 @@ __global__ __launch_bounds__(kSosLanes) void sos_filter_kernel(const float* __re
   for (long long r = blockIdx.x; r < rows; r += gridDim.x) {
     const float* xr = x + r * L;
     float* yr = y + r * L;
-    if (tid < n) {
+    if constexpr (STREAM) {                              // a row's state is read here by the one workgroup that writes it
+      if (tid < n) {
+        carry[0][tid][0] = hp.zi ? hp.zi[(r * n + tid) * 2] : 0.0;
+        carry[0][tid][1] = hp.zi ? hp.zi[(r * n + tid) * 2 + 1] : 0.0;
+      }
+    } else if (tid < n) {
       carry[0][tid][0] = zi ? zi[(r * n + tid) * 2] : 0.0;
       carry[0][tid][1] = zi ? zi[(r * n + tid) * 2 + 1] : 0.0;
     }
@@ -187,6 +219,10 @@ __global__ __launch_bounds__(kSosLanes) void sos_filter_kernel(const float* __re
     long long hop_base = 0, open_hop = 0, handed_hop = 0;
     unsigned hop_off = 0;
     double open_sum = 0.0;
+    if constexpr (STREAM) {                              // the chunk begins inside hop 0, which holds open_in already
+      hop_off = hp.filled;
+      if (tid == 0 && hp.open_in) open_sum = hp.open_in[r];
+    }
     // hop power, lane 0 of the workgroup: what the waves handed over for the tile whose first hop is handed_hop goes onto
     // the open hop, wave by wave -- the piece of the hop that came into the wave, the hop that leaves it, its last lane's
     // tail -- and a hop is stored when the next one opens (and the open one at the row's end).  All twelve cells are read
@@ -201,9 +237,14 @@ __global__ __launch_bounds__(kSosLanes) void sos_filter_kernel(const float* __re
           sum[w][j] = hop_sum[w][j];
           idx[w][j] = hop_idx[w][j];
         }
-      double* pr = hp.power + r * hp.nh;
+      double* pr;
+      if constexpr (STREAM) pr = hp.power + (r * hp.ld + hp.first);
+      else pr = hp.power + r * hp.nh;
       auto close = [&]() {
         if (open_hop < hp.nh) pr[open_hop] = open_sum;
+        else if constexpr (STREAM) {
+          if (open_hop == hp.nh) hp.open_out[r] = open_sum;              // the trailing partial hop
+        }
       };
 #pragma unroll
       for (int w = 0; w < kSosWaves; ++w) {
@@ -226,7 +267,12 @@ __global__ __launch_bounds__(kSosLanes) void sos_filter_kernel(const float* __re
           ++open_hop;
         }
       }
-      if (row_ends) close();
+      if (row_ends) {
+        close();
+        if constexpr (STREAM) {
+          if (open_hop < hp.nh) hp.open_out[r] = 0.0;    // the chunk ended where a hop ends: no lane met hop nh
+        }
+      }
     };
     auto tile = [&](auto tail, long long t0) {
       constexpr bool TAIL = decltype(tail)::value;       // the row's last tile: partial stores, and the final state
@@ -234,7 +280,7 @@ __global__ __launch_bounds__(kSosLanes) void sos_filter_kernel(const float* __re
 #pragma unroll
       for (int q = 0; q < kSosPerLane; ++q) stage[sos_slot(q, tid)] = pf[q];
       __syncthreads();                                   // (also: the tables, and carry[0] at a row's first tile)
-      if constexpr (MODE == kSosHopPower) {
+      if constexpr (SUMS) {
         if (t0 > 0 && tid == 0) chain(false);            // the tile before's hand-over, behind this tile's first barrier
       }
       double v[kSosPerLane];
@@ -250,7 +296,9 @@ __global__ __launch_bounds__(kSosLanes) void sos_filter_kernel(const float* __re
       if constexpr (MODE != kSosFilter) {
         const unsigned at = hop_off + (unsigned)(tid * kSosPerLane);
         hr = at / (unsigned)hp.hop;
-        const long long ends = (long long)(hr + 1) * hp.hop - at, left = hp.nh * hp.hop - (t0 + tid * kSosPerLane);
+        const long long ends = (long long)(hr + 1) * hp.hop - at;
+        // (a stream's trailing partial hop counts: every sample of the chunk is live, and none past it)
+        const long long left = (STREAM ? L : hp.nh * hp.hop) - (t0 + tid * kSosPerLane);
         cut = ends < kSosPerLane ? (int)ends : kSosPerLane;
         live = left < 0 ? 0 : left < kSosPerLane ? (int)left : kSosPerLane;
         if constexpr (MODE == kSosHopScaled) {
@@ -267,7 +315,9 @@ __global__ __launch_bounds__(kSosLanes) void sos_filter_kernel(const float* __re
       }
       // the lane of the row's last sample hands out the final state: it keeps each section's input to its cnt samples
       // aside and, once it knows its s_in, runs the recurrence itself over them
-      const bool owner = TAIL && zf && tid == (rem - 1) / kSosPerLane;
+      double* zout = zf;
+      if constexpr (STREAM) zout = hp.zf;
+      const bool owner = TAIL && zout && tid == (rem - 1) / kSosPerLane;
       const int cnt = rem - tid * kSosPerLane;           // 1 .. S for the owner
       for (int k = 0; k < n; ++k) {
         const double b0 = co.c[k][0], b1 = co.c[k][1], b2 = co.c[k][2], na1 = -co.c[k][3], na2 = -co.c[k][4];
@@ -330,8 +380,8 @@ __global__ __launch_bounds__(kSosLanes) void sos_filter_kernel(const float* __re
             q1 = fma(b1, u, fma(na1, w, q2));
             q2 = fma(b2, u, na2 * w);
           }
-          zf[(r * n + k) * 2] = q1;
-          zf[(r * n + k) * 2 + 1] = q2;
+          zout[(r * n + k) * 2] = q1;
+          zout[(r * n + k) * 2 + 1] = q2;
         }
         // the fix-up: y[i] += (A^i s_in)[0], the homogeneous recurrence from s_in
 #pragma unroll
@@ -342,7 +392,7 @@ __global__ __launch_bounds__(kSosLanes) void sos_filter_kernel(const float* __re
           s0 = t;
         }
       }
-      if constexpr (MODE == kSosHopPower) {
+      if constexpr (SUMS) {
         double head = 0.0, rest = 0.0;                   // the squares in the lane's first hop, and in the next
         if (__all(cut == kSosPerLane && live == kSosPerLane)) {          // the same sums without the selects
 #pragma unroll
@@ -374,7 +424,11 @@ __global__ __launch_bounds__(kSosLanes) void sos_filter_kernel(const float* __re
         if (lane == 63 || ((heads >> (lane + 1)) & 1)) {   // the last lane of its hop in this wave
           if (first == 0) hop_sum[wave][0] = c;
           else if (lane == 63) hop_sum[wave][1] = c;
-          else if (tile_hop + hr < hp.nh) hp.power[r * hp.nh + tile_hop + hr] = c;        // begun and ended inside this wave
+          else if constexpr (STREAM) {                   // begun and ended inside this wave
+            const long long h = tile_hop + hr;
+            if (h < hp.nh) hp.power[r * hp.ld + hp.first + h] = c;
+            else if (h == hp.nh) hp.open_out[r] = c;     // (the lanes after it lie past the chunk)
+          } else if (tile_hop + hr < hp.nh) hp.power[r * hp.nh + tile_hop + hr] = c;      // begun and ended inside this wave
         }
         if (lane == 63) {
           hop_sum[wave][2] = rest;
@@ -405,7 +459,7 @@ __global__ __launch_bounds__(kSosLanes) void sos_filter_kernel(const float* __re
     long long t0 = 0;
     for (; t0 + kSosTile < L; t0 += kSosTile) tile(std::false_type(), t0);
     tile(std::true_type(), t0);
-    if constexpr (MODE == kSosHopPower) {
+    if constexpr (SUMS) {
       __syncthreads();
       if (tid == 0) chain(true);
     }
@@ -530,6 +584,44 @@ int at_sos_hop_power(const float* x, int64_t rows, int64_t L, const double* sos,
 int at_sos_filter_hop_scaled(const float* x, int64_t rows, int64_t L, const double* sos, int n_sections, int64_t hop,
                              const double* w, float* u, void* stream) {
   return sos_hop_launch<kSosHopScaled>(x, rows, L, sos, n_sections, hop, w, nullptr, u, stream);
+}
+
+int at_sos_hop_power_stream(const float* x, int64_t rows, int64_t n, const double* sos, int n_sections, int64_t hop,
+                            int64_t filled, const double* zi, double* zf, const double* open_in, double* open_out,
+                            double* power, int64_t ld, int64_t first, void* stream) {
+  const int rc = sos_check_shape(rows, n, n_sections);
+  if (rc != AT_OK) return rc;
+  if (!sos || hop < 1 || n < 1 || ld < 0 || first < 0) return AT_EINVAL;
+  if (hop < kSosMinHop) return AT_EUNSUPPORTED;
+  if (filled < 0 || filled >= hop) return AT_EINVAL;
+  SosCoef co;
+  if (!sos_pack(sos, n_sections, co)) return AT_EINVAL;
+  if (!x || !zf || !open_out || !power) return AT_EINVAL;
+  if (n > INT64_MAX - filled) return AT_EUNSUPPORTED;
+  const int64_t done = (filled + n) / hop;               // the hops that complete inside this chunk
+  if (first > INT64_MAX - done || ld < first + done) return AT_EINVAL;
+  if (((uintptr_t)x & 3) || (((uintptr_t)zi | (uintptr_t)zf | (uintptr_t)open_in | (uintptr_t)open_out | (uintptr_t)power) & 7))
+    return AT_EINVAL;
+  if (rows == 0) return AT_OK;
+  if (hop > INT32_MAX) return AT_EUNSUPPORTED;
+  if (ld > INT64_MAX / 8 / rows) return AT_EUNSUPPORTED;  // 64-bit byte offsets
+  SosStream hp;
+  hp.hop = (int)hop;
+  hp.nh = done;
+  hp.w = nullptr;
+  hp.power = power;
+  hp.filled = (unsigned)filled;
+  hp.ld = ld;
+  hp.first = first;
+  hp.zi = zi;
+  hp.zf = zf;
+  hp.open_in = open_in;
+  hp.open_out = open_out;
+  const dim3 grid((unsigned)(rows < kSosMaxGrid ? rows : kSosMaxGrid)), block(kSosLanes);
+  const size_t lds = (size_t)n_sections * kSosEntries * 4 * sizeof(double);
+  hipLaunchKernelGGL((sos_filter_kernel<false, kSosHopStream>), grid, block, lds, (hipStream_t)stream, x, (float*)nullptr,
+                     (const double*)nullptr, (double*)nullptr, (long long)rows, (long long)n, co, n_sections, hp);
+  return hipGetLastError() == hipSuccess ? AT_OK : AT_ELAUNCH;
 }
 
 }  // extern "C"

@@ -1822,6 +1822,131 @@ def loudness_blocks_backward(x, power, g, sr, hops_per_block=LOUDNESS_BLOCK_HOPS
     return _loudness_finish(x, plan, w)
 
 
+LOUDNESS_RANGE_REL_RATIO = 0.01                                      # -20 LU (EBU Tech 3342)
+
+
+def _state64(t, shape, what):
+    if t.dtype != torch.float64:
+        raise AcidsHipError("%s is %s: the carried state is float64 (it is no audio: nothing narrows it)"
+                            % (what, str(t.dtype).replace("torch.", "")))
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError("%s is %s, the chunk needs %s" % (what, tuple(t.shape), tuple(shape)))
+    if not t.is_contiguous():
+        raise ValueError("%s is updated in place: it must be contiguous" % what)
+
+
+def sos_hop_power_stream(x, sos, hop, filled, zi, open_sum, power, first):
+    """The next chunk of a stream through sos_hop_power (include/acids_hip.h, at_sos_hop_power_stream): x (..., n) float32,
+    n >= 1; `filled` (0 <= filled < hop) samples of the open hop came with earlier chunks.  UPDATES IN PLACE, all FLOAT64
+    and contiguous on x's device: zi (..., n_sections, 2), the filter state; open_sum (...,), the partial sum of the open
+    hop; power (..., cap), of which entries [first, first + done) receive the hops that complete inside this chunk and no
+    other entry is touched.  Returns done = (filled + n) // hop, computed on the host.  One launch, no allocation.  The
+    hop powers of a chunked stream agree with sos_hop_power of the whole signal within rounding, not to the bit; the same
+    chunking gives the same bits in any batch.  ValueError: shapes that do not match, filled outside [0, hop), first + done
+    past cap, an empty chunk."""
+    co = sos_coefficients(sos)
+    hop = _hop_rows(x, hop, "sos_hop_power_stream")
+    filled, first = int(filled), int(first)
+    lead, n = tuple(x.shape[:-1]), x.shape[-1]
+    if n < 1:
+        raise ValueError("sos_hop_power_stream takes a chunk of at least one sample")
+    if not 0 <= filled < hop:
+        raise ValueError("filled must lie in [0, hop = %d), got %d" % (hop, filled))
+    if power.ndim != len(lead) + 1:
+        raise ValueError("power is %s, the chunk %s needs %s" % (tuple(power.shape), tuple(x.shape), lead + ("cap",)))
+    cap = power.shape[-1]
+    _state64(zi, lead + (co.n, 2), "zi")
+    _state64(open_sum, lead, "open_sum")
+    _state64(power, lead + (cap,), "power")
+    done = (filled + n) // hop
+    if first < 0 or first + done > cap:
+        raise ValueError("hops [%d, %d) do not fit power's %d columns" % (first, first + done, cap))
+    require_device(x, zi, open_sum, power)
+    x = _f32c(x)
+    check(lib().at_sos_hop_power_stream(ptr(x), math.prod(lead), n, co.ptr, co.n, hop, filled, ptr(zi), ptr(zi), ptr(open_sum),
+                                        ptr(open_sum), ptr(power), cap, first, stream_ptr()), "at_sos_hop_power_stream")
+    return done
+
+
+def loudness_stream_plan(sr, samples_seen, n, hops_per_block=LOUDNESS_BLOCK_HOPS):
+    """(hop, filled, first, done, new_blocks) of a chunk of n samples that follows samples_seen samples of a stream at rate
+    sr: the 100 ms hop, the samples the open hop already holds, the index of that hop, the hops that complete inside the
+    chunk, and the blocks of hops_per_block hops that do.  Host arithmetic; reads no device.  ValueError: negative counts,
+    hops_per_block < 1, a rate at which filter_design.k_weighting raises."""
+    _k_weighting(sr)
+    hop, hb, seen, n = int(round(float(sr) / 10.0)), int(hops_per_block), int(samples_seen), int(n)
+    if seen < 0 or n < 0:
+        raise ValueError("samples_seen and n must be >= 0, got %d and %d" % (seen, n))
+    if hb < 1:
+        raise ValueError("hops_per_block must be >= 1, got %d" % hb)
+    filled, first = seen % hop, seen // hop
+    done = (filled + n) // hop
+    new_blocks = max(0, first + done - hb + 1) - max(0, first - hb + 1)
+    return hop, filled, first, done, new_blocks
+
+
+def loudness_gate_window(power, C, offset, nh, sr, hops_per_block=LOUDNESS_BLOCK_HOPS, channel_weights=None, gated=False):
+    """at_loudness_gate_ld on the hops [offset, offset + nh) of a history power (..., C, cap) float64, contiguous, read
+    where it lies: the block loudnesses (..., nh - hops_per_block + 1) float32, or with gated=True the gated loudness
+    (...,) of that window (-inf when it holds no block)."""
+    plan = loudness_plan((C, max(int(nh), int(hops_per_block)) * int(round(float(sr) / 10.0))), sr, hops_per_block, channel_weights)
+    require_device(power)
+    if power.dtype != torch.float64 or power.ndim < 2 or power.shape[-2] != C or not power.is_contiguous():
+        raise ValueError("power must be a contiguous (..., C = %d, cap) float64 tensor, got %s %s" % (C, tuple(power.shape), power.dtype))
+    lead, cap, offset, nh = tuple(power.shape[:-2]), power.shape[-1], int(offset), int(nh)
+    if offset < 0 or nh < 0 or offset + nh > cap:
+        raise ValueError("hops [%d, %d) are not inside the history's %d" % (offset, offset + nh, cap))
+    clips, nb = math.prod(lead), nh - plan.hb + 1
+    base = ctypes.c_void_p(power.data_ptr() + 8 * offset)
+    if gated:
+        if nb < 1:
+            return torch.full(lead, float("-inf"), dtype=torch.float32, device=power.device)
+        lufs = torch.empty(lead, dtype=torch.float32, device=power.device)
+        stats = torch.empty(lead + (3,), dtype=torch.float64, device=power.device)
+        check(lib().at_loudness_gate_ld(base, clips, C, nh, cap, plan.hop, plan.hb, plan.wptr, LOUDNESS_ABS_THRESHOLD,
+                                        LOUDNESS_REL_RATIO, ptr(lufs), ptr(stats), None, stream_ptr()), "at_loudness_gate_ld")
+        return lufs
+    blocks = torch.empty(lead + (max(nb, 0),), dtype=torch.float32, device=power.device)
+    if nb >= 1:
+        check(lib().at_loudness_gate_ld(base, clips, C, nh, cap, plan.hop, plan.hb, plan.wptr, 0.0, 0.0, None, None,
+                                        ptr(blocks), stream_ptr()), "at_loudness_gate_ld")
+    return blocks
+
+
+def loudness_range_from_power(power, nh, sr, channel_weights=None, ld=None, return_state=False):
+    """Loudness range (EBU Tech 3342) in LU from hop powers: power (..., C, ld) float64, contiguous, of which the first nh
+    hops of every row are read (ld: the row length, None for power.shape[-1]) -> (...,) float32.  3 s blocks one hop
+    apart, the -70 LUFS absolute gate, a relative gate 20 LU below the mean of what passed, then
+    10 log10(q[rnd(0.95 (n - 1))] / q[rnd(0.10 (n - 1))]) over the n gated block powers in ascending order, the two picked by
+    an exact radix select (at_loudness_range).  0 when nothing passes (also: no 3 s block); NaN for a clip that holds one.
+    return_state=True: (lra, stats (..., 4) float64 = P_low, P_high, n, Pabs)."""
+    if power.dtype != torch.float64 or power.ndim < 2 or not power.is_contiguous():
+        raise ValueError("power must be a contiguous (..., C, ld) float64 tensor, got %s %s" % (tuple(power.shape), power.dtype))
+    lead, C, nh = tuple(power.shape[:-2]), power.shape[-2], int(nh)
+    ld = power.shape[-1] if ld is None else int(ld)
+    if ld != power.shape[-1] or not 0 <= nh <= ld:
+        raise ValueError("nh = %d hops of rows of ld = %d do not match power %s" % (nh, ld, tuple(power.shape)))
+    hb = LOUDNESS_SHORT_TERM_HOPS
+    plan = loudness_plan((C, hb * int(round(float(sr) / 10.0))), sr, hb, channel_weights)
+    require_device(power)
+    lra = torch.empty(lead, dtype=torch.float32, device=power.device)
+    stats = torch.empty(lead + (4,), dtype=torch.float64, device=power.device)
+    work = torch.empty(lead + (max(nh - hb + 1, 0),), dtype=torch.float64, device=power.device)
+    check(lib().at_loudness_range(ptr(power), math.prod(lead), C, nh, ld, plan.hop, hb, plan.wptr, LOUDNESS_ABS_THRESHOLD,
+                                  LOUDNESS_RANGE_REL_RATIO, ptr(lra), ptr(stats), ptr(work), stream_ptr()), "at_loudness_range")
+    return (lra, stats) if return_state else lra
+
+
+def loudness_range(x, sr, channel_weights=None, return_state=False):
+    """Loudness range (LRA, EBU Tech 3342) of x (..., C, L) float32 -> (...,) float32 in LU; (L,) is one mono clip.  Two
+    launches: the K-weighted hop powers (at_sos_hop_power), then loudness_range_from_power.  ValueError below one 3 s
+    block (see loudness_plan).  return_state=True: (lra, power (..., C, L // hop), stats (..., 4))."""
+    plan = loudness_plan(x.shape, sr, LOUDNESS_SHORT_TERM_HOPS, channel_weights)
+    x, power = _loudness_power(x, plan)
+    lra, stats = loudness_range_from_power(power, plan.nh, sr, channel_weights, return_state=True)
+    return (lra, power, stats) if return_state else lra
+
+
 # ----------------------------------------------------------------------------------------------
 # long-filter convolution (fft_convolve.hip): uniformly partitioned overlap-save
 # ----------------------------------------------------------------------------------------------

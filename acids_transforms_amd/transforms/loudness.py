@@ -26,10 +26,25 @@ The pre-filter is utils.filter_design.k_weighting: the standard's own table at 4
 prototypes through the bilinear transform at every other rate.  torchaudio approximates it with cookbook biquads instead,
 so the two differ by that approximation; parity with torchaudio is unpinned.
 
-Not built: a streaming meter (it would carry the filter state, a partial hop and a ring of hop sums; `realtime()` says so
-and returns the offline module), loudness range (LRA) and true peak, a row-splitting dispatch for one very long row (a row
-is one workgroup, as for SOSFilter), gradients with respect to the channel weights, torchaudio's approximate pre-filter,
-second-order gradients.
+Loudness range (EBU Tech 3342, `Loudness.loudness_range`): the same hop powers, 3 s blocks one hop apart, the absolute gate,
+a relative gate 20 LU below the mean of what passed it, and 10 log10 of the ratio of two order statistics of the n gated
+block powers q in ascending order, q[rnd(0.95 (n - 1))] / q[rnd(0.10 (n - 1))] with rnd(v) = floor(v + 0.5) -- Tech 3342's own
+index rule.  The two are picked by an exact radix select in loudness.hip (no sort), a function of the clip's hop powers
+alone.  It has no graph.
+
+Streaming: RealtimeLoudness (also `Loudness.streaming()`) is the meter over a stream of chunks of any length >= 1.  It
+carries the K-weighting filter's state, the partial sum of the open hop and every whole hop's power since the stream began,
+all float64, and the number of samples seen as a host integer; no call synchronises and nothing of the audio is kept.  A
+`forward` is two launches -- sos_filter.hip's stream ending writes the hops that complete straight into the history, and
+loudness.hip's gate reads the window of history the new blocks cover where it lies -- or one when no block completes.  The
+kernel's tile grid starts at each chunk's first sample, so a chunked stream's hop powers agree with the one-call
+measurement WITHIN ROUNDING (1e-5 normwise, 1e-4 LU), not to the bit; the same chunking gives the same bits in any batch.
+
+Not built: true peak, a bounded-memory (histogram) form of the integrated measure for streams of days (the history grows
+by one float64 per channel per 100 ms), gradients through the streaming meter or the loudness range, bit-equal chunking, a
+row-splitting dispatch for one very long row (a row is one workgroup, as for SOSFilter), gradients with respect to the
+channel weights, torchaudio's approximate pre-filter, second-order gradients.  `Loudness.realtime()` still warns and returns
+the offline module (the reference's protocol drives `realtime()` with whole clips); the streaming form is `streaming()`.
 """
 import warnings
 from typing import Optional
@@ -37,10 +52,12 @@ from typing import Optional
 import torch
 
 from .. import ops
+from .._lib import device_scoped, require_device
 from ..autograd import LoudnessBlocksFunction, LoudnessFunction, wants_grad
 from .base import AudioTransform, InversionEnumType, NotInvertibleError
+from .carried import CarriedState
 
-__all__ = ["Loudness", "LoudnessNormalize"]
+__all__ = ["Loudness", "LoudnessNormalize", "RealtimeLoudness"]
 
 
 class Loudness(AudioTransform):
@@ -76,11 +93,20 @@ class Loudness(AudioTransform):
     def short_term(self, x: torch.Tensor) -> torch.Tensor:
         return self._blocks(x, ops.LOUDNESS_SHORT_TERM_HOPS)
 
+    def loudness_range(self, x: torch.Tensor) -> torch.Tensor:
+        """(..., C, L) -> (...,) loudness range (EBU Tech 3342) in LU.  ValueError below one 3 s block.  No graph: an
+        input that requires grad gets a tensor without one."""
+        return ops.loudness_range(x.detach(), self.sr, self.channel_weights)
+
     def invert(self, x: torch.Tensor, inversion_mode: InversionEnumType = None, **kwargs) -> torch.Tensor:
         raise NotInvertibleError
 
     def forward_with_time(self, x: torch.Tensor, time: torch.Tensor):
         return self.forward(x), time
+
+    def streaming(self) -> "RealtimeLoudness":
+        """The streaming meter of this measure: a RealtimeLoudness with the same rate and channel weights."""
+        return RealtimeLoudness(sr=self.sr, channel_weights=self.channel_weights)
 
     def realtime(self):
         warnings.warn("%s has no streaming form (a streaming meter is not built): realtime() returns the offline module, "
@@ -142,5 +168,181 @@ class LoudnessNormalize(Loudness):
         assert y.shape == x.shape and bool(torch.isfinite(y).all())
         y, time = transform.test_forward(x, torch.zeros(2, 2, device="cuda"))
         assert y.shape == x.shape and time.shape == (2, 2)
+        if invert:
+            transform.invert(y)
+
+
+class RealtimeLoudness(CarriedState, Loudness):
+    """An EBU R128 meter over a stream.  `forward` takes the next (..., C, n) chunk, any n >= 1 (a 1-D chunk is one mono
+    stream), and returns (..., k) float32: the momentary loudness in LUFS of the k 400 ms blocks that completed in this
+    chunk, k = max(0, hops_after - 3) - max(0, hops_before - 3), empty when k is 0 -- the outputs of any chunking
+    concatenate to `Loudness.momentary` of the whole signal (within rounding: module docstring).  `momentary()` and
+    `short_term()` give (...,), the latest 400 ms / 3 s block, -inf before the first is complete; `integrated()` the gated
+    loudness of everything since the stream began (-inf before the first block); `block_loudness(hops_per_block)` every
+    block so far, (..., nb); `loudness_range()` the range in LU, 0 before the first 3 s block.
+
+    Carried, all float64 whatever `.half()` did to the module: `filter_state` (lead..., C, 2, 2), the K-weighting filter's
+    state; `open_power` (lead..., C), the partial sum of the open hop; `hop_power` (lead..., C, cap), every whole hop since
+    the stream began, cap = 1024 doubled by a copy when the host count says it is full.  `samples_seen`, a host integer that
+    is never read back from the device, gives the hop count and where the next chunk falls, and travels through
+    get_extra_state / set_extra_state.  Zeros and 0 on a new leading shape (lead..., C) or device and after `reset()`; any
+    batch shape from a `state_dict`.  A call is two launches (one when no block completes), updates the state in place and
+    allocates nothing but its result, except where a chunk is not float32 and contiguous or the history grows.  `latency`
+    is 0.  The outputs carry no graph: it is a meter, the offline Loudness keeps its gradient."""
+
+    def __repr__(self):
+        return "RealtimeLoudness(sr=%s, channel_weights=%s)" % (self.sr, self.channel_weights)
+
+    def __init__(self, sr: int = 44100, channel_weights=None, _cap: int = 1024):
+        super().__init__(sr=sr, channel_weights=channel_weights)
+        self._cap0 = int(_cap)
+        self._kw = ops._k_weighting(sr)
+        self.samples_seen = 0
+        self.register_buffer("filter_state", torch.zeros(self._kw.n, 2, dtype=torch.float64))
+        self.register_buffer("open_power", torch.zeros((), dtype=torch.float64))
+        self.register_buffer("hop_power", torch.zeros(self._cap0, dtype=torch.float64))
+        self._carries("filter_state", "open_power", "hop_power")
+
+    _STATE = ("filter_state", "open_power", "hop_power")
+
+    def _carried_tail(self, name: str) -> tuple:
+        if name == "hop_power":
+            return (self.hop_power.shape[-1],)               # of what it holds now: the history grows
+        return self._carried[name][0]
+
+    def get_extra_state(self):
+        return {"samples_seen": int(self.samples_seen)}
+
+    def set_extra_state(self, state) -> None:
+        self.samples_seen = int(state["samples_seen"])
+
+    def _reset_extra(self) -> None:
+        self.samples_seen = 0
+
+    @property
+    def latency(self) -> int:
+        return 0
+
+    @property
+    def hops(self) -> int:
+        """Whole hops since the stream began."""
+        return self.samples_seen // int(round(float(self.sr) / 10.0))
+
+    def streaming(self) -> "RealtimeLoudness":
+        return self
+
+    def realtime(self):
+        return self
+
+    def _stream(self, lead, x: torch.Tensor) -> None:
+        """Makes the buffers those of the stream of x: zeros, and no sample seen, on a new leading shape or device; float64
+        and contiguous."""
+        rows = self._carried_rows(self._STATE, lead, x)
+        if rows is None:
+            ops.loudness_plan(lead[-1:] + (1 << 30,), self.sr, ops.LOUDNESS_BLOCK_HOPS, self.channel_weights)    # the channels
+            self.samples_seen = 0
+            for k in self._STATE:
+                tail = (self._cap0,) if k == "hop_power" else self._carried[k][0]
+                setattr(self, k, torch.zeros(lead + tail, dtype=torch.float64, device=x.device))
+        else:
+            for k, r in zip(self._STATE, rows):              # what a module cast or a strided state_dict entry changed
+                if r.data_ptr() != self._buffers[k].data_ptr() or self._buffers[k].dtype != torch.float64:
+                    self._carry(k, r, lead)
+
+    def _room(self, need: int) -> None:
+        """Room for `need` hops in the history: doubled by a copy when the host count says it is full."""
+        cap = self.hop_power.shape[-1]
+        if need > cap:
+            while cap < need:
+                cap *= 2
+            grown = torch.zeros(tuple(self.hop_power.shape[:-1]) + (cap,), dtype=torch.float64, device=self.hop_power.device)
+            grown[..., :self.hop_power.shape[-1]] = self.hop_power
+            self.hop_power = grown
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        if x.ndim < 1:
+            raise ValueError("RealtimeLoudness.forward takes a (..., C, n) chunk, got a scalar")
+        ops._no_fp64(x)
+        x = x.detach()
+        if x.ndim == 1:
+            x = x[None]
+        lead, n = tuple(x.shape[:-1]), x.shape[-1]
+        if n == 0:                                           # nothing arrived: no launch, the state stays
+            return torch.empty(lead[:-1] + (0,), dtype=torch.float32, device=x.device)
+        device_scoped(require_device)(x)                     # before any state is touched: there is no CPU route
+        self._stream(lead, x)
+        hop, filled, first, done, k = ops.loudness_stream_plan(self.sr, self.samples_seen, n)
+        self._room(first + done)
+        ops.sos_hop_power_stream(x, self._kw, hop, filled, self.filter_state, self.open_power, self.hop_power, first)
+        self.samples_seen += n
+        if k == 0:
+            return torch.empty(lead[:-1] + (0,), dtype=torch.float32, device=x.device)
+        j0 = max(0, first - (ops.LOUDNESS_BLOCK_HOPS - 1))   # the first new block, and the first hop it reads
+        return ops.loudness_gate_window(self.hop_power, lead[-1], j0, first + done - j0, self.sr, ops.LOUDNESS_BLOCK_HOPS,
+                                        self.channel_weights)
+
+    def _no_stream(self, fill: float, tail=()) -> Optional[torch.Tensor]:
+        if self.hop_power.ndim < 2:                          # no chunk yet: no batch shape either
+            return torch.full(tuple(tail), fill, dtype=torch.float32, device=self.hop_power.device)
+        return None
+
+    def _history(self) -> torch.Tensor:
+        h = self.hop_power
+        return h if h.dtype == torch.float64 and h.is_contiguous() else h.double().contiguous()
+
+    def block_loudness(self, hops_per_block: int = ops.LOUDNESS_BLOCK_HOPS) -> torch.Tensor:
+        """(..., nb) float32: the ungated loudness of every block of `hops_per_block` hops so far, one per 100 ms."""
+        early = self._no_stream(0.0, (0,))
+        if early is not None:
+            return early
+        return ops.loudness_gate_window(self._history(), self.hop_power.shape[-2], 0, self.hops, self.sr, hops_per_block,
+                                        self.channel_weights)
+
+    def _latest(self, hb: int) -> torch.Tensor:
+        early = self._no_stream(float("-inf"))
+        if early is not None:
+            return early
+        if self.hops < hb:
+            return torch.full(tuple(self.hop_power.shape[:-2]), float("-inf"), dtype=torch.float32, device=self.hop_power.device)
+        return ops.loudness_gate_window(self._history(), self.hop_power.shape[-2], self.hops - hb, hb, self.sr, hb,
+                                        self.channel_weights)[..., 0]
+
+    def momentary(self) -> torch.Tensor:
+        return self._latest(ops.LOUDNESS_BLOCK_HOPS)
+
+    def short_term(self) -> torch.Tensor:
+        return self._latest(ops.LOUDNESS_SHORT_TERM_HOPS)
+
+    def integrated(self) -> torch.Tensor:
+        """(...,) float32: the gated loudness (BS.1770) of everything since the stream began; -inf before the first block."""
+        early = self._no_stream(float("-inf"))
+        if early is not None:
+            return early
+        return ops.loudness_gate_window(self._history(), self.hop_power.shape[-2], 0, self.hops, self.sr,
+                                        ops.LOUDNESS_BLOCK_HOPS, self.channel_weights, gated=True)
+
+    def loudness_range(self) -> torch.Tensor:
+        """(...,) float32: the loudness range (EBU Tech 3342) in LU of everything so far; 0 before the first 3 s block."""
+        early = self._no_stream(0.0)
+        if early is not None:
+            return early
+        if self.hops < ops.LOUDNESS_SHORT_TERM_HOPS:
+            return torch.zeros(tuple(self.hop_power.shape[:-2]), dtype=torch.float32, device=self.hop_power.device)
+        return ops.loudness_range_from_power(self._history(), self.hops, self.sr, self.channel_weights)
+
+    def test_forward(self, x: torch.Tensor, time: Optional[torch.Tensor] = None):
+        return self.forward(x) if time is None else self.forward_with_time(x, time)
+
+    @classmethod
+    def test_scripted_transform(cls, transform, invert: bool = True):
+        g = torch.Generator().manual_seed(0)
+        H = int(round(float(transform.sr) / 10.0))
+        x = (0.1 * torch.randn(2, 2, 5 * H + 7, generator=g)).to("cuda")
+        transform.reset()
+        y = transform.test_forward(x)
+        assert y.shape == (2, 2) and bool(torch.isfinite(y).all())
+        y, time = transform.test_forward(x, torch.zeros(2, 2, device="cuda"))
+        assert y.shape == (2, 5) and bool(torch.isfinite(y).all()) and time.shape == (2, 2)
+        assert bool(torch.isfinite(transform.integrated()).all()) and transform.loudness_range().shape == (2,)
         if invert:
             transform.invert(y)

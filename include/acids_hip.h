@@ -866,6 +866,24 @@ int at_sos_hop_power(const float *x, int64_t rows, int64_t L, const double *sos_
 int at_sos_filter_hop_scaled(const float *x, int64_t rows, int64_t L, const double *sos_host, int n_sections, int64_t hop,
                              const double *w, float *u, void *stream);
 
+/* at_sos_hop_power_stream: the hop-power ending over a STREAM.  x (rows, n) float32, n >= 1, is the next chunk of a stream
+ * whose open hop already holds `filled` samples (0 <= filled < hop) with the partial sum open_in (rows) float64 (NULL:
+ * zeros), and whose filter state is zi (rows, n_sections, 2) float64 (NULL: zeros).  done = (filled + n) / hop hops complete
+ * inside the call: hop k of the chunk goes to power[r * ld + first + k], k < done -- k = 0 is open_in plus the first hop -
+ * filled samples of the chunk -- and nothing else of power is touched; open_out[r] receives the sum over the trailing
+ * (filled + n) % hop samples (+0 when there are none; open_in plus the whole chunk when done == 0) and zf the state after
+ * the chunk, both from the same launch.  zf may be zi and open_out may be open_in: a row's state is read at the row's start
+ * by the one workgroup that writes it at the row's end.  The tile grid is anchored at the chunk's first sample, so the hop
+ * powers of a chunked stream agree with the one-call at_sos_hop_power WITHIN ROUNDING, not to the bit; power[r][first + k],
+ * open_out[r] and zf[r] are functions of (sos, hop, filled, n), row r's samples and row r's incoming state alone -- no
+ * atomics, no workgroup waits for another, sums are selected and never masked by a multiply -- so the same chunking gives
+ * the same bits in any batch.  AT_EINVAL: null x / sos_host / zf / open_out / power, negative sizes, n < 1, filled outside
+ * [0, hop), ld < first + done, a non-finite coefficient, a0 != 1, misalignment.  AT_EUNSUPPORTED: more than 16 sections,
+ * hop < 16, hop >= 2^31.  AT_OK without a kernel for rows == 0. */
+int at_sos_hop_power_stream(const float *x, int64_t rows, int64_t n, const double *sos_host, int n_sections, int64_t hop,
+                            int64_t filled, const double *zi, double *zf, const double *open_in, double *open_out,
+                            double *power, int64_t ld, int64_t first, void *stream);
+
 /* ---- gated loudness (loudness.hip; ops.loudness, ops.loudness_blocks, transforms.Loudness) ------------------------- */
 /* ITU-R BS.1770 / EBU R128 gating of hop powers (restated; no reference counterpart).  power (clips, C, nh) float64 is
  * at_sos_hop_power of the K-weighted channels, a hop has `hop` samples (100 ms), a block hb hops (4: momentary and the
@@ -890,6 +908,23 @@ int at_sos_filter_hop_scaled(const float *x, int64_t rows, int64_t L, const doub
  * nh < hb there is no block: lufs is -inf, stats zeros, w zeros. */
 int at_loudness_gate(const double *power, int64_t clips, int C, int64_t nh, int64_t hop, int hb, const double *weights_host,
                      double abs_threshold, double rel_ratio, float *lufs, double *stats, float *block_lufs, void *stream);
+/* at_loudness_gate_ld: at_loudness_gate on a window of a longer history -- channel c of a clip begins at power + (clip C + c)
+ * ld, ld >= nh hops apart (AT_EINVAL below) -- read where it lies; at_loudness_gate is this call with ld = nh, the same
+ * addresses and the same bits.
+ * at_loudness_range: loudness range of EBU Tech 3342 from the same hop powers (the host passes hb = 30, rel_ratio = 0.01,
+ * -20 LU).  With p_j, J1, Pabs and J2 as above, n = |J2|, q the ascending order of {p_j: j in J2} and rnd(v) = floor(v + 0.5),
+ *   lra = (float)(10 log10(q[rnd(0.95 (n - 1))] / q[rnd(0.10 (n - 1))]))   (clips);  stats (clips, 4) = P_low, P_high, n, Pabs.
+ * n == 0: lra = 0 and P_low = P_high = 0.  A clip with a NaN block reads NaN (lra, P_low, P_high) and touches no other.  The
+ * two order statistics are an exact radix select on the order-preserving unsigned image of the doubles' bits (eight passes of
+ * eight bits, integer histograms in LDS): no sort, no float atomics, a function of the clip's hop powers alone.  workspace
+ * (clips, nb) float64 receives the block powers.  AT_EINVAL as at_loudness_gate, and null lra / stats / workspace;
+ * AT_EUNSUPPORTED also for nb >= 2^31. */
+int at_loudness_gate_ld(const double *power, int64_t clips, int C, int64_t nh, int64_t ld, int64_t hop, int hb,
+                        const double *weights_host, double abs_threshold, double rel_ratio, float *lufs, double *stats,
+                        float *block_lufs, void *stream);
+int at_loudness_range(const double *power, int64_t clips, int C, int64_t nh, int64_t ld, int64_t hop, int hb,
+                      const double *weights_host, double abs_threshold, double rel_ratio, float *lra, double *stats,
+                      double *workspace, void *stream);
 int at_loudness_gate_backward(const double *power, const double *stats, const float *g, int64_t clips, int C, int64_t nh,
                               int64_t hop, int hb, const double *weights_host, double abs_threshold, double rel_ratio,
                               double *w, void *stream);
