@@ -69,6 +69,11 @@ _SIGNATURES = {
     "at_loudness_range": [c_f, c_i64, c_int, c_i64, c_i64, c_i64, c_int, c_f, c_dbl, c_dbl, c_f, c_f, c_f, c_f],
     "at_loudness_gate_backward": [c_f, c_f, c_f, c_i64, c_int, c_i64, c_i64, c_int, c_f, c_dbl, c_dbl, c_f, c_f],
     "at_loudness_blocks_backward": [c_f, c_f, c_i64, c_int, c_i64, c_i64, c_int, c_f, c_f, c_f],
+    "at_true_peak_plan": [c_i64, c_i64, c_int, c_int, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), ctypes.POINTER(c_int),
+                          ctypes.POINTER(c_int)],
+    "at_true_peak_workspace_bytes": [c_i64, c_i64, c_int, c_int],
+    "at_true_peak": [c_f, c_i64, c_i64, c_f, c_int, c_int, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_i64, c_f, c_sz, c_f],
+    "at_true_peak_backward": [c_f, c_f, c_f, c_f, c_int, c_int, c_i64, c_i64, c_f, c_f],
     "at_fft_convolve_plan": [c_i64, c_i64, c_int, ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), ctypes.POINTER(c_i64),
                              ctypes.POINTER(c_int), ctypes.POINTER(c_i64)],
     "at_spectral_fir": [c_f, c_i64, c_f, c_i64, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_f, c_f],
@@ -151,7 +156,8 @@ _RESTYPES = {"at_error_string": ctypes.c_char_p, "at_istft_workspace_bytes": c_s
              "at_sinebank_workspace_bytes": c_sz, "at_stft_backward_workspace_bytes": c_sz,
              "at_istft_backward_workspace_bytes": c_sz, "at_rfft_frames_backward_workspace_bytes": c_sz,
              "at_irfft_frames_backward_workspace_bytes": c_sz, "at_spectral_distance_workspace_bytes": c_sz,
-             "at_mel_distance_workspace_bytes": c_sz, "at_spectral_fir_corr_workspace_bytes": c_sz}
+             "at_mel_distance_workspace_bytes": c_sz, "at_spectral_fir_corr_workspace_bytes": c_sz,
+             "at_true_peak_workspace_bytes": c_sz}
 
 
 class AcidsHipError(RuntimeError):

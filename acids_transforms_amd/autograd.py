@@ -46,6 +46,10 @@ the gates are piecewise constant, hence constants of the graph, and the rest is 
 backward is a weight per hop, the K-weighted signal times it (recomputed, never stored) and the reverse filter.  They keep
 x, the (..., C, hops) powers and the three gating statistics per clip.
 
+TruePeakFunction is transforms.TruePeak's (true_peak.hip): a maximum is piecewise linear, so the backward is the subgradient
+at the attained maximum -- the K taps of one phase, scaled and signed, under one oversampled index -- and the graph keeps a
+peak, an index and a sign per row.
+
 FFTConvolveFunction is ops.fft_convolve's (fft_convolve.hip), the one Function here with two differentiable inputs that are
 both audio-like: it saves x and h and nothing else, and the backward (ops.fft_convolve_backward) rebuilds the spectra chunk
 by chunk and computes only the gradients that are asked for.
@@ -70,7 +74,8 @@ __all__ = ["wants_grad", "StftFunction", "IstftFunction", "IstftPolarFunction", 
            "SpectralDistanceFunction", "specdist_chunk_clips", "MelSpectralDistanceFunction", "meldist_sums",
            "meldist_loss", "PqmfFunction", "PqmfInvertFunction", "PqmfStreamFunction", "PqmfStreamInvertFunction",
            "ResampleFunction", "ResampleStreamFunction", "ResampleDirectFunction", "PhaseVocoderFunction",
-           "SosFilterFunction", "SosFilterStreamFunction", "LoudnessFunction", "LoudnessBlocksFunction", "FFTConvolveFunction", "ImpulseResponseStreamFunction"]
+           "SosFilterFunction", "SosFilterStreamFunction", "LoudnessFunction", "LoudnessBlocksFunction", "FFTConvolveFunction", "ImpulseResponseStreamFunction",
+           "TruePeakFunction", "dbtp"]
 
 
 def wants_grad(x: torch.Tensor) -> bool:
@@ -688,6 +693,34 @@ class LoudnessBlocksFunction(torch.autograd.Function):
         x, power = ctx.saved_tensors
         gx = ops.loudness_blocks_backward(x, power, g, ctx.sr, ctx.hb, ctx.weights)
         return gx.reshape(x.shape).to(x.dtype), None, None, None
+
+
+def dbtp(peak: torch.Tensor) -> torch.Tensor:
+    """A linear peak in dBTP, 20 log10 peak: -inf for silence.  The one expression every true-peak reading goes through, so
+    equal peaks read equal."""
+    return 20.0 * torch.log10(peak)
+
+
+class TruePeakFunction(torch.autograd.Function):
+    """ops.true_peak(x, taps): x (..., L) -> (...,) the linear true peak, or with db=True that peak in dBTP.  The forward is the
+    plain route, bit for bit.  Saves one peak, one oversampled index and one sign per row -- nothing of the audio's size; the
+    backward is ops.true_peak_backward, the subgradient at the attained maximum (one launch).  dBTP multiplies the incoming
+    gradient by 20 / (ln 10 peak); a row that reads -inf (or NaN) gets exactly +0, by selection in the kernel."""
+
+    @staticmethod
+    def forward(ctx, x, taps, db):
+        peak, index, sign = ops.true_peak(x, taps, return_state=True)
+        ctx.taps, ctx.L, ctx.db, ctx.dtype = taps, x.shape[-1], bool(db), x.dtype
+        ctx.save_for_backward(peak, index, sign)
+        return dbtp(peak) if db else peak
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        peak, index, sign = ctx.saved_tensors
+        if ctx.db:
+            g = g * (8.685889638065035 / peak)                   # 20 / ln 10
+        return ops.true_peak_backward(g, sign, index, ctx.taps, ctx.L).to(ctx.dtype), None, None
 
 
 class FFTConvolveFunction(torch.autograd.Function):

@@ -65,7 +65,8 @@ extern "C" {
 //    at_irfft_frames_backward, at_oadd_forward_backward, at_oadd_invert_backward) and spectral_distance.hip's
 //    at_spectral_distance_sums / _backward and mel_distance.hip's at_mel_rows, at_mel_distance_sums / _backward and
 //    pqmf.hip's at_pqmf_tile_blocks, at_pqmf_analysis, at_pqmf_synthesis and their streaming forms
-//    at_pqmf_analysis_stream, at_pqmf_synthesis_stream: additions only.
+//    at_pqmf_analysis_stream, at_pqmf_synthesis_stream, and true_peak.hip's at_true_peak, at_true_peak_plan,
+//    at_true_peak_workspace_bytes, at_true_peak_backward: additions only.
 int at_abi_version(void) { return 4; }
 
 int at_set_variant(int which, int value) {

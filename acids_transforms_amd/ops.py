@@ -1948,6 +1948,113 @@ def loudness_range(x, sr, channel_weights=None, return_state=False):
 
 
 # ----------------------------------------------------------------------------------------------
+# true peak, ITU-R BS.1770-4 Annex 2 (true_peak.hip)
+# ----------------------------------------------------------------------------------------------
+TRUE_PEAK_MAX_PHASES = 8
+TRUE_PEAK_MAX_TAPS = 64
+
+
+def true_peak_plan(rows, L, P, K):
+    """(tile, per_lane, launches, dispatch) of at_true_peak at a shape: the samples of a tile, the consecutive samples of a
+    lane, the launches of a call (0 for empty work, 1 where a row is one tile, else 2) and which copy runs (0: the compiled
+    (4, 12) one, 1: the generic one).  Reads no device state."""
+    tile, per_lane, launches, dispatch = ctypes.c_int64(0), ctypes.c_int64(0), ctypes.c_int(0), ctypes.c_int(0)
+    check(lib().at_true_peak_plan(int(rows), int(L), int(P), int(K), ctypes.byref(tile), ctypes.byref(per_lane),
+                                  ctypes.byref(launches), ctypes.byref(dispatch)), "at_true_peak_plan")
+    return tile.value, per_lane.value, launches.value, dispatch.value
+
+
+def _true_peak_taps(taps, x):
+    if not isinstance(taps, torch.Tensor) or taps.ndim != 2:
+        raise ValueError("taps must be a (phases, taps per phase) tensor")
+    P, K = int(taps.shape[0]), int(taps.shape[1])
+    if not (1 <= P <= TRUE_PEAK_MAX_PHASES and 1 <= K <= TRUE_PEAK_MAX_TAPS):
+        raise ValueError("taps is %s: 1 <= phases <= %d and 1 <= taps per phase <= %d"
+                         % (tuple(taps.shape), TRUE_PEAK_MAX_PHASES, TRUE_PEAK_MAX_TAPS))
+    require_device(x, taps)
+    if taps.dtype != torch.float32 or not taps.is_contiguous():
+        taps = taps.detach().float().contiguous()
+    return taps, P, K
+
+
+def _true_peak_workspace(rows, L, P, K, device):
+    nbytes = lib().at_true_peak_workspace_bytes(rows, L, P, K)
+    return (torch.empty((nbytes,), dtype=torch.uint8, device=device) if nbytes else None), nbytes
+
+
+def true_peak(x, taps, return_state=False):
+    """The true peak of every row: x (..., L) float32, taps (P, K) float32 -> (...,) float32, LINEAR, the maximum of |y| over
+    the P L values y[P n + p] = sum_k taps[p][k] x[n - k] (include/acids_hip.h, at_true_peak); one launch where a row is one
+    tile of 2048 samples, else two.  A row's bits depend neither on the batch nor on the tiling.  Zeros (and L == 0) give +0, a
+    NaN in a row makes that row NaN and no other.  return_state=True: (peak, index (...,) int64 the smallest oversampled
+    index that attains it, sign (...,) float32 the sign of y there, 0 where the peak is 0 or NaN)."""
+    if x.ndim < 1:
+        raise ValueError("true_peak takes (..., L), got a scalar")
+    taps, P, K = _true_peak_taps(taps, x)
+    x = _f32c(x)
+    lead, L = tuple(x.shape[:-1]), x.shape[-1]
+    rows = math.prod(lead)
+    new = torch.zeros if rows * L == 0 else torch.empty
+    peak = new(lead, dtype=torch.float32, device=x.device)
+    index = new(lead, dtype=torch.int64, device=x.device) if return_state else None
+    sign = new(lead, dtype=torch.float32, device=x.device) if return_state else None
+    ws, nbytes = _true_peak_workspace(rows, L, P, K, x.device)
+    check(lib().at_true_peak(ptr(x), rows, L, ptr(taps), P, K, None, None, ptr(peak), ptr(index), ptr(sign), None, None, 0,
+                             ptr(ws), nbytes, stream_ptr()), "at_true_peak")
+    return (peak, index, sign) if return_state else peak
+
+
+def true_peak_stream(x, taps, state, state_next, max_peak, max_index, offset):
+    """The next chunk of a stream through true_peak: x (..., n) float32, n >= 1; state (..., K - 1) float32 the samples before
+    it, oldest first; state_next (same shape, another tensor) receives the last K - 1 samples of [state | x]; max_peak (...,)
+    float32 and max_index (...,) int64, the running maximum and its index in the stream, are updated in place, the index of
+    this chunk's first oversampled value being `offset`.  Returns the chunk's own peak, (...,) float32, linear.  All of them
+    contiguous; with K == 1 there is no state and both may be None.  No torch.cat, no synchronisation, and no allocation but
+    the result (and the partials of a chunk longer than a tile).  The peak of a chunked stream has the bits of the one-call
+    true_peak of the whole signal."""
+    if x.ndim < 1:
+        raise ValueError("true_peak_stream takes (..., n), got a scalar")
+    taps, P, K = _true_peak_taps(taps, x)
+    require_device(x, state, state_next, max_peak, max_index)
+    x = _f32c(x)
+    lead, n = tuple(x.shape[:-1]), x.shape[-1]
+    if n < 1:
+        raise ValueError("true_peak_stream takes a chunk of at least one sample")
+    for t, shape, dtype, what in ((state, lead + (K - 1,), torch.float32, "state"), (state_next, lead + (K - 1,), torch.float32,
+                                  "state_next"), (max_peak, lead, torch.float32, "max_peak"), (max_index, lead, torch.int64,
+                                                                                                "max_index")):
+        if t is None and K == 1 and what.startswith("state"):
+            continue
+        if t is None or tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous %s tensor of shape %s" % (what, str(dtype).replace("torch.", ""), shape))
+    if K > 1 and state.data_ptr() == state_next.data_ptr():
+        raise ValueError("state_next must not be state: a long chunk's tiles read the state while its last tile writes")
+    rows = math.prod(lead)
+    peak = torch.empty(lead, dtype=torch.float32, device=x.device)
+    ws, nbytes = _true_peak_workspace(rows, n, P, K, x.device)
+    check(lib().at_true_peak(ptr(x), rows, n, ptr(taps), P, K, ptr(state) if K > 1 else None,
+                             ptr(state_next) if K > 1 else None, ptr(peak), None, None, ptr(max_peak), ptr(max_index),
+                             int(offset), ptr(ws), nbytes, stream_ptr()), "at_true_peak")
+    return peak
+
+
+def true_peak_backward(g, sign, index, taps, L):
+    """The subgradient of true_peak with respect to x: g (...,) = dL/dpeak (linear), sign and index as return_state gave them
+    -> (..., L) float32, g sign taps[p*][n* - n] on the at most K samples under the attained maximum and +0 elsewhere; a row
+    whose sign is 0 (peak 0 or NaN) gets +0 whatever g holds.  One launch, every element written."""
+    taps, P, K = _true_peak_taps(taps, g)
+    require_device(g, sign, index)
+    lead = tuple(g.shape)
+    if tuple(sign.shape) != lead or tuple(index.shape) != lead or index.dtype != torch.int64:
+        raise ValueError("true_peak_backward: g, sign and index are not those of true_peak(x, taps, return_state=True)")
+    g, sign, index = _f32c(g), _f32c(sign), index.contiguous()
+    gx = torch.empty(lead + (int(L),), dtype=torch.float32, device=g.device)
+    check(lib().at_true_peak_backward(ptr(g), ptr(sign), ptr(index), ptr(taps), P, K, math.prod(lead), int(L), ptr(gx),
+                                      stream_ptr()), "at_true_peak_backward")
+    return gx
+
+
+# ----------------------------------------------------------------------------------------------
 # long-filter convolution (fft_convolve.hip): uniformly partitioned overlap-save
 # ----------------------------------------------------------------------------------------------
 FFT_CONVOLVE_BLOCKS = (128, 256, 512, 1024, 2048)

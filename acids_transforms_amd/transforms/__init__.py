@@ -13,12 +13,12 @@ from .channels import Mono, Stereo, MidSide, Window, Squeeze, Unsqueeze, Transpo
 from .pqmf import PQMF, RealtimePQMF
 from .stretch import TimeStretch, PitchShift
 from .filters import SOSFilter, RealtimeSOSFilter, Preemphasis
-from .loudness import Loudness, LoudnessNormalize, RealtimeLoudness
+from .loudness import Loudness, LoudnessNormalize, RealtimeLoudness, TruePeak, RealtimeTruePeak
 from .convolve import FFTConvolve, Convolve, ImpulseResponse, RealtimeImpulseResponse, fftconvolve
 
 __all__ = ["AudioTransform", "ComposeAudioTransform", "NotInvertibleError", "InversionEnumType",
            "apply_transform_to_list", "apply_invert_transform_to_list", "STFT", "RealtimeSTFT", "DGT", "RealtimeDGT", "DGT_INVERSION_MODES",
            "Normalize", "Magnitude", "Real", "Imaginary", "Phase", "IF", "SpectralRepresentation", "Cartesian", "Polar",
            "PolarIF", "MFCC", "OverlapAdd", "MuLaw", "OneHot", "Mono", "Stereo", "MidSide", "Window", "Squeeze", "Unsqueeze", "Transpose",
-           "PQMF", "RealtimePQMF", "TimeStretch", "PitchShift", "SOSFilter", "RealtimeSOSFilter", "Preemphasis", "Loudness", "LoudnessNormalize", "RealtimeLoudness",
+           "PQMF", "RealtimePQMF", "TimeStretch", "PitchShift", "SOSFilter", "RealtimeSOSFilter", "Preemphasis", "Loudness", "LoudnessNormalize", "RealtimeLoudness", "TruePeak", "RealtimeTruePeak",
            "FFTConvolve", "Convolve", "ImpulseResponse", "RealtimeImpulseResponse", "fftconvolve"]

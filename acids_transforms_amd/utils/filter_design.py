@@ -17,6 +17,9 @@ R. Bristow-Johnson's Audio EQ Cookbook, restated: with w0 = 2 pi f / sr and alph
 prototypes behind the standard's 48 kHz table by the bilinear transform with K = tan(pi fc / sr); at 48 kHz it reproduces
 the printed coefficients.  transforms.Loudness is the gated loudness measure on top of it.
 
+`true_peak_filter(oversample, taps_per_phase, design)` is not a section cascade but the (P, K) polyphase FIR table of
+transforms.TruePeak: the standard's own 48 taps, or a Kaiser-windowed sinc.
+
 ValueError: f outside (0, sr / 2), Q <= 0, a non-finite argument.
 """
 import math
@@ -24,7 +27,7 @@ import math
 import numpy as np
 
 __all__ = ["lowpass", "highpass", "bandpass", "bandreject", "allpass", "equalizer", "low_shelf", "high_shelf",
-           "k_weighting"]
+           "k_weighting", "true_peak_filter"]
 
 _SQRT_HALF = 1.0 / math.sqrt(2.0)
 
@@ -120,3 +123,34 @@ def k_weighting(sr=48000):
     a0 = 1 + K / _K_HP_Q + K * K
     hp = np.array([[1.0, -2.0, 1.0, 1.0, 2 * (K * K - 1) / a0, (1 - K / _K_HP_Q + K * K) / a0]], dtype=np.float64)
     return np.concatenate([shelf, hp], axis=0)
+
+
+# the interpolation filter of ITU-R BS.1770-4 Annex 2 in units of 1 / 8192: phases 0 and 1; phases 2 and 3 are their reversals
+_TRUE_PEAK_BS1770 = ((14, 90, -161, 272, -487, 1125, 7964, -838, 390, -218, 122, -68),
+                     (-239, 240, -424, 730, -1364, 3810, 6388, -1641, 832, -477, 271, -155))
+TRUE_PEAK_KAISER_BETA = 5.0
+
+
+def true_peak_filter(oversample=4, taps_per_phase=12, design="bs1770"):
+    """The polyphase interpolation filter of a true-peak meter: a float64 (P, K) table, P = oversample phases of K =
+    taps_per_phase taps, phase p giving the oversampled value y[P n + p] = sum_k h[p][k] x[n - k].
+
+    design="bs1770": the 48-tap table of ITU-R BS.1770-4 Annex 2, every entry a multiple of 1 / 8192; only (4, 12).
+    design="kaiser": a Kaiser-windowed sinc (beta = 5) of P K taps with its cutoff at the input's Nyquist frequency, each
+    phase scaled to unity DC gain; P in {2, 4, 8}, K in 4 .. 64.  ValueError for anything else."""
+    P, K = int(oversample), int(taps_per_phase)
+    if P != oversample or K != taps_per_phase:
+        raise ValueError("oversample and taps_per_phase must be integers, got %r and %r" % (oversample, taps_per_phase))
+    if design == "bs1770":
+        if (P, K) != (4, 12):
+            raise ValueError("the BS.1770 table is 4 phases of 12 taps, got (%d, %d): use design='kaiser'" % (P, K))
+        a, b = (np.array(r, dtype=np.float64) / 8192.0 for r in _TRUE_PEAK_BS1770)
+        return np.stack([a, b, b[::-1], a[::-1]])
+    if design == "kaiser":
+        if P not in (2, 4, 8) or not 4 <= K <= 64:
+            raise ValueError("the Kaiser design takes oversample in {2, 4, 8} and 4 <= taps_per_phase <= 64, got (%d, %d)" % (P, K))
+        i = np.arange(P * K, dtype=np.float64)
+        g = np.sinc((i - (P * K - 1) / 2.0) / P) * np.kaiser(P * K, TRUE_PEAK_KAISER_BETA)
+        h = g.reshape(K, P).T.copy()                         # g[P k + p] = h[p][k]
+        return h / h.sum(axis=1, keepdims=True)
+    raise ValueError("design must be 'bs1770' or 'kaiser', got %r" % (design,))

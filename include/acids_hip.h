@@ -994,6 +994,42 @@ int at_spectral_fir_stream(const float *X_complex, int64_t x_row_stride, float *
                            int64_t rows, int64_t Tc, int64_t P, int64_t R, int64_t head, int F, float *Y_complex,
                            void *stream);
 
+/* ---- true peak (true_peak.hip; ops.true_peak, transforms.TruePeak, RealtimeTruePeak) -------------------------------- */
+/* The true-peak measure of ITU-R BS.1770-4 Annex 2 for any polyphase table (restated; no reference counterpart).  x (rows,
+ * L) float32; taps (P, K) float32 ON THE DEVICE, P phases of K taps, 1 <= P <= 8, 1 <= K <= 64:
+ *   y[P n + p] = sum over k = 0 .. K - 1 ascending of taps[p][k] x[n - k],   0 <= n < L,   x[n < 0] from state_in or 0,
+ *   peak = max over m of |y[m]|,   index = index_offset + the smallest m that attains it,   sign = sign(y[m]) there.
+ * Every y[m] is one fmaf chain from +0 over k ascending; the reduction is the maximum of the unsigned image of |y|'s bits
+ * (every NaN one image above infinity's: a NaN in a row makes that row's peak NaN at the first NaN output, and no other row's)
+ * paired with the smallest index -- exact, associative and commutative, so a row's bits depend neither on the batch, nor on
+ * the tile, nor on the grid, nor on how a stream was cut into chunks.  No float maximum, no atomics.  Zeros give +0, index
+ * index_offset and sign 0; sign is also 0 where the peak is NaN.  P = K = 1 with tap 1 is the sample peak.
+ * Rows x tiles of *tile = 2048 samples share one 64-bit index on persistent workgroups: no limit on the rows, and one long
+ * row spreads over the chip; a lane takes *per_lane = 8 consecutive samples with their K - 1 halo in registers.  *dispatch: 0
+ * the compiled (4, 12) copy with its taps as uniform values, 1 the generic copy with the table in LDS.  *launches: 0 for
+ * empty work, 1 where a row is one tile, else 2 (a 16-byte partial per tile, then a small kernel that joins them in tile
+ * order) and a workspace of the size the _workspace_bytes entry answers (0 for one tile; 16-byte aligned; AT_EWORKSPACE).
+ * Outputs, each (rows) and each optional except that peak or max_peak_io must be given: peak float32, linear; index int64;
+ * sign float32; max_peak_io float32, read as the running maximum of a stream and replaced, with max_index_io int64, where
+ * this call's peak has the larger image (a tie keeps the earlier index).
+ * Stream form: state_in (rows, K - 1) float32 holds the samples before x, oldest first (NULL: zeros); state_out (rows, K - 1),
+ * never state_in, receives the last K - 1 samples of [state | x] from the same launch; any L >= 1, shorter than K - 1 too.
+ * The plan and workspace entries read no device.  AT_EINVAL: negative sizes, P or K out of range, null x / taps / plan
+ * outputs, neither peak nor max_peak_io, max_index_io without max_peak_io, a state with K == 1, state_out == state_in,
+ * misalignment (4 bytes, 8 for the indices).  AT_OK without a launch when rows == 0 or L == 0: nothing is written.
+ *
+ * The backward entry below: the measure is piecewise linear, so the subgradient at the attained maximum is used,
+ *   gx[n] = g sign taps[p*][n* - n]   for 0 <= n* - n < K, with index = P n* + p*;   +0 elsewhere,
+ * g, sign (rows) float32 and index (rows) int64 as the forward wrote them with index_offset 0, gx (rows, L) float32.  One
+ * launch writes every element: no memset, no atomics.  A row whose sign is 0 gets +0 by selection, whatever g holds. */
+int at_true_peak_plan(int64_t rows, int64_t L, int P, int K, int64_t *tile, int64_t *per_lane, int *launches, int *dispatch);
+size_t at_true_peak_workspace_bytes(int64_t rows, int64_t L, int P, int K);
+int at_true_peak(const float *x, int64_t rows, int64_t L, const float *taps, int P, int K, const float *state_in,
+                 float *state_out, float *peak, int64_t *index, float *sign, float *max_peak_io, int64_t *max_index_io,
+                 int64_t index_offset, void *workspace, size_t workspace_bytes, void *stream);
+int at_true_peak_backward(const float *g, const float *sign, const int64_t *index, const float *taps, int P, int K,
+                          int64_t rows, int64_t L, float *gx, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
